@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the cosine-embedding training + retrieval hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload retrieval|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload retrieval|train] [--dump-outputs DIR]
 
 One JSON line on stdout (rank 0).  See DESIGN.md section 6 for what a "step" is:
 
@@ -18,6 +18,10 @@ One JSON line on stdout (rank 0).  See DESIGN.md section 6 for what a "step" is:
   N x 160,146 gallery rows x D = 1000, per-shard fused distance + top-251 -> RCCL all-gather -> k-way merge, with the
   three phases timed separately).
 * ``--workload train`` makes the training step the primary metric.
+* ``--dump-outputs DIR`` (retrieval): after the timed steps, rank 0 writes what the last timed step computed -- a fixed, seeded
+  sample of the rows of its distance matrix and ranking, and those rows of the features they were computed from -- as float32 /
+  float64 ``DIR/<name>.npy``, under 64 MB in all (``dump_outputs``).  The inputs are seeded, so two builds run with the same
+  arguments can be compared output for output.
 
 ``--gpus N`` with N > 1 and no torch.distributed environment makes this process re-launch itself as N ranks
 (``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...``); under an existing launcher the
@@ -90,7 +94,14 @@ def parse(argv=None):
                          "reference's multi_gpu_model semantics for training (global batch 128), query rows sharded for retrieval")
     ap.add_argument("--dry", action="store_true",
                     help="CPU plumbing test: gloo process group, tiny shapes, CPU stand-ins for the kernels (no measurement)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="retrieval: write a seeded row sample of the last timed step's outputs to DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and (args.dry or args.workload != "retrieval"):
+        ap.error("--dump-outputs applies to the retrieval workload only")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -377,6 +388,9 @@ def bench_retrieval(args, rank, world):
     barrier_sync(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world, "cuda")
     kms = timer.avg_ms()
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last["g"] if last["q"] is None else last["q"], pd, rk)
 
     pairs_per_step = float(n) * n if strong else float(q) * n * world
     value = pairs_per_step * args.steps / elapsed / 1e6
@@ -432,12 +446,45 @@ def bench_retrieval(args, rank, world):
                                   else "%d independent feature sets, one per GPU (no collective)" % world},
         "roofline": roofline, "kernels": kernels,
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if args.verify:
         out.update(verify_last_step(last, pd, rk, metric, world))
         # scalars the driver's parsed subset keeps (it drops nested objects below `roofline` / `config`)
         out["roofline"]["verified"] = out["verified"]
         out["config"]["verified"] = out["verified"]
     return out, feats_h, rk
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # --dump-outputs: below 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(out_dir, feats, pd, rk, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: what the last timed step returned to its caller, as .npy files in float32 / float64.  The [q, n] outputs
+    are too large to write whole (2 x 10 GB at 50k x 50k), so the same seeded sample of their rows is written on every run with
+    the same shapes -- as many rows as fit in `budget` bytes:
+        rows.npy       [r]     float64  the sampled query rows, ascending
+        features.npy   [r, d]  float32  those rows of the features the distances were computed from (normalised in place for cosine)
+        distances.npy  [r, n]  float32  those rows of the pairwise_dist output
+        ranking.npy    [r, n]  float64  those rows of the rank_rows output (gallery indices, exact in float64)"""
+    q, n = pd.shape
+    d = feats.shape[1]
+    r = min(q, budget // (8 + 4 * d + 4 * n + 8 * n))
+    if r < 1:
+        raise ValueError("--dump-outputs: one row of a %d-column output does not fit in %d bytes" % (n, budget))
+    rows = np.sort(np.random.default_rng(seed).choice(q, size=r, replace=False))
+    idx = torch.from_numpy(rows).to(pd.device)
+    arrays = {"rows": rows.astype(np.float64),
+              "features": feats.index_select(0, idx).cpu().numpy().astype(np.float32),
+              "distances": pd.index_select(0, idx).cpu().numpy().astype(np.float32),
+              "ranking": rk.index_select(0, idx).cpu().numpy().astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    nbytes = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        nbytes += os.path.getsize(path)
+    return {"dir": os.path.abspath(out_dir), "rows": int(r), "files": sorted(arrays), "bytes": nbytes}
 
 
 def bench_metrics(args, rk, reps=3):

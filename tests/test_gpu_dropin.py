@@ -624,13 +624,16 @@ def test_labelembed_model_mirrors_the_reference_head():
     assert all(torch.isfinite(v).all() for v in g.values() if v is not None)
 
 
-def test_bench_line_schema_on_a_small_problem():
+def test_bench_line_schema_on_a_small_problem(tmp_path):
     """bench.py end to end at a reduced size (so that a broken bench cannot reach the driver): one JSON line with the contract's
-    keys, the roofline / kernels objects, the post-run oracle verification and the sharded-gallery leg."""
+    keys, the roofline / kernels objects, the post-run oracle verification and the sharded-gallery leg; --dump-outputs writes
+    the sampled rows of the last timed step (normalised features, distances, canonical ranking)."""
     import json
     import subprocess
+    dump = tmp_path / "dump"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "4096", "--steps", "2", "--warmup", "1", "--no-train",
-                          "--shard-rows", "3000", "--shard-queries", "500", "--shard-dim", "64", "--shard-k", "17", "--cpu-sample-queries", "256"],
+                          "--shard-rows", "3000", "--shard-queries", "500", "--shard-dim", "64", "--shard-k", "17", "--cpu-sample-queries", "256",
+                          "--dump-outputs", str(dump)],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -647,6 +650,14 @@ def test_bench_line_schema_on_a_small_problem():
     sg = d["sharded_gallery"]
     assert "error" not in sg and sg["merged_lists_sorted_with_index_tiebreak"] and sg["merged_indices_in_range"]
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
+    dumped = {k: np.load(str(dump / (k + ".npy"))) for k in ("rows", "features", "distances", "ranking")}
+    assert all(v.dtype in (np.float32, np.float64) for v in dumped.values())
+    assert d["dump_outputs"]["bytes"] <= 64e6 and sum(os.path.getsize(str(p)) for p in dump.iterdir()) == d["dump_outputs"]["bytes"]
+    rows = dumped["rows"].astype(np.int64)
+    assert len(rows) == d["dump_outputs"]["rows"] > 0 and dumped["distances"].shape == dumped["ranking"].shape == (len(rows), 4096)
+    feats = np.random.default_rng(0).standard_normal((4096, 100)).astype(np.float32)       # bench.py's rank-0 features
+    assert np.array_equal(dumped["features"], ro.canon_normalize_rows(feats)[rows])
+    assert np.array_equal(dumped["ranking"], np.argsort(dumped["distances"], axis=1, kind="stable").astype(np.float64))
 
 
 def test_cifar_pipeline_on_the_device_matches_reference_and_augmentation_statistics(tmp_path):

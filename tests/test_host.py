@@ -364,6 +364,36 @@ def test_bench_cost_model_counts_executed_flops():
     assert ex_g == full and 3.1 < floor_g < 3.3
 
 
+def test_bench_dump_outputs_writes_a_seeded_row_sample_within_budget(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, the same seeded rows on every call, no more bytes than the budget, and the
+    written rows are the rows of the step's outputs; --steps sets the timed steps, so fewer than one is refused."""
+    import bench
+    q, n, d = 300, 500, 7
+    rng = np.random.default_rng(3)
+    feats = torch.from_numpy(rng.standard_normal((q, d)).astype(np.float32))
+    pd = torch.from_numpy(rng.standard_normal((q, n)).astype(np.float32))
+    rk = torch.from_numpy(np.argsort(pd.numpy(), axis=1, kind="stable").astype(np.int32))
+    budget = 200000
+    a = bench.dump_outputs(str(tmp_path / "a"), feats, pd, rk, budget=budget)
+    b = bench.dump_outputs(str(tmp_path / "b"), feats, pd, rk, budget=budget)
+    assert a["files"] == ["distances", "features", "ranking", "rows"] and 0 < a["bytes"] <= budget + 4 * 128
+    assert a["rows"] == budget // (8 + 4 * d + 12 * n) < q
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in a["files"]}
+    for k, v in got.items():
+        assert v.dtype in (np.float32, np.float64), k
+        assert np.array_equal(v, np.load(str(tmp_path / "b" / (k + ".npy")))), k
+    rows = got["rows"].astype(np.int64)
+    assert len(rows) == a["rows"] and np.all(np.diff(rows) > 0) and rows[-1] < q
+    assert np.array_equal(got["features"], feats.numpy()[rows]) and np.array_equal(got["distances"], pd.numpy()[rows])
+    assert np.array_equal(got["ranking"], rk.numpy()[rows].astype(np.float64))
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "c"), feats, pd, rk, budget=1000)
+    assert bench.parse(["--steps", "7", "--dump-outputs", "x"]).steps == 7
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--workload", "train", "--dump-outputs", "x"], ["--dry", "--dump-outputs", "x"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
 def _write_cifar100(root, n_train=60, n_test=24, seed=0):
     import pickle
     rng = np.random.default_rng(seed)
