@@ -387,6 +387,48 @@ int64_t se_hprec_curve_len(int64_t list_len);
 int se_hprec_reciprocal_curves(const double *best_wup, const double *best_lcs, int64_t ldb,
                                int num_classes, int64_t list_len, double *rcp, se_stream_t stream);
 
+/*
+ * Positions of the relevant items in every query's ranking: the exact primary data of the recall-precision curve and the mAP.
+ * Replaces: the relevance list of plot_recall_precision.py:52-79 (`labels[r] == labels[qid] for r in retrieved if r != qid`).
+ *   rank      [q, list_len] int32 gallery indices, best first (ldr elements between rows)
+ *   cls       [gallery] int32 class index (0 .. num_classes - 1) of every gallery item; qcls [q] class index of every query
+ *   qidx      [q] int32 gallery index of the query itself (dropped from its ranking), NULL = keep everything
+ *   hit_off   [q + 1] int64 device array: prefix sum of R_i, the number of relevant items of query i (items of its class other
+ *             than itself); built by the caller from the class counts
+ *   hit_pos   [hit_off[q]] int32 out: hit_pos[hit_off[i] + j - 1] = 1-based position (query removed) of the j-th relevant item of
+ *             query i.  A row stops being read once its R_i hits are found; positions of hits a row does not have read 0.
+ */
+int se_relevant_positions(const int32_t *rank, int64_t ldr, int64_t q, int64_t list_len,
+                          const int32_t *cls, int64_t gallery, const int32_t *qcls, const int32_t *qidx,
+                          int num_classes, const int64_t *hit_off, int32_t *hit_pos, se_stream_t stream);
+/* The same for rankings of uint16 gallery indices (se_rank_rows with idx64 == 2; gallery <= 65,536): identical results, half the
+ * ranking bytes to read.  Replaces the same lines of plot_recall_precision.py:52-79. */
+int se_relevant_positions_r16(const uint16_t *rank, int64_t ldr, int64_t q, int64_t list_len,
+                              const int32_t *cls, int64_t gallery, const int32_t *qcls, const int32_t *qidx,
+                              int num_classes, const int64_t *hit_off, int32_t *hit_pos, se_stream_t stream);
+
+/*
+ * Average precision and recall-precision sums of a tile of queries from se_relevant_positions' output, in a fixed summation order
+ * (no atomics: the same inputs give the same bits; tiles accumulate in tile order and the result does not depend on the tiling).
+ * Replaces: the AP and `recprec` accumulation of plot_recall_precision.py:52-79 (average_precision_score, cumsum, max precision
+ *           per recall level or per --bins bin).
+ *   hit_pos, hit_off  as written / read by se_relevant_positions for these q queries
+ *   order     [q] int32: the tile's queries (0 .. q - 1) sorted by class, ascending query index inside a class;
+ *   class_start [num_classes + 1] int32: the queries of class c are order[class_start[c] .. class_start[c + 1])
+ *   class_off [num_classes + 1] int64: prefix sum of R_c, the relevant items of every query of class c (all queries of a class
+ *             must have the same R); class_len = class_off[num_classes]
+ *   ap        [q] f64 out: (1 / R_i) sum_j j / p_ij, 0 when R_i = 0
+ *   prec_sum  [class_len] f64 in/out: element class_off[c] + j - 1 += sum over the class's queries of j / p_j (recall level j / R_c)
+ *   first_miss [num_classes] int64 in/out: += queries of the class whose first item is not relevant (recall level 0, precision 0)
+ *   bins      0: no binning; B > 0 (at most 2^20): also bin_sum / bin_count [num_classes, B + 1] in/out, bin b of query i being the
+ *             j with int((j / R_i) * B) == b (IEEE float64, as Python computes it): bin_sum += the max of j / p_j over the bin
+ *             (0.0 for a first-position miss in bin 0), bin_count += 1, for every query of the class that has the bin
+ */
+int se_recall_precision_reduce(const int32_t *hit_pos, const int64_t *hit_off, int64_t q, const int32_t *order,
+                               const int32_t *class_start, int num_classes, const int64_t *class_off, int64_t class_len,
+                               int bins, double *ap, double *prec_sum, int64_t *first_miss, double *bin_sum,
+                               int64_t *bin_count, se_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

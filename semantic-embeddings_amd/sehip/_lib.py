@@ -29,6 +29,7 @@ EXPORTS = (
     "se_topk_rows", "se_topk_merge", "se_topk_merge_packed",
     "se_retrieve_topk_workspace_bytes", "se_retrieve_topk", "se_hierarchical_precision", "se_hierarchical_precision_r16",
     "se_hprec_order_workspace_bytes", "se_hprec_curve_len", "se_hprec_reciprocal_curves",
+    "se_relevant_positions", "se_relevant_positions_r16", "se_recall_precision_reduce",
 )
 
 
@@ -103,6 +104,9 @@ def lib():
     L.se_hprec_curve_len.argtypes = [c_i64]
     L.se_hprec_curve_len.restype = c_i64
     L.se_hprec_reciprocal_curves.argtypes = [vp, vp, c_i64, c_int, c_i64, vp, vp]
+    L.se_relevant_positions.argtypes = [vp, c_i64, c_i64, c_i64, vp, c_i64, vp, vp, c_int, vp, vp, vp]
+    L.se_relevant_positions_r16.argtypes = L.se_relevant_positions.argtypes
+    L.se_recall_precision_reduce.argtypes = [vp, vp, c_i64, vp, vp, c_int, vp, c_i64, c_int, vp, vp, vp, vp, vp, vp]
     L.se_rank_rows_workspace_bytes.argtypes = [c_i64, c_i64]
     L.se_rank_rows_workspace_bytes.restype = c_i64
     L.se_rank_rows.argtypes = [vp, c_i64, c_i64, c_i64, vp, c_int, c_i64, vp, c_i64, vp]

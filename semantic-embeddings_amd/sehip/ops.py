@@ -17,7 +17,7 @@ __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "l2norm", "nn_accuracy", "labelembed_loss",
     "devise_ranking_loss",
     "row_sqnorm", "normalize_rows_", "pairwise_dist", "rank_rows", "rank_rows_check", "topk_rows", "topk_merge", "retrieve_topk",
-    "hierarchical_precision", "hprec_reciprocal_curves",
+    "hierarchical_precision", "hprec_reciprocal_curves", "relevant_positions", "recall_precision_reduce",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
 ]
 
@@ -665,3 +665,78 @@ def hierarchical_precision(rank, cls, qcls, qidx, wup, lcs, best_wup, best_lcs, 
                 int(ahp_len), int(bool(want_ap)), ptr(out), out.stride(0), ptr(order_ws), stream_ptr()),
           "se_hierarchical_precision")
     return out
+
+
+def _i32(t, name):
+    if t.dtype != torch.int32 or not t.is_contiguous():
+        raise SehipError("%s must be contiguous int32" % name)
+
+
+def _i64(t, name):
+    if t.dtype != torch.int64 or not t.is_contiguous():
+        raise SehipError("%s must be contiguous int64" % name)
+
+
+def relevant_positions(rank, cls, qcls, qidx, hit_off, list_len=None, out=None, num_classes=None, total=None):
+    """1-based positions (query removed) of the items of each query's class in its ranking (plot_recall_precision.py:52-79).
+
+    rank [Q, >=L] int32 (or int16: the uint16 bit patterns rank_rows(idx16=True) writes), cls [N] int32 class of every gallery
+    item, qcls [Q] int32, qidx [Q] int32 | None (gallery index of the query, dropped from its ranking), hit_off [Q + 1] int64 (prefix
+    sum of R_i, the relevant items of query i).  Returns int32 [hit_off[Q]]: the positions of query i at hit_off[i] .. hit_off[i + 1].
+    ``num_classes`` (classes are 0 .. num_classes - 1) and ``total`` (= hit_off[Q]) spare the two device reads that find them
+    otherwise; callers that evaluate tile after tile know both on the host."""
+    require_gpu(rank, cls, qcls, qidx, hit_off, out)
+    if rank.dtype not in (torch.int32, torch.int16) or rank.dim() != 2 or rank.stride(1) != 1:
+        raise SehipError("rank must be a 2-d int32 (or int16) tensor with contiguous rows")
+    for t, name in ((cls, "cls"), (qcls, "qcls")) + (((qidx, "qidx"),) if qidx is not None else ()):
+        _i32(t, name)
+    _i64(hit_off, "hit_off")
+    Q = rank.shape[0]
+    if qcls.numel() != Q or hit_off.numel() != Q + 1 or (qidx is not None and qidx.numel() != Q):
+        raise SehipError("qcls / qidx need one entry per ranking row and hit_off one more")
+    L = rank.shape[1] if list_len is None else int(list_len)
+    total = int(total) if total is not None else (int(hit_off[-1].item()) if Q > 0 else 0)
+    if out is None:
+        out = torch.empty((max(total, 1),), dtype=torch.int32, device=rank.device)
+    else:
+        _i32(out, "out")
+        if out.numel() < total:
+            raise SehipError("out holds %d positions, hit_off asks for %d" % (out.numel(), total))
+    if num_classes is not None:
+        C = int(num_classes)
+    else:
+        C = int(max(int(cls.max().item()), int(qcls.max().item()) if Q > 0 else 0)) + 1 if cls.numel() > 0 else 1
+    entry = lib().se_relevant_positions_r16 if rank.dtype == torch.int16 else lib().se_relevant_positions
+    check(entry(ptr(rank), rank.stride(0), Q, L, ptr(cls), cls.numel(), ptr(qcls), ptr(qidx), C, ptr(hit_off), ptr(out),
+                stream_ptr()), "se_relevant_positions")
+    return out[:total]
+
+
+def recall_precision_reduce(hit_pos, hit_off, order, class_start, class_off, bins, ap, prec_sum, first_miss, bin_sum=None,
+                            bin_count=None):
+    """Per-query AP and per-class recall-precision sums of one tile (se_recall_precision_reduce; plot_recall_precision.py:52-79).
+
+    hit_pos / hit_off: from ``relevant_positions``; order [Q] int32 (queries sorted by class, stable), class_start [C + 1] int32,
+    class_off [C + 1] int64 (prefix sum of the per-class R).  Writes ap [Q] f64; ADDS to prec_sum [class_off[C]] f64,
+    first_miss [C] int64 and, with bins > 0, bin_sum [C, bins + 1] f64 / bin_count [C, bins + 1] int64 (accumulate tiles in order)."""
+    bins = int(bins or 0)
+    require_gpu(hit_pos, hit_off, order, class_start, class_off, ap, prec_sum, first_miss, bin_sum, bin_count)
+    _i32(hit_pos, "hit_pos"); _i32(order, "order"); _i32(class_start, "class_start")
+    _i64(hit_off, "hit_off"); _i64(class_off, "class_off"); _i64(first_miss, "first_miss")
+    for t, name in ((ap, "ap"), (prec_sum, "prec_sum")) + (((bin_sum, "bin_sum"),) if bins > 0 else ()):
+        if t is None or t.dtype != torch.float64 or not t.is_contiguous():
+            raise SehipError("%s must be contiguous float64" % name)
+    Q = order.numel()
+    C = class_start.numel() - 1
+    if C < 1 or class_off.numel() != C + 1 or first_miss.numel() != C or hit_off.numel() != Q + 1 or ap.numel() != Q:
+        raise SehipError("recall_precision_reduce: inconsistent shapes (Q = %d, C = %d)" % (Q, C))
+    class_len = prec_sum.numel()
+    if bins > 0:
+        _i64(bin_count, "bin_count")
+        if bin_sum.numel() != C * (bins + 1) or bin_count.numel() != C * (bins + 1):
+            raise SehipError("bin_sum / bin_count must hold [C, bins + 1] entries")
+    check(lib().se_recall_precision_reduce(ptr(hit_pos), ptr(hit_off), Q, ptr(order), ptr(class_start), C, ptr(class_off),
+                                           class_len, bins, ptr(ap), ptr(prec_sum), ptr(first_miss),
+                                           ptr(bin_sum if bins > 0 else None), ptr(bin_count if bins > 0 else None), stream_ptr()),
+          "se_recall_precision_reduce")
+    return ap

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Kernel-level microbenchmarks (HIP-event timing on the launch stream) used while tuning.
-    python tools/bench_kernels.py pdist|rank|loss|topk [--n 50000 --d 100 --reps 5]"""
+    python tools/bench_kernels.py pdist|rank|loss|topk [--n 50000 --d 100 --reps 5]
+    python tools/bench_kernels.py recprec        (10k x 10k and 50k x 50k, 100 classes; --n is not used)"""
 import argparse
 import os
 import sys
@@ -27,7 +28,7 @@ def timeit(fn, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "shard", "rownorm"])
+    ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -109,6 +110,53 @@ def main():
                 print("hprec sweep list_len=%d: median %.3f ms" % (ll, med))
         med, mn = timeit(lambda: sehip.hprec_reciprocal_curves(best_d, best_d), args.reps)
         print("hprec reciprocal curves C=%d n=%d: median %.3f ms" % (C, n, med))
+    elif args.what == "recprec":
+        # se_relevant_positions (kernel A) and se_recall_precision_reduce (kernel B) on full all-pairs rankings of clustered features,
+        # 100 classes; labels drawn at random per item, or class-sorted (item i of class i * C // n).  Kernel A's bytes are those of
+        # the 2048-rank chunks it streams before its early exit (one chunk of look-ahead included).
+        C, chunk = 100, 2048
+        for nn in (10000, 50000):
+            rng = np.random.default_rng(7)
+            for layout in ("random ids", "class-sorted ids"):
+                lab = rng.integers(0, C, size=nn) if layout == "random ids" else (np.arange(nn) * C // nn)
+                feats = (rng.standard_normal((C, d)) * 0.5)[lab] + rng.standard_normal((nn, d))
+                xf = torch.from_numpy(feats.astype(np.float32)).cuda()
+                sehip.normalize_rows_(xf)
+                rk = sehip.rank_rows(sehip.pairwise_dist(xf, None, metric=sehip.METRIC_COSINE))
+                cls_h = lab.astype(np.int32)
+                counts = np.bincount(cls_h, minlength=C)
+                r_cls = counts - 1
+                hit_off_h = np.concatenate([[0], np.cumsum(r_cls[cls_h])]).astype(np.int64)
+                class_off = torch.from_numpy(np.concatenate([[0], np.cumsum(r_cls)]).astype(np.int64)).cuda()
+                order = torch.from_numpy(np.argsort(cls_h, kind="stable").astype(np.int32)).cuda()
+                cstart = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).cuda()
+                cls, hit_off = torch.from_numpy(cls_h).cuda(), torch.from_numpy(hit_off_h).cuda()
+                qidx = torch.arange(nn, dtype=torch.int32, device="cuda")
+                out = torch.empty(int(hit_off_h[-1]), dtype=torch.int32, device="cuda")
+                run_a = lambda r: sehip.relevant_positions(r, cls, cls, qidx, hit_off, num_classes=C, total=int(hit_off_h[-1]), out=out)
+                med, mn = timeit(lambda: run_a(rk), args.reps)
+                last = out.cpu().numpy()[hit_off_h[1:] - 1].astype(np.int64)
+                read = np.minimum((last + chunk) // chunk + 1, (nn + chunk - 1) // chunk) * chunk
+                frac = float(np.minimum(read, nn).sum()) / (float(nn) * nn)
+                gbs = 4.0 * frac * nn * nn / med / 1e6
+                print("recprec A  int32 %-16s %d x %d: median %.3f ms (min %.3f)  %.1f%% of rank bytes read, %.2f TB/s over them "
+                      "(%.0f%% of ~6.3 TB/s)" % (layout, nn, nn, med, mn, 100 * frac, gbs / 1e3, gbs / 63.0))
+                rk16 = sehip.rank_rows(sehip.pairwise_dist(xf, None, metric=sehip.METRIC_COSINE), idx16=True)
+                med, mn = timeit(lambda: run_a(rk16), args.reps)
+                print("recprec A  uint16 %-15s %d x %d: median %.3f ms (min %.3f)" % (layout, nn, nn, med, mn))
+                del rk16
+                apv = torch.zeros(nn, dtype=torch.float64, device="cuda")
+                psum = torch.zeros(int(class_off[-1].item()), dtype=torch.float64, device="cuda")
+                miss = torch.zeros(C, dtype=torch.int64, device="cuda")
+                for bins in (0, 10, 1000):
+                    bs = torch.zeros((C, bins + 1), dtype=torch.float64, device="cuda")
+                    bc = torch.zeros((C, bins + 1), dtype=torch.int64, device="cuda")
+                    med, mn = timeit(lambda: sehip.recall_precision_reduce(out, hit_off, order, cstart, class_off, bins, apv, psum, miss,
+                                                                           bs, bc), args.reps)
+                    print("recprec B  bins=%-5d %-16s %d x %d: median %.3f ms (min %.3f)  %d positions" %
+                          (bins, layout, nn, nn, med, mn, int(hit_off_h[-1])))
+                del rk, xf, out
+                torch.cuda.empty_cache()
     elif args.what == "shard":
         # BASELINE.json configs[4], one rank's share: 50,000 queries x (1,281,167 / 8) gallery rows, D = 1000, top-251, then the
         # merge of the 8 all-gathered lists (synthetic: 8 copies with shifted indices)
