@@ -429,6 +429,69 @@ int se_recall_precision_reduce(const int32_t *hit_pos, const int64_t *hit_off, i
                                int bins, double *ap, double *prec_sum, int64_t *first_miss, double *bin_sum,
                                int64_t *bin_count, se_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Classification side: linear SVM
+ * ------------------------------------------------------------------------------------------ */
+
+/* epilogue modes of se_svm_margin */
+#define SE_SVM_GRAD 0  /* squared-hinge derivative, active-set mask, loss partial sums */
+#define SE_SVM_HV 1    /* generalised Hessian-vector product's per-sample factor     */
+#define SE_SVM_SCORE 2 /* decision scores                                            */
+
+/*
+ * Margins of a linear model, with a fused epilogue (fp32 MFMA; the margins themselves are never stored).
+ * Replaces: the per-class X w products of scikit-learn's LinearSVC (liblinear, primal trust-region Newton solver) in
+ *           LinearSVC.fit and the X coef_^T + intercept_ of decision_function (evaluate_classification_accuracy.py:43-48).
+ * The objective of class column j is  f_j(w, b) = 1/2 (|w|^2 + b^2) + cpen sum_i max(0, 1 - y_ij (x_i . w + b))^2.
+ *   x          [n, d] f32 samples (ldx)
+ *   w          [c, d + 1] f32 (ldw >= d + 1): row j = (w_j, b_j), the bias in column d.  HV mode: the direction (v_j, v_b,j)
+ *   labels     [n] int32 class of every sample; col_class [c] int32 the class of column j: y_ij = +1 if labels[i] == col_class[j],
+ *              -1 otherwise (SE_SVM_GRAD only; NULL otherwise)
+ *   mask       [n, ldm] uint32, ldm >= ceil(c / 32): bit j % 32 of word j / 32 of row i = active set A_ij = (1 - y_ij m_ij > 0).
+ *              Written by SE_SVM_GRAD, read by SE_SVM_HV (the mask of the last gradient call), unused by SE_SVM_SCORE (NULL)
+ *   out        [n, c] f32 (ldo >= c):  SE_SVM_GRAD   z_ij = -2 cpen y_ij max(0, 1 - y_ij m_ij),  m = x w^T + b
+ *                                      SE_SVM_HV     z_ij = 2 cpen A_ij (x_i . v_j + v_b,j)
+ *                                      SE_SVM_SCORE  s_ij = x_i . w_j + b_j
+ *   loss_part  [c, ldl] f32, ldl >= se_svm_loss_blocks(n) (SE_SVM_GRAD only): element (j, r) = sum over rows 64 r .. 64 r + 63 of
+ *              max(0, 1 - y_ij m_ij)^2, summed in a fixed order
+ *   cpen       the penalty C of LinearSVC (> 0)
+ * c >= 3 (binary problems are out of scope); every argument is checked before any device work.
+ */
+int64_t se_svm_loss_blocks(int64_t n);
+int se_svm_margin(int mode, const float *x, int64_t ldx, int64_t n, int64_t d, const float *w, int64_t ldw,
+                  int64_t c, const int32_t *labels, const int32_t *col_class, float cpen, uint32_t *mask,
+                  int64_t ldm, float *out, int64_t ldo, float *loss_part, int64_t ldl, se_stream_t stream);
+
+/*
+ * Contraction over the samples: g = plus + z^T [x | 1], i.e. g[j, k] = plus[j, k] + sum_i z_ij x_ik for k < d and
+ * g[j, d] = plus[j, d] + sum_i z_ij -- the gradient (plus = w) or the Hessian-vector product (plus = v) of f_j from
+ * se_svm_margin's output.
+ * Replaces: liblinear's X^T z products of the same solver.
+ *   z [n, c] f32 (ldz), x [n, d] f32 (ldx), plus [c, d + 1] f32 (ldp) or NULL, g [c, d + 1] f32 out (ldg >= d + 1)
+ *   workspace  se_svm_reduce_workspace_bytes(n, d, c) bytes, 16-byte aligned: fp32 partial tiles of fixed slices of at most 4096
+ *              samples, combined per element in slice order in fp64.  No atomics: the same inputs give the same bits, and the
+ *              round-off does not grow with n.
+ */
+int64_t se_svm_reduce_workspace_bytes(int64_t n, int64_t d, int64_t c);
+int se_svm_reduce(const float *z, int64_t ldz, const float *x, int64_t ldx, int64_t n, int64_t d, int64_t c,
+                  const float *plus, int64_t ldp, float *g, int64_t ldg, void *workspace,
+                  int64_t workspace_bytes, se_stream_t stream);
+
+/*
+ * Per-row fp64 scalars of the solver's [c, len] f32 vectors (row j = class column j; all with leading dimension ld).
+ *   se_svm_gram    out [c, nv (nv + 1) / 2] f64: sum_k v_a[j, k] v_b[j, k] for a <= b, row-major upper triangle
+ *                  ((0,0), (0,1), .., (0,nv-1), (1,1), ..); 1 <= nv <= 4, unused vectors NULL
+ *   se_svm_rowsum  out [c] f64: sum_k a[j, k]
+ *   se_svm_axpby   out[j, k] = (float)(alpha[j] x[j, k] + beta[j] y[j, k]) evaluated in f64; alpha, beta [c] f64 device arrays;
+ *                  out may alias x or y
+ * Fixed reduction orders: the same inputs give the same bits.
+ */
+int se_svm_gram(const float *v0, const float *v1, const float *v2, const float *v3, int nv, int64_t ld, int64_t c,
+                int64_t len, double *out, se_stream_t stream);
+int se_svm_rowsum(const float *a, int64_t lda, int64_t c, int64_t len, double *out, se_stream_t stream);
+int se_svm_axpby(const double *alpha, const float *x, int64_t ldx, const double *beta, const float *y, int64_t ldy,
+                 int64_t c, int64_t len, float *out, int64_t ldo, se_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

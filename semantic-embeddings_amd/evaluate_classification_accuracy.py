@@ -11,9 +11,21 @@ Mirrors the pieces of the reference's ``evaluate_classification_accuracy.py`` th
 * ``evaluate`` (evaluate_classification_accuracy.py:88-108): accuracy, top-5 accuracy, class-balanced accuracy and
   hierarchical accuracy ``1 - lcs_height`` of a class ranking / prediction vector.
 
-The SVM and softmax-prediction modes of the reference script (``train_and_predict``, ``extract_predictions``) use
-scikit-learn / the classifier head and are outside this build's scope.
+* ``train_and_predict`` / ``svm_classification`` (evaluate_classification_accuracy.py:20-48): the reference's default mode --
+  scale the features, fit a one-vs-rest ``LinearSVC(C)`` and rank the classes by decision score -- on the device
+  (``linear_svm.LinearSVC``: the svm.hip kernels; float32 where scikit-learn uses float64).
+* ``extract_predictions`` (evaluate_classification_accuracy.py:74-85): the ``--prob_features`` mode, a descending ranking of
+  the model output.
+* ``main`` / ``__main__``: the reference's command line and result table (``print_performance``), with features extracted on the
+  device from a ``--model_dump`` of learn_image_embeddings.py (``torch.save`` of the module).
+
+Class rankings of the new modes come from ``se_rank_rows`` on the negated scores: descending score, ties in ascending class
+index (the reference's ``argsort(-1)[:, ::-1]`` breaks ties in an unspecified order).
 """
+import argparse
+import os
+import pickle
+import sys
 from collections import OrderedDict
 
 import numpy as np
@@ -69,3 +81,238 @@ def evaluate(y_pred, data_generator, hierarchy=None):
             total += 1.0 - hierarchy.lcs_height(classes[int(yp)], classes[int(yt)])
         perf['Hierarchical Accuracy'] = total / len(y_true)
     return perf
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# SVM and prediction modes, feature extraction, command line (evaluate_classification_accuracy.py:20-48, 74-85, 126-188)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+def _device():
+    import torch
+    import sehip
+    sehip._lib.require_gpu()
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _as_device_f32(a):
+    import torch
+    if torch.is_tensor(a):
+        return a.detach().to(device=_device(), dtype=torch.float32).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(_device())
+
+
+def _rank_descending(scores):
+    """Class ranking [N, C] of device scores, best first: ``se_rank_rows`` of the negated scores (ties: ascending column)."""
+    import sehip
+    return sehip.rank_rows(-scores).cpu().numpy()
+
+
+def preprocess_features(X_train, X_test, normalize):
+    """The reference's scaling (evaluate_classification_accuracy.py:33-39) on the device, float32: L2-normalised rows with
+    ``normalize``, otherwise both sets divided by ``max(1e-8, max |X_train|)`` per column.  Returns two device tensors."""
+    import torch
+    X_train, X_test = _as_device_f32(X_train), _as_device_f32(X_test)
+    if normalize:
+        return (X_train / torch.linalg.vector_norm(X_train, dim=-1, keepdim=True),
+                X_test / torch.linalg.vector_norm(X_test, dim=-1, keepdim=True))
+    X_max = torch.clamp(X_train.abs().amax(dim=0, keepdim=True), min=1e-8)
+    return X_train / X_max, X_test / X_max
+
+
+def svm_classification(X_train, y_train, X_test, normalize=False, C=1.0, tol=1e-4, max_iter=1000, verbose=0, return_model=False):
+    """Scale the features, fit ``linear_svm.LinearSVC(C)`` on (X_train, y_train) and rank the classes of every test row by
+    decision score, best first (evaluate_classification_accuracy.py:33-48).  Features: NumPy arrays or device tensors.
+    The ranking holds column indices of ``classes_`` (= class indices when every class occurs in y_train)."""
+    from linear_svm import LinearSVC
+    P_train, P_test = preprocess_features(X_train, X_test, normalize)
+    sys.stderr.write('Training SVM...\n')
+    svm = LinearSVC(C=C, tol=tol, max_iter=max_iter, verbose=verbose).fit(P_train, y_train)
+    sys.stderr.write('Predicting and evaluating...\n')
+    rank = _rank_descending(svm.decision_function(P_test, return_device=True))
+    return (rank, svm) if return_model else rank
+
+
+def _layer_output(model, layer):
+    """A module around ``model`` whose output is one layer's output (forward hook), or the model output.
+
+    ``layer``: None or -1 -> the model output (its first element when the model returns several); another integer i ->
+    ``list(model.children())[i]``, the i-th top-level layer (Keras' ``model.layers[i]``); a string -> the module of that name in
+    ``model.named_modules()``.  Outputs with more than 2 dimensions are flattened per sample."""
+    import torch
+
+    class LayerOutput(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.model, self.out, self.handle = model, None, None
+            target = None
+            if isinstance(layer, int) and layer != -1:
+                target = list(model.children())[layer]
+            elif isinstance(layer, str):
+                modules = dict(model.named_modules())
+                if layer not in modules:
+                    raise ValueError('model has no layer named %r' % layer)
+                target = modules[layer]
+            if target is not None:
+                self.handle = target.register_forward_hook(self._hook)
+
+        def _hook(self, mod, inp, out):
+            self.out = out
+
+        def forward(self, X):
+            out = self.model(X)
+            if self.handle is not None:
+                out = self.out
+            if isinstance(out, (tuple, list)):
+                out = out[0]
+            return out.flatten(1) if out.dim() > 2 else out
+
+        def close(self):
+            if self.handle is not None:
+                self.handle.remove()
+
+    return LayerOutput()
+
+
+def _load_model(model):
+    import torch
+    if isinstance(model, str):
+        model = torch.load(model, map_location=_device(), weights_only=False)
+    return model.to(_device())
+
+
+def extract_features(data, model, layer=None, which='test', batch_size=1, augmentation_epochs=1):
+    """Features of the test set (``which='test'``, batches of ``batch_size``, num_test // batch_size of them) or of
+    ``augmentation_epochs`` passes over the training set (batches of 10, augmented when augmentation_epochs > 1), as a float32
+    device tensor -- ``Trainer.predict(..., to_host=False)`` over the dataset's device sequences."""
+    import torch
+    from engine import Trainer
+    model = _load_model(model)
+    wrap = _layer_output(model, layer)
+    try:
+        trainer = Trainer(wrap, {}, {}, autocast_dtype=None)
+        if which == 'test':
+            return trainer.predict(data.test_sequence(batch_size, shuffle=False, augment=False), steps=data.num_test // batch_size,
+                                   to_host=False)
+        parts = [trainer.predict(data.train_sequence(10, shuffle=False, augment=augmentation_epochs > 1),
+                                 steps=data.num_train // 10, to_host=False) for _ in range(augmentation_epochs)]
+        return torch.cat(parts)
+    finally:
+        wrap.close()
+
+
+def train_and_predict(data, model, layer=None, normalize=False, augmentation_epochs=1, C=1.0, custom_objects={}, batch_size=1):
+    """Extract train / test features, fit a linear SVM and return the class ranking of every test image, best first
+    (evaluate_classification_accuracy.py:20-48).  ``model``: a module or the path of a ``--model_dump``; ``custom_objects`` is
+    accepted for the reference's signature and unused."""
+    sys.stderr.write('Extracting features...\n')
+    X_train = extract_features(data, model, layer, 'train', augmentation_epochs=augmentation_epochs)
+    X_test = extract_features(data, model, layer, 'test', batch_size)
+    n = (data.num_train // 10) * 10
+    y_train = np.tile(np.asarray(data.labels_train)[:n], augmentation_epochs)
+    return svm_classification(X_train, y_train, X_test, normalize, C)
+
+
+def extract_predictions(data, model, layer=None, custom_objects={}, batch_size=1):
+    """Class ranking by descending model output (``--prob_features``, evaluate_classification_accuracy.py:74-85)."""
+    sys.stderr.write('Predicting and evaluating...\n')
+    return _rank_descending(extract_features(data, model, layer, 'test', batch_size))
+
+
+def nn_classification_model(data, centroids, model, layer=None, custom_objects={}, batch_size=1):
+    """``--centroids`` mode: test features of ``model`` -> ``nn_classification`` (evaluate_classification_accuracy.py:51-71)."""
+    sys.stderr.write('Extracting features...\n')
+    feat = extract_features(data, model, layer, 'test', batch_size)
+    sys.stderr.write('Searching for nearest class centroids...\n')
+    return nn_classification(feat, centroids)
+
+
+def print_performance(perf, metrics=METRICS):
+    """The reference's result table (evaluate_classification_accuracy.py:111-126)."""
+    print()
+    max_name_len = max(len(lbl) for lbl in perf.keys())
+    print(' | '.join([' ' * max_name_len] + ['{:^6s}'.format(metric) for metric in metrics]))
+    print('-' * (max_name_len + sum(3 + max(6, len(metric)) for metric in metrics)))
+    for lbl, results in perf.items():
+        print('{:{}s} | {}'.format(lbl, max_name_len, ' | '.join(
+            '{:>{}.4f}'.format(results[metric], max(len(metric), 6)) if metric in results
+            else '{:>{}s}'.format('--', max(len(metric), 6)) for metric in metrics)))
+    print()
+
+
+def str2bool(v):
+    if v.lower() in ('yes', 'true', 't', 'y', '1'):
+        return True
+    elif v.lower() in ('no', 'false', 'f', 'n', '0'):
+        return False
+    raise argparse.ArgumentTypeError('Boolean value expected.')
+
+
+def build_parser():
+    import utils
+    parser = argparse.ArgumentParser(description='Evaluates flat, balanced, and hierarchical accuracy of several models.',
+                                     formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    g = parser.add_argument_group('Dataset')
+    g.add_argument('--dataset', type=str, required=True, help='Training dataset. See README.md for a list of available datasets.')
+    g.add_argument('--data_root', type=str, required=True, help='Root directory of the dataset.')
+    g.add_argument('--hierarchy', type=str, default=None, help='Path to a file containing parent-child relationships (one per line). Used for evaluating hierarchical accuracy.')
+    g.add_argument('--is_a', action='store_true', default=False, help='If given, --hierarchy is assumed to contain is-a instead of parent-child relationships.')
+    g.add_argument('--str_ids', action='store_true', default=False, help='If given, class IDs are treated as strings instead of integers.')
+    g.add_argument('--classes_from', type=str, default=None, help='Optionally, a path to a pickle dump containing a dictionary with item "ind2label" specifying the classes to be considered. These should be in the same order as the classes predicted by the model.')
+    g.add_argument('--augmentation_epochs', type=int, default=1, help='Number of training image augmentations when training an SVM on top of embeddings.')
+    g.add_argument('--C', type=float, default=0.1, help='Weight of the error in SVM loss.')
+    g.add_argument('--batch_size', type=int, default=1, help='Batch size for feature extraction. Must divide the number of test images evenly.')
+    g = parser.add_argument_group('Features')
+    g.add_argument('--architecture', type=str, default='simple', choices=utils.ARCHITECTURES, help='Type of network architecture.')
+    g.add_argument('--model', type=str, action='append', required=True, help='Path to a --model_dump of learn_image_embeddings.py (torch.save of the module) used for extracting image features.')
+    g.add_argument('--layer', type=str, action='append', required=True, help='Name (in named_modules()) or index (into the top-level children; -1: the model output) of the layer to extract features from.')
+    g.add_argument('--label', type=str, action='append', help='Label for the corresponding features.')
+    g.add_argument('--norm', type=str2bool, action='append', help='Whether to L2-normalize the corresponding features or not (defaults to False).')
+    g.add_argument('--prob_features', type=str2bool, action='append', help='Whether to use the extracted features as class probabilities instead of training an SVM.')
+    g.add_argument('--centroids', type=str, action='append', help='Optionally, a pickle dump containing a dictionary with an item "embedding" referring to a numpy array of class centroids for performing nearest-neighbor classification.')
+    return parser
+
+
+def _layer_arg(v):
+    try:
+        return int(v)
+    except ValueError:
+        return v
+
+
+def main(argv=None, modes=None):
+    """The reference's command line (evaluate_classification_accuracy.py:138-188); returns the table's OrderedDict.
+    ``modes`` (tests): a dict overriding 'svm' / 'centroids' / 'prob' with callables of the same signatures."""
+    from datasets import get_data_generator
+    from class_hierarchy import ClassHierarchy
+    args = build_parser().parse_args(argv)
+    if args.classes_from:
+        with open(args.classes_from, 'rb') as f:
+            embed_labels = pickle.load(f)['ind2label']
+    else:
+        embed_labels = None
+    data_generator = get_data_generator(args.dataset, args.data_root, classes=embed_labels)
+    id_type = str if args.str_ids else int
+    hierarchy = ClassHierarchy.from_file(args.hierarchy, is_a_relations=args.is_a, id_type=id_type) if args.hierarchy else None
+    run = {'svm': train_and_predict, 'centroids': nn_classification_model, 'prob': extract_predictions}
+    run.update(modes or {})
+    perf = OrderedDict()
+    for i, model in enumerate(args.model):
+        model_name = args.label[i] if (args.label is not None) and (i < len(args.label)) else os.path.splitext(os.path.basename(model))[0]
+        layer = _layer_arg(args.layer[i]) if (args.layer is not None) and (i < len(args.layer)) else None
+        normalize = args.norm[i] if (args.norm is not None) and (i < len(args.norm)) else False
+        prob_features = args.prob_features[i] if (args.prob_features is not None) and (i < len(args.prob_features)) else False
+        centroids = args.centroids[i] if (args.centroids is not None) and (i < len(args.centroids)) else ''
+        sys.stderr.write('-- {} --\n'.format(model_name))
+        if prob_features:
+            pred = run['prob'](data_generator, model, layer, {}, args.batch_size)
+        elif centroids:
+            pred = run['centroids'](data_generator, centroids, model, layer, {}, args.batch_size)
+        else:
+            pred = run['svm'](data_generator, model, layer, normalize, args.augmentation_epochs, args.C, {}, args.batch_size)
+        perf[model_name] = evaluate(pred, data_generator, hierarchy)
+    print_performance(perf)
+    return perf
+
+
+if __name__ == '__main__':
+    main()

@@ -16,6 +16,7 @@ TUNING_LIB_PATH = os.path.join(_HERE, "libsehip_tuning.so")   # -DSE_TUNING buil
 SE_OK = 0
 DTYPE_F32, DTYPE_BF16 = 0, 1
 METRIC_COSINE, METRIC_EUCLID, METRIC_DOT = 0, 1, 2
+SVM_GRAD, SVM_HV, SVM_SCORE = 0, 1, 2
 TOPK_MAX = 2048
 
 # every symbol include/sehip.h declares (checked by tests/test_abi.py)
@@ -30,6 +31,8 @@ EXPORTS = (
     "se_retrieve_topk_workspace_bytes", "se_retrieve_topk", "se_hierarchical_precision", "se_hierarchical_precision_r16",
     "se_hprec_order_workspace_bytes", "se_hprec_curve_len", "se_hprec_reciprocal_curves",
     "se_relevant_positions", "se_relevant_positions_r16", "se_recall_precision_reduce",
+    "se_svm_loss_blocks", "se_svm_margin", "se_svm_reduce_workspace_bytes", "se_svm_reduce", "se_svm_gram", "se_svm_rowsum",
+    "se_svm_axpby",
 )
 
 
@@ -107,6 +110,15 @@ def lib():
     L.se_relevant_positions.argtypes = [vp, c_i64, c_i64, c_i64, vp, c_i64, vp, vp, c_int, vp, vp, vp]
     L.se_relevant_positions_r16.argtypes = L.se_relevant_positions.argtypes
     L.se_recall_precision_reduce.argtypes = [vp, vp, c_i64, vp, vp, c_int, vp, c_i64, c_int, vp, vp, vp, vp, vp, vp]
+    L.se_svm_loss_blocks.argtypes = [c_i64]
+    L.se_svm_loss_blocks.restype = c_i64
+    L.se_svm_margin.argtypes = [c_int, vp, c_i64, c_i64, c_i64, vp, c_i64, c_i64, vp, vp, c_f, vp, c_i64, vp, c_i64, vp, c_i64, vp]
+    L.se_svm_reduce_workspace_bytes.argtypes = [c_i64, c_i64, c_i64]
+    L.se_svm_reduce_workspace_bytes.restype = c_i64
+    L.se_svm_reduce.argtypes = [vp, c_i64, vp, c_i64, c_i64, c_i64, c_i64, vp, c_i64, vp, c_i64, vp, c_i64, vp]
+    L.se_svm_gram.argtypes = [vp, vp, vp, vp, c_int, c_i64, c_i64, c_i64, vp, vp]
+    L.se_svm_rowsum.argtypes = [vp, c_i64, c_i64, c_i64, vp, vp]
+    L.se_svm_axpby.argtypes = [vp, vp, c_i64, vp, vp, c_i64, c_i64, c_i64, vp, c_i64, vp]
     L.se_rank_rows_workspace_bytes.argtypes = [c_i64, c_i64]
     L.se_rank_rows_workspace_bytes.restype = c_i64
     L.se_rank_rows.argtypes = [vp, c_i64, c_i64, c_i64, vp, c_int, c_i64, vp, c_i64, vp]

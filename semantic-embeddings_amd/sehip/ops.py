@@ -18,6 +18,7 @@ __all__ = [
     "devise_ranking_loss",
     "row_sqnorm", "normalize_rows_", "pairwise_dist", "rank_rows", "rank_rows_check", "topk_rows", "topk_merge", "retrieve_topk",
     "hierarchical_precision", "hprec_reciprocal_curves", "relevant_positions", "recall_precision_reduce",
+    "svm_margin", "svm_reduce", "svm_reduce_workspace_bytes", "svm_gram", "svm_rowsum", "svm_axpby",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
 ]
 
@@ -740,3 +741,113 @@ def recall_precision_reduce(hit_pos, hit_off, order, class_start, class_off, bin
                                            ptr(bin_sum if bins > 0 else None), ptr(bin_count if bins > 0 else None), stream_ptr()),
           "se_recall_precision_reduce")
     return ap
+
+
+# ---- linear SVM (svm.hip; the solver is linear_svm.py) ----
+
+def _f32_2d(t, name, min_cols):
+    if t is None or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[1] < min_cols:
+        raise SehipError("%s must be a 2-d float32 tensor with contiguous rows and >= %d columns" % (name, min_cols))
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def svm_margin(mode, x, w, d=None, labels=None, col_class=None, cpen=1.0, mask=None, out=None, loss_part=None):
+    """``se_svm_margin``: margins x w[:, :d]^T + w[:, d] with the fused epilogue of ``mode`` (SVM_GRAD / SVM_HV / SVM_SCORE).
+
+    x [N, >= d] float32, w [C, >= d + 1] float32 (bias in column d; d defaults to w.shape[1] - 1).  SVM_GRAD needs labels [N] /
+    col_class [C] int32, mask [N, >= ceil(C / 32)] int32 (written) and loss_part [C, >= se_svm_loss_blocks(N)] float32 (written);
+    SVM_HV reads mask.  Returns ``out`` [N, C] float32 (Z, Z' or the scores)."""
+    require_gpu(x, w, labels, col_class, mask, out, loss_part)
+    d = w.shape[1] - 1 if d is None else int(d)
+    ldx, ldw = _f32_2d(x, "x", d), _f32_2d(w, "w", d + 1)
+    N, C = x.shape[0], w.shape[0]
+    if out is None:
+        out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+    ldo = _f32_2d(out, "out", C)
+    ldm = 0
+    if mask is not None:
+        if mask.dtype != torch.int32 or mask.dim() != 2 or mask.stride(1) != 1:
+            raise SehipError("mask must be a 2-d int32 tensor with contiguous rows")
+        ldm = mask.stride(0) if mask.shape[0] > 1 else mask.shape[1]
+    for t, name in ((labels, "labels"), (col_class, "col_class")):
+        if t is not None:
+            _i32(t, name)
+    ldl = _f32_2d(loss_part, "loss_part", 1) if loss_part is not None else 0
+    check(lib().se_svm_margin(int(mode), ptr(x), ldx, N, d, ptr(w), ldw, C, ptr(labels), ptr(col_class), float(cpen), ptr(mask), ldm,
+                              ptr(out), ldo, ptr(loss_part), ldl, stream_ptr()), "se_svm_margin")
+    return out
+
+
+def svm_loss_blocks(n):
+    return int(lib().se_svm_loss_blocks(int(n)))
+
+
+def svm_reduce_workspace_bytes(n, d, c):
+    return int(lib().se_svm_reduce_workspace_bytes(int(n), int(d), int(c)))
+
+
+def svm_reduce(z, x, d=None, plus=None, out=None, workspace=None):
+    """``se_svm_reduce``: out [C, d + 1] = plus + z^T [x[:, :d] | 1] (fp32 partials over fixed row slices, fp64 combine).
+    z [N, >= C] float32 (C = out.shape[0], or z.shape[1] when out is None), x [N, >= d] float32."""
+    require_gpu(z, x, plus, out, workspace)
+    d = x.shape[1] if d is None else int(d)
+    N = x.shape[0]
+    C = out.shape[0] if out is not None else z.shape[1]
+    ldz, ldx = _f32_2d(z, "z", C), _f32_2d(x, "x", d)
+    if z.shape[0] != N:
+        raise SehipError("z and x need the same number of rows")
+    if out is None:
+        out = torch.empty((C, d + 1), dtype=torch.float32, device=x.device)
+    ldg = _f32_2d(out, "out", d + 1)
+    ldp = _f32_2d(plus, "plus", d + 1) if plus is not None else 0
+    need = svm_reduce_workspace_bytes(N, d, C)
+    ws = _workspace(need, x.device) if workspace is None else workspace
+    check(lib().se_svm_reduce(ptr(z), ldz, ptr(x), ldx, N, d, C, ptr(plus), ldp, ptr(out), ldg, ptr(ws), ws.numel(), stream_ptr()),
+          "se_svm_reduce")
+    return out
+
+
+def svm_gram(vecs, length=None, out=None):
+    """``se_svm_gram``: per-row fp64 dot products of 1..4 float32 [C, >= length] tensors with one leading dimension ->
+    float64 [C, nv (nv + 1) / 2] (pairs (a, b), a <= b, row-major)."""
+    vecs = list(vecs)
+    require_gpu(*vecs)
+    if not 1 <= len(vecs) <= 4:
+        raise SehipError("svm_gram takes 1 to 4 vectors")
+    length = vecs[0].shape[1] if length is None else int(length)
+    lds = {_f32_2d(v, "vector", length) for v in vecs}
+    if len(lds) != 1 or any(v.shape[0] != vecs[0].shape[0] for v in vecs):
+        raise SehipError("svm_gram: the vectors need one shape and one leading dimension")
+    C, nv = vecs[0].shape[0], len(vecs)
+    if out is None:
+        out = torch.empty((C, nv * (nv + 1) // 2), dtype=torch.float64, device=vecs[0].device)
+    p = [ptr(v) for v in vecs] + [ptr(None)] * (4 - nv)
+    check(lib().se_svm_gram(p[0], p[1], p[2], p[3], nv, lds.pop(), C, length, ptr(out), stream_ptr()), "se_svm_gram")
+    return out
+
+
+def svm_rowsum(a, length=None, out=None):
+    """``se_svm_rowsum``: fp64 sum of every row of a float32 [C, >= length] tensor."""
+    require_gpu(a, out)
+    length = a.shape[1] if length is None else int(length)
+    lda = _f32_2d(a, "a", length)
+    if out is None:
+        out = torch.empty((a.shape[0],), dtype=torch.float64, device=a.device)
+    check(lib().se_svm_rowsum(ptr(a), lda, a.shape[0], length, ptr(out), stream_ptr()), "se_svm_rowsum")
+    return out
+
+
+def svm_axpby(alpha, x, beta, y, out=None, length=None):
+    """``se_svm_axpby``: out = alpha[:, None] x + beta[:, None] y over the first ``length`` columns, in fp64, rounded to float32.
+    alpha / beta: float64 [C] device tensors; out may be x or y."""
+    require_gpu(alpha, x, beta, y, out)
+    length = x.shape[1] if length is None else int(length)
+    for t, name in ((alpha, "alpha"), (beta, "beta")):
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != x.shape[0]:
+            raise SehipError("%s must be a contiguous float64 tensor with one entry per row" % name)
+    if out is None:
+        out = torch.zeros_like(x)
+    ldx, ldy, ldo = _f32_2d(x, "x", length), _f32_2d(y, "y", length), _f32_2d(out, "out", length)
+    check(lib().se_svm_axpby(ptr(alpha), ptr(x), ldx, ptr(beta), ptr(y), ldy, x.shape[0], length, ptr(out), ldo, stream_ptr()),
+          "se_svm_axpby")
+    return out

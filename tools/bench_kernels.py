@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Kernel-level microbenchmarks (HIP-event timing on the launch stream) used while tuning.
     python tools/bench_kernels.py pdist|rank|loss|topk [--n 50000 --d 100 --reps 5]
-    python tools/bench_kernels.py recprec        (10k x 10k and 50k x 50k, 100 classes; --n is not used)"""
+    python tools/bench_kernels.py recprec        (10k x 10k and 50k x 50k, 100 classes; --n is not used)
+    python tools/bench_kernels.py svm            (margin + reduction kernels and whole LinearSVC fits: 50,000 x 100 x 100 and
+                                                  1,281,167 x 1000 x 1000; --n / --d are not used; --svm-sizes small skips the large one)"""
 import argparse
 import os
 import sys
@@ -28,13 +30,14 @@ def timeit(fn, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm"])
+    ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
     ap.add_argument("--d", type=int, default=100)
     ap.add_argument("--k", type=int, default=251)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--svm-sizes", default="all", choices=["all", "small"], help="svm: both sizes, or 50,000 x 100 x 100 only")
     args = ap.parse_args()
     n, d = args.n, args.d
     q = args.q or n
@@ -157,6 +160,48 @@ def main():
                           (bins, layout, nn, nn, med, mn, int(hit_off_h[-1])))
                 del rk, xf, out
                 torch.cuda.empty_cache()
+    elif args.what == "svm":
+        # Both kernels of svm.hip and whole fits (linear_svm.LinearSVC, C = 0.1, tol 1e-4) on clustered features: class centres
+        # plus noise, labels uniform.  MFMA peak: 157.3 TFLOP/s fp32 (MI355X_MICROARCH.md); a kernel's FLOPs are 2 N D C.
+        import time
+        import linear_svm as ls
+        peak = 157.3e12
+        sizes = [(50000, 100, 100)] + ([] if args.svm_sizes == "small" else [(1281167, 1000, 1000)])
+        for n, dd, c in sizes:
+            g = torch.Generator(device="cuda").manual_seed(0)
+            y = torch.randint(0, c, (n,), device="cuda", generator=g)
+            X = torch.randn((c, dd), device="cuda", generator=g)[y] / np.sqrt(dd)
+            X += 0.5 * torch.randn((n, dd), device="cuda", generator=g) / np.sqrt(dd)
+            y_h = y.cpu().numpy()
+            ops = ls._DeviceOps(X, y_h, 0.1, c)
+            ops.set_columns(np.arange(c))
+            W = ops.zeros(c)
+            W[:, :dd + 1] = 0.01 * torch.randn((c, dd + 1), device="cuda", generator=g)
+            flops = 2.0 * n * dd * c
+            nblk = sehip.ops.svm_loss_blocks(n)
+            for mode, name in ((sehip.SVM_GRAD, "margin/grad"), (sehip.SVM_HV, "margin/Hv"), (sehip.SVM_SCORE, "margin/score")):
+                run = lambda: sehip.svm_margin(mode, X, W, d=dd, labels=ops.labels, col_class=ops.cols, cpen=0.1, mask=ops.mask,
+                                               out=ops.Z, loss_part=ops.loss if mode == sehip.SVM_GRAD else None)
+                med, mn = timeit(run, args.reps)
+                print("svm %-13s %d x %d x %d: median %.3f ms (min %.3f)  %.1f TFLOP/s = %.2f of fp32 MFMA peak" %
+                      (name, n, dd, c, med, mn, flops / med / 1e9, flops / med / 1e9 / (peak / 1e12)))
+            ws = ops._workspace(c)
+            G = ops.zeros(c)
+            med, mn = timeit(lambda: sehip.svm_reduce(ops.Z, X, d=dd, plus=W, out=G, workspace=ws), args.reps)
+            f2 = 2.0 * n * (dd + 1) * c
+            print("svm %-13s %d x %d x %d: median %.3f ms (min %.3f)  %.1f TFLOP/s = %.2f of fp32 MFMA peak  (workspace %.0f MB)" %
+                  ("reduce", n, dd, c, med, mn, f2 / med / 1e9, f2 / med / 1e9 / (peak / 1e12), ws.numel() / 1e6))
+            del ops, G, ws, W
+            torch.cuda.empty_cache()
+            for rep in range(2):             # the first fit includes first-launch costs
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                svm = ls.LinearSVC(C=0.1).fit(X, y_h)
+                torch.cuda.synchronize()
+                t = time.perf_counter() - t0
+            print("svm fit           %d x %d x %d: %.3f s (second fit), %d outer iterations (max over classes)" % (n, dd, c, t, svm.n_iter_))
+            del X, svm
+            torch.cuda.empty_cache()
     elif args.what == "shard":
         # BASELINE.json configs[4], one rank's share: 50,000 queries x (1,281,167 / 8) gallery rows, D = 1000, top-251, then the
         # merge of the 8 all-gathered lists (synthetic: 8 copies with shifted indices)
