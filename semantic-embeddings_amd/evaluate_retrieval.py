@@ -106,21 +106,20 @@ def release_tile_cache(device=None):
     if device is None:
         _tile_cache.clear()
     else:
-        import torch
-        dev = torch.device(device)
-        _tile_cache.pop(dev.index if dev.index is not None else torch.cuda.current_device(), None)
+        from sehip.ops import _device_index
+        _tile_cache.pop(_device_index(device), None)
 
 
 def _cached_rows(kind, rows, n, dtype, device):
     """``[rows, n]`` view (row pitch a multiple of 16 bytes, like ``sehip.empty_rows``) of the device's grow-only cached buffer
     ``kind``: a second evaluation in the same process -- the CLI loops over its --feat files -- pays no 10 GB allocation."""
     import torch
+    from sehip.ops import _device_index
     esz = torch.empty((), dtype=dtype).element_size()
     per16 = 16 // esz
     pitch = (n + per16 - 1) // per16 * per16
     need = rows * pitch * esz
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    slot = _tile_cache.setdefault(key, {})
+    slot = _tile_cache.setdefault(_device_index(device), {})
     buf = slot.get(kind)
     if buf is None or buf.numel() < need:
         slot.pop(kind, None)
@@ -167,8 +166,7 @@ def ranking_tiles(features, normalize=False, tile_rows=None, idx64=False, querie
             # distances + ranks of all queries, plus what the ranking will ask of the (grow-only) workspace cache on top of what that
             # cache already holds -- up to ~3 GB for rows above 53,248 columns
             extra_ws = max(0, sehip.rank_rows_workspace_bytes(q1 - q0, n) - sehip.workspace_bytes(features.device))
-            key = features.device.index if features.device.index is not None else torch.cuda.current_device()
-            held = sum(int(b.numel()) for b in _tile_cache.get(key, {}).values())
+            held = sum(int(b.numel()) for b in _tile_cache.get(sehip.ops._device_index(features.device), {}).values())
             need = (4 + (2 if idx16 else (8 if idx64 else 4))) * n * (q1 - q0)
             if need + extra_ws <= (torch.cuda.mem_get_info(features.device)[0] + held) // 3:
                 tile_rows = max(tile_rows, q1 - q0)

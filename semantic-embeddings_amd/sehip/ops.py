@@ -1,7 +1,7 @@
 """Torch-facing wrappers of the HIP hot path (device tensors in, device tensors out).
 
-Every function here calls straight through the C ABI of libsehip.so on the current torch stream;
-PyTorch only provides device memory, streams and autograd plumbing.  Reference citations are into
+Every function here calls straight through the C ABI of libsehip.so on the current torch stream (``_lib.call``: the declarations
+come from include/sehip.h); PyTorch only provides device memory, streams and autograd plumbing.  Reference citations are into
 the cvjena/semantic-embeddings checkout.
 """
 import ctypes
@@ -9,32 +9,96 @@ import os
 
 import torch
 
-from . import _lib
-from ._lib import (DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, METRIC_EUCLID, SehipError, check, lib, ptr,
-                   require_gpu, stream_ptr)
+from ._lib import DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, METRIC_EUCLID, SehipError, call, require_gpu
 
 __all__ = [
-    "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "l2norm", "nn_accuracy", "labelembed_loss",
-    "devise_ranking_loss",
-    "row_sqnorm", "normalize_rows_", "pairwise_dist", "rank_rows", "rank_rows_check", "topk_rows", "topk_merge", "retrieve_topk",
-    "hierarchical_precision", "hprec_reciprocal_curves", "relevant_positions", "recall_precision_reduce",
-    "svm_margin", "svm_reduce", "svm_reduce_workspace_bytes", "svm_gram", "svm_rowsum", "svm_axpby",
+    "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
+    "sqdist_loss_backward", "l2norm", "nn_accuracy", "labelembed_loss", "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
+    "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
+    "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
+    "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
+    "recall_precision_reduce", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
+    "svm_axpby",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
 ]
 
 
+# --------------------------------------------------------------------------------------------
+# argument helpers
+# --------------------------------------------------------------------------------------------
+
+def _device_index(device=None):
+    """Ordinal of a CUDA ``device``; None or a device without an index is the current device."""
+    index = None if device is None else torch.device(device).index
+    return torch.cuda.current_device() if index is None else index
+
+
 def _dtype_code(t):
-    if t.dtype == torch.float32:
-        return DTYPE_F32
-    if t.dtype == torch.bfloat16:
-        return DTYPE_BF16
-    raise SehipError("features must be float32 or bfloat16, got %s" % t.dtype)
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        raise SehipError("features must be float32 or bfloat16, got %s" % t.dtype)
+    return DTYPE_F32 if t.dtype == torch.float32 else DTYPE_BF16
+
+
+_RANK_WIDTH_CODES = {torch.int32: 0, torch.int64: 1, torch.int16: 2}
+
+
+def _rank_width_code(t):
+    """Index width code of se_rank_rows / se_rank_rows_check for a rank tensor: int32 -> 0, int64 -> 1, int16 (the BIT PATTERN of
+    uint16 gallery indices: torch has no full uint16) -> 2."""
+    if t.dtype not in _RANK_WIDTH_CODES:
+        raise SehipError("ranks must be int32, int64 or int16 (uint16 bit patterns), not %s" % t.dtype)
+    return _RANK_WIDTH_CODES[t.dtype]
+
+
+def _kblocks_arg(kblocks):
+    if kblocks is None or len(kblocks) <= 1:
+        return None, 0
+    return (ctypes.c_int32 * len(kblocks))(*[int(v) for v in kblocks]), len(kblocks)
 
 
 def _rows(t, what):
     if t.dim() != 2 or t.stride(1) != 1:
         raise SehipError("%s must be a 2-d tensor with contiguous rows" % what)
     return t
+
+
+def _f32_rows(t, what):
+    if t.dtype != torch.float32:
+        raise SehipError("%s must be float32" % what)
+    return _rows(t, what)
+
+
+def _i32(t, name):
+    if t.dtype != torch.int32 or not t.is_contiguous():
+        raise SehipError("%s must be contiguous int32" % name)
+
+
+def _i64(t, name):
+    if t.dtype != torch.int64 or not t.is_contiguous():
+        raise SehipError("%s must be contiguous int64" % name)
+
+
+def _check_curves(*tables):
+    for t in tables:
+        if t.dtype != torch.float64 or t.dim() != 2 or t.stride(1) != 1:
+            raise SehipError("the similarity tables / best curves must be float64 matrices with contiguous rows")
+
+
+def _f32_2d(t, name, min_cols):
+    if t is None or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[1] < min_cols:
+        raise SehipError("%s must be a 2-d float32 tensor with contiguous rows and >= %d columns" % (name, min_cols))
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def _class_loss_shapes(x, labels, embedding):
+    """(B, D, C) of a loss of the rows of x [B, D] against embedding[labels]: embedding float32 [C, D], labels contiguous int64 [B]."""
+    _rows(x, "x"); _rows(embedding, "embedding")
+    B, D = x.shape
+    if embedding.shape[1] != D or embedding.dtype != torch.float32:
+        raise SehipError("embedding must be float32 [C, %d]" % D)
+    if labels.dtype != torch.int64 or labels.numel() != B or not labels.is_contiguous():
+        raise SehipError("labels must be a contiguous int64 [B] tensor")
+    return B, D, embedding.shape[0]
 
 
 # --------------------------------------------------------------------------------------------
@@ -47,38 +111,31 @@ def cosine_loss_forward(x, labels, embedding, want_xhat=True):
     reference: utils.l2norm (utils.py:125-127), transform_inputs (learn_image_embeddings.py:48-50),
     utils.inv_correlation (utils.py:44-46).  Returns (xhat | None, inv_norm, loss_i, loss_mean)."""
     require_gpu(x, labels, embedding)
-    _rows(x, "x"); _rows(embedding, "embedding")
-    B, D = x.shape
-    C = embedding.shape[0]
-    if embedding.shape[1] != D or embedding.dtype != torch.float32:
-        raise SehipError("embedding must be float32 [C, %d]" % D)
-    if labels.dtype != torch.int64 or labels.numel() != B or not labels.is_contiguous():
-        raise SehipError("labels must be a contiguous int64 [B] tensor")
+    B, D, C = _class_loss_shapes(x, labels, embedding)
     xhat = torch.empty((B, D), dtype=torch.float32, device=x.device) if want_xhat else None
     inv_norm = torch.empty((B,), dtype=torch.float32, device=x.device)
     loss_i = torch.empty((B,), dtype=torch.float32, device=x.device)
     loss_mean = torch.empty((1,), dtype=torch.float32, device=x.device)
-    check(lib().se_cosine_loss_fwd(ptr(x), _dtype_code(x), x.stride(0), ptr(labels), ptr(embedding),
-                                   embedding.stride(0), B, D, C, ptr(xhat), D, ptr(inv_norm), ptr(loss_i),
-                                   ptr(loss_mean), stream_ptr()), "se_cosine_loss_fwd")
+    call("se_cosine_loss_fwd", x, _dtype_code(x), x.stride(0), labels, embedding, embedding.stride(0), B, D, C, xhat, D, inv_norm,
+         loss_i, loss_mean)
     return xhat, inv_norm, loss_i, loss_mean
+
+
+def _class_loss_backward(entry, x, labels, embedding, grad_loss_i, grad_scale, out_dtype):
+    require_gpu(x, labels, embedding, grad_loss_i)
+    B, D, C = _class_loss_shapes(x, labels, embedding)
+    dx = torch.empty((B, D), dtype=out_dtype or x.dtype, device=x.device)
+    if grad_loss_i is not None:
+        grad_loss_i = grad_loss_i.to(torch.float32).contiguous()
+    call(entry, x, _dtype_code(x), x.stride(0), labels, embedding, embedding.stride(0), grad_loss_i, float(grad_scale), B, D, C, dx,
+         _dtype_code(dx), D)
+    return dx
 
 
 def cosine_loss_backward(x, labels, embedding, grad_loss_i=None, grad_scale=1.0, out_dtype=None):
     """Closed-form backward of cosine_loss_forward w.r.t. x (what TF autodiff derives from
     utils.py:44-46,125-127)."""
-    require_gpu(x, labels, embedding, grad_loss_i)
-    _rows(x, "x"); _rows(embedding, "embedding")
-    B, D = x.shape
-    C = embedding.shape[0]
-    out_dtype = out_dtype or x.dtype
-    dx = torch.empty((B, D), dtype=out_dtype, device=x.device)
-    if grad_loss_i is not None:
-        grad_loss_i = grad_loss_i.to(torch.float32).contiguous()
-    check(lib().se_cosine_loss_bwd(ptr(x), _dtype_code(x), x.stride(0), ptr(labels), ptr(embedding),
-                                   embedding.stride(0), ptr(grad_loss_i), ctypes.c_float(grad_scale), B, D, C,
-                                   ptr(dx), _dtype_code(dx), D, stream_ptr()), "se_cosine_loss_bwd")
-    return dx
+    return _class_loss_backward("se_cosine_loss_bwd", x, labels, embedding, grad_loss_i, grad_scale, out_dtype)
 
 
 def _check_loss_inputs(labels, embedding, what):
@@ -135,33 +192,18 @@ def sqdist_loss_forward(x, labels, embedding, want_dist=False):
     learn_image_embeddings.py:48-50) and, on request, dist_i = sqrt(loss_i) (utils.mean_distance, utils.py:39-41).
     Returns (loss_i, dist_i | None, loss_mean)."""
     require_gpu(x, labels, embedding)
-    _rows(x, "x"); _rows(embedding, "embedding")
-    B, D = x.shape
-    C = embedding.shape[0]
-    if embedding.shape[1] != D or embedding.dtype != torch.float32:
-        raise SehipError("embedding must be float32 [C, %d]" % D)
-    if labels.dtype != torch.int64 or labels.numel() != B or not labels.is_contiguous():
-        raise SehipError("labels must be a contiguous int64 [B] tensor")
+    B, D, C = _class_loss_shapes(x, labels, embedding)
     loss_i = torch.empty((B,), dtype=torch.float32, device=x.device)
     dist_i = torch.empty((B,), dtype=torch.float32, device=x.device) if want_dist else None
     loss_mean = torch.empty((1,), dtype=torch.float32, device=x.device)
-    check(lib().se_sqdist_loss_fwd(ptr(x), _dtype_code(x), x.stride(0), ptr(labels), ptr(embedding), embedding.stride(0), B, D, C,
-                                   ptr(loss_i), ptr(dist_i), ptr(loss_mean), stream_ptr()), "se_sqdist_loss_fwd")
+    call("se_sqdist_loss_fwd", x, _dtype_code(x), x.stride(0), labels, embedding, embedding.stride(0), B, D, C, loss_i, dist_i,
+         loss_mean)
     return loss_i, dist_i, loss_mean
 
 
 def sqdist_loss_backward(x, labels, embedding, grad_loss_i=None, grad_scale=1.0, out_dtype=None):
     """``se_sqdist_loss_bwd``: dx = 2 w (x - E[y])."""
-    require_gpu(x, labels, embedding, grad_loss_i)
-    _rows(x, "x"); _rows(embedding, "embedding")
-    B, D = x.shape
-    C = embedding.shape[0]
-    dx = torch.empty((B, D), dtype=out_dtype or x.dtype, device=x.device)
-    if grad_loss_i is not None:
-        grad_loss_i = grad_loss_i.to(torch.float32).contiguous()
-    check(lib().se_sqdist_loss_bwd(ptr(x), _dtype_code(x), x.stride(0), ptr(labels), ptr(embedding), embedding.stride(0), ptr(grad_loss_i),
-                                   ctypes.c_float(grad_scale), B, D, C, ptr(dx), _dtype_code(dx), D, stream_ptr()), "se_sqdist_loss_bwd")
-    return dx
+    return _class_loss_backward("se_sqdist_loss_bwd", x, labels, embedding, grad_loss_i, grad_scale, out_dtype)
 
 
 class _SquaredDistanceLoss(torch.autograd.Function):
@@ -200,8 +242,7 @@ class _L2Norm(torch.autograd.Function):
         B, D = x2.shape
         xhat = torch.empty((B, D), dtype=torch.float32, device=x.device)
         inv = torch.empty((B,), dtype=torch.float32, device=x.device)
-        check(lib().se_l2norm_fwd(ptr(x2), _dtype_code(x2), x2.stride(0), B, D, ptr(xhat), D, ptr(inv), stream_ptr()),
-              "se_l2norm_fwd")
+        call("se_l2norm_fwd", x2, _dtype_code(x2), x2.stride(0), B, D, xhat, D, inv)
         ctx.save_for_backward(xhat, inv)
         ctx.in_dtype = x.dtype
         return xhat.reshape(shape)
@@ -212,7 +253,7 @@ class _L2Norm(torch.autograd.Function):
         B, D = xhat.shape
         g = grad.reshape(B, D).to(torch.float32).contiguous()
         dx = torch.empty_like(xhat)
-        check(lib().se_l2norm_bwd(ptr(g), D, ptr(xhat), D, ptr(inv), B, D, ptr(dx), D, stream_ptr()), "se_l2norm_bwd")
+        call("se_l2norm_bwd", g, D, xhat, D, inv, B, D, dx, D)
         return dx.reshape(grad.shape).to(ctx.in_dtype)
 
 
@@ -233,11 +274,10 @@ def nn_accuracy(y_pred, labels, embedding, dot_prod_sim=False, k=1, want_scores=
     acc = torch.empty((B,), dtype=torch.float32, device=y_pred.device)
     scores = torch.empty((B, C), dtype=torch.float32, device=y_pred.device) if want_scores else None
     best = torch.empty((B,), dtype=torch.int32, device=y_pred.device) if want_best else None
-    need = int(lib().se_nn_accuracy_workspace_bytes(B, C))
+    need = call("se_nn_accuracy_workspace_bytes", B, C)
     ws = torch.empty((need // 8,), dtype=torch.int64, device=y_pred.device) if need else None     # (fresh: the call may be captured in a HIP graph)
-    check(lib().se_nn_accuracy(ptr(y_pred), y_pred.stride(0), ptr(labels), ptr(embedding), embedding.stride(0),
-                               B, D, C, int(bool(dot_prod_sim)), int(k), ptr(acc), ptr(scores), C, ptr(best),
-                               ptr(ws), need, stream_ptr()), "se_nn_accuracy")
+    call("se_nn_accuracy", y_pred, y_pred.stride(0), labels, embedding, embedding.stride(0), B, D, C, int(bool(dot_prod_sim)), int(k),
+         acc, scores, C, best, ws, need)
     out = (acc,)
     if want_scores:
         out += (scores,)
@@ -260,10 +300,9 @@ class _LabelEmbedLoss(torch.autograd.Function):
         if targets.dtype != torch.int64 or targets.numel() != B or not targets.is_contiguous():
             raise SehipError("targets must be a contiguous int64 [B] tensor")
         loss_i = torch.empty((B,), dtype=torch.float32, device=out1.device)
-        aux = torch.empty((max(int(lib().se_labelembed_aux_floats(B)), 1),), dtype=torch.float32, device=out1.device)
-        check(lib().se_labelembed_loss_fwd(ptr(out1), out1.stride(0), ptr(out2), out2.stride(0), ptr(tar), tar.stride(0),
-                                           ptr(targets), B, C, float(tau), float(alpha), float(beta), ptr(loss_i), ptr(aux),
-                                           stream_ptr()), "se_labelembed_loss_fwd")
+        aux = torch.empty((max(call("se_labelembed_aux_floats", B), 1),), dtype=torch.float32, device=out1.device)
+        call("se_labelembed_loss_fwd", out1, out1.stride(0), out2, out2.stride(0), tar, tar.stride(0), targets, B, C, float(tau),
+             float(alpha), float(beta), loss_i, aux)
         ctx.save_for_backward(out1, out2, tar, targets, aux)
         ctx.hyper = (float(tau), float(alpha), float(beta))
         return loss_i
@@ -278,9 +317,8 @@ class _LabelEmbedLoss(torch.autograd.Function):
         d1 = torch.empty_like(out1, memory_format=torch.contiguous_format) if need[0] else None
         d2 = torch.empty_like(out2, memory_format=torch.contiguous_format) if need[1] else None
         dt = torch.empty_like(tar, memory_format=torch.contiguous_format) if need[2] else None
-        check(lib().se_labelembed_loss_bwd(ptr(out1), out1.stride(0), ptr(out2), out2.stride(0), ptr(tar), tar.stride(0),
-                                           ptr(targets), ptr(grad), 0.0, B, C, tau, alpha, beta, ptr(aux),
-                                           ptr(d1), C, ptr(d2), C, ptr(dt), C, stream_ptr()), "se_labelembed_loss_bwd")
+        call("se_labelembed_loss_bwd", out1, out1.stride(0), out2, out2.stride(0), tar, tar.stride(0), targets, grad, 0.0, B, C,
+             tau, alpha, beta, aux, d1, C, d2, C, dt, C)
         return d1, d2, dt, None, None, None, None
 
 
@@ -289,8 +327,6 @@ def labelembed_loss(out1, out2, tar, targets, tau=2.0, alpha=0.9, beta=0.5):
     return _LabelEmbedLoss.apply(out1, out2, tar, targets, tau, alpha, beta)
 
 
-# --------------------------------------------------------------------------------------------
-# retrieval side
 class _DeviseLoss(torch.autograd.Function):
     """reference: utils.devise_ranking_loss (utils.py:103-122) and its TF-autodiff backward w.r.t. y_pred."""
 
@@ -312,9 +348,8 @@ class _DeviseLoss(torch.autograd.Function):
             labels, yt = None, _rows(target.to(torch.float32).contiguous(), "y_true")
             ldt = yt.stride(0)
         loss_i = torch.empty((B,), dtype=torch.float32, device=yp.device)
-        aux = torch.empty((max(int(lib().se_devise_aux_floats(B, C)), 1),), dtype=torch.float32, device=yp.device)
-        check(lib().se_devise_loss_fwd(ptr(yp), yp.stride(0), ptr(labels), ptr(yt), ldt, ptr(embedding), embedding.stride(0), B, D, C,
-                                       ctypes.c_float(margin), ptr(loss_i), ptr(aux), stream_ptr()), "se_devise_loss_fwd")
+        aux = torch.empty((max(call("se_devise_aux_floats", B, C), 1),), dtype=torch.float32, device=yp.device)
+        call("se_devise_loss_fwd", yp, yp.stride(0), labels, yt, ldt, embedding, embedding.stride(0), B, D, C, margin, loss_i, aux)
         ctx.save_for_backward(aux, embedding, labels if labels is not None else yt)
         ctx.by_label, ctx.shape, ctx.in_dtype = labels is not None, (B, D, C), y_pred.dtype
         return loss_i
@@ -326,8 +361,8 @@ class _DeviseLoss(torch.autograd.Function):
         g = grad_loss_i.to(torch.float32).contiguous()
         dp = torch.empty((B, D), dtype=torch.float32, device=g.device)
         labels, yt = (tgt, None) if ctx.by_label else (None, tgt)
-        check(lib().se_devise_loss_bwd(ptr(labels), ptr(yt), 0 if yt is None else yt.stride(0), ptr(embedding), embedding.stride(0),
-                                       ptr(g), ctypes.c_float(1.0), B, D, C, ptr(aux), ptr(dp), D, stream_ptr()), "se_devise_loss_bwd")
+        call("se_devise_loss_bwd", labels, yt, 0 if yt is None else yt.stride(0), embedding, embedding.stride(0), g, 1.0, B, D, C,
+             aux, dp, D)
         return dp.to(ctx.in_dtype), None, None, None
 
 
@@ -354,19 +389,15 @@ def devise_ranking_loss(y_pred, target, embedding, margin=0.1):
 
 
 # --------------------------------------------------------------------------------------------
-
-def _f32_rows(t, what):
-    if t.dtype != torch.float32:
-        raise SehipError("%s must be float32" % what)
-    return _rows(t, what)
-
+# retrieval side
+# --------------------------------------------------------------------------------------------
 
 def row_sqnorm(x):
     """float32 ``np.sum(x ** 2, axis=-1)``, bit-exact (evaluate_retrieval.py:61)."""
     require_gpu(x)
     _f32_rows(x, "x")
     sq = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
-    check(lib().se_row_sqnorm(ptr(x), x.stride(0), x.shape[0], x.shape[1], ptr(sq), stream_ptr()), "se_row_sqnorm")
+    call("se_row_sqnorm", x, x.stride(0), x.shape[0], x.shape[1], sq)
     return sq
 
 
@@ -374,7 +405,7 @@ def normalize_rows_(x):
     """In-place ``x /= np.linalg.norm(x, axis=-1, keepdims=True)``, bit-exact (evaluate_retrieval.py:58)."""
     require_gpu(x)
     _f32_rows(x, "x")
-    check(lib().se_normalize_rows(ptr(x), x.stride(0), x.shape[0], x.shape[1], stream_ptr()), "se_normalize_rows")
+    call("se_normalize_rows", x, x.stride(0), x.shape[0], x.shape[1])
     return x
 
 
@@ -390,8 +421,8 @@ def empty_rows(q, n, dtype, device):
 
 def pairwise_dist(a, b=None, metric=METRIC_COSINE, sqa=None, sqb=None, kblocks=None, out=None):
     """All-pairs distances [q, n] (evaluate_retrieval.py:59 / :61-62) with the canonical FMA chain."""
-    b = a if b is None else b
     require_gpu(a, b, sqa, sqb, out)
+    b = a if b is None else b
     _f32_rows(a, "a"); _f32_rows(b, "b")
     q, d = a.shape
     n = b.shape[0]
@@ -405,8 +436,7 @@ def pairwise_dist(a, b=None, metric=METRIC_COSINE, sqa=None, sqb=None, kblocks=N
     if out is None:
         out = empty_rows(q, n, torch.float32, a.device)
     kb, nkb = _kblocks_arg(kblocks)
-    check(lib().se_pairwise_dist(ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(sqa), ptr(sqb), q, n, d, int(metric),
-                                 kb, nkb, ptr(out), out.stride(0), stream_ptr()), "se_pairwise_dist")
+    call("se_pairwise_dist", a, a.stride(0), b, b.stride(0), sqa, sqb, q, n, d, int(metric), kb, nkb, out, out.stride(0))
     return out
 
 
@@ -415,7 +445,7 @@ _ws_cache = {}
 
 def _workspace(nbytes, device):
     """Grow-only per-device scratch buffer (the C ABI never allocates)."""
-    key = (device.index if device.index is not None else torch.cuda.current_device())
+    key = _device_index(device)
     ws = _ws_cache.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = None
@@ -433,18 +463,16 @@ def rank_rows_init(device=None):
     variant; the one synchronising call of the ranking.  ``rank_rows`` calls it by itself before its first ranking on a device, so
     that every later ``se_rank_rows`` is purely asynchronous (graph-capturable)."""
     require_gpu()
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = _device_index(device)
     with torch.cuda.device(key):
-        ws = torch.empty((int(lib().se_rank_rows_init_workspace_bytes()),), dtype=torch.uint8, device=dev)
-        check(lib().se_rank_rows_init(ptr(ws), ws.numel(), stream_ptr()), "se_rank_rows_init")
+        ws = torch.empty((call("se_rank_rows_init_workspace_bytes"),), dtype=torch.uint8, device=torch.device("cuda", key))
+        call("se_rank_rows_init", ws, ws.numel())
     _rank_ready.add(key)
 
 
 def workspace_bytes(device=None):
     """Bytes the per-device workspace cache currently holds."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    ws = _ws_cache.get(dev.index if dev.index is not None else torch.cuda.current_device())
+    ws = _ws_cache.get(_device_index(device))
     return 0 if ws is None else int(ws.numel())
 
 
@@ -454,13 +482,12 @@ def release_workspace(device=None):
     if device is None:
         _ws_cache.clear()
     else:
-        dev = torch.device(device)
-        _ws_cache.pop(dev.index if dev.index is not None else torch.cuda.current_device(), None)
+        _ws_cache.pop(_device_index(device), None)
 
 
 def phase_timing(on=True):
     """``se_phase_timing``: switch the library's phase events on / off (a measuring aid: bench.py's per-leg rooflines)."""
-    check(lib().se_phase_timing(1 if on else 0), "se_phase_timing")
+    call("se_phase_timing", 1 if on else 0)
 
 
 def phase_timing_read():
@@ -470,9 +497,7 @@ def phase_timing_read():
     names = (ctypes.c_char_p * cap)()
     ms = (ctypes.c_float * cap)()
     cnt = (ctypes.c_int64 * 5)()
-    n = lib().se_phase_timing_read(names, ms, cap, cnt)
-    if n < 0:
-        check(n, "se_phase_timing_read")
+    n = call("se_phase_timing_read", names, ms, cap, cnt)
     out = {}
     for i in range(n):
         out[names[i].decode()] = out.get(names[i].decode(), 0.0) + float(ms[i])
@@ -481,22 +506,10 @@ def phase_timing_read():
 
 
 def rank_rows_workspace_bytes(q, n):
-    return int(lib().se_rank_rows_workspace_bytes(int(q), int(n)))
+    return call("se_rank_rows_workspace_bytes", int(q), int(n))
 
 
 RANK_U16_MAX_N = 53248     # rows the register-resident ranking kernel takes: the only ones it writes 16-bit ranks for
-
-
-def _rank_width_code(t):
-    """Index width code of se_rank_rows / se_rank_rows_check for a rank tensor: int32 -> 0, int64 -> 1, int16 (the BIT PATTERN of
-    uint16 gallery indices: torch has no full uint16) -> 2."""
-    if t.dtype == torch.int32:
-        return 0
-    if t.dtype == torch.int64:
-        return 1
-    if t.dtype == torch.int16:
-        return 2
-    raise SehipError("ranks must be int32, int64 or int16 (uint16 bit patterns), not %s" % t.dtype)
 
 
 def rank_rows(pdist, idx64=False, out=None, idx16=False):
@@ -505,15 +518,13 @@ def rank_rows(pdist, idx64=False, out=None, idx16=False):
     bytes for ``hierarchical_precision`` to read."""
     require_gpu(pdist, out)
     _f32_rows(pdist, "pdist")
-    if (pdist.device.index if pdist.device.index is not None else torch.cuda.current_device()) not in _rank_ready:
+    if _device_index(pdist.device) not in _rank_ready:
         rank_rows_init(pdist.device)
     q, n = pdist.shape
     if out is None:
         out = empty_rows(q, n, torch.int16 if idx16 else (torch.int64 if idx64 else torch.int32), pdist.device)
-    need = lib().se_rank_rows_workspace_bytes(q, n)
-    ws = _workspace(need, pdist.device)
-    check(lib().se_rank_rows(ptr(pdist), pdist.stride(0), q, n, ptr(out), _rank_width_code(out),
-                             out.stride(0), ptr(ws), ws.numel(), stream_ptr()), "se_rank_rows")
+    ws = _workspace(call("se_rank_rows_workspace_bytes", q, n), pdist.device)
+    call("se_rank_rows", pdist, pdist.stride(0), q, n, out, _rank_width_code(out), out.stride(0), ws, ws.numel())
     return out
 
 
@@ -525,10 +536,10 @@ def rank_rows_check(pdist, rank):
     if rank.dtype not in (torch.int32, torch.int64, torch.int16) or rank.stride(1) != 1 or rank.shape != pdist.shape:
         raise SehipError("rank must be an int32 / int64 / int16 (uint16 bit patterns) matrix of pdist's shape with contiguous rows")
     q, n = pdist.shape
-    ws = torch.empty((int(lib().se_rank_rows_check_workspace_bytes()),), dtype=torch.uint8, device=pdist.device)
+    ws = torch.empty((call("se_rank_rows_check_workspace_bytes"),), dtype=torch.uint8, device=pdist.device)
     bad = ctypes.c_int64(0)
-    check(lib().se_rank_rows_check(ptr(pdist), pdist.stride(0), q, n, ptr(rank), _rank_width_code(rank), rank.stride(0),
-                                   ptr(ws), ws.numel(), ctypes.byref(bad), stream_ptr()), "se_rank_rows_check")
+    call("se_rank_rows_check", pdist, pdist.stride(0), q, n, rank, _rank_width_code(rank), rank.stride(0), ws, ws.numel(),
+         ctypes.byref(bad))
     return int(bad.value)
 
 
@@ -539,8 +550,7 @@ def topk_rows(pdist, k, col_offset=0):
     q, n = pdist.shape
     od = torch.empty((q, k), dtype=torch.float32, device=pdist.device)
     oi = torch.empty((q, k), dtype=torch.int32, device=pdist.device)
-    check(lib().se_topk_rows(ptr(pdist), pdist.stride(0), q, n, int(col_offset), int(k), ptr(od), ptr(oi),
-                             stream_ptr()), "se_topk_rows")
+    call("se_topk_rows", pdist, pdist.stride(0), q, n, int(col_offset), int(k), od, oi)
     return od, oi
 
 
@@ -549,27 +559,17 @@ def topk_merge(d, idx=None):
     int32 buffer [parts, 2, q, k] -- per part the float32 distance bits followed by the indices, the receive buffer of ONE
     all-gather (``se_topk_merge_packed``)."""
     require_gpu(d, idx)
-    if idx is None:
-        if d.dim() != 4 or d.shape[1] != 2 or d.dtype != torch.int32:
-            raise SehipError("packed lists must be an int32 tensor [parts, 2, q, k]")
-        d = d.contiguous()
-        parts, _, q, k = d.shape
-        od = torch.empty((q, k), dtype=torch.float32, device=d.device)
-        oi = torch.empty((q, k), dtype=torch.int32, device=d.device)
-        check(lib().se_topk_merge_packed(ptr(d), parts, q, k, ptr(od), ptr(oi), stream_ptr()), "se_topk_merge_packed")
-        return od, oi
-    d = d.contiguous(); idx = idx.contiguous()
-    parts, q, k = d.shape
+    if idx is None and (d.dim() != 4 or d.shape[1] != 2 or d.dtype != torch.int32):
+        raise SehipError("packed lists must be an int32 tensor [parts, 2, q, k]")
+    d = d.contiguous()
+    parts, q, k = (d.shape[0], d.shape[2], d.shape[3]) if idx is None else d.shape
     od = torch.empty((q, k), dtype=torch.float32, device=d.device)
     oi = torch.empty((q, k), dtype=torch.int32, device=d.device)
-    check(lib().se_topk_merge(ptr(d), ptr(idx), parts, q, k, ptr(od), ptr(oi), stream_ptr()), "se_topk_merge")
+    if idx is None:
+        call("se_topk_merge_packed", d, parts, q, k, od, oi)
+    else:
+        call("se_topk_merge", d, idx.contiguous(), parts, q, k, od, oi)
     return od, oi
-
-
-def _kblocks_arg(kblocks):
-    if kblocks is None or len(kblocks) <= 1:
-        return None, 0
-    return (ctypes.c_int32 * len(kblocks))(*[int(v) for v in kblocks]), len(kblocks)
 
 
 def retrieve_topk(queries, gallery, k, metric=METRIC_COSINE, col_offset=0, sqq=None, sqg=None, kblocks=None, out=None):
@@ -594,19 +594,11 @@ def retrieve_topk(queries, gallery, k, metric=METRIC_COSINE, col_offset=0, sqq=N
         if od.dtype != torch.float32 or oi.dtype != torch.int32 or tuple(od.shape) != (q, k) or tuple(oi.shape) != (q, k) \
                 or not od.is_contiguous() or not oi.is_contiguous():
             raise SehipError("out must be contiguous (float32 [q, k], int32 [q, k]) tensors")
-    need = lib().se_retrieve_topk_workspace_bytes(q, n, d, gallery.stride(0), int(k))
-    ws = _workspace(need, queries.device)
+    ws = _workspace(call("se_retrieve_topk_workspace_bytes", q, n, d, gallery.stride(0), int(k)), queries.device)
     kb, nkb = _kblocks_arg(kblocks)
-    check(lib().se_retrieve_topk(ptr(queries), queries.stride(0), ptr(gallery), gallery.stride(0), ptr(sqq), ptr(sqg),
-                                 q, n, d, int(metric), kb, nkb, int(col_offset), int(k), ptr(od), ptr(oi), ptr(ws), ws.numel(),
-                                 stream_ptr()), "se_retrieve_topk")
+    call("se_retrieve_topk", queries, queries.stride(0), gallery, gallery.stride(0), sqq, sqg, q, n, d, int(metric), kb, nkb,
+         int(col_offset), int(k), od, oi, ws, ws.numel())
     return od, oi
-
-
-def _check_curves(*tables):
-    for t in tables:
-        if t.dtype != torch.float64 or t.dim() != 2 or t.stride(1) != 1:
-            raise SehipError("the similarity tables / best curves must be float64 matrices with contiguous rows")
 
 
 class HprecCurves:
@@ -626,9 +618,8 @@ def hprec_reciprocal_curves(best_wup, best_lcs, list_len=None):
         raise SehipError("best_wup and best_lcs must have the same shape and row stride")
     L = best_wup.shape[1] if list_len is None else int(list_len)
     C = best_wup.shape[0]
-    out = torch.empty((C, 2, int(lib().se_hprec_curve_len(L)), 2), dtype=torch.float64, device=best_wup.device)
-    check(lib().se_hprec_reciprocal_curves(ptr(best_wup), ptr(best_lcs), best_wup.stride(0), C, L, ptr(out), stream_ptr()),
-          "se_hprec_reciprocal_curves")
+    out = torch.empty((C, 2, call("se_hprec_curve_len", L), 2), dtype=torch.float64, device=best_wup.device)
+    call("se_hprec_reciprocal_curves", best_wup, best_lcs, best_wup.stride(0), C, L, out)
     return HprecCurves(out, L)
 
 
@@ -645,8 +636,7 @@ def hierarchical_precision(rank, cls, qcls, qidx, wup, lcs, best_wup, best_lcs, 
     if rank.dtype not in (torch.int32, torch.int16) or rank.stride(1) != 1:
         raise SehipError("rank must be int32 (or int16: the uint16 bit patterns rank_rows(idx16=True) writes) with contiguous rows")
     for t, name in ((cls, "cls"), (qcls, "qcls"), (ks, "ks")):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise SehipError("%s must be contiguous int32" % name)
+        _i32(t, name)
     _check_curves(wup, lcs, best_wup, best_lcs)
     Q = rank.shape[0]
     L = rank.shape[1] if list_len is None else int(list_len)
@@ -659,23 +649,11 @@ def hierarchical_precision(rank, cls, qcls, qidx, wup, lcs, best_wup, best_lcs, 
     out = torch.zeros((Q, 2 * nk + 3), dtype=torch.float64, device=rank.device)
     if class_order is None:
         class_order = L >= 4096
-    order_ws = torch.empty((int(lib().se_hprec_order_workspace_bytes(Q)),), dtype=torch.uint8, device=rank.device) if class_order else None
-    entry = lib().se_hierarchical_precision_r16 if rank.dtype == torch.int16 else lib().se_hierarchical_precision
-    check(entry(ptr(rank), rank.stride(0), Q, L, ptr(cls), cls.numel(), ptr(qcls), ptr(qidx), ptr(wup), ptr(lcs), C,
-                ptr(curves.data), curves.list_len, ptr(ks), nk,
-                int(ahp_len), int(bool(want_ap)), ptr(out), out.stride(0), ptr(order_ws), stream_ptr()),
-          "se_hierarchical_precision")
+    order_ws = torch.empty((call("se_hprec_order_workspace_bytes", Q),), dtype=torch.uint8, device=rank.device) if class_order else None
+    call("se_hierarchical_precision_r16" if rank.dtype == torch.int16 else "se_hierarchical_precision",
+         rank, rank.stride(0), Q, L, cls, cls.numel(), qcls, qidx, wup, lcs, C, curves.data, curves.list_len, ks, nk,
+         int(ahp_len), int(bool(want_ap)), out, out.stride(0), order_ws)
     return out
-
-
-def _i32(t, name):
-    if t.dtype != torch.int32 or not t.is_contiguous():
-        raise SehipError("%s must be contiguous int32" % name)
-
-
-def _i64(t, name):
-    if t.dtype != torch.int64 or not t.is_contiguous():
-        raise SehipError("%s must be contiguous int64" % name)
 
 
 def relevant_positions(rank, cls, qcls, qidx, hit_off, list_len=None, out=None, num_classes=None, total=None):
@@ -707,9 +685,8 @@ def relevant_positions(rank, cls, qcls, qidx, hit_off, list_len=None, out=None, 
         C = int(num_classes)
     else:
         C = int(max(int(cls.max().item()), int(qcls.max().item()) if Q > 0 else 0)) + 1 if cls.numel() > 0 else 1
-    entry = lib().se_relevant_positions_r16 if rank.dtype == torch.int16 else lib().se_relevant_positions
-    check(entry(ptr(rank), rank.stride(0), Q, L, ptr(cls), cls.numel(), ptr(qcls), ptr(qidx), C, ptr(hit_off), ptr(out),
-                stream_ptr()), "se_relevant_positions")
+    call("se_relevant_positions_r16" if rank.dtype == torch.int16 else "se_relevant_positions",
+         rank, rank.stride(0), Q, L, cls, cls.numel(), qcls, qidx, C, hit_off, out)
     return out[:total]
 
 
@@ -736,20 +713,14 @@ def recall_precision_reduce(hit_pos, hit_off, order, class_start, class_off, bin
         _i64(bin_count, "bin_count")
         if bin_sum.numel() != C * (bins + 1) or bin_count.numel() != C * (bins + 1):
             raise SehipError("bin_sum / bin_count must hold [C, bins + 1] entries")
-    check(lib().se_recall_precision_reduce(ptr(hit_pos), ptr(hit_off), Q, ptr(order), ptr(class_start), C, ptr(class_off),
-                                           class_len, bins, ptr(ap), ptr(prec_sum), ptr(first_miss),
-                                           ptr(bin_sum if bins > 0 else None), ptr(bin_count if bins > 0 else None), stream_ptr()),
-          "se_recall_precision_reduce")
+    call("se_recall_precision_reduce", hit_pos, hit_off, Q, order, class_start, C, class_off, class_len, bins, ap, prec_sum,
+         first_miss, bin_sum if bins > 0 else None, bin_count if bins > 0 else None)
     return ap
 
 
-# ---- linear SVM (svm.hip; the solver is linear_svm.py) ----
-
-def _f32_2d(t, name, min_cols):
-    if t is None or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[1] < min_cols:
-        raise SehipError("%s must be a 2-d float32 tensor with contiguous rows and >= %d columns" % (name, min_cols))
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
-
+# --------------------------------------------------------------------------------------------
+# classification side: linear SVM (svm.hip; the solver is linear_svm.py)
+# --------------------------------------------------------------------------------------------
 
 def svm_margin(mode, x, w, d=None, labels=None, col_class=None, cpen=1.0, mask=None, out=None, loss_part=None):
     """``se_svm_margin``: margins x w[:, :d]^T + w[:, d] with the fused epilogue of ``mode`` (SVM_GRAD / SVM_HV / SVM_SCORE).
@@ -773,17 +744,16 @@ def svm_margin(mode, x, w, d=None, labels=None, col_class=None, cpen=1.0, mask=N
         if t is not None:
             _i32(t, name)
     ldl = _f32_2d(loss_part, "loss_part", 1) if loss_part is not None else 0
-    check(lib().se_svm_margin(int(mode), ptr(x), ldx, N, d, ptr(w), ldw, C, ptr(labels), ptr(col_class), float(cpen), ptr(mask), ldm,
-                              ptr(out), ldo, ptr(loss_part), ldl, stream_ptr()), "se_svm_margin")
+    call("se_svm_margin", int(mode), x, ldx, N, d, w, ldw, C, labels, col_class, float(cpen), mask, ldm, out, ldo, loss_part, ldl)
     return out
 
 
 def svm_loss_blocks(n):
-    return int(lib().se_svm_loss_blocks(int(n)))
+    return call("se_svm_loss_blocks", int(n))
 
 
 def svm_reduce_workspace_bytes(n, d, c):
-    return int(lib().se_svm_reduce_workspace_bytes(int(n), int(d), int(c)))
+    return call("se_svm_reduce_workspace_bytes", int(n), int(d), int(c))
 
 
 def svm_reduce(z, x, d=None, plus=None, out=None, workspace=None):
@@ -802,8 +772,7 @@ def svm_reduce(z, x, d=None, plus=None, out=None, workspace=None):
     ldp = _f32_2d(plus, "plus", d + 1) if plus is not None else 0
     need = svm_reduce_workspace_bytes(N, d, C)
     ws = _workspace(need, x.device) if workspace is None else workspace
-    check(lib().se_svm_reduce(ptr(z), ldz, ptr(x), ldx, N, d, C, ptr(plus), ldp, ptr(out), ldg, ptr(ws), ws.numel(), stream_ptr()),
-          "se_svm_reduce")
+    call("se_svm_reduce", z, ldz, x, ldx, N, d, C, plus, ldp, out, ldg, ws, ws.numel())
     return out
 
 
@@ -821,8 +790,7 @@ def svm_gram(vecs, length=None, out=None):
     C, nv = vecs[0].shape[0], len(vecs)
     if out is None:
         out = torch.empty((C, nv * (nv + 1) // 2), dtype=torch.float64, device=vecs[0].device)
-    p = [ptr(v) for v in vecs] + [ptr(None)] * (4 - nv)
-    check(lib().se_svm_gram(p[0], p[1], p[2], p[3], nv, lds.pop(), C, length, ptr(out), stream_ptr()), "se_svm_gram")
+    call("se_svm_gram", *(vecs + [None] * (4 - nv)), nv, lds.pop(), C, length, out)
     return out
 
 
@@ -833,7 +801,7 @@ def svm_rowsum(a, length=None, out=None):
     lda = _f32_2d(a, "a", length)
     if out is None:
         out = torch.empty((a.shape[0],), dtype=torch.float64, device=a.device)
-    check(lib().se_svm_rowsum(ptr(a), lda, a.shape[0], length, ptr(out), stream_ptr()), "se_svm_rowsum")
+    call("se_svm_rowsum", a, lda, a.shape[0], length, out)
     return out
 
 
@@ -848,6 +816,5 @@ def svm_axpby(alpha, x, beta, y, out=None, length=None):
     if out is None:
         out = torch.zeros_like(x)
     ldx, ldy, ldo = _f32_2d(x, "x", length), _f32_2d(y, "y", length), _f32_2d(out, "out", length)
-    check(lib().se_svm_axpby(ptr(alpha), ptr(x), ldx, ptr(beta), ptr(y), ldy, x.shape[0], length, ptr(out), ldo, stream_ptr()),
-          "se_svm_axpby")
+    call("se_svm_axpby", alpha, x, ldx, beta, y, ldy, x.shape[0], length, out, ldo)
     return out
