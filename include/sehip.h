@@ -273,6 +273,7 @@ int se_rank_rows_init(void *workspace, int64_t workspace_bytes, se_stream_t stre
  * on a hardware property the library can probe but the ISA does not promise), on every row of every call when SE_RANK_CHECK=1
  * is set -- and re-ranks with the guaranteed-order kernel when it finds a violation; this entry point lets a caller audit any
  * ranking in full (np.argsort(pdist, axis=-1, kind='stable') passes it).
+ *   idx64: index width code of the ranking, as for se_rank_rows: 0 = int32, 1 = int64, 2 = uint16 (n <= 65536 only).
  *   workspace: se_rank_rows_check_workspace_bytes() bytes; *bad_rows_host (HOST pointer) receives the count; synchronises.
  */
 int64_t se_rank_rows_check_workspace_bytes(void);

@@ -20,7 +20,7 @@
 // two float64 divisions per rank into two multiplications; and the queries are visited in class order (`order_ws`: a counting
 // sort of `qcls`, one contiguous segment of that order per XCD, handed out by per-XCD atomic counters, the next draw in flight
 // while a query is processed) so that the workgroups resident on an XCD stream the SAME 16 N-byte curve and it stays in that
-// XCD's 4 MB L2 instead of coming from HBM once per query.  Measured bound (phase profile, -DSE_HP_PROFILE=1): the interior
+// XCD's 4 MB L2 instead of coming from HBM once per query.  Measured bound (phase profile): the interior
 // chunks wait on their 20 B per rank of L2 -> L1 traffic (~9 TB/s aggregate); DESIGN.md section 5.3b has the numbers.
 // Bookkeeping kept from the reference: the query itself is dropped from its ranking (position q_pos), which shifts
 // the best curve left there and subtracts its self-similarity 1.0 (class_hierarchy.py:280-290); AHP is numpy's
@@ -33,30 +33,14 @@
 
 namespace se {
 
-#ifndef SE_HP_THREADS           // geometry of a chunk: threads x consecutive ranks per thread, and the occupancy the registers are
-#define SE_HP_THREADS 256       // bounded for (waves per SIMD); tools/experiments/README.md has the measured alternatives
-#define SE_HP_ITEMS 8          // (round 6: 8 ranks per thread and chunk -- two queries of a class share a pass, their state doubles)
-#define SE_HP_WAVES_PER_SIMD 2
-#endif
-#ifndef SE_HP_PAIR
-#define SE_HP_PAIR 1            // two queries of one class per workgroup pass (0: one, the round-5 kernel)
-#endif
-#ifndef SE_HP_PF
-#define SE_HP_PF 1              // chunks of rank look-ahead
-#endif
-#ifndef SE_HP_PROFILE
-#define SE_HP_PROFILE 0         // experiment build: shader-clock cycles per phase of wave 0 of every workgroup, printed after each launch
-#endif
-#if SE_HP_PROFILE
-__device__ unsigned long long hp_prof[16];
-#define HP_T(i) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long now_ = __builtin_amdgcn_s_memtime(); if (tid == 0) hp_acc[i] += now_ - hp_last; hp_last = now_; }
-#else
-#define HP_T(i) {}
-#endif
-constexpr int HP_THREADS = SE_HP_THREADS;
+// geometry of a chunk: threads x consecutive ranks per thread, and the occupancy the registers are bounded for (waves per SIMD);
+// tools/experiments/README.md has the measured alternatives.  (Round 6: 8 ranks per thread and chunk -- two queries of a class share
+// a pass, their state doubles.)
+constexpr int HP_THREADS = 256;
 constexpr int HP_WAVES = HP_THREADS / WAVE;
-constexpr int HP_ITEMS = SE_HP_ITEMS;
-constexpr int HP_PF = SE_HP_PF;
+constexpr int HP_ITEMS = 8;
+constexpr int HP_WAVES_PER_SIMD = 2;
+constexpr int HP_PF = 1;                // chunks of rank look-ahead
 constexpr int HP_CHUNK = HP_THREADS * HP_ITEMS;
 constexpr int HP_MAX_KS = 512;
 constexpr int HP_WS_HEAD = 16;      // order_ws (ints): [0, 8) per-XCD cursors, then one int4 per query in class order: (query, its class, its own gallery index or -1, 0)
@@ -167,7 +151,7 @@ __global__ __launch_bounds__(HP_ORDER_THREADS) void hprec_order_kernel(const int
 // 128-byte L2 -> L1 line per rank, 32x the ranking itself, and was what bounded the kernel before the LDS copy.
 // RT: element type of the rankings -- int32_t, or uint16_t (se_rank_rows with idx64 == 2: one 16-byte load brings a thread's 8 ranks)
 template <int CLSW, typename RT>
-__global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel(const RT *__restrict__ rank, int64_t ldr, int64_t Q, int64_t L,
+__global__ __launch_bounds__(HP_THREADS, HP_WAVES_PER_SIMD) void hprec_kernel(const RT *__restrict__ rank, int64_t ldr, int64_t Q, int64_t L,
                                                               const int32_t *__restrict__ cls, int64_t gallery,
                                                               const int32_t *__restrict__ qcls, const int32_t *__restrict__ qidx,
                                                               const double *__restrict__ wup, const double *__restrict__ lcs, int C,
@@ -188,9 +172,6 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
     unsigned short *s_cls16 = reinterpret_cast<unsigned short *>(s_cls8);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-#if SE_HP_PROFILE
-    unsigned long long hp_acc[16] = {}, hp_last = __builtin_amdgcn_s_memtime();
-#endif
     // ---- once per workgroup: the gallery's classes into LDS, the cut-offs sorted (rank by counting; ties keep their order) ----
     if (CLSW == 1) {
         unsigned *w = reinterpret_cast<unsigned *>(s_cls8);
@@ -238,7 +219,6 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
     bool iota = true;
     for (int s = tid; s < nk; s += HP_THREADS) iota = iota && (s_ks[s] == s + 1) && (s_perm[s] == s);
     const bool ks_iota = __syncthreads_and(iota ? 1 : 0) != 0;
-    HP_T(0)
 
     // ---- which queries this workgroup takes: class order, one segment of it per XCD (blockIdx round-robins the XCDs), stealing
     //      from the next segments once its own is empty; or every gridDim-th query when no workspace was given ----
@@ -368,7 +348,6 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
                 const int i_last = (eff_len - 1 < qpos) ? eff_len - 1 : eff_len;
                 t_last = rc[hp_slot(i_last) + (i_last < qpos ? half : 0)];
             }
-            HP_T(1)
             double car_w[NQ], car_l[NQ];          // running similarity sums up to the current chunk (the same value in every thread)
             int car_r[NQ];                        // relevant items so far
             double acc_w[NQ], acc_l[NQ], acc_ap[NQ];                                // this thread's share of sum(cum / best) and of the AP terms
@@ -424,7 +403,6 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
                     // (behind the barrier, as in round 5, they had half a chunk to arrive in and the look-ups waited for HBM)
 #pragma unroll
                     for (int u = 0; u < NQ; u++) load_ranks(r[u][SLOT], rrow[u], i0 + HP_PF * HP_CHUNK, last_pos);
-                    if (FAST) HP_T(2)
                     // ---- workgroup exclusive scan of the thread totals: DPP inside the wave, wave totals through LDS ----
                     double iw[NQ], il[NQ];
                     int ir[NQ];
@@ -435,9 +413,7 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
                         ir[u] = wave_incl_scan_i32(tr[u]);
                         if (lane == 63) { part[(u * HP_WAVES + wave) * 3 + 0] = iw[u]; part[(u * HP_WAVES + wave) * 3 + 1] = il[u]; part[(u * HP_WAVES + wave) * 3 + 2] = (double)ir[u]; }
                     }
-                    if (FAST) HP_T(3)
                     wg_barrier();   // the only barrier of a chunk (of all NQ queries): the other half of s_part is written next time
-                    if (FAST) HP_T(4)
                     double cw[NQ], cl[NQ];
                     int cr[NQ];
 #pragma unroll
@@ -452,7 +428,6 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
                             car_w[u] += pw; car_l[u] += pl; car_r[u] += pr;
                         }
                     }
-                    if (FAST) HP_T(5)
                     // ---- walk the positions: cumulative sums, cum / best, trapezoid terms, the cut-offs ----
                     int kat0 = 0, knext0 = 0x7FFFFFFF;
                     if (MODE == 0 && cuts && !ks_iota) {   // lower bound of this thread's first effective rank + 1 among the sorted cut-offs
@@ -498,7 +473,6 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
                         }
                         if (FAST) { acc_w[u] += odd_w; acc_l[u] += odd_l; }
                     }
-                    if (FAST) HP_T(6)
                     // ---- AP: precision at the relevant ranks (about one in C ranks: a loop over the set bits, not a test per rank) ----
                     if (want_ap) {
 #pragma unroll
@@ -512,15 +486,13 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
                 };
                 const bool interior = vec_ok && ahp_len >= 0 && !cuts && base > qpos && base + HP_CHUNK <= last_pos && base + HP_CHUNK - 2 < alen - 1;
                 const bool tail = ahp_len == 0 && !cuts && base > qpos;
-                if (interior) { chunk(std::integral_constant<int, 1>{}); HP_T(7) }
-                else if (tail) { chunk(std::integral_constant<int, 2>{}); HP_T(8) }
-                else { chunk(std::integral_constant<int, 0>{}); HP_T(8) }
+                if (interior) chunk(std::integral_constant<int, 1>{});
+                else if (tail) chunk(std::integral_constant<int, 2>{});
+                else chunk(std::integral_constant<int, 0>{});
                 base += HP_CHUNK; par ^= 1; rct += HP_CHUNK;
             };
             while (base < last_pos) {
-                static_assert(HP_PF >= 1 && HP_PF <= 2, "rank look-ahead: one or two chunks");
                 if (base < last_pos) step(std::integral_constant<int, 0>{});
-                if (HP_PF > 1 && base < last_pos) step(std::integral_constant<int, HP_PF - 1>{});
             }
             // ---- finish: trapezoid and AP (the end points were left in LDS by whichever thread owned ranks 0 and alen - 1) ----
             {
@@ -546,10 +518,9 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
                     }
                 }
             }
-            HP_T(9)
         };
         // flags of the order kernel: 1 = the query is the first entry of its own ranking, 2 = it is not in the gallery, 0 = look for it
-        const bool pair = SE_HP_PAIR && order_ws && nq_drawn == 2 && qcv[0] == qcv[1] && flagv[0] == flagv[1] && flagv[0] != 0;
+        const bool pair = order_ws && nq_drawn == 2 && qcv[0] == qcv[1] && flagv[0] == flagv[1] && flagv[0] != 0;
         if (pair) {
             run(std::integral_constant<int, 2>{}, qv, selfv, qcv[0], flagv[0] == 1 ? 0 : 0x7FFFFFFF);
         } else {
@@ -560,10 +531,6 @@ __global__ __launch_bounds__(HP_THREADS, SE_HP_WAVES_PER_SIMD) void hprec_kernel
             }
         }
     }
-#if SE_HP_PROFILE
-    if (tid == 0)
-        for (int i = 0; i < 16; i++) atomicAdd(&hp_prof[i], hp_acc[i]);
-#endif
 }
 
 }  // namespace se
@@ -658,20 +625,6 @@ static int hp_run(const RT *rank, int64_t ldr, int64_t q, int64_t list_len, cons
     else SE_HP_LAUNCH(0);
 #undef SE_HP_LAUNCH
     SE_LAUNCH_CHECK();
-#if SE_HP_PROFILE
-    {
-        unsigned long long h[16], z[16] = {};
-        SE_HIP_CHECK(hipStreamSynchronize(s));
-        SE_HIP_CHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(hp_prof), sizeof(h)));
-        SE_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(hp_prof), z, sizeof(z)));
-        static const char *names[10] = {"setup", "query-prologue", "lookups", "scans", "barrier", "parts", "walk", "ap+rest(fast)", "slow-chunk", "finish"};
-        double tot = 0;
-        for (int i = 0; i < 10; i++) tot += (double)h[i];
-        fprintf(stderr, "[se_hierarchical_precision profile] grid=%lld q=%lld len=%lld: cycles per workgroup %.0f;", (long long)grid, (long long)q, (long long)list_len, tot / (double)grid);
-        for (int i = 0; i < 10; i++) fprintf(stderr, " %s %.1f%%", names[i], 100.0 * (double)h[i] / tot);
-        fprintf(stderr, "\n");
-    }
-#endif
     return SE_OK;
 }
 

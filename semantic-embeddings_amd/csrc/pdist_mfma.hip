@@ -36,17 +36,8 @@ namespace se {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef SE_PD_BK
-#define SE_PD_BK 64
-#endif
-#ifndef SE_PD_WGS
-#define SE_PD_WGS 2
-#endif
-constexpr int PD_BM = 128, PD_BN = 128, PD_BK = SE_PD_BK;   // K-chunk staged per barrier pair: 64 or 32
-#ifndef SE_PD_THREADS
-#define SE_PD_THREADS 512        // 512: 4 x 2 waves of 32 x 64 outputs; 256: 2 x 2 waves of 64 x 64 (smaller workgroups, more of them per CU)
-#endif
-constexpr int PD_THREADS = SE_PD_THREADS;
+constexpr int PD_BM = 128, PD_BN = 128, PD_BK = 64;         // K-chunk staged per barrier pair
+constexpr int PD_THREADS = 512;                               // 4 x 2 waves of 32 x 64 outputs
 constexpr int PD_WAVES = PD_THREADS / 64;
 constexpr int PD_WROWS = PD_BM / (PD_WAVES / 2);              // tile rows per wave (its columns: 64)
 constexpr int PD_MI = PD_WROWS / 32;                          // 32-row MFMA blocks per wave along m
@@ -57,7 +48,7 @@ constexpr int PD_SR = (PD_BM * PD_SP <= (PD_BM + PD_BN) * PD_LD) ? PD_BM : PD_BM
 static_assert(PD_SR * PD_SP <= (PD_BM + PD_BN) * PD_LD, "epilogue stage must fit in the operand LDS");
 constexpr int PD_GROUP_M = 16;
 constexpr int PD_MAX_KB = 16;
-constexpr int PD_WGS_PER_CU = SE_PD_WGS;
+constexpr int PD_WGS_PER_CU = 2;
 constexpr int PD_F4R = PD_BK / 4;                            // 16-byte pieces per operand row of a chunk
 constexpr int PD_RPP = PD_THREADS / PD_F4R;                  // operand rows covered by one piece per thread
 constexpr int PD_NLOAD = PD_BM / PD_RPP;                     // pieces per operand per thread (4 at BK = 64, 2 at BK = 32)
@@ -265,11 +256,6 @@ __global__ __launch_bounds__(PD_THREADS, (PD_WAVES / 4) * PD_WGS_PER_CU) void pd
         for (int i = 0; i < slot * 2; i++) __builtin_amdgcn_s_sleep(127);
     }
 
-#ifdef SE_PD_PRIO
-    // experiment: static priority for the second workgroup slot of every CU, so that the two co-resident workgroups cannot
-    // phase-lock (both in their MFMA phase at half speed, then both staging with the matrix pipe idle)
-    if (b >= (G >> 1)) __builtin_amdgcn_s_setprio(SE_PD_PRIO);
-#endif
     const int lane = lane_id(), wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1;      // (PD_WAVES / 2) x 2 waves: PD_WROWS rows x 64 cols each
     const int col = lane & 31, hi = lane >> 5;
@@ -693,17 +679,6 @@ __global__ __launch_bounds__(PD_THREADS, (PD_WAVES / 4) * PD_WGS_PER_CU) void pd
 #undef PD_FETCH
 }
 
-static int pd_num_cus()
-{
-    static const int cus = [] {   // (thread-safe one-time initialisation; one process drives one GPU model)
-        int dev = 0, n = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        return n > 0 ? n : 256;
-    }();
-    return cus;
-}
-
 template <int METRIC, bool MULTI, bool SYM, bool VEC, int EPI = EPI_STORE>
 static int launch_pdist3(const float *a, int64_t lda, const float *b, int64_t ldb, const float *sqa, const float *sqb,
                          int64_t q, int64_t n, int64_t d, const KBlocks &kbs, float *out, int64_t ldo, hipStream_t s,
@@ -732,7 +707,7 @@ static int launch_pdist3(const float *a, int64_t lda, const float *b, int64_t ld
     }
     int nchunks = 0;
     for (int i = 0; i < kbs.n; i++) nchunks += (kbs.len[i] + PD_BK - 1) / PD_BK;
-    int64_t grid = (int64_t)pd_num_cus() * PD_WGS_PER_CU;
+    int64_t grid = (int64_t)num_cus() * PD_WGS_PER_CU;
     grid = grid / 8 * 8;
     if (grid > ntiles) grid = ntiles;
     if (grid < 1) grid = 1;
@@ -854,15 +829,6 @@ int make_kblocks(const char *who, const int32_t *kblocks, int nkb, int64_t d, KB
 
 }  // namespace se
 
-#ifdef SE_PD_WS_BUILD
-namespace se {
-// tools/experiments/pdist_ws.hip: wave-specialised variant, measured slower (3.8 vs 3.4 ms) and therefore NOT part of the product
-// library; a tuning build can link it in with -DSE_PD_WS_BUILD.  SE_OK = done, 1 = not applicable (use the kernel in this file)
-int pdist_ws_try(const float *a, int64_t lda, const float *b, int64_t ldb, const float *sqa, const float *sqb, int64_t q, int64_t n,
-                 int64_t d, int metric, float *out, int64_t ldo, hipStream_t s);
-}
-#endif
-
 using namespace se;
 
 extern "C" int se_pairwise_dist(const float *a, int64_t lda, const float *b, int64_t ldb, const float *sqa,
@@ -880,12 +846,6 @@ extern "C" int se_pairwise_dist(const float *a, int64_t lda, const float *b, int
     bool multi = false;
     if (const int rc = make_kblocks("se_pairwise_dist", kblocks, nkb, d, kbs, multi)) return rc;
     hipStream_t s = (hipStream_t)stream;
-#ifdef SE_PD_WS_BUILD
-    if (!multi && (metric == SE_METRIC_COSINE || metric == SE_METRIC_EUCLID || metric == SE_METRIC_DOT)) {
-        const int rc = pdist_ws_try(a, lda, b, ldb, sqa, sqb, q, n, d, metric, out, ldo, s);
-        if (rc != 1) return rc;
-    }
-#endif
     switch (metric) {
         case SE_METRIC_COSINE: return launch_pdist<SE_METRIC_COSINE>(a, lda, b, ldb, sqa, sqb, q, n, d, kbs, multi, out, ldo, s);
         case SE_METRIC_EUCLID: return launch_pdist<SE_METRIC_EUCLID>(a, lda, b, ldb, sqa, sqb, q, n, d, kbs, multi, out, ldo, s);

@@ -41,13 +41,10 @@ namespace se {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef float pf_f32x16 __attribute__((ext_vector_type(16)));
 
-#ifndef SE_PF_BM
-#define SE_PF_BM 128      // 256: 512-thread workgroups, one per CU (measured: 28.8 vs 26.6 ms on the D = 1000 shard -- with one workgroup per CU
-#endif                    // every wave is in the same phase at the same time and nothing overlaps the load bursts)
-#ifndef SE_PF_BK
-#define SE_PF_BK 128
-#endif
-constexpr int PF_BM = SE_PF_BM, PF_BN = 128, PF_BK = SE_PF_BK;   // tile (gallery rows x queries), K-chunk (fp16 elements)
+// tile (gallery rows x queries), K-chunk (fp16 elements).  256-row tiles -- 512-thread workgroups, one per CU -- measured slower, 28.8
+// vs 26.6 ms on the D = 1000 shard: with one workgroup per CU every wave is in the same phase at the same time and nothing overlaps
+// the load bursts.
+constexpr int PF_BM = 128, PF_BN = 128, PF_BK = 128;
 constexpr int PF_THREADS = PF_BM * 2;                       // (PF_BM / 64) x 2 waves of 64 x 64 outputs
 constexpr int PF_ROWB = PF_BK * 2;                          // bytes of one operand row of a chunk (256)
 constexpr int PF_PITCH = PF_ROWB + 16;                      // LDS row pitch in bytes: 68 dwords -> conflict-free ds_read_b128 over 16 rows
@@ -56,15 +53,10 @@ constexpr int PF_NLOAD_A = PF_BM * PF_PPR / PF_THREADS;     // pieces per thread
 constexpr int PF_NLOAD_B = PF_BN * PF_PPR / PF_THREADS;     // query operand (4)
 // The filter epilogue's accumulator dump (36 dwords per thread) lives in the gallery operand's LDS plus this gap in front of the query
 // operand: the query panel of a one-chunk job (padded width 128) stays in LDS for all tiles of the job and must not be overwritten.
-constexpr int PF_DUMP_BYTES = SE_PF_BM * 2 * 36 * 4;
+constexpr int PF_DUMP_BYTES = PF_BM * 2 * 36 * 4;
 constexpr int PF_GAP = PF_DUMP_BYTES > PF_BM * PF_PITCH ? PF_DUMP_BYTES - PF_BM * PF_PITCH : 0;
-#ifndef SE_PF_CB
-#define SE_PF_CB 3        // candidates per lane, query and tile taken in straight-line code by the filter epilogue (0: the loop only)
-#endif
-#ifndef SE_PF_WGS
-#define SE_PF_WGS (256 / SE_PF_BM)
-#endif
-constexpr int PF_WGS_PER_CU = SE_PF_WGS;                    // default: 8 waves per CU, <= 256 registers each
+constexpr int PF_CB = 3;                                    // candidates per lane, query and tile taken in straight-line code by the filter epilogue
+constexpr int PF_WGS_PER_CU = 256 / PF_BM;                  // 8 waves per CU, <= 256 registers each
 
 constexpr int PF_GROUPMIN = PF_EPI_GROUPMIN, PF_FILTER = PF_EPI_FILTER, PF_STORE = PF_EPI_STORE;
 
@@ -259,24 +251,6 @@ __device__ __forceinline__ void pf_load(uint4 (&v)[NL], const uint16_t *__restri
     }
 }
 
-// pieces [first, first + CNT) of the same chunk (loads dealt over the MFMA steps)
-template <int NL, int CNT>
-__device__ __forceinline__ void pf_load_part(uint4 (&v)[NL], int first, const uint16_t *__restrict__ src, uint32_t ld, int64_t row0, int64_t nrows, int k0)
-{
-    constexpr int ROWS = NL * PF_THREADS / PF_PPR;
-    const int tid = threadIdx.x;
-    const char *base = (const char *)(src + row0 * (int64_t)ld);
-    const int rows_here = (int)((nrows - row0 < ROWS) ? (nrows - row0) : ROWS);
-#pragma unroll
-    for (int i = 0; i < NL; i++) {
-        if (i < first || i >= first + CNT) continue;
-        const int p = tid + i * PF_THREADS;
-        const int r = p / PF_PPR, c = p % PF_PPR;
-        const int rc = r < rows_here ? r : rows_here - 1;
-        v[i] = *(const uint4 *)(base + ((uint32_t)rc * ld * 2u + (uint32_t)k0 * 2u + (uint32_t)c * 16u));
-    }
-}
-
 template <int NL>
 __device__ __forceinline__ void pf_stage(char *lds, const uint4 (&v)[NL])
 {
@@ -416,13 +390,10 @@ __global__ __launch_bounds__(PF_THREADS, PF_WGS_PER_CU) void pf_tile_kernel(
                 have_next = pf_next_job(nx, 8, nsq, nsuper, gi, gj, gi_i, gj_j, tiles_m, tiles_n, tpp);
             }
         }
-#ifndef SE_PF_SPREAD
-#define SE_PF_SPREAD 0
-#endif
         // one-chunk jobs (padded width 128, e.g. D = 100): the job's query panel is already in LDS and stays there -- every tile of the
         // job used to fetch and stage it again (a third of the operand traffic and LDS writes of the 391 tiles of a 50k x 50k job)
         const bool keep_b = nchunks == 1 && !job_ends;
-        if (have_next && !SE_PF_SPREAD) {
+        if (have_next) {
             pf_load<PF_NLOAD_A>(ra, A, lda, (int64_t)nx.t * PF_BM, NA, nc * PF_BK);
             if (!keep_b) pf_load<PF_NLOAD_B>(rb, B, ldb, (int64_t)nx.tn * PF_BN, NB, nc * PF_BK);
         }
@@ -434,15 +405,6 @@ __global__ __launch_bounds__(PF_THREADS, PF_WGS_PER_CU) void pf_tile_kernel(
 #pragma unroll
         for (int s = 0; s < PF_BK / 16; s++) {
             if (s >= nsteps) break;
-#if SE_PF_SPREAD
-            // experiment: the next chunk's loads dealt over the MFMA steps instead of one burst in front of them
-            if (have_next) {
-                constexpr int PA = PF_NLOAD_A / (PF_BK / 16) > 0 ? PF_NLOAD_A / (PF_BK / 16) : 1, PB = PF_NLOAD_B / (PF_BK / 16) > 0 ? PF_NLOAD_B / (PF_BK / 16) : 1;
-                pf_load_part<PF_NLOAD_A, PA>(ra, s * PA, A, lda, (int64_t)nx.t * PF_BM, NA, nc * PF_BK);
-                pf_load_part<PF_NLOAD_B, PB>(rb, s * PB, B, ldb, (int64_t)nx.tn * PF_BN, NB, nc * PF_BK);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
             f16x8 a0 = __builtin_bit_cast(f16x8, *(const uint4 *)(pa + s * 32));
             f16x8 a1 = __builtin_bit_cast(f16x8, *(const uint4 *)(pa + 32 * PF_PITCH + s * 32));
             f16x8 b0 = __builtin_bit_cast(f16x8, *(const uint4 *)(pb + s * 32));
@@ -451,9 +413,6 @@ __global__ __launch_bounds__(PF_THREADS, PF_WGS_PER_CU) void pf_tile_kernel(
             acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc[0][1], 0, 0, 0);
             acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc[1][0], 0, 0, 0);
             acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1, acc[1][1], 0, 0, 0);
-#if SE_PF_SPREAD
-            __builtin_amdgcn_sched_barrier(0);
-#endif
         }
         PF_T(2)
         // the next chunk's operands are waited for HERE (value barriers: no use of a loaded register in front of the MFMA phase)
@@ -593,9 +552,8 @@ __global__ __launch_bounds__(PF_THREADS, PF_WGS_PER_CU) void pf_tile_kernel(
                     // the first PF_CB candidates of every lane in straight-line code: their LDS reads are in flight together (a lane holds
                     // 0.5 candidates per query and tile on average, the busiest lane of a wave ~3: the divergent loop below paid one LDS
                     // round trip per iteration); the loop takes what is left
-                    constexpr int PF_CB = SE_PF_CB;
-                    int ci[PF_CB > 0 ? PF_CB : 1];
-                    float ca[PF_CB > 0 ? PF_CB : 1];
+                    int ci[PF_CB];
+                    float ca[PF_CB];
 #pragma unroll
                     for (int t = 0; t < PF_CB; t++) {
                         const int i = m ? __builtin_clz(m) : -1;                          // value index: mi = i >> 4, r = i & 15
@@ -962,20 +920,9 @@ __global__ __launch_bounds__(PB_THREADS, 1) void pf_big_kernel(
 #undef PB_TILE_SIDE
 }
 
-static int pf_num_cus()
-{
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
-        return n > 0 ? n : 256;
-    }();
-    return cus;
-}
-
 static int64_t pf_grid()
 {
-    int64_t grid = (int64_t)pf_num_cus() * PF_WGS_PER_CU;
+    int64_t grid = (int64_t)num_cus() * PF_WGS_PER_CU;
     return grid / 8 * 8 > 0 ? grid / 8 * 8 : 8;
 }
 
@@ -990,7 +937,7 @@ PfGeom pf_geometry(int64_t n_a, int64_t n_q, int want_parts, int kp)
     if (const char *e = tuning_env("SE_PF_BIG")) g.big = (kp > 0 && atoi(e) != 0) ? 1 : 0;      // -DSE_TUNING build: pins the kernel
     const int bm = g.big ? PB_BM : PF_BM, bn = g.big ? PB_BN : PF_BN;
     const int64_t tiles_m = (n_a + bm - 1) / bm, tiles_n = (n_q + bn - 1) / bn;
-    const int per_xcd = (int)((g.big ? (int64_t)pf_num_cus() / 8 * 8 : pf_grid()) / 8);
+    const int per_xcd = (int)((g.big ? (int64_t)num_cus() / 8 * 8 : pf_grid()) / 8);
     g.gi = 8;
     if (const char *e = tuning_env("SE_PF_GI")) g.gi = atoi(e) > 0 ? atoi(e) : 8;   // -DSE_TUNING build: shape of the per-XCD workgroup grid
     while (g.gi > 1 && (g.gi > tiles_n || per_xcd % g.gi)) g.gi >>= 1;          // few queries: fewer query tiles side by side, more gallery sequences

@@ -239,22 +239,11 @@ __global__ __launch_bounds__(RK_THREADS) void rank_rows_kernel(const float *__re
 //   * indices travel as 16 bits (N <= 65536 by construction) packed with the 16-bit destination;
 //   * after the last pass the exchange buffer IS the ranking: it is streamed to HBM with 16-byte
 //     stores.
-#ifndef SE_RR_THREADS
-#define SE_RR_THREADS 512   // 512 (8 waves, 2 per SIMD, <= 256 VGPRs) or 768 (12 waves, 3 per SIMD, <= 168 VGPRs)
-#endif
-constexpr int RR_THREADS = SE_RR_THREADS;
-// instantiations (keys per thread) of the 512-thread build; -DSE_RR_DEV: a quick-to-compile subset for kernel work (NOT a product build)
-#ifdef SE_RR_DEV98
-#define SE_RR_CASES_512 SE_RR_CASE(98)
-#elif defined(SE_RR_DEV)
-#define SE_RR_CASES_512 SE_RR_CASE(8) SE_RR_CASE(72) SE_RR_CASE(98)
-#else
-#define SE_RR_CASES_512 SE_RR_CASE(2) SE_RR_CASE(8) SE_RR_CASE(12) SE_RR_CASE(20) SE_RR_CASE(30) SE_RR_CASE(40) SE_RR_CASE(46) SE_RR_CASE(52) SE_RR_CASE(58) SE_RR_CASE(64) SE_RR_CASE(72) SE_RR_CASE(80) SE_RR_CASE(88) SE_RR_CASE(98) SE_RR_CASE(104)
-#endif
+constexpr int RR_THREADS = 512;                       // 8 waves, 2 per SIMD, <= 256 VGPRs
 constexpr int RR_WAVES = RR_THREADS / WAVE;
 constexpr int RR_SCAN_THREADS = 512;                  // threads that scan the packed counters (2 words each of the 1024 per wave)
 constexpr int RR_SCAN_WAVES = RR_SCAN_THREADS / WAVE;
-static_assert((53248 + RR_THREADS - 1) / RR_THREADS <= 104, "rows of up to 53,248 columns: 104 keys per thread (512 threads) / 70 (768 threads)");
+static_assert((53248 + RR_THREADS - 1) / RR_THREADS <= 104, "rows of up to 53,248 columns: 104 keys per thread");
 constexpr int RR_G = 8;                               // steps ranked together (latency overlap vs live registers)
 constexpr int RR_MAX_N = 53248;
 
@@ -324,10 +313,7 @@ __device__ __forceinline__ void lds_ld16(uint32_t &dst, uint32_t addr) { asm vol
 template <int K>
 __device__ __forceinline__ void lds_wait_le(uint32_t &landed) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(landed) : "n"(K) : "memory"); }
 
-#ifndef SE_RR_RING
-#define SE_RR_RING 12
-#endif
-constexpr int RR_RING = SE_RR_RING;   // 16-bit loads in flight per lane (lgkmcnt counts to 15)
+constexpr int RR_RING = 12;   // 16-bit loads in flight per lane (lgkmcnt counts to 15)
 // Software-pipelined read of this lane's ITEMS new 16-bit values (read slot of step s = addr + 128 s)
 // into the HIGH (HI = true) or LOW half of a[s]: read i is issued RR_RING - 1 reads ahead of its merge.
 template <int ITEMS, bool HI, int I = 0>
@@ -401,38 +387,12 @@ struct RRRank {
 // workgroup hammering the LDS), but the ISA does not promise it, so this variant is only selected after the
 // same property has been re-verified on the device at first use (se_rank_rows: probe kernel) and can be
 // switched off with SE_RANK_SAFE=1.  ~5 VALU per key and pass instead of ~41.
-#ifndef SE_RR_NT
-#define SE_RR_NT 1   // 1: nontemporal rank stores (round 6: -2 % on the image path once the next row is loaded straight from HBM; neutral elsewhere)
-#endif
+// The rank write-outs use nontemporal stores (round 6: -2 % on the image path once the next row is loaded straight from HBM; neutral elsewhere).
 typedef int rr_i32x4 __attribute__((ext_vector_type(4)));
 typedef long long rr_i64x2 __attribute__((ext_vector_type(2)));
-#ifndef SE_RR_PF
-#define SE_RR_PF 1
-#endif
-#ifndef SE_RR_GH
-#define SE_RR_GH 8
-#endif
-constexpr int RR_GH = SE_RR_GH;    // returning adds in flight per lane
+constexpr int RR_GH = 8;    // returning adds in flight per lane
 constexpr int RR_HW_BITS = 11;   // digit width of the hardware-ordered variant: 3 passes (11 + 11 + 10 bits; rows of >= 32,768 columns: 10 + 10 + 12) instead of 4
 constexpr int RR_WIDE_WORDS = 2048;   // counter words per wave of the 12-bit pass (4096 packed 16-bit counters)
-#ifndef SE_RR_TWO
-#define SE_RR_TWO 1                   // build parameter: 0 = never take the two-pass path below
-#endif
-#ifndef SE_RR_PROF_BARRIER
-#define SE_RR_PROF_BARRIER 0          // profile build: 1 = a barrier in front of every timestamp (phase times include the skew between the waves)
-#endif
-#ifndef SE_RR_EARLY
-#define SE_RR_EARLY 1                 // build parameter: image path -- next row's loads issued behind the last pass, waited for before the rank stores
-#endif
-#ifndef SE_RR_SCAN_DEPTH
-#define SE_RR_SCAN_DEPTH 1            // build parameter: groups of the image path's tag scan whose random reads are in flight ahead of the arithmetic
-#endif
-#ifndef SE_RR_WO
-#define SE_RR_WO 4                    // build parameter: steps of the int32 write-out loop whose LDS reads are in flight together
-#endif
-#ifndef SE_RR_IMG
-#define SE_RR_IMG 1                   // build parameter: 0 = never take the image path (two passes on a 24-bit image + repair)
-#endif
 // Two-pass path of the long-row kernel: when all keys of a row but at most RR_TWO_OUT lie within RR_TWO_SPAN codes below its largest
 // key (Euclidean-distance rows of one data set do: the outliers are the query's own distance and its near-duplicates; the reference's
 // cosine rows -- -dot, both signs around zero, ~2^31 codes wide -- do not), the row is
@@ -620,7 +580,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
     // key read-back ends in one anyway.  The round-5 form -- 36 64-bit counters with a run-time index, a barrier per timestamp -- was
     // 74 KB of code with 208 B of scratch: above the 64 KB instruction cache, it overstated every phase.)
     uint32_t t_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t_last = PROF ? (uint32_t)__builtin_amdgcn_s_memtime() : 0;
-#define RR_T(i) if constexpr (PROF) { if (SE_RR_PROF_BARRIER) { lds_wait(); wg_barrier(); } const uint32_t now = (uint32_t)__builtin_amdgcn_s_memtime(); t_acc[i] += now - t_last; t_last = now; } else { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
+#define RR_T(i) if constexpr (PROF) { const uint32_t now = (uint32_t)__builtin_amdgcn_s_memtime(); t_acc[i] += now - t_last; t_last = now; } else { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
 
     // The row loop is software-pipelined over HBM: the NEXT row is prefetched into L2 during the last pass (one dword per 128-byte
     // line), loaded into the key registers right after it -- BEFORE this row's rank stores are issued, so the memory pipeline serves
@@ -810,7 +770,8 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                 opaque(wpos);
 #pragma unroll
                 for (int s = 0; s < ITEMS; s++) below_l += ((int32_t)key[s] < lo) ? 1u : 0u;        // v_cmp + v_addc
-                // padding slots hold a copy of the row's last element: take them out again (only the wave(s) that have any)
+                // padding slots read as 0 (range-checked buffer loads), which lies below the window because lo >= 1: take them out
+                // again (only the wave(s) that have any)
                 // (`lo_b`, `lo_c` below: opaque copies -- hipcc otherwise shares the 98 compare masks between the three loops and spills the
                 // SGPR pairs to VGPR lanes, ~600 v_writelane / v_readlane per row)
                 if (wave_s * (ITEMS * WAVE) + ITEMS * WAVE > n_row) {
@@ -899,7 +860,6 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
             lds_wait();
             RR_T(1)
             wg_barrier();
-            if (SE_RR_PF == 3) { RR_PREFETCH_NEXT_ROW() }
             // ---- S: counters -> first destination of every (wave, digit) ----
             if constexpr (!HWORD) {
             uint32_t ex = 0;
@@ -985,10 +945,9 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
             RR_T(2)
             // L2 prefetch of this workgroup's NEXT row (one workgroup per CU: nothing else hides its 200 KB of HBM latency): one dword
             // per 128-byte line, all into one sink register that stays reserved until the loads after the pass loop have been waited for.
-            // SE_RR_PF (build-time tuning aid): 0 = no prefetch, 1 = before the destination phase of the last pass (default), 2 = after it, 3 = before its scan
-            // (image path: the row's scan + repair follow the last pass -- its prefetch is issued in front of the scan instead: lines brought
-            // in this early were evicted again before the loads, 19 % of the row bytes fetched twice)
-            if (SE_RR_PF == 1 && !(IMG && two)) { RR_PREFETCH_NEXT_ROW() }
+            // Issued before the destination phase of the last pass.  The image path takes none: its next row is loaded straight from HBM
+            // behind the last pass (lines prefetched this early were evicted again before the loads, 19 % of the row bytes fetched twice).
+            if (!(IMG && two)) { RR_PREFETCH_NEXT_ROW() }
             // ---- X: destinations, then the 2-byte exchanges ----
             if (wave_live) {
 #pragma unroll
@@ -1009,7 +968,6 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                 __builtin_amdgcn_sched_barrier(0);
             }
             }
-            if (SE_RR_PF == 2) { RR_PREFETCH_NEXT_ROW() }
             if (wide) wg_barrier();   // the scatter below overwrites the (aliased) counters other waves may still be looking up
             RR_T(3)
             if (wave_live) {
@@ -1077,7 +1035,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
         }
         // ---- image path: the exchange buffer is sorted by (image, index); put the runs of equal tags into (key, index) order ----
         [[maybe_unused]] bool img_fail = false;
-        if constexpr (IMG && SE_RR_EARLY) {
+        if constexpr (IMG) {
             // The NEXT row's loads are issued here, straight from HBM (no L2 prefetch): the key registers are dead behind the last pass, and
             // the scan + repair (~20k cycles) cover the latency.  They are waited for BEFORE this row's rank stores are issued, so that
             // nothing has to wait for the stores to drain: the next row's maximum / image phase (VALU only) runs under them.
@@ -1102,7 +1060,6 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                 // the worklist (bit 8 b + 4 h of a group's word: position 4 h + b); ONE returning add per thread reserves its slots and
                 // only the (rare) set bits are walked -- nothing in this phase waits for LDS inside a divergent loop.  Pairs that reach
                 // into the padding become empty entries.
-                if (SE_RR_PF == 1 && !SE_RR_EARLY) { RR_PREFETCH_NEXT_ROW_IF(more) }
                 constexpr int NS = RR_THREADS * ITEMS;
                 constexpr int NG = (NS / 8 + RR_THREADS - 1) / RR_THREADS;   // groups per thread
                 uint32_t S[NG];
@@ -1118,7 +1075,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                     xg[g] = *reinterpret_cast<const uint4 *>(xbuf + bs);
                     nxg[g] = xbuf[bs + 8 < NS ? bs + 8 : bs];
                 }
-                constexpr int TD = SE_RR_SCAN_DEPTH;   // groups whose tag reads are in flight ahead of the arithmetic
+                constexpr int TD = 1;   // groups whose tag reads are in flight ahead of the arithmetic
                 uint32_t t[TD + 1][9];
                 auto tag_reads = [&](int g, uint32_t (&tt)[9]) {
                     const uint32_t xi[4] = {xg[g].x, xg[g].y, xg[g].z, xg[g].w};
@@ -1250,14 +1207,14 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
         // hipcc copy all ITEMS index registers there, and a separate straight-line instance of the last pass -- measured, DESIGN.md 5.2 --
         // pushes the 98-key build into scratch; the row was prefetched into L2 during the last pass.  They are issued BEFORE the rank
         // stores and waited for after them: the memory pipeline serves them first and the write-out covers most of their latency.)
-        if (!(IMG && SE_RR_EARLY) || img_fail) {
+        if (!IMG || img_fail) {
             const float *drow = row_ptr((IMG && img_fail) ? row : (more ? row + gridDim.x : row));   // (image path given up: the same row again)
             int wpos = wpos0;
             opaque(wpos);   // per-row opaque: otherwise hipcc hoists ITEMS row-invariant clamps out of the row loop and keeps them live
 #pragma unroll
             for (int s = 0; s < ITEMS; s++) RR_LOAD_ONE(drow, wpos, s, n_next)
         }
-        if constexpr (IMG && SE_RR_EARLY) {
+        if constexpr (IMG) {
             // the next row's keys have landed (and the prefetch dwords of a row that took the three passes): nothing is outstanding when the stores start
 #pragma unroll
             for (int s = 0; s < ITEMS; s++) opaque(key[s]);
@@ -1277,8 +1234,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
             _Pragma("unroll 2") for (int j = wt * 8; j < N; j += RR_THREADS * 8) {
                 if (vec_ok && j + 7 < N) {
                     const rr_i32x4 v = *reinterpret_cast<const rr_i32x4 *>(xbuf + j);
-                    if (SE_RR_NT) __builtin_nontemporal_store(v, reinterpret_cast<rr_i32x4 *>(o + j));
-                    else *reinterpret_cast<rr_i32x4 *>(o + j) = v;
+                    __builtin_nontemporal_store(v, reinterpret_cast<rr_i32x4 *>(o + j));
                 } else {
                     for (int e = 0; e < 8 && j + e < N; e++) o[j + e] = xbuf[j + e];
                 }
@@ -1293,13 +1249,8 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                 nv = *reinterpret_cast<const uint2 *>(xbuf + (jn < N ? jn : 0));
                 const int64_t e0 = v.x & 0xFFFFu, e1 = v.x >> 16, e2 = v.y & 0xFFFFu, e3 = v.y >> 16;
                 if (vec_ok && j + 3 < N) {
-                    if (SE_RR_NT) {
-                        __builtin_nontemporal_store((rr_i64x2){e0, e1}, reinterpret_cast<rr_i64x2 *>(o + j));
-                        __builtin_nontemporal_store((rr_i64x2){e2, e3}, reinterpret_cast<rr_i64x2 *>(o + j + 2));
-                    } else {
-                        *reinterpret_cast<longlong2 *>(o + j) = make_longlong2(e0, e1);
-                        *reinterpret_cast<longlong2 *>(o + j + 2) = make_longlong2(e2, e3);
-                    }
+                    __builtin_nontemporal_store((rr_i64x2){e0, e1}, reinterpret_cast<rr_i64x2 *>(o + j));
+                    __builtin_nontemporal_store((rr_i64x2){e2, e3}, reinterpret_cast<rr_i64x2 *>(o + j + 2));
                 } else {
                     o[j] = e0;
                     if (j + 1 < N) o[j + 1] = e1;
@@ -1311,7 +1262,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
             int32_t *o = (int32_t *)rank + row * ldr;
             // RR_WO steps per trip: their LDS reads are in flight together, then the stores (with one step per trip and one read ahead, as the
             // int64 path does, the loop paid an LDS round trip per 16-byte store: ~12k of a row's ~100k cycles)
-            constexpr int RR_WO = SE_RR_WO;
+            constexpr int RR_WO = 4;
             _Pragma("unroll 1") for (int j0 = wt * 4; j0 < N; j0 += RR_THREADS * 4 * RR_WO) {
                 uint2 v[RR_WO];
 #pragma unroll
@@ -1325,8 +1276,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                     if (j >= N) break;
                     const int e0 = v[u].x & 0xFFFFu, e1 = v[u].x >> 16, e2 = v[u].y & 0xFFFFu, e3 = v[u].y >> 16;
                     if (vec_ok && j + 3 < N) {
-                        if (SE_RR_NT) __builtin_nontemporal_store((rr_i32x4){e0, e1, e2, e3}, reinterpret_cast<rr_i32x4 *>(o + j));
-                        else *reinterpret_cast<int4 *>(o + j) = make_int4(e0, e1, e2, e3);
+                        __builtin_nontemporal_store((rr_i32x4){e0, e1, e2, e3}, reinterpret_cast<rr_i32x4 *>(o + j));
                     } else {
                         o[j] = e0;
                         if (j + 1 < N) o[j + 1] = e1;
@@ -1341,7 +1291,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
         if constexpr (PROF) {   // keep the canonicalisation (and with it the wait for the loads) inside the 'load' interval of the phase profile
             _Pragma("unroll") for (int s = 0; s < ITEMS; s++) opaque(key[s]);
         }
-        if constexpr (!(IMG && SE_RR_EARLY))
+        if constexpr (!IMG)
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(pf_sink) : : "memory");   // prefetch dwords landed too: the sink register is free again, nothing is outstanding
         RR_T(0)
         // (the next row's pass-0 barriers order these reads before its first exchange write)
@@ -1457,6 +1407,21 @@ __global__ __launch_bounds__(256) void rank_skew_detect_kernel(const float *__re
     }
 }
 
+// resident workgroups of a register-resident kernel = CUs x occupancy; every instantiation computes it once (thread-safe static
+// initialisation of a const)
+struct Resident { hipError_t err; int64_t grid; };
+static Resident rank_resident(const void *kern, size_t lds)
+{
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    int dev = 0, occ = 0;
+    hipDeviceProp_t prop;
+    if (e == hipSuccess) e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, RR_THREADS, lds);
+    if (e != hipSuccess) return {e, 0};
+    return {hipSuccess, (int64_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * (occ > 0 ? occ : 1)};
+}
+
 template <int ITEMS, bool HW, int VAR>
 static int launch_rank_reg_variant(const float *pdist, int64_t ldp, int64_t q, int n, void *rank, int idx64, int64_t ldr,
                                    const uint32_t *skew_flag, hipStream_t s)
@@ -1466,18 +1431,7 @@ static int launch_rank_reg_variant(const float *pdist, int64_t ldp, int64_t q, i
     static_assert(rr_region0_bytes<ITEMS, HW, VAR>() + 32 * sizeof(uint32_t) + (size_t)RR_THREADS * ITEMS * sizeof(uint16_t) <= 160 * 1024, "LDS of one CU");
     static const bool profile = tuning_env("SE_RR_PROFILE") != nullptr;   // -DSE_TUNING build only: allocates, synchronises, prints
     auto kern = (kTuning && profile) ? rank_rows_reg_kernel<ITEMS, kTuning && (ITEMS == 98), HW, VAR> : rank_rows_reg_kernel<ITEMS, false, HW, VAR>;
-    // per instantiation, computed once (thread-safe static initialisation): resident workgroups = CUs x occupancy
-    struct Resident { hipError_t err; int64_t grid; };
-    static const Resident res = [&]() -> Resident {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int dev = 0, occ = 0;
-        hipDeviceProp_t prop;
-        if (e == hipSuccess) e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kern, RR_THREADS, lds);
-        if (e != hipSuccess) return {e, 0};
-        return {hipSuccess, (int64_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * (occ > 0 ? occ : 1)};
-    }();
+    static const Resident res = rank_resident((const void *)kern, lds);
     if (res.err != hipSuccess) return fail(SE_ERR_HIP, "se_rank_rows: kernel set-up failed: %s", hipGetErrorString(res.err));
     int64_t grid = res.grid;
     if (grid > q) grid = q;
@@ -1517,8 +1471,8 @@ static int launch_rank_reg(const float *pdist, int64_t ldp, int64_t q, int n, vo
     if (!hw) return launch_rank_reg_variant<ITEMS, false, 0>(pdist, ldp, q, n, rank, idx64, ldr, nullptr, s);
     // long rows (12-bit last digit, counters aliased onto the exchange buffer: WIDE in the kernel) also have the two-pass variant
     constexpr bool wide = (size_t)RR_THREADS * ITEMS * sizeof(uint16_t) >= (size_t)RR_WAVES * RR_WIDE_WORDS * sizeof(uint32_t);
-    constexpr bool two_ok = wide && SE_RR_TWO;
-    constexpr bool img_ok = wide && SE_RR_IMG && ITEMS <= RR_IMG_MAX_ITEMS && RR_THREADS == 512;
+    constexpr bool two_ok = wide;
+    constexpr bool img_ok = wide && ITEMS <= RR_IMG_MAX_ITEMS;
     static const char *force = tuning_env("SE_RANK_PEEL");   // -DSE_TUNING build only: "0" / "1" / "2" / "3" pins the variant
     if (force || !scratch) {
         if (force && force[0] == '1') return launch_rank_reg_variant<ITEMS, true, 1>(pdist, ldp, q, n, rank, idx64, ldr, nullptr, s);
@@ -1787,17 +1741,7 @@ static int launch_rank_runs(const float *pdist, int64_t ldp, int64_t q, int n, v
     const size_t cnt_words = (size_t)(1 << RR_HW_BITS) / 2;
     const size_t lds = (RR_WAVES * cnt_words + 32) * sizeof(uint32_t) + (size_t)RR_THREADS * ITEMS * sizeof(uint16_t);
     auto kern = rank_rows_reg_kernel<ITEMS, false, true, 0, true>;
-    struct Resident { hipError_t err; int64_t grid; };
-    static const Resident res = [&]() -> Resident {
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int dev = 0, occ = 0;
-        hipDeviceProp_t prop;
-        if (e == hipSuccess) e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)kern, RR_THREADS, lds);
-        if (e != hipSuccess) return {e, 0};
-        return {hipSuccess, (int64_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * (occ > 0 ? occ : 1)};
-    }();
+    static const Resident res = rank_resident((const void *)kern, lds);
     if (res.err != hipSuccess) return fail(SE_ERR_HIP, "se_rank_rows: kernel set-up failed: %s", hipGetErrorString(res.err));
     const RunsLayout y = rank_runs_layout(q, n);
     if (y.cap != (int64_t)RR_THREADS * ITEMS) return fail(SE_ERR_INVALID, "se_rank_rows: run layout mismatch");
@@ -1982,6 +1926,16 @@ static int rank_check_launch(const float *pdist, int64_t ldp, int64_t q, int n, 
     return SE_OK;
 }
 
+// product switches of the ranking, read once per process: SE_RANK_SAFE (ballot kernels only), SE_RANK_CHECK (the order guard
+// audits every row of every call; "0" = off), SE_RANK_VERBOSE (the probe's and the self-test's verdicts on stderr)
+struct RankEnv { bool safe, check, verbose; };
+static const RankEnv &rank_env()
+{
+    static const RankEnv env = {getenv("SE_RANK_SAFE") != nullptr, getenv("SE_RANK_CHECK") != nullptr && getenv("SE_RANK_CHECK")[0] != '0',
+                                getenv("SE_RANK_VERBOSE") != nullptr};
+    return env;
+}
+
 static std::atomic<int> rr_hw_state[64];   // per device: 0 unknown, 1 verified, -1 refuted (zero-initialised; two threads racing on the
                                            // probe both run it on their own workspace and store the same verdict)
 static std::atomic<int> rr_checked[64];    // per device: the guard has run once behind a hardware-ordered ranking
@@ -1990,8 +1944,7 @@ static std::atomic<int> rr_checked[64];    // per device: the guard has run once
 // runs the probe (needs 256 bytes of caller workspace, synchronises the stream once); SE_RANK_SAFE=1 forces 0.
 static int rank_hw_order_ok(void *workspace, int64_t workspace_bytes, hipStream_t s)
 {
-    static const bool forced_safe = getenv("SE_RANK_SAFE") != nullptr;
-    if (forced_safe) return 0;
+    if (rank_env().safe) return 0;
     std::atomic<int> *state = rr_hw_state;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
@@ -2005,7 +1958,7 @@ static int rank_hw_order_ok(void *workspace, int64_t workspace_bytes, hipStream_
             return 0;
         const int verdict = (h[0] == 0u && h[1] == (uint32_t)(RR_PROBE_BLOCKS * RR_WAVES)) ? 1 : -1;
         state[dev].store(verdict, std::memory_order_release);
-        if (getenv("SE_RANK_VERBOSE"))
+        if (rank_env().verbose)
             fprintf(stderr, "[se_rank_rows] LDS returning-add order probe on device %d: %u mismatches, %u waves -> %s kernel\n", dev,
                     h[0], h[1], verdict == 1 ? "hardware-ordered" : "ballot");
     }
@@ -2061,8 +2014,7 @@ extern "C" int se_rank_rows_init(void *workspace, int64_t workspace_bytes, se_st
         // SE_RANK_SAFE, or the probe refuted the lane order: ballot kernels, nothing to audit.  A probe that could NOT run (stream under
         // capture, a failed synchronise / copy) leaves the verdict open: the device must not count as audited then -- a later se_rank_rows
         // could probe successfully and would run the hardware-ordered kernels with neither this self-test nor its first-call guard.
-        static const bool forced_safe = getenv("SE_RANK_SAFE") != nullptr;
-        if (!forced_safe && rr_hw_state[dev].load(std::memory_order_acquire) == 0)
+        if (!rank_env().safe && rr_hw_state[dev].load(std::memory_order_acquire) == 0)
             return fail(SE_ERR_HIP, "se_rank_rows_init: the capability probe could not run on this stream (under capture?); the device stays unaudited");
         rr_checked[dev].store(1, std::memory_order_release);
         return SE_OK;
@@ -2074,14 +2026,13 @@ extern "C" int se_rank_rows_init(void *workspace, int64_t workspace_bytes, se_st
     int32_t *rk = (int32_t *)w;                                  w += (RI_ROWS * ld * 4 + 255) / 256 * 256;
     void *runs_ws = w;
     uint32_t total_bad = 0;
-    const bool verbose = getenv("SE_RANK_VERBOSE") != nullptr;
     auto audit = [&](const char *what, int n, int rc) -> int {
         if (rc != SE_OK) return rc;
         if (const int rc2 = rank_check_launch(pd, ld, RI_ROWS, n, rk, 0, ld, bad, RC_CAP, 1, s)) return rc2;
         uint32_t h = 0;
         SE_HIP_CHECK(hipStreamSynchronize(s));
         SE_HIP_CHECK(hipMemcpy(&h, bad, sizeof(h), hipMemcpyDeviceToHost));
-        if (verbose || h) fprintf(stderr, "[se_rank_rows_init] device %d, %s: %u of %d rows out of canonical order\n", dev, what, h, RI_ROWS);
+        if (rank_env().verbose || h) fprintf(stderr, "[se_rank_rows_init] device %d, %s: %u of %d rows out of canonical order\n", dev, what, h, RI_ROWS);
         total_bad += h;
         return SE_OK;
     };
@@ -2089,11 +2040,7 @@ extern "C" int se_rank_rows_init(void *workspace, int64_t workspace_bytes, se_st
         hipLaunchKernelGGL(rank_selftest_fill_kernel, dim3((unsigned)(((int64_t)RI_ROWS * n + 255) / 256)), dim3(256), 0, s, pd, ld, RI_ROWS, n, mode);
     };
     constexpr int IS = (RI_N_SHORT + RR_THREADS - 1) / RR_THREADS <= 8 ? 8 : 12;          // short instantiation that holds RI_N_SHORT
-#if SE_RR_THREADS == 512
     constexpr int IL = 72;                                                                // long instantiation that holds RI_N_LONG (and the 35,000-column segments)
-#else
-    constexpr int IL = 70;
-#endif
     static_assert((int64_t)IL * RR_THREADS >= RI_N_LONG, "self-test row does not fit its instantiation");
     int rc;
     fill(RI_N_SHORT, 0);
@@ -2104,20 +2051,14 @@ extern "C" int se_rank_rows_init(void *workspace, int64_t workspace_bytes, se_st
     if ((rc = audit("long rows, plain", RI_N_LONG, launch_rank_reg_variant<IL, true, 0>(pd, ld, RI_ROWS, RI_N_LONG, rk, 0, ld, nullptr, s)))) return rc;
     fill(RI_N_LONG, 1);
     if ((rc = audit("long rows, group-peeling", RI_N_LONG, launch_rank_reg_variant<IL, true, 1>(pd, ld, RI_ROWS, RI_N_LONG, rk, 0, ld, nullptr, s)))) return rc;
-#if SE_RR_TWO
     fill(RI_N_LONG, 2);
     if ((rc = audit("long rows, two-pass", RI_N_LONG, launch_rank_reg_variant<IL, true, 2>(pd, ld, RI_ROWS, RI_N_LONG, rk, 0, ld, nullptr, s)))) return rc;
-#endif
-#if SE_RR_IMG && SE_RR_THREADS == 512
     fill(RI_N_LONG, 3);
     if ((rc = audit("long rows, image path", RI_N_LONG, launch_rank_reg_variant<IL, true, 3>(pd, ld, RI_ROWS, RI_N_LONG, rk, 0, ld, nullptr, s)))) return rc;
-#endif
-#if SE_RR_THREADS == 512
     if (rank_runs_ok(RI_N_SEG) && rank_runs_items(RI_N_SEG) == IL) {
         fill(RI_N_SEG, 1);
         if ((rc = audit("segment runs + merge", RI_N_SEG, launch_rank_runs<IL>(pd, ld, RI_ROWS, RI_N_SEG, rk, 0, ld, runs_ws, s)))) return rc;
     }
-#endif
     if (total_bad) {
         rr_hw_state[dev].store(-1, std::memory_order_release);
         fprintf(stderr, "[se_rank_rows_init] device %d leaves the hardware-ordered ranking kernels (ballot / tiled kernels from now on)\n", dev);
@@ -2134,6 +2075,57 @@ extern "C" int64_t se_rank_rows_workspace_bytes(int64_t q, int64_t n)
     if (!rank_runs_ok(n)) return tiled;
     const int64_t runs = rank_runs_bytes(q, n);              // sorted runs + merge; the tiled kernel stays the fallback (same buffer)
     return runs > tiled ? runs : tiled;
+}
+
+// The register-resident instantiations (keys per thread), smallest first: a row takes the first that holds it.  First launch,
+// whole-call redo and per-row repair share this one table; the run path has its own.
+static int launch_rank_reg_items(int items, const float *pdist, int64_t ldp, int64_t q, int n, void *rank, int idx64, int64_t ldr, bool hw,
+                                 void *scratch, hipStream_t s)
+{
+    using Launch = int (*)(const float *, int64_t, int64_t, int, void *, int, int64_t, bool, void *, hipStream_t);
+    static constexpr struct { int items; Launch launch; } table[] = {
+        {2, launch_rank_reg<2>},   {8, launch_rank_reg<8>},   {12, launch_rank_reg<12>}, {20, launch_rank_reg<20>}, {30, launch_rank_reg<30>},
+        {40, launch_rank_reg<40>}, {46, launch_rank_reg<46>}, {52, launch_rank_reg<52>}, {58, launch_rank_reg<58>}, {64, launch_rank_reg<64>},
+        {72, launch_rank_reg<72>}, {80, launch_rank_reg<80>}, {88, launch_rank_reg<88>}, {98, launch_rank_reg<98>}, {104, launch_rank_reg<104>}};
+    for (const auto &e : table)
+        if (items <= e.items) return e.launch(pdist, ldp, q, n, rank, idx64, ldr, hw, scratch, s);
+    return SE_ERR_INVALID;
+}
+
+// items: rank_runs_items(n), one of the long-row instantiations below
+static int launch_rank_runs_items(int items, const float *pdist, int64_t ldp, int64_t q, int n, void *rank, int idx64, int64_t ldr, void *workspace,
+                                  hipStream_t s)
+{
+    using Launch = int (*)(const float *, int64_t, int64_t, int, void *, int, int64_t, void *, hipStream_t);
+    static constexpr struct { int items; Launch launch; } table[] = {
+        {64, launch_rank_runs<64>}, {72, launch_rank_runs<72>}, {80, launch_rank_runs<80>}, {88, launch_rank_runs<88>}, {98, launch_rank_runs<98>},
+        {104, launch_rank_runs<104>}};
+    for (const auto &e : table)
+        if (items <= e.items) return e.launch(pdist, ldp, q, n, rank, idx64, ldr, workspace, s);
+    return SE_ERR_INVALID;
+}
+
+// rows the order guard looks at: every row under SE_RANK_CHECK=1, else 512 evenly spaced ones (a broken lane order is systematic)
+static int64_t rank_guard_stride(int64_t q) { return rank_env().check ? 1 : (q > 512 ? q / 512 : 1); }
+
+// Order guard behind a hardware-ordered ranking (see rank_check_kernel): checks every row_stride-th row, lists the offending ones
+// behind the workspace's first 256 bytes (count, then up to RC_CAP rows) and marks the device as audited.  Returns the number of rows out of order, or a
+// negative error code.  On a violation the device leaves the hardware-ordered kernels; the caller repairs the ranking.
+static int64_t rank_order_guard(const float *pdist, int64_t ldp, int64_t q, int n, void *rank, int idx64, int64_t ldr, void *workspace,
+                                int64_t row_stride, int dev, hipStream_t s)
+{
+    if (kTuning && tuning_env("SE_RANK_INJECT")) {
+        hipLaunchKernelGGL(rank_inject_kernel, dim3((unsigned)((q / 7 + 256) / 256)), dim3(256), 0, s, rank, idx64, ldr, q, n);
+        SE_LAUNCH_CHECK();
+    }
+    uint32_t *bad = (uint32_t *)((char *)workspace + 256);
+    if (const int rc = rank_check_launch(pdist, ldp, q, n, rank, idx64, ldr, bad, RC_CAP, row_stride, s)) return rc;
+    uint32_t nbad = 0;
+    SE_HIP_CHECK(hipStreamSynchronize(s));
+    SE_HIP_CHECK(hipMemcpy(&nbad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    rr_checked[dev].store(1, std::memory_order_release);
+    if (nbad != 0) rr_hw_state[dev].store(-1, std::memory_order_release);
+    return nbad;
 }
 
 extern "C" int se_rank_rows(const float *pdist, int64_t ldp, int64_t q, int64_t n, void *rank, int idx64,
@@ -2154,60 +2146,27 @@ extern "C" int se_rank_rows(const float *pdist, int64_t ldp, int64_t q, int64_t 
         // se_rank_rows_init, and under SE_RANK_CHECK=1
         int dev = 0;
         const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
-        static const bool check_always = getenv("SE_RANK_CHECK") != nullptr && getenv("SE_RANK_CHECK")[0] != '0';
         const bool audited = have_dev && rr_checked[dev].load(std::memory_order_acquire) != 0;
         const bool can_guard = have_dev && workspace && workspace_bytes >= 256 + 4 * (RC_CAP + 2);
         if (hw && !audited && !can_guard) hw = false;   // never run the hardware-ordered kernel unaudited: no room for the guard -> ballot kernel
-        const bool guard = hw && can_guard && (check_always || !audited);
-        int rc = SE_ERR_INVALID;
-#define SE_RR_CASE(I) if (rc == SE_ERR_INVALID && items <= I) rc = launch_rank_reg<I>(pdist, ldp, q, (int)n, rank, idx64, ldr, hw, scratch, s);
-#if SE_RR_THREADS == 512
-        SE_RR_CASES_512
-#else
-        SE_RR_CASE(2) SE_RR_CASE(6) SE_RR_CASE(14) SE_RR_CASE(28) SE_RR_CASE(44) SE_RR_CASE(56) SE_RR_CASE(66) SE_RR_CASE(70)
-#endif
-#undef SE_RR_CASE
+        const bool guard = hw && can_guard && (rank_env().check || !audited);
+        const int rc = launch_rank_reg_items(items, pdist, ldp, q, (int)n, rank, idx64, ldr, hw, scratch, s);
         if (rc != SE_OK || !guard) return rc;
-        if (kTuning && tuning_env("SE_RANK_INJECT")) {
-            hipLaunchKernelGGL(rank_inject_kernel, dim3((unsigned)((q / 7 + 256) / 256)), dim3(256), 0, s, rank, idx64, ldr, q, (int)n);
-            SE_LAUNCH_CHECK();
-        }
-        uint32_t *bad = (uint32_t *)((char *)workspace + 256);
-        const int64_t row_stride = check_always ? 1 : (q > 512 ? q / 512 : 1);      // first call: a sample of the rows
-        if (const int rc2 = rank_check_launch(pdist, ldp, q, (int)n, rank, idx64, ldr, bad, RC_CAP, row_stride, s)) return rc2;
-        uint32_t h[RC_CAP + 1];
-        SE_HIP_CHECK(hipStreamSynchronize(s));
-        SE_HIP_CHECK(hipMemcpy(h, bad, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        rr_checked[dev].store(1, std::memory_order_release);
-        if (h[0] == 0) return SE_OK;
-        // the hardware-ordered ranking broke its own invariant: never use it again on this device, repair with the ballot kernel
-        rr_hw_state[dev].store(-1, std::memory_order_release);
+        const int64_t row_stride = rank_guard_stride(q);
+        const int64_t nbad = rank_order_guard(pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, row_stride, dev, s);
+        if (nbad <= 0) return (int)nbad;
+        // the hardware-ordered ranking broke its own invariant: repair with the ballot kernel
         fprintf(stderr, "[se_rank_rows] order guard: %u of %lld rows out of canonical order behind the hardware-ordered kernel -- re-ranking them "
-                        "with the ballot kernel; device %d uses the ballot kernel from now on\n", h[0], (long long)q, dev);
-        const uint32_t nbad = h[0];
-        if (nbad > (uint32_t)RC_CAP || row_stride > 1) {   // more than the list holds, or only a sample was looked at: redo the whole call
-#define SE_RR_CASE(I) if (items <= I) return launch_rank_reg<I>(pdist, ldp, q, (int)n, rank, idx64, ldr, false, scratch, s);
-#if SE_RR_THREADS == 512
-            SE_RR_CASES_512
-#else
-            SE_RR_CASE(2) SE_RR_CASE(6) SE_RR_CASE(14) SE_RR_CASE(28) SE_RR_CASE(44) SE_RR_CASE(56) SE_RR_CASE(66) SE_RR_CASE(70)
-#endif
-#undef SE_RR_CASE
-        }
-        SE_HIP_CHECK(hipMemcpy(h + 1, bad + 1, nbad * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                        "with the ballot kernel; device %d uses the ballot kernel from now on\n", (unsigned)nbad, (long long)q, dev);
+        if (nbad > RC_CAP || row_stride > 1)   // more than the list holds, or only a sample was looked at: redo the whole call
+            return launch_rank_reg_items(items, pdist, ldp, q, (int)n, rank, idx64, ldr, false, scratch, s);
+        uint32_t rows[RC_CAP];
+        SE_HIP_CHECK(hipMemcpy(rows, (uint32_t *)((char *)workspace + 256) + 1, nbad * sizeof(uint32_t), hipMemcpyDeviceToHost));
         const size_t esz = rank_idx_bytes(idx64);
-        for (uint32_t i = 0; i < nbad; i++) {
-            const int64_t row = h[1 + i];
+        for (int64_t i = 0; i < nbad; i++) {
+            const int64_t row = rows[i];
             void *rrow = (char *)rank + (size_t)row * (size_t)ldr * esz;
-            int rc3 = SE_ERR_INVALID;
-#define SE_RR_CASE(I) if (rc3 == SE_ERR_INVALID && items <= I) rc3 = launch_rank_reg<I>(pdist + row * ldp, ldp, 1, (int)n, rrow, idx64, ldr, false, nullptr, s);
-#if SE_RR_THREADS == 512
-            SE_RR_CASES_512
-#else
-            SE_RR_CASE(2) SE_RR_CASE(6) SE_RR_CASE(14) SE_RR_CASE(28) SE_RR_CASE(44) SE_RR_CASE(56) SE_RR_CASE(66) SE_RR_CASE(70)
-#endif
-#undef SE_RR_CASE
-            if (rc3 != SE_OK) return rc3;
+            if (const int rc2 = launch_rank_reg_items(items, pdist + row * ldp, ldp, 1, (int)n, rrow, idx64, ldr, false, nullptr, s)) return rc2;
         }
         return SE_OK;
     }
@@ -2216,51 +2175,22 @@ extern "C" int se_rank_rows(const float *pdist, int64_t ldp, int64_t q, int64_t 
     if ((((uintptr_t)workspace) & 15) != 0) return fail(SE_ERR_INVALID, "se_rank_rows: workspace must be 16-byte aligned");
     if (rank_runs_ok(n) && rank_hw_order_ok(workspace, workspace_bytes, s)) {
         // RR_MAX_N < n <= 8 RR_MAX_N: 2 / 4 / 8 sorted runs per row (hardware-ordered register-resident kernel on the segments) + merge tree
-        const int items = rank_runs_items(n);
-        int rc = SE_ERR_INVALID;
-#ifdef SE_RR_DEV
-        if (items != 98) return fail(SE_ERR_INVALID, "se_rank_rows: -DSE_RR_DEV build");
-        rc = launch_rank_runs<98>(pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, s);
-#else
-        if (items == 64) rc = launch_rank_runs<64>(pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, s);
-        else if (items == 72) rc = launch_rank_runs<72>(pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, s);
-        else if (items == 80) rc = launch_rank_runs<80>(pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, s);
-        else if (items == 88) rc = launch_rank_runs<88>(pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, s);
-        else if (items == 98) rc = launch_rank_runs<98>(pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, s);
-        else rc = launch_rank_runs<104>(pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, s);
-#endif
+        const int rc = launch_rank_runs_items(rank_runs_items(n), pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, s);
         if (rc != SE_OK) return rc;
         int dev = 0;
         const bool have_dev = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
-        static const bool check_always = getenv("SE_RANK_CHECK") != nullptr && getenv("SE_RANK_CHECK")[0] != '0';
-        if (!have_dev || !(check_always || rr_checked[dev].load(std::memory_order_acquire) == 0)) return SE_OK;
+        if (!have_dev || !(rank_env().check || rr_checked[dev].load(std::memory_order_acquire) == 0)) return SE_OK;
         if (kTuning && tuning_env("SE_RANK_NOGUARD")) return SE_OK;   // -DSE_TUNING build only: look at the raw output of the run kernels
-        if (kTuning && tuning_env("SE_RANK_INJECT")) {
-            hipLaunchKernelGGL(rank_inject_kernel, dim3((unsigned)((q / 7 + 256) / 256)), dim3(256), 0, s, rank, idx64, ldr, q, (int)n);
-            SE_LAUNCH_CHECK();
-        }
-        // order guard, as for the short rows: a sample of the rows behind the first hardware-ordered call of the process (every row
-        // under SE_RANK_CHECK=1); on a violation the whole call is redone by the tiled kernel below and the device leaves the fast paths
-        uint32_t *bad = (uint32_t *)((char *)workspace + 256);
-        const int64_t row_stride = check_always ? 1 : (q > 512 ? q / 512 : 1);
-        if (const int rc2 = rank_check_launch(pdist, ldp, q, (int)n, rank, idx64, ldr, bad, RC_CAP, row_stride, s)) return rc2;
-        uint32_t nbad = 0;
-        SE_HIP_CHECK(hipStreamSynchronize(s));
-        SE_HIP_CHECK(hipMemcpy(&nbad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        rr_checked[dev].store(1, std::memory_order_release);
-        if (nbad == 0) return SE_OK;
-        rr_hw_state[dev].store(-1, std::memory_order_release);
+        // order guard, as for the short rows; on a violation the whole call is redone by the tiled kernel below
+        const int64_t nbad = rank_order_guard(pdist, ldp, q, (int)n, rank, idx64, ldr, workspace, rank_guard_stride(q), dev, s);
+        if (nbad <= 0) return (int)nbad;
         fprintf(stderr, "[se_rank_rows] order guard: %u of %lld rows out of canonical order behind the hardware-ordered run kernel -- re-ranking the "
-                        "call with the tiled kernel; device %d leaves the hardware-ordered paths\n", nbad, (long long)q, dev);
+                        "call with the tiled kernel; device %d leaves the hardware-ordered paths\n", (unsigned)nbad, (long long)q, dev);
     }
     const size_t lds = sizeof(RankLds);
-    if (idx64) {
-        SE_HIP_CHECK(hipFuncSetAttribute((const void *)rank_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(rank_rows_kernel<true>, dim3((unsigned)rank_grid(q)), dim3(RK_THREADS), lds, s, pdist, ldp, q, (int)n, rank, ldr, (uint32_t *)workspace, rank_npad(n));
-    } else {
-        SE_HIP_CHECK(hipFuncSetAttribute((const void *)rank_rows_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(rank_rows_kernel<false>, dim3((unsigned)rank_grid(q)), dim3(RK_THREADS), lds, s, pdist, ldp, q, (int)n, rank, ldr, (uint32_t *)workspace, rank_npad(n));
-    }
+    auto kern = idx64 ? rank_rows_kernel<true> : rank_rows_kernel<false>;
+    SE_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)rank_grid(q)), dim3(RK_THREADS), lds, s, pdist, ldp, q, (int)n, rank, ldr, (uint32_t *)workspace, rank_npad(n));
     SE_LAUNCH_CHECK();
     return SE_OK;
 }

@@ -14,6 +14,10 @@ namespace se {
 char *err_buf();
 int fail(int code, const char *fmt, ...);
 
+// compute units of the current device (256 when the query fails), read once per process: one process drives one GPU model.
+// (Hidden: an internal helper, not part of the library's exported symbols.)
+__attribute__((visibility("hidden"))) int num_cus();
+
 // Phase timing (se_phase_timing / se_phase_timing_read, include/sehip.h): when switched on, multi-kernel entry points record a HIP
 // event on their stream behind each phase.  Off (the default): one relaxed atomic load per mark.
 void phase_mark(const char *name, hipStream_t s);

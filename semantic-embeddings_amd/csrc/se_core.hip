@@ -67,6 +67,17 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
+int num_cus()
+{
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
+        return n > 0 ? n : 256;
+    }();
+    return cus;
+}
+
 }  // namespace se
 
 extern "C" int se_version(void) { return 310; /* 0.3.1: se_phase_timing / se_phase_timing_read */ }

@@ -853,11 +853,8 @@ __global__ __launch_bounds__(TK_THREADS) void topk_lists_kernel(const uint2 *__r
 constexpr int RF_MAX = 1024;            // exact recomputations per query the refinement takes
 constexpr int RF_WAVES = 4;
 constexpr int PF_K_MAX = RF_MAX / 2;
-#ifndef SE_RF_LPC
-#define SE_RF_LPC 4
-#endif
 constexpr int RF_STAGE_M = 384, RF_STAGE_D = 256;      // lists of up to RF_STAGE_M candidates with rows of RF_STAGE_D columns and more are staged through LDS:
-constexpr int RF_LPC = SE_RF_LPC;                       //   lanes per candidate row and load instruction (each 16 bytes)
+constexpr int RF_LPC = 4;                               //   lanes per candidate row and load instruction (each 16 bytes)
 constexpr int RF_KC = RF_LPC * 4;                       //   columns per chunk
 constexpr int RF_CPR = 1024 / RF_KC;                    //   candidates per round (a 4 KB block of rows per chunk)
 constexpr int RF_NI = RF_CPR * RF_LPC / 64;             //   load instructions per chunk
