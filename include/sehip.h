@@ -493,6 +493,53 @@ int se_svm_rowsum(const float *a, int64_t lda, int64_t c, int64_t len, double *o
 int se_svm_axpby(const double *alpha, const float *x, int64_t ldx, const double *beta, const float *y, int64_t ldy,
                  int64_t c, int64_t len, float *out, int64_t ldo, se_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Class embeddings: similarity tables of a hierarchy, unit-sphere / spheres embeddings
+ * ------------------------------------------------------------------------------------------ */
+
+/* flags of se_class_pair_tables */
+#define SE_CLASSEMB_DIAG_ONE 1 /* diagonal of the lcs table 1 (distance mode: 0), the convention of compute_class_embedding.py */
+#define SE_CLASSEMB_DIST 2     /* the lcs table receives the distance h / H instead of the similarity 1 - h / H            */
+#define SE_CLASSEMB_MAX_ANC 48 /* longest ancestor list of one class the pair-table kernel stages                            */
+
+/*
+ * Wu-Palmer and LCS-height tables of a list of classes.
+ * Replaces: ClassHierarchy.similarity_tables (the double loop over wup_similarity / lcs) and the lcs_height loop of
+ *           compute_class_embedding.py:212-216.
+ * Encoding (built on the host, ClassHierarchy.pair_table_encoding): every node of the classes' ancestor closure has a preference
+ * rank -- depth descending, height ascending, repr ascending, the tie-break of ClassHierarchy.lcs -- so lcs(a, b) is the common
+ * ancestor of smallest rank.
+ *   anc_off     [c + 1] int32 CSR offsets into anc_rank / anc_spl (nnz entries); a class's list holds itself and every ancestor,
+ *               at most max_anc (1 .. SE_CLASSEMB_MAX_ANC) entries, ranks ascending
+ *   anc_spl     shortest_path_length(class, ancestor) of every entry (in a DAG not always the upward distance)
+ *   rank_depth, rank_height  [n_ranks] int32 depth and height of the node of every rank; max_height the hierarchy's height H >= 1
+ *   wup, lcs    [c, c] f64 out (ldw / ldl elements between rows), either may be NULL (not both):
+ *               wup = 2 ds / ((ds + spl_a) + (ds + spl_b)), lcs = 1 - h / H (SE_CLASSEMB_DIST: h / H), with ds / h the depth /
+ *               height of lcs(a, b); IEEE divisions in float64 -- bitwise the host's values.  The diagonal of lcs is
+ *               1 - h(class) / H (ClassHierarchy.similarity_tables) unless SE_CLASSEMB_DIAG_ONE
+ *   missing     [1] int64 out: i c + j of the first pair (row-major, i < j) without a common ancestor, -1 if every pair has one;
+ *               the tables hold NaN at such pairs (the reference raises KeyError there)
+ * c = 0 is accepted (only `missing` is written).  Asynchronous; no workspace.
+ */
+int se_class_pair_tables(const int32_t *anc_off, const int32_t *anc_rank, const int32_t *anc_spl, int64_t nnz, int64_t c,
+                         int max_anc, const int32_t *rank_depth, const int32_t *rank_height, int64_t n_ranks, int max_height,
+                         int flags, double *wup, int64_t ldw, double *lcs, int64_t ldl, int64_t *missing, se_stream_t stream);
+
+/*
+ * In-place lower Cholesky factor of a symmetric float64 matrix: L L^T = A, L written over the lower triangle, exact zeros above the
+ * diagonal (only the lower triangle of A is read).
+ * Replaces: unitsphere_embedding (compute_class_embedding.py:14-40 -- row c solves E[:c, :c] x = S[c, :c] and sets E[c, c] =
+ *           sqrt(1 - |x|^2), which is the Cholesky factor of S) and the hypersphere intersections of euclidean_embedding
+ *           (:76-130), which are the Cholesky factor of the Gram matrix of the classes 1 .. n - 1 around class 0.
+ *   a      [n, n] f64 (lda >= n elements between rows), in / out
+ *   info   [1] int32 out (device): -1 on success, else the first row whose pivot is <= 0 or NaN (LAPACK potrf's rule, 0-based);
+ *          then L[info, info] and every row after it are NaN, like the reference's sqrt of a negative; rows before it are valid
+ * Blocked right-looking, block column 64, trailing update on v_mfma_f64_16x16x4_f64; no host synchronisation, no workspace;
+ * n = 0 is accepted (info = -1).  Not bit-equal to LAPACK (another summation order): for a well-conditioned S with unit
+ * diagonal, |L - L_lapack| and |L L^T - S| stay within a few n eps (tests/test_gpu_class_embedding.py: <= 1e-12 up to n = 8142).
+ */
+int se_cholesky_f64(double *a, int64_t lda, int64_t n, int32_t *info, se_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,50 @@ class ClassHierarchy(object):
             self._luts[key] = (wup, lcs)
         return self._luts[key]
 
+    def pair_table_encoding(self, classes):
+        """What ``se_class_pair_tables`` reads, built in time linear in the size of the hierarchy (no pairwise loop).
+
+        Every node of the ancestor closure of ``classes`` gets a preference rank: depth descending, height ascending, repr
+        ascending -- the order in which ``lcs`` picks among common ancestors -- so that ``lcs(a, b)`` is the common ancestor of
+        smallest rank.  Per class (CSR): the ranks of its ancestors (itself included), ascending, and ``shortest_path_length``
+        to each (in a DAG the path may pass through a higher common ancestor, so it is not always the upward distance).
+        Returns a dict of int32 arrays ``off`` [C + 1], ``rank`` / ``spl`` [nnz], ``depth`` / ``height`` [R] (per rank), the
+        ``nodes`` in rank order, ``max_anc`` (longest list) and ``max_height``."""
+        key = tuple(classes)
+        anc = [self.all_hypernym_depths(c) for c in key]
+        nodes = sorted(set().union(*anc), key=lambda h: (-self.depth(h), self.heights[h], repr(h)))
+        pos = {h: r for r, h in enumerate(nodes)}
+        off = np.zeros(len(key) + 1, dtype=np.int32)
+        ranks, spls = [], []
+        for i, (c, a) in enumerate(zip(key, anc)):
+            rs = sorted(pos[h] for h in a)
+            ranks.extend(rs)
+            spls.extend(self.shortest_path_length(c, nodes[r]) for r in rs)
+            off[i + 1] = len(ranks)
+        return {'off': off, 'rank': np.asarray(ranks, dtype=np.int32), 'spl': np.asarray(spls, dtype=np.int32),
+                'depth': np.asarray([self.depth(h) for h in nodes], dtype=np.int32),
+                'height': np.asarray([self.heights[h] for h in nodes], dtype=np.int32), 'nodes': nodes,
+                'max_anc': int(np.diff(off).max()) if len(key) else 1, 'max_height': self.max_height}
+
+    def similarity_tables_device(self, classes, diag_one=False, distance=False, want_wup=True, want_lcs=True, device=None):
+        """``similarity_tables(classes)`` as float64 [C, C] device tensors, bitwise (``se_class_pair_tables``): (wup, lcs), an
+        unrequested table is None.  ``diag_one``: lcs diagonal 1 (compute_class_embedding.py's convention) instead of
+        1 - height(c) / H; ``distance``: the lcs table holds the LCS height h / H instead of 1 - h / H.  Raises KeyError naming
+        the first pair of classes without a common ancestor."""
+        import torch
+        import sehip
+        key = tuple(classes)
+        enc = self.pair_table_encoding(key)
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        ints = {k: torch.from_numpy(enc[k]).to(dev) for k in ('off', 'rank', 'spl', 'depth', 'height')}
+        wup, lcs, missing = sehip.class_pair_tables(ints['off'], ints['rank'], ints['spl'], ints['depth'], ints['height'],
+                                                    enc['max_anc'], enc['max_height'], diag_one=diag_one, distance=distance,
+                                                    want_wup=want_wup, want_lcs=want_lcs)
+        miss = int(missing.item())
+        if miss >= 0:
+            raise KeyError('classes {!r} and {!r} have no common ancestor'.format(key[miss // len(key)], key[miss % len(key)]))
+        return wup, lcs
+
     # ------------------------------------------------------------------ retrieval metrics
 
     def hierarchical_precision(self, retrieved, labels, ks=[1, 10, 50, 100], compute_ahp=False, compute_ap=False,
@@ -304,6 +348,7 @@ class ClassHierarchy(object):
         import torch
         from sharded_retrieval import shard_bounds, sharded_topk
         kernels = dict(kernels or {})
+        stand_ins = bool(kernels)
         native_metrics = 'hierarchical_precision' not in kernels
         native_ranking = 'ranking_tiles' not in kernels
         if 'ranking_tiles' not in kernels or 'hierarchical_precision' not in kernels:
@@ -320,15 +365,26 @@ class ClassHierarchy(object):
         class_list = sorted(set(lab), key=lambda c: (str(type(c)), c))
         pos = {c: i for i, c in enumerate(class_list)}
         cls_h = np.array([pos[c] for c in lab], dtype=np.int32)
-        wup_t, lcs_t = self.similarity_tables(class_list)
+        dev = kernels.get('device') or torch.device('cuda', torch.cuda.current_device())
+        # with the native kernels the class tables are built on the device as well (se_class_pair_tables: the same bits as
+        # similarity_tables, whose double loop costs ~18 us per pair on the host); CPU stand-ins keep the host tables
+        native_tables = (not stand_ins) and torch.device(dev).type == 'cuda'
+        if native_tables:
+            wup_t, lcs_t = self.similarity_tables_device(class_list, device=dev)
+        else:
+            wup_t, lcs_t = self.similarity_tables(class_list)
         # best-possible cumulative similarity per query class: descending-sorted similarities of the whole gallery.  The C x N float64
         # curves are built ON THE DEVICE (round 6: 180 host cumsums of 50,000 entries + 80 MB of host-to-device copies were 25 of the 56 ms
         # of a 50,000-item evaluation): per class the C similarity values in descending order, each repeated by its class count,
         # then one float64 prefix sum per row.
         counts = np.bincount(cls_h, minlength=len(class_list))
-        dev = kernels.get('device') or torch.device('cuda', torch.cuda.current_device())
 
         def best_curves(table):
+            if torch.is_tensor(table):      # device table: the descending values are the same whatever order ties take
+                vals, order = torch.sort(table, dim=1, descending=True)
+                reps = torch.from_numpy(counts.astype(np.int64)).to(dev)[order]
+                flat = torch.repeat_interleave(vals.reshape(-1), reps.reshape(-1), output_size=len(class_list) * n)
+                return flat.view(len(class_list), n).cumsum(dim=1)
             table = np.asarray(table, dtype=np.float64)
             order = np.argsort(-table, axis=1, kind='stable')
             vals = torch.from_numpy(np.take_along_axis(table, order, axis=1)).to(dev)
@@ -364,7 +420,7 @@ class ClassHierarchy(object):
             # ---- top-L lists are enough for every requested metric: fused distance + top-L (the N x N matrix is never written),
             #      over this rank's shard of the gallery when there are several ranks ----
             L = min(n, max(ks + [ahp_clip or 0]) + 1)
-            args_d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (wup_t, lcs_t)] + [best_w[:, :L + 1].contiguous(), best_l[:, :L + 1].contiguous()]
+            args_d = [_on_device(a, dev) for a in (wup_t, lcs_t)] + [best_w[:, :L + 1].contiguous(), best_l[:, :L + 1].contiguous()]
             g0, g1 = shard_bounds(n, world)[rank]
             if 'local_topk' not in kernels:
                 import sehip
@@ -382,7 +438,7 @@ class ClassHierarchy(object):
                                                              qidx_d[q0:q1].contiguous(), *args_d, ks_d, ahp_len=ahp_len, want_ap=False,
                                                              **curves(args_d)))
         else:
-            args_d = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (wup_t, lcs_t)] + [best_w, best_l]
+            args_d = [_on_device(a, dev) for a in (wup_t, lcs_t)] + [best_w, best_l]
             extra = curves(args_d)      # once per gallery, shared by every tile
             # (16-bit ranks between the two kernels -- ranking_tiles(idx16=True), se_hierarchical_precision_r16 -- give the same results
             # from half the bytes, but measured at 50k x 50k the ranking gains 0.24 ms and the metric kernel, which is not bound by its
@@ -431,6 +487,11 @@ class ClassHierarchy(object):
             sums = sums.cpu().numpy()
             return {name: float(sums[c]) / n for name, c in col.items()}, prec
         return {metric: sum(values.values()) / len(values) for metric, values in prec.items()}, prec
+
+
+def _on_device(table, dev):
+    import torch
+    return table if torch.is_tensor(table) else torch.from_numpy(np.ascontiguousarray(table)).to(dev)
 
 
 def _average_precision(relevant):

@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from ._lib import DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, METRIC_EUCLID, SehipError, call, require_gpu
+from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, METRIC_EUCLID, SehipError, call, require_gpu
 
 __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
@@ -18,7 +18,7 @@ __all__ = [
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
     "recall_precision_reduce", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
-    "svm_axpby",
+    "svm_axpby", "class_pair_tables", "cholesky_lower_",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
 ]
 
@@ -818,3 +818,46 @@ def svm_axpby(alpha, x, beta, y, out=None, length=None):
     ldx, ldy, ldo = _f32_2d(x, "x", length), _f32_2d(y, "y", length), _f32_2d(out, "out", length)
     call("se_svm_axpby", alpha, x, ldx, beta, y, ldy, x.shape[0], length, out, ldo)
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# class embeddings: similarity tables of a hierarchy, Cholesky factor (classemb.hip; the CLI is compute_class_embedding.py)
+# --------------------------------------------------------------------------------------------
+
+def class_pair_tables(off, rank, spl, depth, height, max_anc, max_height, diag_one=False, distance=False, want_wup=True,
+                      want_lcs=True):
+    """``se_class_pair_tables`` over the encoding of ``ClassHierarchy.pair_table_encoding`` (contiguous int32 device tensors).
+    Returns ``(wup, lcs, missing)``: float64 [C, C] tables (None when not wanted) and an int64 [1] device tensor holding
+    i C + j of the first pair without a common ancestor, or -1.  ``distance``: lcs holds h / H; ``diag_one``: lcs diagonal 1
+    (0 with ``distance``)."""
+    require_gpu(off, rank, spl, depth, height)
+    for t, name in ((off, "off"), (rank, "rank"), (spl, "spl"), (depth, "depth"), (height, "height")):
+        _i32(t, name)
+    if rank.numel() != spl.numel() or depth.numel() != height.numel():
+        raise SehipError("class_pair_tables: rank / spl and depth / height need one length each")
+    if not (want_wup or want_lcs):
+        raise SehipError("class_pair_tables: no table requested")
+    C = off.numel() - 1
+    dev = off.device
+    wup = torch.empty((C, C), dtype=torch.float64, device=dev) if want_wup else None
+    lcs = torch.empty((C, C), dtype=torch.float64, device=dev) if want_lcs else None
+    missing = torch.empty((1,), dtype=torch.int64, device=dev)
+    flags = (DEFINES["SE_CLASSEMB_DIAG_ONE"] if diag_one else 0) | (DEFINES["SE_CLASSEMB_DIST"] if distance else 0)
+    call("se_class_pair_tables", off, rank, spl, rank.numel(), C, int(max_anc), depth, height, depth.numel(), int(max_height), flags,
+         wup, max(C, 1), lcs, max(C, 1), missing)
+    return wup, lcs, missing
+
+
+def cholesky_lower_(a, info=None):
+    """``se_cholesky_f64`` in place on a float64 [n, n] device tensor with contiguous rows: the lower Cholesky factor, exact zeros
+    above the diagonal.  Returns ``(a, info)``: info an int32 [1] device tensor, -1 on success, else the first row (0-based)
+    whose pivot was <= 0 or NaN -- that row's diagonal and every later row are NaN.  Nothing is synchronised."""
+    require_gpu(a, info)
+    if a.dtype != torch.float64 or a.dim() != 2 or a.shape[0] != a.shape[1] or (a.shape[0] > 1 and a.stride(1) != 1):
+        raise SehipError("cholesky_lower_ takes a square float64 matrix with contiguous rows")
+    n = a.shape[0]
+    if info is None:
+        info = torch.empty((1,), dtype=torch.int32, device=a.device)
+    _i32(info, "info")
+    call("se_cholesky_f64", a, a.stride(0) if n > 1 else max(n, 1), n, info)
+    return a, info

@@ -3,7 +3,9 @@
     python tools/bench_kernels.py pdist|rank|loss|topk [--n 50000 --d 100 --reps 5]
     python tools/bench_kernels.py recprec        (10k x 10k and 50k x 50k, 100 classes; --n is not used)
     python tools/bench_kernels.py svm            (margin + reduction kernels and whole LinearSVC fits: 50,000 x 100 x 100 and
-                                                  1,281,167 x 1000 x 1000; --n / --d are not used; --svm-sizes small skips the large one)"""
+                                                  1,281,167 x 1000 x 1000; --n / --d are not used; --svm-sizes small skips the large one)
+    python tools/bench_kernels.py classemb       (class pair tables and fp64 Cholesky at C = 1000 (ILSVRC WordNet DAG) and 8,142 (iNat
+                                                  2018), and the whole compute_class_embedding.py run on the iNat hierarchy)"""
 import argparse
 import os
 import sys
@@ -30,7 +32,7 @@ def timeit(fn, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm"])
+    ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -39,6 +41,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--svm-sizes", default="all", choices=["all", "small"], help="svm: both sizes, or 50,000 x 100 x 100 only")
     args = ap.parse_args()
+    if args.what == "classemb":
+        return bench_classemb(args.reps)
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -264,6 +268,59 @@ def main():
         x2, y2, E2 = torch.randn(B2, 100, device="cuda"), torch.randint(0, 100, (B2,), device="cuda"), E[:100, :100].contiguous()
         med, mn = timeit(lambda: sehip.cosine_loss_forward(x2, y2, E2), 20)
         print("loss fwd B=128 D=100: median %.1f us" % (med * 1e3))
+
+
+def bench_classemb(reps):
+    """se_class_pair_tables (both tables) and se_cholesky_f64 of S = 1 - lcs_height (unit diagonal), plus the full CLI on iNat."""
+    import pickle
+    import subprocess
+    import tempfile
+    import time
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_class_embedding_host import load_hierarchy
+    for name in ("wordnet_dag", "inat2018"):
+        h, classes = load_hierarchy(name)
+        enc = h.pair_table_encoding(classes)
+        ints = {k: torch.from_numpy(enc[k]).cuda() for k in ("off", "rank", "spl", "depth", "height")}
+        C = len(classes)
+
+        def tables():
+            return sehip.class_pair_tables(ints["off"], ints["rank"], ints["spl"], ints["depth"], ints["height"], enc["max_anc"],
+                                           enc["max_height"])
+        med, mn = timeit(tables, reps)
+        print("pair tables C=%d (%s, max %d ancestors): median %.3f ms (min %.3f)  %.1f GB/s written"
+              % (C, name, enc["max_anc"], med, mn, 16.0 * C * C / med / 1e6))
+        _, s, _ = sehip.class_pair_tables(ints["off"], ints["rank"], ints["spl"], ints["depth"], ints["height"], enc["max_anc"],
+                                          enc["max_height"], diag_one=True, want_wup=False)
+        a = torch.empty_like(s)
+
+        def chol():
+            a.copy_(s)
+            sehip.cholesky_lower_(a)
+        cp, _ = timeit(lambda: a.copy_(s), reps)
+        med, mn = timeit(chol, reps)
+        flop = C ** 3 / 3.0
+        print("cholesky n=%d f64: median %.3f ms (min %.3f; %.3f ms of it the copy)  %.2f TFLOP/s"
+              % (C, med, mn, cp, flop / ((med - cp) * 1e-3) / 1e12))
+    g = np.load(os.path.join(ROOT, "tests", "golden", "hierarchy_inat2018.npz"))
+    with tempfile.TemporaryDirectory() as tmp:
+        hp, cl, out = os.path.join(tmp, "h.txt"), os.path.join(tmp, "c.txt"), os.path.join(tmp, "e.pickle")
+        with open(hp, "w") as f:
+            f.writelines("%s %s\n" % (p, c) for p, c in g["edges"].tolist())
+        with open(cl, "w") as f:
+            f.writelines("%s\n" % c for c in g["classes"].tolist())
+        t0 = time.time()
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "semantic-embeddings_amd", "compute_class_embedding.py"), "--hierarchy", hp,
+                            "--str_ids", "--class_list", cl, "--out", out], capture_output=True, text=True)
+        wall = time.time() - t0
+        print(r.stdout.strip())
+        if r.returncode != 0:
+            print(r.stderr[-2000:])
+            raise SystemExit(r.returncode)
+        with open(out, "rb") as f:
+            e = pickle.load(f)["embedding"]
+        print("compute_class_embedding.py iNat 2018 (8,142 classes, unitsphere): %.1f s wall (process start to exit), finite %s"
+              % (wall, bool(np.isfinite(e).all())))
 
 
 if __name__ == "__main__":
