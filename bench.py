@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the cosine-embedding training + retrieval hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload retrieval|train] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload retrieval|train] [--dump-outputs DIR] [--full]
 
 One JSON line on stdout (rank 0).  See DESIGN.md section 6 for what a "step" is:
 
@@ -10,14 +10,18 @@ One JSON line on stdout (rank 0).  See DESIGN.md section 6 for what a "step" is:
   resident in HBM -- row normalisation, all-pairs cosine distance matrix, full canonical ranking.
   value = query x gallery pairs ranked per second (Mpairs/s), summed over ranks.  With N > 1 every
   rank evaluates its own 50k x 50k feature set (weak scaling, no data-path collective: retrieval jobs
-  and the rows of a ranking are independent -- SURVEY.md section 8e row 2).  AFTER the timed region the
-  last step's results are checked against the oracle at full size (``"verified"``, oracle/verify.py).
-* the same line carries, as objects next to the headline (all timed the same way, none part of ``value``):
-  ``train`` (BASELINE.json configs[1]: ResNet-110-fc step, images/s), ``train_r50`` (configs[3]: ResNet-50 224x224,
-  200 classes, per-GPU batch 64) and ``sharded_gallery`` (configs[4], the north_star retrieval split: 50,000 queries x
-  N x 160,146 gallery rows x D = 1000, per-shard fused distance + top-251 -> RCCL all-gather -> k-way merge, with the
-  three phases timed separately).
-* ``--workload train`` makes the training step the primary metric.
+  and the rows of a ranking are independent -- SURVEY.md section 8e row 2).
+* a plain run does only what the headline needs: set-up, warm-up, the timed steps, ``--dump-outputs`` and the line, whose
+  ``roofline`` / ``kernels`` objects come from the HIP events of the timed steps themselves (no runs of their own).
+* ``--full`` adds everything else, none of it part of ``value``: AFTER the timed region the last step's results are checked
+  against the oracle at full size (``"verified"``, oracle/verify.py), and the line carries, as objects next to the headline
+  (all timed the same way): ``train`` (BASELINE.json configs[1]: ResNet-110-fc step, images/s), ``train_r50`` (configs[3]:
+  ResNet-50 224x224, 200 classes, per-GPU batch 64), ``sharded_gallery`` (configs[4], the north_star retrieval split: 50,000
+  queries x N x 160,146 gallery rows x D = 1000, per-shard fused distance + top-251 -> RCCL all-gather -> k-way merge, with the
+  three phases timed separately), the CPU baselines, hierarchical precision, the guaranteed-order ranking, fused top-k,
+  long-row ranking and end-to-end evaluation legs, and at N > 1 the preflight's gradient all-reduce timings.
+* ``--workload train`` makes the training step the primary metric (``--full``: with its loss-head kernel times, standalone
+  gradient all-reduce and CPU baseline).
 * ``--dump-outputs DIR`` (retrieval): after the timed steps, rank 0 writes what the last timed step computed -- a fixed, seeded
   sample of the rows of its distance matrix and ranking, and those rows of the features they were computed from -- as float32 /
   float64 ``DIR/<name>.npy``, under 64 MB in all (``dump_outputs``).  The inputs are seeded, so two builds run with the same
@@ -75,14 +79,17 @@ def parse(argv=None):
     ap.add_argument("--q", type=int, default=None, help="query rows per rank (retrieval; default = n)")
     ap.add_argument("--d", type=int, default=100, help="feature dimension (retrieval)")
     ap.add_argument("--metric", default="cosine", choices=["cosine", "euclid"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every check and secondary measurement: post-run oracle check, CPU baselines, "
+                         "the other retrieval and training legs, per-leg rooflines (default off: the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-sample-queries", type=int, default=16384, help="query rows of the timed CPU sample (~13 s of host work, ~10 GB of host memory)")
     ap.add_argument("--with-train", dest="with_train", action="store_true", default=True,
-                    help="also time the ResNet-110-fc and ResNet-50 training steps (adds 'train' / 'train_r50' objects; default on)")
+                    help="--full: also time the ResNet-110-fc and ResNet-50 training steps (adds 'train' / 'train_r50' objects; default on)")
     ap.add_argument("--no-train", dest="with_train", action="store_false")
     ap.add_argument("--no-sharded", dest="with_sharded", action="store_false", default=True,
-                    help="skip the sharded-gallery top-k leg (configs[4])")
-    ap.add_argument("--no-verify", dest="verify", action="store_false", default=True, help="skip the post-run oracle check")
+                    help="--full: skip the sharded-gallery top-k leg (configs[4])")
+    ap.add_argument("--no-verify", dest="verify", action="store_false", default=True, help="--full: skip the post-run oracle check")
     ap.add_argument("--batch", type=int, default=128, help="per-GPU batch (train)")
     ap.add_argument("--arch", default="resnet-110-fc")
     ap.add_argument("--shard-rows", type=int, default=160146, help="gallery rows per rank of the sharded-gallery leg (1,281,167 / 8)")
@@ -152,8 +159,8 @@ def preflight(args, rank, world, local):
     """Before any large allocation: prove that the communicator this run depends on exists and moves data in the shapes the legs use,
     and say which rank drives which device.  N > 1 only (the first 8-GPU run of this repository is also its first RCCL run with more
     than one rank): a 4-byte all-reduce, ONE all_gather_into_tensor of the packed [2, 8, 251] top-k layout of the sharded-gallery leg,
-    the rank -> device -> PCI bus id map gathered through the communicator, and the standalone all-reduce time of the two gradient
-    buffers the training legs exchange (ResNet-110-fc: 7 MB, ResNet-50: 96 MB) as one flat call and as 25 MB buckets.  Any
+    the rank -> device -> PCI bus id map gathered through the communicator, and with --full the standalone all-reduce time of the two
+    gradient buffers the training legs exchange (ResNet-110-fc: 7 MB, ResNet-50: 96 MB) as one flat call and as 25 MB buckets.  Any
     inconsistency ends the run with ONE line naming it.  --dry runs the same sequence on gloo / CPU tensors."""
     info = {"world": world}
     if world <= 1:
@@ -194,10 +201,11 @@ def preflight(args, rank, world, local):
     if not args.dry and all(b >= 0 for _, _, b, _ in rows) and len({(b) for _, _, b, _ in rows}) != world:
         raise SystemExit("bench.py preflight: %d ranks share %d distinct PCI devices -- two ranks drive one GPU (LOCAL_RANK / visible-device mismatch)"
                          % (world, len({(b) for _, _, b, _ in rows})))
-    # standalone gradient all-reduce of the two training buffers: one flat call vs 25 MB buckets (what engine.BucketedAllReduce issues)
+    # --full: standalone gradient all-reduce of the two training buffers: one flat call vs 25 MB buckets (what engine.BucketedAllReduce
+    # issues)
     sizes = {"resnet110_fc_7MB": 6986752, "resnet50_96MB": 95777792} if not args.dry else {"tiny_64KB": 65536}
     ar = {}
-    for key, nbytes in sizes.items():
+    for key, nbytes in sizes.items() if args.full else ():
         buf = torch.zeros(nbytes // 4, dtype=torch.float32, device=dev)
         bucket = 25 * (1 << 20) // 4
         res = {}
@@ -220,7 +228,8 @@ def preflight(args, rank, world, local):
             res[mode + "_busbw_GBps"] = 2.0 * (world - 1) / world * nbytes / 1e6 / ms
         ar[key] = dict(res, bytes=nbytes)
         del buf
-    info["grad_allreduce"] = ar
+    if args.full:
+        info["grad_allreduce"] = ar
     info["seconds"] = time.perf_counter() - t0
     if rank == 0:
         print("[bench.py preflight] %d ranks, backend %s: %s" % (world, dist.get_backend(), json.dumps(info)), file=sys.stderr, flush=True)
@@ -448,7 +457,7 @@ def bench_retrieval(args, rank, world):
     }
     if dumped is not None:
         out["dump_outputs"] = dumped
-    if args.verify:
+    if args.full and args.verify:
         out.update(verify_last_step(last, pd, rk, metric, world))
         # scalars the driver's parsed subset keeps (it drops nested objects below `roofline` / `config`)
         out["roofline"]["verified"] = out["verified"]
@@ -948,72 +957,73 @@ def main(argv=None):
     elif args.workload == "train":
         from train_bench import bench_train
         out = bench_train(args, rank, world, scaling=args.scaling)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             from train_bench import cpu_baseline_train
             out["cpu_baseline"] = cpu_baseline_train(args)
     else:
         out, feats_h, rk = bench_retrieval(args, rank, world)
+        if args.full:                 # a plain run stops at the headline: every secondary leg below is --full only
 
-        def leg(name, fn):        # the retrieval line must survive a failure of a secondary leg -- but every rank must agree
-            try:
-                out[name] = fn()
-            except Exception as e:
-                out[name] = {"error": "%s: %s" % (type(e).__name__, e)}
-
-        leg("hierarchical_precision", lambda: bench_metrics(args, rk))
-        if rank == 0 and world == 1 and "error" not in out and args.metric == "cosine":
-            leg("guaranteed_order", lambda: bench_guaranteed_order(args))
-            if "kernels" in out and "error" not in out.get("guaranteed_order", {"error": 1}):
-                out["kernels"]["rank_rows"]["guaranteed_order_ms"] = out["guaranteed_order"]["ms_scaled_to_step"]
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported baseline: rank 0 at N = 1 only, bounded sample; it also
-            leg("cpu_baseline", lambda: cpu_baseline_retrieval(args, feats_h, rk))   # compares rk with the host ranks
-        del rk
-        torch.cuda.empty_cache()
-        leg("retrieve_topk", lambda: bench_topk_all_pairs(args, feats_h))
-        torch.cuda.empty_cache()
-        leg("rank_long_rows", lambda: bench_rank_long_rows(args))
-        torch.cuda.empty_cache()
-        if rank == 0 and world == 1:
-            leg("eval_e2e", lambda: bench_eval_e2e(args))
-            torch.cuda.empty_cache()
-        if args.with_sharded:
-            leg("sharded_gallery", lambda: bench_sharded_gallery(args, rank, world))
-            torch.cuda.empty_cache()
-        if args.with_train:
-            from train_bench import bench_train
-            sc = args.scaling
-            # configs[1]: ResNet-110-fc, batch 128.  The product default for the CIFAR nets is fp32 + HIP-graph replay (bf16 autocast only
-            # adds cast launches to 16-64-channel convolutions); BASELINE says bf16, so that number stands beside it.
-            leg("train", lambda: bench_train(args, rank, world, scaling=sc))
-            leg("train_bf16", lambda: bench_train(args, rank, world, dtype="bf16", scaling=sc))
-            if "error" not in out["train"] and "error" not in out["train_bf16"]:
-                out["train"]["bf16_images_per_sec"] = out["train_bf16"]["value"]
-            if "error" not in out["train"] and sc == "weak":
-                # per-GPU batch sweep beside the stated batch: shows how far configs[1] sits inside the launch-bound regime
-                sweep = {str(args.batch): {"images_per_sec": out["train"]["value"], "ms_per_step": out["train"]["ms_per_step"]}}
-                for bsz in (256, 512):
-                    if bsz == args.batch:
-                        continue
-                    try:
-                        r = bench_train(argparse.Namespace(**dict(vars(args), batch=bsz, steps=min(args.steps, 10), warmup=min(args.warmup, 3))), rank, world, scaling=sc)
-                        sweep[str(bsz)] = {"images_per_sec": r["value"], "ms_per_step": r["ms_per_step"]}
-                    except Exception as e:
-                        sweep[str(bsz)] = {"error": "%s: %s" % (type(e).__name__, e)}
-                    torch.cuda.empty_cache()
-                out["train"]["batch_sweep_per_gpu"] = sweep
-            r50 = argparse.Namespace(**dict(vars(args), arch="resnet-50", batch=64))
-            leg("train_r50", lambda: bench_train(r50, rank, world, scaling=sc))                            # configs[3]: CUB, 200 classes
-            leg("train_r50_ilsvrc", lambda: bench_train(r50, rank, world, classes=1000, scaling=sc))    # configs[4]: C = D = 1000
-            r50b = argparse.Namespace(**dict(vars(args), arch="resnet-50", batch=128))                  # B = 128 per GPU
-            leg("train_r50_b128", lambda: bench_train(r50b, rank, world, scaling=sc))
-            leg("train_r50_ilsvrc_b128", lambda: bench_train(r50b, rank, world, classes=1000, scaling=sc))
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported baselines: rank 0 at N = 1 only, bounded samples
-            if args.with_train and "error" not in out["train"]:
+            def leg(name, fn):        # the retrieval line must survive a failure of a secondary leg -- but every rank must agree
                 try:
-                    from train_bench import cpu_baseline_train
-                    out["train"]["cpu_baseline"] = cpu_baseline_train(args)
+                    out[name] = fn()
                 except Exception as e:
-                    out["train"]["cpu_baseline"] = {"error": "%s: %s" % (type(e).__name__, e)}
+                    out[name] = {"error": "%s: %s" % (type(e).__name__, e)}
+
+            leg("hierarchical_precision", lambda: bench_metrics(args, rk))
+            if rank == 0 and world == 1 and "error" not in out and args.metric == "cosine":
+                leg("guaranteed_order", lambda: bench_guaranteed_order(args))
+                if "kernels" in out and "error" not in out.get("guaranteed_order", {"error": 1}):
+                    out["kernels"]["rank_rows"]["guaranteed_order_ms"] = out["guaranteed_order"]["ms_scaled_to_step"]
+            if rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported baseline: rank 0 at N = 1 only, bounded sample; it also
+                leg("cpu_baseline", lambda: cpu_baseline_retrieval(args, feats_h, rk))   # compares rk with the host ranks
+            del rk
+            torch.cuda.empty_cache()
+            leg("retrieve_topk", lambda: bench_topk_all_pairs(args, feats_h))
+            torch.cuda.empty_cache()
+            leg("rank_long_rows", lambda: bench_rank_long_rows(args))
+            torch.cuda.empty_cache()
+            if rank == 0 and world == 1:
+                leg("eval_e2e", lambda: bench_eval_e2e(args))
+                torch.cuda.empty_cache()
+            if args.with_sharded:
+                leg("sharded_gallery", lambda: bench_sharded_gallery(args, rank, world))
+                torch.cuda.empty_cache()
+            if args.with_train:
+                from train_bench import bench_train
+                sc = args.scaling
+                # configs[1]: ResNet-110-fc, batch 128.  The product default for the CIFAR nets is fp32 + HIP-graph replay (bf16 autocast only
+                # adds cast launches to 16-64-channel convolutions); BASELINE says bf16, so that number stands beside it.
+                leg("train", lambda: bench_train(args, rank, world, scaling=sc))
+                leg("train_bf16", lambda: bench_train(args, rank, world, dtype="bf16", scaling=sc))
+                if "error" not in out["train"] and "error" not in out["train_bf16"]:
+                    out["train"]["bf16_images_per_sec"] = out["train_bf16"]["value"]
+                if "error" not in out["train"] and sc == "weak":
+                    # per-GPU batch sweep beside the stated batch: shows how far configs[1] sits inside the launch-bound regime
+                    sweep = {str(args.batch): {"images_per_sec": out["train"]["value"], "ms_per_step": out["train"]["ms_per_step"]}}
+                    for bsz in (256, 512):
+                        if bsz == args.batch:
+                            continue
+                        try:
+                            r = bench_train(argparse.Namespace(**dict(vars(args), batch=bsz, steps=min(args.steps, 10), warmup=min(args.warmup, 3))), rank, world, scaling=sc)
+                            sweep[str(bsz)] = {"images_per_sec": r["value"], "ms_per_step": r["ms_per_step"]}
+                        except Exception as e:
+                            sweep[str(bsz)] = {"error": "%s: %s" % (type(e).__name__, e)}
+                        torch.cuda.empty_cache()
+                    out["train"]["batch_sweep_per_gpu"] = sweep
+                r50 = argparse.Namespace(**dict(vars(args), arch="resnet-50", batch=64))
+                leg("train_r50", lambda: bench_train(r50, rank, world, scaling=sc))                            # configs[3]: CUB, 200 classes
+                leg("train_r50_ilsvrc", lambda: bench_train(r50, rank, world, classes=1000, scaling=sc))    # configs[4]: C = D = 1000
+                r50b = argparse.Namespace(**dict(vars(args), arch="resnet-50", batch=128))                  # B = 128 per GPU
+                leg("train_r50_b128", lambda: bench_train(r50b, rank, world, scaling=sc))
+                leg("train_r50_ilsvrc_b128", lambda: bench_train(r50b, rank, world, classes=1000, scaling=sc))
+            if rank == 0 and world == 1 and not args.no_cpu_baseline:      # reported baselines: rank 0 at N = 1 only, bounded samples
+                if args.with_train and "error" not in out["train"]:
+                    try:
+                        from train_bench import cpu_baseline_train
+                        out["train"]["cpu_baseline"] = cpu_baseline_train(args)
+                    except Exception as e:
+                        out["train"]["cpu_baseline"] = {"error": "%s: %s" % (type(e).__name__, e)}
     if isinstance(out.get("roofline"), dict) and isinstance(out.get("config"), dict) and not args.dry and args.workload != "train":
         # scalars mirrored to where the driver's parsed subset keeps them
         sg, cb = out.get("sharded_gallery"), out.get("cpu_baseline")

@@ -1,7 +1,7 @@
 """oracle/verify.py -- TEST INFRASTRUCTURE ONLY: full-size checks of one retrieval step against the oracle.
 
-Used by tests/test_gpu_retrieval.py (the benchmarked 50,000 x 50,000 x 100 configuration) and by bench.py AFTER its
-timed region (``"verified"`` in the bench line) -- as the checker, never as the thing measured.
+Used by tests/test_gpu_retrieval.py (the benchmarked 50,000 x 50,000 x 100 configuration) and by bench.py --full AFTER
+its timed region (``"verified"`` in the bench line) -- as the checker, never as the thing measured.
 
 What is checked on device results ``pd`` [Q, N] f32 (distances) and ``rk`` [Q, N] int32 / int64 (ranking) that the HIP path
 produced from the feature rows ``feats`` (exactly as the distance kernel saw them: normalised for the cosine branch):

@@ -624,14 +624,44 @@ def test_labelembed_model_mirrors_the_reference_head():
     assert all(torch.isfinite(v).all() for v in g.values() if v is not None)
 
 
-def test_bench_line_schema_on_a_small_problem(tmp_path):
-    """bench.py end to end at a reduced size (so that a broken bench cannot reach the driver): one JSON line with the contract's
-    keys, the roofline / kernels objects, the post-run oracle verification and the sharded-gallery leg; --dump-outputs writes
-    the sampled rows of the last timed step (normalised features, distances, canonical ranking)."""
+def test_plain_bench_line_is_the_headline_alone(tmp_path):
+    """bench.py without --full at a reduced size: set-up, warm-up, the timed steps, --dump-outputs and one JSON line with the
+    contract's keys and the roofline / kernels objects of the timed steps' own HIP events -- none of the checks or legs --full adds."""
     import json
     import subprocess
     dump = tmp_path / "dump"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "4096", "--steps", "2", "--warmup", "1", "--no-train",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", "4096", "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump)],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(line) == 1
+    d = json.loads(line[0])
+    assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"], d["n_gpus"], d["steps"], d["warmup"]) == \
+        ("retrieval_Mpairs_per_sec", "Mpairs/s", True, "f32", 1, 2, 1)
+    assert d["value"] > 0 and abs(d["value"] - 4096.0 * 4096 / d["ms_per_step"] / 1e3) <= 1e-9 * d["value"]
+    assert set(("bound", "achieved", "peak", "unit", "frac", "traffic")) <= set(d["roofline"])
+    assert d["kernels"]["pairwise_dist"]["ms"] > 0 and d["kernels"]["rank_rows"]["ms"] > 0
+    for k in ("verified", "verify_detail", "cpu_baseline", "hierarchical_precision", "guaranteed_order", "retrieve_topk", "rank_long_rows",
+              "eval_e2e", "sharded_gallery", "train", "train_bf16", "train_r50", "train_r50_ilsvrc", "train_r50_b128", "train_r50_ilsvrc_b128"):
+        assert k not in d, k
+    assert "verified" not in d["roofline"] and "guaranteed_order_ms" not in d["kernels"]["rank_rows"]
+    dumped = {k: np.load(str(dump / (k + ".npy"))) for k in ("rows", "features", "distances", "ranking")}
+    assert d["dump_outputs"]["bytes"] == sum(os.path.getsize(str(p)) for p in dump.iterdir()) <= 64e6
+    rows = dumped["rows"].astype(np.int64)
+    assert len(rows) == d["dump_outputs"]["rows"] > 0 and dumped["distances"].shape == dumped["ranking"].shape == (len(rows), 4096)
+    feats = np.random.default_rng(0).standard_normal((4096, 100)).astype(np.float32)       # bench.py's rank-0 features
+    assert np.array_equal(dumped["features"], ro.canon_normalize_rows(feats)[rows])
+    assert np.array_equal(dumped["ranking"], np.argsort(dumped["distances"], axis=1, kind="stable").astype(np.float64))
+
+
+def test_bench_line_schema_on_a_small_problem(tmp_path):
+    """bench.py --full end to end at a reduced size (so that a broken bench cannot reach the driver): one JSON line with the
+    contract's keys, the roofline / kernels objects, the post-run oracle verification and the sharded-gallery leg; --dump-outputs
+    writes the sampled rows of the last timed step (normalised features, distances, canonical ranking)."""
+    import json
+    import subprocess
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "4096", "--steps", "2", "--warmup", "1", "--no-train",
                           "--shard-rows", "3000", "--shard-queries", "500", "--shard-dim", "64", "--shard-k", "17", "--cpu-sample-queries", "256",
                           "--dump-outputs", str(dump)],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)

@@ -315,14 +315,14 @@ def test_bench_gpus_flag_spawns_that_many_ranks():
 
 
 def test_bench_dry_run_with_8_ranks_completes_every_leg():
-    """`bench.py --gpus 8 --dry --scaling strong` (gloo, 8 ranks on CPU): the launcher, the 8-way gallery shards + all-gather + merge
-    of the `sharded_gallery` leg, the query-sharded ranking and the DP training step all complete and agree with one process."""
+    """`bench.py --gpus 8 --dry --scaling strong --full` (gloo, 8 ranks on CPU): the launcher, the 8-way gallery shards + all-gather +
+    merge of the `sharded_gallery` leg, the query-sharded ranking and the DP training step all complete and agree with one process."""
     import json
     import subprocess
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dry", "--scaling", "strong"], env=env,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dry", "--scaling", "strong", "--full"], env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -350,6 +350,42 @@ def test_bench_refuses_more_gpus_than_visible():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "64"], env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, timeout=300)
     assert out.returncode != 0 and "visible" in (out.stderr + out.stdout)
+
+
+def test_bench_plain_run_leaves_every_secondary_leg_to_full(monkeypatch, capsys):
+    """A plain run prints the headline line and starts none of the checks or secondary legs; --full starts every one of them, for
+    the retrieval and the training workload alike (the legs and the step are stand-ins here: this is the dispatch in main)."""
+    import json
+    import bench
+    import train_bench
+    calls = []
+
+    def stand_in(name, ret):
+        return lambda *a, **k: calls.append(name) or dict(ret)
+    monkeypatch.setattr(bench, "init_dist", lambda args: (0, 1, 0))
+    monkeypatch.setattr(bench, "comm_identity", lambda world, dry=False: {"backend": "none (single process)"})
+    monkeypatch.setattr(bench, "bench_retrieval", lambda args, rank, world: (
+        {"metric": "retrieval_Mpairs_per_sec", "value": 1.0, "roofline": {}, "config": {}, "kernels": {"rank_rows": {}}}, None, None))
+    legs = ("bench_metrics", "bench_guaranteed_order", "cpu_baseline_retrieval", "bench_topk_all_pairs", "bench_rank_long_rows",
+            "bench_eval_e2e", "bench_sharded_gallery")
+    for name in legs:
+        monkeypatch.setattr(bench, name, stand_in(name, {"ms_scaled_to_step": 1.0}))
+    monkeypatch.setattr(train_bench, "bench_train", stand_in("bench_train", {"value": 1.0, "ms_per_step": 1.0}))
+    monkeypatch.setattr(train_bench, "cpu_baseline_train", stand_in("cpu_baseline_train", {}))
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    bench.main(["--steps", "3"])
+    assert calls == [] and json.loads(capsys.readouterr().out) == {"metric": "retrieval_Mpairs_per_sec", "value": 1.0, "roofline": {},
+                                                                   "config": {}, "kernels": {"rank_rows": {}},
+                                                                   "rccl": {"backend": "none (single process)"}}
+    bench.main(["--steps", "3", "--full"])
+    assert set(calls) == set(legs) | {"bench_train", "cpu_baseline_train"}
+    assert {"hierarchical_precision", "guaranteed_order", "cpu_baseline", "retrieve_topk", "rank_long_rows", "eval_e2e", "sharded_gallery",
+            "train", "train_r50"} <= set(json.loads(capsys.readouterr().out))
+    del calls[:]
+    bench.main(["--workload", "train"])
+    assert calls == ["bench_train"] and "cpu_baseline" not in json.loads(capsys.readouterr().out)
+    bench.main(["--workload", "train", "--full"])
+    assert calls == ["bench_train"] * 2 + ["cpu_baseline_train"] and "cpu_baseline" in json.loads(capsys.readouterr().out)
 
 
 def test_bench_cost_model_counts_executed_flops():
