@@ -48,7 +48,7 @@ __device__ __forceinline__ void bitonic_sort_u64(uint64_t *v, int P, int nthread
 }
 
 // One row: exact radix SELECT of the k-th smallest canonical key, tie-aware collection, sort, output (whole workgroup).
-// lds: P * 8 + (TK_NB + TK_WAVES + 1 + 4) * 4 bytes.
+// lds: select_lds_bytes(k).
 __device__ __forceinline__ void topk_select_row(const float *__restrict__ drow, int N, int64_t col_offset, int k, int P,
                                                 float *__restrict__ od, int32_t *__restrict__ oi, uint64_t *lds)
 {
@@ -249,23 +249,6 @@ __device__ __forceinline__ void blocked_bitonic_sort(T (&v)[PER], T *lds)
 constexpr int TK_SAMPLES = 2048;
 constexpr int TK_CAP = 8192;
 
-__device__ __forceinline__ void bitonic_sort_u32(uint32_t *v, int P, int nthreads)
-{
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            wg_barrier();
-            for (int t = threadIdx.x; t < P / 2; t += nthreads) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const int l = i | j;
-                const bool up = ((i & k) == 0);
-                const uint32_t a = v[i], b = v[l];
-                if ((a > b) == up) { v[i] = b; v[l] = a; }
-            }
-        }
-    }
-    wg_barrier();
-}
-
 __global__ __launch_bounds__(TK_THREADS, 4) void topk_sample_kernel(const float *__restrict__ pdist, int64_t ldp, int64_t Q, int N,
                                                                  int64_t col_offset, int k, int pivot_rank,
                                                                  float *__restrict__ out_d, int32_t *__restrict__ out_i)
@@ -371,6 +354,9 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
 
 static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
+// LDS of topk_select_row: P = next_pow2(k) candidates, the histogram, per-wave tie counts and 4 control words
+static size_t select_lds_bytes(int k) { return (size_t)next_pow2(k) * 8 + (TK_NB + TK_WAVES + 1 + 4) * sizeof(uint32_t); }
+
 }  // namespace se
 
 using namespace se;
@@ -383,7 +369,7 @@ extern "C" int se_topk_rows(const float *pdist, int64_t ldp, int64_t q, int64_t 
     if (q == 0) return SE_OK;
     if (!pdist || !out_d || !out_i || ldp < n) return fail(SE_ERR_INVALID, "se_topk_rows: bad argument");
     const int P = next_pow2(k);
-    const size_t lds = (size_t)P * 8 + (TK_NB + TK_WAVES + 1 + 4) * sizeof(uint32_t);
+    const size_t lds = select_lds_bytes(k);
     const int64_t grid = q < 2048 ? q : 2048;
     hipStream_t s = (hipStream_t)stream;
     // sample-select fast path: pivot = sample of rank r, r - 4 sqrt(r) >= m = k S / N  (r = (2 + sqrt(4 + m))^2 + 4);
@@ -665,143 +651,16 @@ __global__ __launch_bounds__(256) void topk_tau_kernel(const float *__restrict__
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Candidate lists -> top-k, one WAVE per query (k <= 256, lists of <= 2048 candidates: the sizes the fused path produces):
-//   1. the candidates sit PER per lane in registers;
-//   2. radix SELECT of the k-th smallest key: 4 passes of 8 bits, a 256-bin histogram in wave-private LDS (one LDS add per key
-//      and pass), wave scan of the bins;
-//   3. every candidate with key <= that key (k plus the ties of the k-th key: a few hundred of ~760) is compacted into LDS,
-//   4. sorted on the canonical 64-bit (key, index) composite by an in-register wave bitonic sort, and the first k are written.
-// ~1.5k wave instructions per query instead of the ~13k of a full sort of the list.  Queries it cannot finish (k > 256, huge tie
-// groups) are marked TK_WIDE for the workgroup-wide kernel below; lists outside [k, cap] are marked TK_REDO for the exact kernel.
-constexpr int32_t TK_WIDE = -2;
-constexpr int TL_WAVES = 4;
-constexpr int TL_SEL = 512;             // compacted candidates per query the wave sort takes
-
-template <int PER>
-__device__ __forceinline__ bool topk_wave_select(const uint2 *__restrict__ lst, int total, int k, int64_t col_offset, uint32_t *hist,
-                                                 uint64_t *sel, float *__restrict__ od, int32_t *__restrict__ oi, int lane)
-{
-    uint32_t key[PER], idx[PER];
-#pragma unroll
-    for (int r = 0; r < PER; r++) {
-        const int e = r * 64 + lane;
-        const uint2 c = lst[e < total ? e : 0];
-        key[r] = e < total ? canon_key(__uint_as_float(c.x)) : 0xFFFFFFFFu;   // (list entries are never NaN: padding sorts behind everything)
-        idx[r] = e < total ? c.y : 0xFFFFFFFFu;
-    }
-    // ---- k-th smallest key ----
-    uint32_t prefix = 0, pmask = 0, remaining = (uint32_t)k, n_eq = 0;
-#pragma unroll 1
-    for (int shift = 24; shift >= 0; shift -= 8) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) hist[lane * 4 + i] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-        for (int r = 0; r < PER; r++)
-            if ((key[r] & pmask) == prefix && r * 64 + lane < total) atomicAdd(&hist[(key[r] >> shift) & 255u], 1u);
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        uint32_t c[4], local = 0;
-#pragma unroll
-        for (int i = 0; i < 4; i++) { c[i] = hist[lane * 4 + i]; local += c[i]; }
-        uint32_t incl = local;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        uint32_t run = incl - local, digit = 0, rem = 0, cnt = 0;
-        const bool mine = remaining > run && remaining <= incl;             // exactly one lane
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const bool hit = mine && remaining > run && remaining <= run + c[i];
-            digit = hit ? (uint32_t)(lane * 4 + i) : digit;
-            rem = hit ? remaining - run : rem;
-            cnt = hit ? c[i] : cnt;
-            run += c[i];
-        }
-        const int src = __ffsll((long long)__ballot(mine)) - 1;
-        digit = (uint32_t)__shfl((int)digit, src, 64);
-        remaining = (uint32_t)__shfl((int)rem, src, 64);
-        n_eq = (uint32_t)__shfl((int)cnt, src, 64);
-        prefix |= digit << shift;
-        pmask |= 255u << shift;
-    }
-    const uint32_t kth = prefix;
-    const uint32_t n_le = (uint32_t)k - remaining + n_eq;                   // keys below the k-th key + ALL its ties
-    if (n_le > (uint32_t)TL_SEL) return false;
-    // ---- compact the candidates with key <= kth into LDS, sort them on (key, index), write the first k ----
-    uint32_t base = 0;
-#pragma unroll
-    for (int r = 0; r < PER; r++) {
-        const bool take = key[r] <= kth && r * 64 + lane < total;
-        const uint64_t m = __ballot(take);
-        if (take) sel[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = ((uint64_t)key[r] << 32) | idx[r];
-        base += (uint32_t)__popcll(m);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#define TL_SORT_OUT(P2)                                                                        \
-    {                                                                                          \
-        uint64_t sv[P2];                                                                       \
-        _Pragma("unroll") for (int r = 0; r < P2; r++) {                                       \
-            const int e = lane * P2 + r;                                                       \
-            sv[r] = e < (int)n_le ? sel[e] : ~0ull;                                            \
-        }                                                                                      \
-        wave_bitonic_sort<uint64_t, P2>(sv, lane);                                             \
-        _Pragma("unroll") for (int r = 0; r < P2; r++) {                                       \
-            const int e = lane * P2 + r;                                                       \
-            if (e < k) {                                                                       \
-                od[e] = key_to_float((uint32_t)(sv[r] >> 32));                                 \
-                oi[e] = (int32_t)(col_offset + (int64_t)(uint32_t)sv[r]);                      \
-            }                                                                                  \
-        }                                                                                      \
-    }
-    if (n_le <= 64) TL_SORT_OUT(1)
-    else if (n_le <= 128) TL_SORT_OUT(2)
-    else if (n_le <= 256) TL_SORT_OUT(4)
-    else TL_SORT_OUT(8)
-#undef TL_SORT_OUT
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                  // sel / hist are reused by this wave's next query
-    return true;
-}
-
-__global__ __launch_bounds__(TL_WAVES * 64) void topk_lists_wave_kernel(const uint2 *__restrict__ lists, const unsigned *__restrict__ rowcnt, int64_t cap,
-                                                                       int64_t Q, int64_t col_offset, int k, float *__restrict__ out_d,
-                                                                       int32_t *__restrict__ out_i, unsigned *__restrict__ nflag)
-{
-    __shared__ uint32_t hist_all[TL_WAVES][256];
-    __shared__ uint64_t sel_all[TL_WAVES][TL_SEL];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t *hist = hist_all[wave];
-    uint64_t *sel = sel_all[wave];
-    for (int64_t row = (int64_t)blockIdx.x * TL_WAVES + wave; row < Q; row += (int64_t)gridDim.x * TL_WAVES) {
-        const unsigned total = rowcnt[row];
-        if (total < (unsigned)k || total > (unsigned)cap) {
-            if (lane == 0) { out_i[row * k] = TK_REDO; atomicAdd(&nflag[1], 1u); }
-            continue;
-        }
-        const uint2 *lst = lists + row * cap;
-        bool done = false;
-        if (k <= 256 && total <= 2048u) {
-            if (total <= 512u) done = topk_wave_select<8>(lst, (int)total, k, col_offset, hist, sel, out_d + row * k, out_i + row * k, lane);
-            else if (total <= 1024u) done = topk_wave_select<16>(lst, (int)total, k, col_offset, hist, sel, out_d + row * k, out_i + row * k, lane);
-            else done = topk_wave_select<32>(lst, (int)total, k, col_offset, hist, sel, out_d + row * k, out_i + row * k, lane);
-        }
-        if (!done && lane == 0) { out_i[row * k] = TK_WIDE; atomicAdd(&nflag[0], 1u); }
-    }
-}
-
-// candidates of every query -> canonical top-k; queries whose list missed [k, cap] are flagged for the exact kernel
+// candidate lists of the fp32 fused passes -> canonical top-k, one workgroup per query: the whole list sorted on the (key, index)
+// composite, the first k written; queries whose list missed [k, cap] are flagged for the exact kernel
 __global__ __launch_bounds__(TK_THREADS) void topk_lists_kernel(const uint2 *__restrict__ lists, const unsigned *__restrict__ rowcnt, int64_t cap,
                                                                 int64_t Q, int64_t col_offset, int k, float *__restrict__ out_d,
-                                                                int32_t *__restrict__ out_i, int only_wide, unsigned *__restrict__ nflag)
+                                                                int32_t *__restrict__ out_i, unsigned *__restrict__ nflag)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t tl_lds64[];
     uint64_t *cand = tl_lds64;
     const int tid = threadIdx.x;
-    if (only_wide && nflag[0] == 0) return;                        // nothing was handed over: the usual case
     for (int64_t row = blockIdx.x; row < Q; row += gridDim.x) {
-        if (only_wide && out_i[row * k] != TK_WIDE) continue;      // behind topk_lists_wave_kernel: only the queries it handed over (uniform)
         const unsigned total = rowcnt[row];
         if (total < (unsigned)k || total > (unsigned)cap) {
             if (tid == 0) { out_i[row * k] = TK_REDO; atomicAdd(&nflag[1], 1u); }
@@ -1425,6 +1284,36 @@ static FusedLayout fused_layout(int64_t q, int64_t n, int64_t d, const FusedPlan
     return L;
 }
 
+// se_retrieve_topk's path and workspace: the bf16 pre-filter (pf), the fp32 fused passes (p.ok, !pf) or the distance slab (!p.ok)
+struct RetrievePlan {
+    FusedPlan p;
+    bool pf;
+    FusedLayout L;          // fused forms only
+    int64_t need;           // workspace bytes
+};
+static RetrievePlan retrieve_topk_plan(int64_t q, int64_t n, int64_t d, int64_t ldg, int k)
+{
+    RetrievePlan r = {fused_plan(n, ldg, k)};
+    r.pf = prefilter_wanted(r.p, k);
+    if (r.p.ok) r.L = fused_layout(q, n, d, r.p, r.pf);
+    r.need = r.p.ok ? r.L.total : topk_qtile(q, n) * ((n + 3) / 4 * 4) * 4;   // slab rows on a 16-byte pitch (16-byte row stores of the distance kernel)
+    return r;
+}
+
+// the exact fallback behind both fused forms: redoes the queries of one tile flagged TK_REDO (nflag[1] counts them, 0: it returns at once)
+static int launch_topk_fallback(int metric, const float *qs, int64_t ldq, const float *gallery, int64_t ldg, const float *sq, const float *sqg,
+                                int64_t rows, int64_t n, int64_t d, const KBlocks &kbs, int64_t col_offset, int k, float *scratch,
+                                float *out_d, int32_t *out_i, const unsigned *nflag, hipStream_t s)
+{
+    const int64_t grid = rows < FB_GRID ? rows : FB_GRID;
+    const size_t sel = (select_lds_bytes(k) + 15) & ~(size_t)15;       // the wave row buffers behind it start 16-byte aligned
+    auto kern = metric == SE_METRIC_COSINE ? topk_fallback_kernel<SE_METRIC_COSINE> : topk_fallback_kernel<SE_METRIC_EUCLID>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(TK_THREADS), sel + FB_ROWBUF_BYTES, s, qs, ldq, gallery, ldg, sq, sqg, rows, (int)n, (int)d,
+                       kbs, col_offset, k, next_pow2(k), (int)sel, scratch, out_d, out_i, nflag);
+    SE_LAUNCH_CHECK();
+    return SE_OK;
+}
+
 static int topk_merge_launch(const char *who, const float *d, const int32_t *idx, int64_t part_stride, int parts, int64_t q, int k, float *out_d,
                              int32_t *out_i, se_stream_t stream)
 {
@@ -1470,9 +1359,7 @@ extern "C" int se_topk_merge_packed(const void *packed, int parts, int64_t q, in
 extern "C" int64_t se_retrieve_topk_workspace_bytes(int64_t q, int64_t n, int64_t d, int64_t ldg, int k)
 {
     if (q <= 0 || n <= 0 || d <= 0) return 0;
-    const FusedPlan p = fused_plan(n, ldg, k);
-    if (p.ok) return fused_layout(q, n, d, p, prefilter_wanted(p, k)).total;
-    return topk_qtile(q, n) * ((n + 3) / 4 * 4) * 4;          // slab rows on a 16-byte pitch (16-byte row stores of the distance kernel)
+    return retrieve_topk_plan(q, n, d, ldg, k).need;
 }
 
 // the bf16 pre-filter path of one query tile (see the block comment above pf_thr_kernel)
@@ -1488,8 +1375,6 @@ static int retrieve_topk_prefilter(const float *queries, int64_t ldq, const floa
     uint16_t *gimg = (uint16_t *)(ws + L.off_gimg), *qimg = (uint16_t *)(ws + L.off_qimg);
     float *gnrm = (float *)(ws + L.off_gnrm), *gres = (float *)(ws + L.off_gres), *qnrm = (float *)(ws + L.off_qnrm), *qres = (float *)(ws + L.off_qres);
     const int kp = L.kp;
-    const int P = next_pow2(k);
-    const size_t lds_sel = (size_t)P * 8 + (TK_NB + TK_WAVES + 1 + 4) * sizeof(uint32_t);
     const bool vec = (ldg % 4 == 0) && ((((uintptr_t)gallery) & 15) == 0);
     // ---- gallery image (once per call) ----
     phase_mark("start", s);
@@ -1565,14 +1450,8 @@ static int retrieve_topk_prefilter(const float *queries, int64_t ldq, const floa
                     (long long)n, (long long)d, kp, k, p.S, p.G, p.j, L.parts, (long long)L.cap, (long long)rows, (int)sym, h[1],
                     okq > 0 ? (double)h[3] / okq : 0.0, okq > 0 ? (double)h[2] / okq : 0.0, (double)gmaxn, (double)gmaxr, hc[2]);
         }
-        const int64_t fgrid = rows < FB_GRID ? rows : FB_GRID;
-        if (metric == SE_METRIC_COSINE)
-            hipLaunchKernelGGL(topk_fallback_kernel<SE_METRIC_COSINE>, dim3((unsigned)fgrid), dim3(TK_THREADS), ((lds_sel + 15) & ~(size_t)15) + FB_ROWBUF_BYTES, s, qs, ldq, gallery, ldg, sq, sqg,
-                               rows, (int)n, (int)d, kbs, col_offset, k, P, (int)((lds_sel + 15) & ~(size_t)15), scratch, out_d + q0 * k, out_i + q0 * k, nflag);
-        else
-            hipLaunchKernelGGL(topk_fallback_kernel<SE_METRIC_EUCLID>, dim3((unsigned)fgrid), dim3(TK_THREADS), ((lds_sel + 15) & ~(size_t)15) + FB_ROWBUF_BYTES, s, qs, ldq, gallery, ldg, sq, sqg,
-                               rows, (int)n, (int)d, kbs, col_offset, k, P, (int)((lds_sel + 15) & ~(size_t)15), scratch, out_d + q0 * k, out_i + q0 * k, nflag);
-        SE_LAUNCH_CHECK();
+        rc = launch_topk_fallback(metric, qs, ldq, gallery, ldg, sq, sqg, rows, n, d, kbs, col_offset, k, scratch, out_d + q0 * k, out_i + q0 * k, nflag, s);
+        if (rc != SE_OK) return rc;
         phase_mark("fallback", s);
         phase_note_counters(nflag, rows, s);      // final by now (refinement + exact fallback have been enqueued): copied on this stream
     }
@@ -1594,13 +1473,12 @@ extern "C" int se_retrieve_topk(const float *queries, int64_t ldq, const float *
     bool multi = false;
     if (const int rc = make_kblocks("se_retrieve_topk", kblocks, nkb, d, kbs, multi)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const FusedPlan p = fused_plan(n, ldg, k);
-    const bool pf = prefilter_wanted(p, k);
-    const FusedLayout L = p.ok ? fused_layout(q, n, d, p, pf) : FusedLayout{};
-    const int64_t need = p.ok ? L.total : topk_qtile(q, n) * ((n + 3) / 4 * 4) * 4;
-    if (!workspace || workspace_bytes < need) return fail(SE_ERR_WORKSPACE, "se_retrieve_topk: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+    const RetrievePlan plan = retrieve_topk_plan(q, n, d, ldg, k);
+    const FusedPlan &p = plan.p;
+    const FusedLayout &L = plan.L;
+    if (!workspace || workspace_bytes < plan.need) return fail(SE_ERR_WORKSPACE, "se_retrieve_topk: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)plan.need);
     if (p.ok && (((uintptr_t)workspace) & 255) != 0) return fail(SE_ERR_INVALID, "se_retrieve_topk: workspace must be 256-byte aligned");
-    if (pf) return retrieve_topk_prefilter(queries, ldq, gallery, ldg, sqq, sqg, q, n, d, metric, kbs, col_offset, k, out_d, out_i, (char *)workspace, p, L, s);
+    if (plan.pf) return retrieve_topk_prefilter(queries, ldq, gallery, ldg, sqq, sqg, q, n, d, metric, kbs, col_offset, k, out_d, out_i, (char *)workspace, p, L, s);
 
     if (!p.ok) {   // ---- small problems: [rows, n] distance slab -> se_topk_rows, query tile by query tile ----
         const int64_t qt = topk_qtile(q, n);
@@ -1617,7 +1495,7 @@ extern "C" int se_retrieve_topk(const float *queries, int64_t ldq, const float *
         return SE_OK;
     }
 
-    // ---- fused path, fp32 passes (k > 512, or pinned by the tuning build) ----
+    // ---- fused path, fp32 passes: the product path for k > PF_K_MAX, and what SE_TOPK_PREFILTER=0 pins in the tuning build ----
     char *ws = (char *)workspace;
     float *tau = (float *)(ws + L.off_tau);
     unsigned *rowcnt = (unsigned *)(ws + L.off_cnt);
@@ -1627,14 +1505,12 @@ extern "C" int se_retrieve_topk(const float *queries, int64_t ldq, const float *
     int PER = 1;
     while (PER * TK_THREADS < p.cap) PER <<= 1;
     const size_t lds_lists = (size_t)PER * TK_THREADS * 8;
-    const int P = next_pow2(k);
-    const size_t lds_sel = (size_t)P * 8 + (TK_NB + TK_WAVES + 1 + 4) * sizeof(uint32_t);
     SE_HIP_CHECK(hipFuncSetAttribute((const void *)topk_lists_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_lists));
     for (int64_t q0 = 0; q0 < q; q0 += L.qt) {
         const int64_t rows = (q - q0 < L.qt) ? (q - q0) : L.qt;
         const float *qs = queries + q0 * ldq;
         const float *sq = sqq ? sqq + q0 : nullptr;
-        unsigned *nflag = rowcnt + rows;                               // [0] queries handed to the workgroup-wide sort, [1] to the exact kernel
+        unsigned *nflag = rowcnt + rows;                               // [1] queries handed to the exact kernel; [0], [2..3] unused
         SE_HIP_CHECK(hipMemsetAsync(rowcnt, 0, (size_t)rows * 4 + 16, s));
         FusedArgs fa = {gm, p.G, tau, rowcnt, lists, p.cap, p.step};
         int rc = launch_fused_pass(EPI_GROUPMIN, gallery, p.step * ldg, qs, ldq, sqg, sq, p.S, rows, d, metric, kbs, multi, fa, s);
@@ -1645,16 +1521,8 @@ extern "C" int se_retrieve_topk(const float *queries, int64_t ldq, const float *
         rc = launch_fused_pass(EPI_FILTER, gallery, ldg, qs, ldq, sqg, sq, n, rows, d, metric, kbs, multi, fa, s);
         if (rc != SE_OK) return rc;
         const int64_t grid = rows < 2048 ? rows : 2048;
-        int only_wide = 0;
-        if (k <= 256 && !tuning_env("SE_TOPK_NOWAVE")) {     // one wave per query (radix select + small sort); hands the rest on
-            const int64_t wgrid = (rows + TL_WAVES - 1) / TL_WAVES < 4096 ? (rows + TL_WAVES - 1) / TL_WAVES : 4096;
-            hipLaunchKernelGGL(topk_lists_wave_kernel, dim3((unsigned)wgrid), dim3(TL_WAVES * 64), 0, s, lists, rowcnt, (int64_t)p.cap, rows,
-                               col_offset, k, out_d + q0 * k, out_i + q0 * k, nflag);
-            SE_LAUNCH_CHECK();
-            only_wide = 1;
-        }
         hipLaunchKernelGGL(topk_lists_kernel, dim3((unsigned)grid), dim3(TK_THREADS), lds_lists, s, lists, rowcnt, (int64_t)p.cap, rows,
-                           col_offset, k, out_d + q0 * k, out_i + q0 * k, only_wide, nflag);
+                           col_offset, k, out_d + q0 * k, out_i + q0 * k, nflag);
         SE_LAUNCH_CHECK();
         if (kTuning && tuning_env("SE_TOPK_VERBOSE")) {   // -DSE_TUNING build only: synchronises and reports how the lists came out
             SE_HIP_CHECK(hipStreamSynchronize(s));
@@ -1667,14 +1535,8 @@ extern "C" int se_retrieve_topk(const float *queries, int64_t ldq, const float *
             fprintf(stderr, "[se_retrieve_topk] fused: n=%lld k=%d S=%d step=%lld G=%d j=%d cap=%d rows=%lld flagged=%lld mean_candidates=%.1f\n",
                     (long long)n, k, p.S, (long long)p.step, p.G, p.j, p.cap, (long long)rows, (long long)flagged, sum / (double)rows);
         }
-        const int64_t fgrid = rows < FB_GRID ? rows : FB_GRID;
-        if (metric == SE_METRIC_COSINE)
-            hipLaunchKernelGGL(topk_fallback_kernel<SE_METRIC_COSINE>, dim3((unsigned)fgrid), dim3(TK_THREADS), ((lds_sel + 15) & ~(size_t)15) + FB_ROWBUF_BYTES, s, qs, ldq, gallery, ldg, sq, sqg,
-                               rows, (int)n, (int)d, kbs, col_offset, k, P, (int)((lds_sel + 15) & ~(size_t)15), scratch, out_d + q0 * k, out_i + q0 * k, nflag);
-        else
-            hipLaunchKernelGGL(topk_fallback_kernel<SE_METRIC_EUCLID>, dim3((unsigned)fgrid), dim3(TK_THREADS), ((lds_sel + 15) & ~(size_t)15) + FB_ROWBUF_BYTES, s, qs, ldq, gallery, ldg, sq, sqg,
-                               rows, (int)n, (int)d, kbs, col_offset, k, P, (int)((lds_sel + 15) & ~(size_t)15), scratch, out_d + q0 * k, out_i + q0 * k, nflag);
-        SE_LAUNCH_CHECK();
+        rc = launch_topk_fallback(metric, qs, ldq, gallery, ldg, sq, sqg, rows, n, d, kbs, col_offset, k, scratch, out_d + q0 * k, out_i + q0 * k, nflag, s);
+        if (rc != SE_OK) return rc;
     }
     return SE_OK;
 }

@@ -199,6 +199,30 @@ def test_product_path_takes_fused_kernels_from_16384_rows(sehip, metric):
 
 
 @pytest.mark.parametrize("metric", [0, 1])
+def test_product_path_takes_fp32_fused_passes_above_k_512(sehip, metric):
+    """The product library's own path choice (no switches) for k > 512, past what the bf16 pre-filter's refinement takes: a
+    50,000-row gallery runs the fp32 fused passes (sample pass, topk_tau_kernel, filter pass, topk_lists_kernel, exact fallback).
+    Ragged query count, a K-block list and a shard offset; then an all-pairs call (symmetric filter walk), sampled rows."""
+    rng = np.random.default_rng(60 + metric)
+    n, d, q, k, kb = 50000, 100, 150, 1000, [48, 52]
+    g = rng.standard_normal((n, d)).astype(np.float32)
+    if metric == 0:
+        g = ro.canon_normalize_rows(g)
+    qs = np.ascontiguousarray(g[rng.permutation(n)[:q]])
+    dd, ii = sehip.retrieve_topk(dev(qs), dev(g), k, metric=metric, kblocks=kb, col_offset=n)
+    wd, wi = want_topk(qs, g, k, metric, kb, n)
+    assert np.array_equal(ii.cpu().numpy(), wi)
+    assert np.array_equal(dd.cpu().numpy(), wd)
+    x = dev(g)
+    sq = sehip.row_sqnorm(x) if metric == 1 else None
+    d2, i2 = sehip.retrieve_topk(x, x, k, metric=metric, sqq=sq, sqg=sq)
+    rows = [0, 31, 32, 4097, 25000, n - 1]
+    wd, wi = want_topk(g[rows], g, k, metric)
+    assert np.array_equal(i2[rows].cpu().numpy(), wi)
+    assert np.array_equal(d2[rows].cpu().numpy(), wd)
+
+
+@pytest.mark.parametrize("metric", [0, 1])
 def test_class_sorted_gallery_stays_on_the_fast_path(sehip, metric):
     """A gallery sorted by class (ILSVRC training features come that way) puts every query's neighbours into a few adjacent gallery
     tiles, i.e. into two or three of its candidate sub-lists.  Round 4 sized the sub-lists for shuffled galleries: they overflowed and
@@ -346,8 +370,9 @@ def test_topk_merge_accepts_unsorted_parts(sehip):
 # ---------------------------------------------------------------- bf16 pre-filter (prefilter.hip + pf_refine_kernel)
 
 def test_fp32_fused_passes_stay_covered():
-    """SE_TOPK_PREFILTER=0 (tuning build) pins the fp32 form of the fused passes (what k > 512 takes in the product): reference heads
-    with K-blocks and the ragged cases, as before the bf16 pre-filter existed."""
+    """SE_TOPK_PREFILTER=0 (tuning build) pins the fp32 form of the fused passes (what k > 512 takes in the product,
+    test_product_path_takes_fp32_fused_passes_above_k_512) at every k: reference heads with K-blocks and the ragged cases (k = 1 ...
+    1024: topk_lists_kernel sorts every query's list), as before the bf16 pre-filter existed."""
     run_with_tuning_lib(
         "for p in T.GOLDEN:\n"
         "    T.check_against_reference_head(sehip, p)\n", env={"SE_TOPK_FUSED": "1", "SE_TOPK_PREFILTER": "0"})
