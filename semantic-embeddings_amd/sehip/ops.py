@@ -242,18 +242,19 @@ class _L2Norm(torch.autograd.Function):
         B, D = x2.shape
         xhat = torch.empty((B, D), dtype=torch.float32, device=x.device)
         inv = torch.empty((B,), dtype=torch.float32, device=x.device)
-        call("se_l2norm_fwd", x2, _dtype_code(x2), x2.stride(0), B, D, xhat, D, inv)
-        ctx.save_for_backward(xhat, inv)
+        sumsq = torch.empty((B,), dtype=torch.float32, device=x.device)
+        call("se_l2norm_fwd", x2, _dtype_code(x2), x2.stride(0), B, D, xhat, D, inv, sumsq)
+        ctx.save_for_backward(xhat, inv, sumsq)
         ctx.in_dtype = x.dtype
         return xhat.reshape(shape)
 
     @staticmethod
     def backward(ctx, grad):
-        xhat, inv = ctx.saved_tensors
+        xhat, inv, sumsq = ctx.saved_tensors
         B, D = xhat.shape
         g = grad.reshape(B, D).to(torch.float32).contiguous()
         dx = torch.empty_like(xhat)
-        call("se_l2norm_bwd", g, D, xhat, D, inv, B, D, dx, D)
+        call("se_l2norm_bwd", g, D, xhat, D, inv, sumsq, B, D, dx, D)
         return dx.reshape(grad.shape).to(ctx.in_dtype)
 
 

@@ -65,6 +65,9 @@ def test_argument_validation_without_gpu():
     one = ctypes.c_void_p(16)
     assert lib.se_pairwise_dist(one, 8, one, 8, z, z, 2, 2, 8, 0, kb, 2, one, 2, z) == -1   # blocks sum to 7 != 8
     assert b"K-blocks" in lib.se_last_error()
+    # the l2norm backward decides the epsilon clamp from the forward's sum x^2, which it cannot do without
+    assert lib.se_l2norm_bwd(one, 8, one, 8, one, z, 2, 8, one, 8, z) == -1
+    assert b"se_l2norm_bwd" in lib.se_last_error()
 
 
 def test_product_never_imports_the_oracle():
