@@ -304,6 +304,16 @@ __device__ __forceinline__ uint32_t lds_off(const void *p) { return (uint32_t)(u
 __device__ __forceinline__ void lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void lds_st16_lo(uint32_t addr, uint32_t v) { asm volatile("ds_write_b16 %0, %1" ::"v"(addr), "v"(v) : "memory"); }
 __device__ __forceinline__ void lds_st16_hi(uint32_t addr, uint32_t v) { asm volatile("ds_write_b16_d16_hi %0, %1" ::"v"(addr), "v"(v) : "memory"); }
+// byte address of exchange slot (ir & 0xFFFF) in the buffer at `xb`: ONE v_mad_u32_u16 (8 bytes) where hipcc emits shift + mask with a
+// literal + add (16 bytes) -- the image path's index scatter has two copies, and every byte of them counts against the instruction cache.
+// (A VALU that rewrites the address register a ds_write has just read still gets an s_nop from hipcc: the scatter without loads keeps
+// one per store.)
+__device__ __forceinline__ uint32_t rr_dst_mad(uint32_t ir, uint32_t xb)
+{
+    uint32_t a;
+    asm("v_mad_u32_u16 %0, %1, 2, %2" : "=v"(a) : "v"(ir), "s"(xb));
+    return a;
+}
 // (gfx950 runs with SRAM-ECC: a d16 load ZEROES the other register half, so the 16-bit loads go to a
 // small ring of temporaries and one v_perm_b32 merges each into the live register.)
 template <int OFF>
@@ -647,6 +657,20 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
             _Pragma("unroll") for (int s = 0; s < ITEMS; s++) { BODY }                                                \
         }                                                                                                             \
     }
+    // Index scatter of the image path (every wave live), one copy per call site: the slot address is one v_mad_u32_u16 and the next
+    // slot's is formed before the current store.  AFTER_STORE runs behind the store of step s (the last pass: load s of the next row).
+#define RR_IDX_SCATTER_IMG(AFTER_STORE)                                                                               \
+    {                                                                                                                 \
+        opaque(ir[0]);                                                                                                \
+        uint32_t a_ = rr_dst_mad(ir[0], xb);                                                                          \
+        _Pragma("unroll") for (int s = 0; s < ITEMS; s++) {                                                           \
+            uint32_t an_ = 0;                                                                                         \
+            if (s + 1 < ITEMS) { opaque(ir[s + 1]); an_ = rr_dst_mad(ir[s + 1], xb); }                                \
+            lds_st16_hi(a_, ir[s]);   /* index */                                                                     \
+            AFTER_STORE                                                                                               \
+            a_ = an_;                                                                                                 \
+        }                                                                                                             \
+    }
     if ((int64_t)blockIdx.x < Q) {
         const float *drow = row_ptr(blockIdx.x);
         const int n0 = row_len(blockIdx.x);
@@ -673,6 +697,8 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
         // instantiations keep the unconditional code: a branch around their unrolled phases makes hipcc copy the key registers.)
         constexpr bool SKIP_WAVES = HWORD && ITEMS <= 88;
         const bool wave_live = !SKIP_WAVES || wave * (ITEMS * WAVE) < row_len(row);
+        // image path, every wave live: the last pass's index scatter issues the next row's loads (below the pass loop)
+        constexpr bool LOAD_IN_SCATTER = IMG && !SKIP_WAVES;
         // ---- does the row qualify for the two-pass path?  (uniform per row; before the index registers exist: only the keys are live) ----
         bool two = false;
         [[maybe_unused]] int n_out = 0;
@@ -946,7 +972,8 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
             // L2 prefetch of this workgroup's NEXT row (one workgroup per CU: nothing else hides its 200 KB of HBM latency): one dword
             // per 128-byte line, all into one sink register that stays reserved until the loads after the pass loop have been waited for.
             // Issued before the destination phase of the last pass.  The image path takes none: its next row is loaded straight from HBM
-            // behind the last pass (lines prefetched this early were evicted again before the loads, 19 % of the row bytes fetched twice).
+            // by the last pass's index scatter, or (instantiations whose waves may sit a row out) behind the last pass (lines prefetched
+            // this early were evicted again before the loads, 19 % of the row bytes fetched twice).
             if (!(IMG && two)) { RR_PREFETCH_NEXT_ROW() }
             // ---- X: destinations, then the 2-byte exchanges ----
             if (wave_live) {
@@ -970,9 +997,16 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
             }
             if (wide) wg_barrier();   // the scatter below overwrites the (aliased) counters other waves may still be looking up
             RR_T(3)
+            if constexpr (LOAD_IN_SCATTER) {
+                if (end >= 32) break;   // the last index scatter follows the loop: it also issues the next row's loads
+            }
             if (wave_live) {
+                if constexpr (LOAD_IN_SCATTER) {
+                    RR_IDX_SCATTER_IMG()
+                } else {
 #pragma unroll
-                for (int s = 0; s < ITEMS; s++) { opaque(ir[s]); lds_st16_hi(RR_DST(ir[s]), ir[s]); }       // index
+                    for (int s = 0; s < ITEMS; s++) { opaque(ir[s]); lds_st16_hi(RR_DST(ir[s]), ir[s]); }       // index
+                }
             }
             lds_wait();
             wg_barrier();
@@ -1036,14 +1070,26 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
         // ---- image path: the exchange buffer is sorted by (image, index); put the runs of equal tags into (key, index) order ----
         [[maybe_unused]] bool img_fail = false;
         if constexpr (IMG) {
-            // The NEXT row's loads are issued here, straight from HBM (no L2 prefetch): the key registers are dead behind the last pass, and
-            // the scan + repair (~20k cycles) cover the latency.  They are waited for BEFORE this row's rank stores are issued, so that
-            // nothing has to wait for the stores to drain: the next row's maximum / image phase (VALU only) runs under them.
+            // The last pass's index scatter, with the NEXT row's loads, straight from HBM (no L2 prefetch): the key registers are dead once
+            // the destinations are known, and load s goes out right behind the store of step s -- under the LDS-bound scatter, whose
+            // stores leave the vector-memory path idle.  (Round 6 issued the same 98 loads per lane as one burst behind this barrier: they
+            // were accepted wave by wave in front of the tag scan, 5.6 % of the row waiting at the scan's barrier.)  The scan + repair
+            // (~20k cycles) cover the latency; the loads are waited for BEFORE this row's rank stores are issued, so that nothing has to
+            // wait for the stores to drain: the next row's maximum / image phase (VALU only) runs under them.  The scatter sits outside the
+            // pass loop: loads in flight across the loop's `break` make hipcc route the key registers through scratch.  A row the image
+            // path gives up is loaded again below (the key registers hold the next row by then).
             const float *drow = row_ptr(more ? row + gridDim.x : row);
             int wpos = wpos0;
             opaque(wpos);
+            if constexpr (LOAD_IN_SCATTER) {
+                RR_IDX_SCATTER_IMG(RR_LOAD_ONE(drow, wpos, s, n_next))
+                lds_wait();
+                wg_barrier();
+                RR_T(4)
+            } else {   // (instantiations whose waves may sit the passes out: the burst in front of the scan)
 #pragma unroll
-            for (int s = 0; s < ITEMS; s++) RR_LOAD_ONE(drow, wpos, s, n_next)
+                for (int s = 0; s < ITEMS; s++) RR_LOAD_ONE(drow, wpos, s, n_next)
+            }
         }
         if constexpr (IMG) {
             if (two) {
@@ -1055,8 +1101,10 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                 opaque(tsc);
                 const float *drow_cur = row_ptr(row);
                 // (1) scan: the tag of final position i is tagb[xbuf[i]] (the tags were written in column order).  Groups of 8 positions, group
-                // G = tid + RR_THREADS g: one conflict-free 16-byte read of the indices, 9 random tag reads (the 9th: the next group's first
-                // position), E = "tag(i) == tag(i + 1)" by byte-parallel arithmetic on the packed tags.  Every pair with equal tags goes to
+                // G = tid + RR_THREADS g: one conflict-free 16-byte read of the indices, 8 random tag reads, the 9th tag -- the next group's
+                // first position, i.e. lane + 1's first tag at the same g -- by a DPP lane shift (wave_shl:1, no LDS operation); lane 63,
+                // whose neighbour sits in the next wave, reads it while the other 63 lanes read one common byte (a broadcast: 1 / 9 of the
+                // scan's random tag reads gone).  E = "tag(i) == tag(i + 1)" by byte-parallel arithmetic on the packed tags.  Every pair with equal tags goes to
                 // the worklist (bit 8 b + 4 h of a group's word: position 4 h + b); ONE returning add per thread reserves its slots and
                 // only the (rare) set bits are walked -- nothing in this phase waits for LDS inside a divergent loop.  Pairs that reach
                 // into the padding become empty entries.
@@ -1071,9 +1119,10 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
 #pragma unroll
                 for (int g = 0; g < NG; g++) {
                     const int b0 = (tsc + RR_THREADS * g) * 8;
-                    const int bs = b0 < n_row - 1 ? b0 : 0;
+                    // (every group inside the buffer reads its own positions, live or not: the first tag of group G + 1 is then the 9th of G)
+                    const int bs = b0 < NS ? b0 : 0;
                     xg[g] = *reinterpret_cast<const uint4 *>(xbuf + bs);
-                    nxg[g] = xbuf[bs + 8 < NS ? bs + 8 : bs];
+                    nxg[g] = xbuf[(tsc & 63) == 63 ? (bs + 8 < NS ? bs + 8 : bs) : 0];
                 }
                 constexpr int TD = 1;   // groups whose tag reads are in flight ahead of the arithmetic
                 uint32_t t[TD + 1][9];
@@ -1094,7 +1143,9 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                     const uint32_t (&tc)[9] = t[g % (TD + 1)];
                     const bool live = (tsc + RR_THREADS * g) * 8 < n_row - 1;
                     const uint32_t A = tc[0] | (tc[1] << 8) | (tc[2] << 16) | (tc[3] << 24), B = tc[4] | (tc[5] << 8) | (tc[6] << 16) | (tc[7] << 24);
-                    const uint32_t zA = A ^ __builtin_amdgcn_alignbyte(B, A, 1), zB = B ^ __builtin_amdgcn_alignbyte(tc[8], B, 1);   // byte i: tag(i) ^ tag(i + 1)
+                    // the next group's first tag: lane + 1's tc[0]; lane 63 has no source lane and keeps its own read (bound_ctrl off)
+                    const uint32_t t8 = (uint32_t)__builtin_amdgcn_update_dpp((int)tc[8], (int)tc[0], 0x130, 0xF, 0xF, false);   // wave_shl:1
+                    const uint32_t zA = A ^ __builtin_amdgcn_alignbyte(B, A, 1), zB = B ^ __builtin_amdgcn_alignbyte(t8, B, 1);   // byte i: tag(i) ^ tag(i + 1)
                     const uint32_t uA = (zA & 0x7F7F7F7Fu) + 0x7F7F7F7Fu, uB = (zB & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;               // bit 7 of byte i: the low 7 bits of the byte are not all zero
                     const uint32_t eA = __builtin_amdgcn_bitop3_b32(uA, zA, 0x80808080u, 0x02), eB = __builtin_amdgcn_bitop3_b32(uB, zB, 0x80808080u, 0x02);   // ~u & ~z & mask
                     S[g] = live ? ((eA >> 7) | (eB >> 3)) : 0u;
@@ -1118,10 +1169,11 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                         slot++;
                     }
                 }
+                if constexpr (PROF) { RR_T(9) }   // (profile build: the wait at the scan's barrier is timed on its own)
                 wg_barrier();
                 const uint32_t nwork = ictl[0];
                 img_fail = nwork > (uint32_t)RR_IMG_WL;
-                RR_T(9)
+                RR_T(11)
                 if (!img_fail) {
                     // (2) repair: worklist entries dealt round-robin over the threads, GB per thread in flight.  An entry is a pair of equal
                     // tags; the thread whose pair has no such pair in front of it owns the run: it finds the length from the tags behind the
@@ -1449,7 +1501,7 @@ static int launch_rank_reg_variant(const float *pdist, int64_t ldp, int64_t q, i
         SE_HIP_CHECK(hipStreamSynchronize(s));
         SE_HIP_CHECK(hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost));
         SE_HIP_CHECK(hipFree(prof));
-        static const char *names[12] = {"load", "rank", "scan", "dest", "idx-write", "idx-read", "key-exchange", "write-out", "image-map|window-map", "tag-scan|window-max", "repair|window-barrier-1", "window-count"};
+        static const char *names[12] = {"load", "rank", "scan", "dest", "idx-write", "idx-read", "key-exchange", "write-out", "image-map|window-map", "tag-scan|window-max", "repair|window-barrier-1", "window-count|scan-barrier"};
         double tot = 0;
         for (int i = 0; i < 12; i++) tot += (double)h[i];
         if (tot > 0) {
