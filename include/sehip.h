@@ -206,6 +206,21 @@ int se_devise_loss_bwd(const int64_t *labels, const float *y_true, int64_t ldt, 
                        const float *grad_loss_i, float grad_scale, int64_t B, int64_t D, int64_t C, const float *aux,
                        float *d_pred, int64_t lddp, se_stream_t stream);
 
+/*
+ * Center loss (Wen et al.): gradient with respect to the LEARNED class centroids.
+ * Replaces: what TF autodiff derives for the `cls_centroids` Embedding of learn_center_loss.py:17-41, whose loss is
+ *           center_loss_i = sum_d (x[i, d] - centroids[y_i, d])^2 / 2.  That loss is exactly 0.5 * se_sqdist_loss_fwd, and its
+ *           gradient with respect to x is exactly se_sqdist_loss_bwd with the weights w_i / 2: no entry point of their own.
+ *   x [B, D] f32 / bf16 (ldx), labels [B] int64 (clamped to [0, C - 1] like the gather of the loss kernels), centroids [C, D] f32 (ldc)
+ *   dcent [C, D] f32 out (lddc).  EVERY row is written: dcent[k, d] starts at +0, then acc = acc - fl(w_i * fl(x[i, d] - centroids[k, d]))
+ *   runs over the rows i with labels[i] == k in increasing i; w_i = grad_loss_i[i] (NULL: grad_scale for every row).  Rows of
+ *   absent classes are +0; B = 0 writes zeros (x and labels may then be NULL).  No atomics, no workspace, no host synchronisation:
+ *   the same inputs give the same bits whatever the launch geometry or concurrent work, and the call can be captured in a HIP graph.
+ */
+int se_center_loss_centroid_grad(const void *x, int x_dtype, int64_t ldx, const int64_t *labels, const float *centroids,
+                                 int64_t ldc, const float *grad_loss_i, float grad_scale, int64_t B, int64_t D, int64_t C,
+                                 float *dcent, int64_t lddc, se_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Retrieval side  (evaluate_retrieval.pairwise_retrieval, evaluate_retrieval.py:22-73)
  * ------------------------------------------------------------------------------------------ */

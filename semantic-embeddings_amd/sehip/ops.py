@@ -13,7 +13,7 @@ from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, MET
 
 __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
-    "sqdist_loss_backward", "l2norm", "nn_accuracy", "labelembed_loss", "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
+    "sqdist_loss_backward", "center_loss", "l2norm", "nn_accuracy", "labelembed_loss", "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
@@ -145,6 +145,11 @@ def _check_loss_inputs(labels, embedding, what):
     (one synchronising min / max per call: a debugging aid); a table that asks for a gradient is refused always."""
     if embedding.requires_grad:
         raise SehipError("%s: the class-embedding table is a constant of this loss (no gradient is computed for it); detach() it" % what)
+    _check_labels(labels, embedding, what)
+
+
+def _check_labels(labels, embedding, what):
+    """``SEHIP_CHECK_LABELS=1``: the labels must index rows of ``embedding`` (one synchronising min / max)."""
     if os.environ.get("SEHIP_CHECK_LABELS"):
         lo, hi = int(labels.min()), int(labels.max())
         if lo < 0 or hi >= embedding.shape[0]:
@@ -225,6 +230,50 @@ def squared_distance_loss(x, labels, embedding, reduction="none"):
     """Differentiable ``utils.squared_distance(embedding[labels], x)`` (the `--loss mse` training loss) in one HIP launch forward,
     one backward; ``reduction``: "none" (Keras-style per-sample tensor), "mean" or "sum"."""
     loss_i = _SquaredDistanceLoss.apply(x, labels, embedding)
+    if reduction == "mean":
+        return loss_i.mean()
+    if reduction == "sum":
+        return loss_i.sum()
+    return loss_i
+
+
+class _CenterLoss(torch.autograd.Function):
+    """reference: the center loss of learn_center_loss.py:35-39, sum_d (x - c[y])^2 / 2, and what TF autodiff derives from it for the
+    features and the (learned) centroids.  Halving is exact, so the forward pass is 0.5 * se_sqdist_loss_fwd and the feature gradient
+    se_sqdist_loss_bwd with the weights w / 2 (2 (w / 2) = w); the centroid gradient is se_center_loss_centroid_grad."""
+
+    @staticmethod
+    def forward(ctx, x, labels, centroids):
+        require_gpu(x, labels, centroids)
+        x = x if x.stride(-1) == 1 else x.contiguous()
+        B, D, C = _class_loss_shapes(x, labels, centroids)
+        _check_labels(labels, centroids, "center_loss")
+        loss_i = torch.empty((B,), dtype=torch.float32, device=x.device)
+        call("se_sqdist_loss_fwd", x, _dtype_code(x), x.stride(0), labels, centroids, centroids.stride(0), B, D, C, loss_i, None, None)
+        ctx.save_for_backward(x, labels, centroids)
+        return loss_i.mul_(0.5)
+
+    @staticmethod
+    def backward(ctx, grad_loss_i):
+        x, labels, centroids = ctx.saved_tensors
+        B, D, C = _class_loss_shapes(x, labels, centroids)
+        g = grad_loss_i.to(torch.float32).contiguous()
+        dx = dc = None
+        if ctx.needs_input_grad[0]:
+            dx = sqdist_loss_backward(x, labels, centroids, g * 0.5)
+        if ctx.needs_input_grad[2]:
+            dc = torch.empty((C, D), dtype=torch.float32, device=x.device)
+            call("se_center_loss_centroid_grad", x, _dtype_code(x), x.stride(0), labels, centroids, centroids.stride(0), g, 0.0, B, D, C,
+                 dc, D)
+        return dx, None, dc
+
+
+def center_loss(x, labels, centroids, reduction="none"):
+    """Differentiable center loss (Wen et al.; learn_center_loss.py:35-39): sum_d (x - centroids[labels])^2 / 2 per row of ``x``
+    [B, D] (float32 or bfloat16; ``dx`` in x's dtype), labels contiguous int64 [B] (clamped to [0, C - 1] like every loss gather;
+    ``SEHIP_CHECK_LABELS=1`` checks them), centroids float32 [C, D] -- learned (``requires_grad``: its gradient is the fixed-order
+    per-class sum of se_center_loss_centroid_grad) or fixed.  ``reduction``: "none" (per-sample [B]), "mean" or "sum"."""
+    loss_i = _CenterLoss.apply(x, labels, centroids)
     if reduction == "mean":
         return loss_i.mean()
     if reduction == "sum":

@@ -1,0 +1,379 @@
+"""GPU: the center loss (Wen et al.; reference learn_center_loss.py) on the HIP kernels.
+
+se_center_loss_centroid_grad bit for bit against a float32 NumPy loop in batch order (its rule in include/sehip.h), the loss and the
+feature gradient of sehip.center_loss against float64 / float32 oracles, autograd against PyTorch in float64, determinism (repeats,
+a busy second stream, HIP-graph replay), one Trainer step, the learn_center_loss.py CLI end to end and a world-2 data-parallel run."""
+import json
+import os
+import pickle
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+U = 2.0 ** -24
+SENT32 = np.int32(0x7FC0DEAD)       # a quiet NaN with a payload no kernel writes
+F32, BF16 = 0, 1
+
+
+def call(name, *args):
+    from sehip._lib import call as c
+    return c(name, *args)
+
+
+def oracle_centroid_grad(x, labels, cent, w, C):
+    """The rule of se_center_loss_centroid_grad in float32: dcent[k] = +0, then dcent[k] -= fl(w_i * fl(x_i - c_k)) over the rows of
+    class k (labels clamped to [0, C - 1]) in increasing i."""
+    x, cent, w = x.astype(np.float32), cent.astype(np.float32), w.astype(np.float32)
+    out = np.zeros(cent.shape, dtype=np.float32)
+    for i, k in enumerate(np.clip(labels, 0, C - 1)):
+        out[k] = out[k] - w[i] * (x[i] - cent[k])
+    return out
+
+
+def place(a, ld, dtype):
+    """Device copy of the float32 matrix ``a`` [rows, d] with row pitch ``ld`` and NaN in the pitch padding."""
+    rows, d = a.shape
+    buf = torch.full((max(rows, 1), ld), float("nan"), dtype=dtype, device="cuda")
+    buf[:rows, :d] = torch.from_numpy(np.ascontiguousarray(a)).cuda().to(dtype)
+    return buf[:rows, :d]
+
+
+def guarded(rows, cols, ld):
+    """A [rows, cols] float32 output of pitch ``ld`` inside a sentinel buffer (one guard row before, two after)."""
+    buf = torch.full((rows + 3, ld), int(SENT32), dtype=torch.int32, device="cuda")
+    return buf, buf.view(torch.float32)[1:rows + 1, :cols]
+
+
+def read_guarded(buf, rows, cols):
+    b = buf.cpu().numpy()
+    inside = np.zeros(b.shape, dtype=bool)
+    inside[1:rows + 1, :cols] = True
+    assert (b[~inside] == SENT32).all(), "a store left the output (pitch padding or guard rows)"
+    return b[1:rows + 1, :cols].view(np.float32).copy()
+
+
+def centroid_grad(x, dtype, labels, cent, w, scale, C, pad=0):
+    """se_center_loss_centroid_grad through the C ABI on NaN-padded inputs of pitch D + pad into a guarded output."""
+    B, D = x.shape
+    xd = place(x, D + pad, torch.bfloat16 if dtype == BF16 else torch.float32)
+    cd = place(cent, D + pad, torch.float32)
+    yd = torch.from_numpy(labels.astype(np.int64)).cuda()
+    wd = None if w is None else torch.from_numpy(w.astype(np.float32)).cuda()
+    buf, out = guarded(C, D, D + pad)
+    call("se_center_loss_centroid_grad", xd if B else None, dtype, D + pad, yd if B else None, cd, D + pad, wd, float(scale), B, D, C,
+         out, D + pad)
+    return read_guarded(buf, C, D)
+
+
+CASES = [(B, D) for B in (0, 1, 37, 128, 4096) for D in (1, 3, 63, 100, 129, 1000)]
+
+
+@pytest.mark.parametrize("B,D", CASES, ids=["B%d-D%d" % c for c in CASES])
+def test_centroid_grad_bit_exact(B, D):
+    """Every (B, D) against the float32 loop, f32 and bf16 features, per-row weights and grad_scale, pitches wider than D, labels
+    with duplicates, absent classes (+0 rows) and out-of-range values (== the clamped labels)."""
+    Cs = (1, 33, 1000, 8142)
+    rng = np.random.default_rng(B * 7919 + D)
+    for n, C in enumerate(Cs):
+        dtype = (n + B) % 2
+        x = rng.standard_normal((B, D)).astype(np.float32) * np.float32(2.0 ** rng.integers(-4, 5))
+        if dtype == BF16:
+            x = torch.from_numpy(x).bfloat16().float().numpy()
+        cent = (rng.standard_normal((C, D)) * 0.5).astype(np.float32)
+        labels = rng.integers(-3, C + 3, size=B) if B else np.zeros(0, dtype=np.int64)
+        if B > 1:
+            labels[: B // 3] = labels[0]                                  # one heavily repeated class
+        w = rng.uniform(0.01, 2.0, size=B).astype(np.float32) if n % 2 == 0 else None
+        scale = np.float32(0.1 / max(B, 1))
+        got = centroid_grad(x, dtype, labels, cent, w, scale, C, pad=(n * 3) % 5)
+        want = oracle_centroid_grad(x, labels, cent, w if w is not None else np.full(B, scale, np.float32), C)
+        assert np.array_equal(got.view(np.int32), want.view(np.int32)), (B, D, C, dtype, w is None)
+        present = np.unique(np.clip(labels, 0, C - 1))
+        absent = np.setdiff1d(np.arange(C), present)
+        assert (got[absent].view(np.int32) == 0).all()                    # +0, not -0
+        if B:
+            clamped = centroid_grad(x, dtype, np.clip(labels, 0, C - 1), cent, w, scale, C)
+            assert np.array_equal(got.view(np.int32), clamped.view(np.int32))
+
+
+def test_centroid_grad_all_rows_in_one_class():
+    rng = np.random.default_rng(5)
+    B, D, C = 4096, 129, 8142
+    x = rng.standard_normal((B, D)).astype(np.float32)
+    cent = rng.standard_normal((C, D)).astype(np.float32)
+    labels = np.full(B, 8141)
+    w = rng.uniform(0.5, 1.5, size=B).astype(np.float32)
+    got = centroid_grad(x, F32, labels, cent, w, 0.0, C, pad=3)
+    want = oracle_centroid_grad(x, labels, cent, w, C)
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
+    assert (got[:-1].view(np.int32) == 0).all() and np.abs(got[-1]).max() > 0
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("B,D,C", [(1, 1, 1), (37, 63, 33), (128, 100, 100), (1024, 1000, 1000), (256, 129, 8142)])
+def test_loss_and_feature_gradient(B, D, C, dtype):
+    """loss_i within c (D + 4) 2^-24 sum|terms| of float64; dx == float32 w (x - c[y]) bit for bit (bf16: its RNE rounding); the
+    centroid gradient of autograd == the float32 loop."""
+    import sehip
+    rng = np.random.default_rng(B + D + C)
+    x = torch.from_numpy(rng.standard_normal((B, D)).astype(np.float32)).cuda().to(dtype).requires_grad_(True)
+    c = torch.from_numpy(rng.standard_normal((C, D)).astype(np.float32)).cuda().requires_grad_(True)
+    y = torch.from_numpy(rng.integers(0, C, size=B)).cuda()
+    g = torch.from_numpy(rng.uniform(0.01, 1.0, size=B).astype(np.float32)).cuda()
+    loss = sehip.center_loss(x, y, c)
+    loss.backward(g)
+    xf, cn, yn, gn = x.detach().float().cpu().numpy(), c.detach().cpu().numpy(), y.cpu().numpy(), g.cpu().numpy()
+    terms = 0.5 * (xf.astype(np.float64) - cn[yn].astype(np.float64)) ** 2
+    ref = terms.sum(-1)
+    assert loss.dtype == torch.float32 and loss.shape == (B,)
+    assert np.all(np.abs(loss.detach().cpu().numpy() - ref) <= 4.0 * (D + 4) * U * ref)
+    dx32 = gn[:, None] * (xf - cn[yn])                                     # float32: fl(w fl(x - c))
+    assert x.grad.dtype == dtype
+    if dtype == torch.float32:
+        assert np.array_equal(x.grad.cpu().numpy().view(np.int32), dx32.view(np.int32))
+    else:
+        assert torch.equal(x.grad.view(torch.int16).cpu(), torch.from_numpy(dx32).bfloat16().view(torch.int16))
+    want = oracle_centroid_grad(xf, yn, cn, gn, C)
+    assert np.array_equal(c.grad.cpu().numpy().view(np.int32), want.view(np.int32))
+
+
+def test_autograd_against_float64_torch_and_frozen_table():
+    import sehip
+    rng = np.random.default_rng(11)
+    B, D, C = 300, 100, 50
+    x = torch.from_numpy(rng.standard_normal((B, D)).astype(np.float32)).cuda().requires_grad_(True)
+    c = torch.from_numpy(rng.standard_normal((C, D)).astype(np.float32)).cuda().requires_grad_(True)
+    y = torch.from_numpy(rng.integers(0, C, size=B)).cuda()
+    sehip.center_loss(x, y, c, reduction="mean").mul(0.1).backward()
+    x64, c64 = x.detach().double().requires_grad_(True), c.detach().double().requires_grad_(True)
+    (0.5 * ((x64 - c64[y]) ** 2).sum(-1)).mean().mul(0.1).backward()
+    assert torch.allclose(x.grad.double(), x64.grad, rtol=1e-5, atol=1e-9)
+    assert torch.allclose(c.grad.double(), c64.grad, rtol=1e-4, atol=1e-8)
+    assert float(c.grad.abs().sum()) > 0
+    # a frozen table: the feature gradient only
+    x.grad = None
+    cf = c.detach()
+    sehip.center_loss(x, y, cf, reduction="sum").backward()
+    assert cf.grad is None and torch.allclose(x.grad.double(), (x64 - c64[y]).detach(), rtol=1e-5, atol=1e-6)
+    # the refusing check of the constant-table losses is unchanged
+    with pytest.raises(sehip.SehipError):
+        sehip.squared_distance_loss(x, y, c)
+
+
+def _centroid_grad_call(x, y, c, g, out):
+    call("se_center_loss_centroid_grad", x, F32, x.stride(0), y, c, c.stride(0), g, 0.0, x.shape[0], x.shape[1], c.shape[0], out,
+         out.stride(0))
+
+
+def test_determinism_repeats_and_busy_second_stream():
+    rng = np.random.default_rng(3)
+    B, D, C = 1024, 100, 1000
+    x = torch.from_numpy(rng.standard_normal((B, D)).astype(np.float32)).cuda()
+    c = torch.from_numpy(rng.standard_normal((C, D)).astype(np.float32)).cuda()
+    y = torch.from_numpy(rng.integers(0, C // 10, size=B)).cuda()          # ~10 rows per present class
+    g = torch.from_numpy(rng.uniform(0.1, 1.0, size=B).astype(np.float32)).cuda()
+    outs = [torch.empty((C, D), device="cuda") for _ in range(20)]
+    for o in outs:
+        _centroid_grad_call(x, y, c, g, o)
+    torch.cuda.synchronize()
+    for o in outs[1:]:
+        assert torch.equal(o.view(torch.int32), outs[0].view(torch.int32))
+    a = torch.randn(2048, 2048, device="cuda")
+    side = torch.cuda.Stream()
+    busy = [torch.empty((C, D), device="cuda") for _ in range(10)]
+    with torch.cuda.stream(side):
+        for _ in range(40):
+            a = torch.tanh(a @ a * 1e-3)
+    for o in busy:
+        _centroid_grad_call(x, y, c, g, o)
+    torch.cuda.synchronize()
+    for o in busy:
+        assert torch.equal(o.view(torch.int32), outs[0].view(torch.int32))
+
+
+def test_graph_capture_replays_bit_equal_to_eager():
+    import sehip
+    rng = np.random.default_rng(4)
+    B, D, C = 128, 100, 100
+    x = torch.from_numpy(rng.standard_normal((B, D)).astype(np.float32)).cuda().requires_grad_(True)
+    c = torch.nn.Parameter(torch.from_numpy(rng.uniform(-0.05, 0.05, size=(C, D)).astype(np.float32)).cuda())
+    y = torch.from_numpy(rng.integers(0, C, size=B)).cuda()
+
+    def step():
+        x.grad, c.grad = None, None
+        loss = sehip.center_loss(x, y, c, reduction="mean") * 0.1
+        loss.backward()
+        return loss
+
+    eager = step().detach().clone()
+    ex, ec = x.grad.clone(), c.grad.clone()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    x.grad, c.grad = None, None
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        gl = step()
+    for _ in range(3):
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(gl.view(torch.int32), eager.view(torch.int32))
+        assert torch.equal(x.grad.view(torch.int32), ex.view(torch.int32))
+        assert torch.equal(c.grad.view(torch.int32), ec.view(torch.int32))
+
+
+def test_trainer_step_moves_present_centroids_only():
+    """One engine.Trainer step (eager): the centroid rows of the batch's classes move by -lr x the clipped gradient, which is a
+    positive multiple (<= 1: clipnorm) of -(w / B) sum (x_i - c_k); the rows of absent classes do not move."""
+    import utils
+    import learn_center_loss as lcl
+    from datasets import SyntheticGenerator
+    from engine import Trainer
+    torch.manual_seed(0)
+    model = lcl.CenterLossModel(utils.build_network(100, "resnet-110-fc", input_channels=3), 100).cuda()
+    losses, metrics = lcl.build_losses(model, 0.1)
+    tr = Trainer(model, losses, metrics, lr=0.05, momentum=0.9, clipnorm=10.0, autocast_dtype=None, memory_format=torch.contiguous_format)
+    gen = SyntheticGenerator(100, 32, 3, 64, 32)
+    seq = gen.train_sequence(32, shuffle=False, batch_transform=lcl.transform_inputs, batch_transform_kwargs={"num_classes": 100})
+    X, ys = seq[0]
+    W = model.cls_centroids.weight
+    before = W.detach().clone()
+    with torch.no_grad():
+        _, emb = model(X)                        # train mode: the same batch statistics as the step's forward
+    labels = ys[1].cpu().numpy()
+    dC = torch.zeros_like(before)
+    dC.index_add_(0, ys[1], -(0.1 / 32) * (emb.float() - before[ys[1]]))
+    tr.train_step(X, ys, {})
+    torch.cuda.synchronize()
+    idx = next(i for i, p in enumerate(tr.flat.params) if p is W)
+    off, n = tr.flat.offsets[idx]
+    g = tr.flat.flat_g[off:off + n].view(100, 100)          # the clipped gradient the update used
+    present = np.unique(labels)
+    absent = np.setdiff1d(np.arange(100), present)
+    assert len(absent) > 0
+    after = W.detach()
+    assert torch.equal(after[absent], before[absent]) and not g[absent].any()
+    assert torch.allclose(after[present], before[present] - 0.05 * g[present], rtol=0, atol=1e-7)
+    assert bool((after[present] != before[present]).any(dim=1).all())
+    factor = float((g * dC).sum() / (dC * dC).sum())
+    assert 0.0 < factor <= 1.0 + 1e-5
+    assert torch.allclose(g[present], factor * dC[present], rtol=2e-3, atol=1e-7)
+
+
+def _cli(lcl, tmp_path, tag, *extra):
+    feat, wts, logd = str(tmp_path / (tag + "_feat.pickle")), str(tmp_path / (tag + "_w.pt")), str(tmp_path / (tag + "_log"))
+    final = lcl.main(["--dataset", "synthetic:100x32x192x64", "--data_root", "-", "--architecture", "resnet-110-fc", "--lr_schedule",
+                      "SGD", "--sgd_lr", "0.05", "--batch_size", "32", "--val_batch_size", "32", "--feature_dump", feat, "--weight_dump",
+                      wts, "--log_dir", logd] + list(extra))
+    return final, feat, wts, logd
+
+
+def test_learn_center_loss_cli_end_to_end(tmp_path, capsys):
+    """The training CLI with the reference's flags: two epochs of ResNet-110-fc with learned centroids (HIP-graph replay of the
+    step, validation, log under the Keras names, Average Accuracy, dumps); the raw features go through pairwise_retrieval."""
+    import learn_center_loss as lcl
+    import evaluate_retrieval as er
+    import utils
+    final, feat, wts, logd = _cli(lcl, tmp_path, "learned", "--epochs", "2")
+    out = capsys.readouterr().out
+    assert "Average Accuracy:" in out
+    assert "[engine] training step: HIP-graph replay" in out and "staying eager" not in out
+    keys = {"loss", "prob_loss", "center_loss_loss", "prob_acc"}
+    assert keys <= set(final) and all(np.isfinite(final[k]) for k in keys), final
+    log = [json.loads(l) for l in open(os.path.join(logd, "training_log.jsonl"))]
+    assert [e["epoch"] for e in log] == [1, 2]
+    for e in log:
+        assert keys | {"val_" + k for k in keys} <= set(e) and all(np.isfinite(v) for v in e.values()), e
+    model = lcl.CenterLossModel(utils.build_network(100, "resnet-110-fc", input_channels=3), 100)
+    model.load_state_dict(torch.load(wts))
+    with open(feat, "rb") as f:
+        dump = pickle.load(f)
+    feats = np.stack([dump["feat"][i] for i in range(64)])
+    assert feats.shape == (64, 100) and np.isfinite(feats).all()
+    assert not np.allclose(np.linalg.norm(feats, axis=-1), 1.0, atol=1e-3)                  # raw, not normalised
+    ranked = dict(er.pairwise_retrieval(feat, normalize=True, return_generator=False))
+    assert sorted(ranked) == list(range(64)) and all(ranked[i][0] == i and len(ranked[i]) == 64 for i in ranked)
+
+
+def test_learn_center_loss_cli_with_fixed_centroids(tmp_path, capsys):
+    """--centroids: the table stays the pickle's bit for bit; with --finetune --finetune_init 1 the reference's layer loops make it
+    trainable, so it changes."""
+    import learn_center_loss as lcl
+    E = np.load(os.path.join(GOLDEN, "embeddings.npz"))["cifar100_unitsphere"]
+    emb = str(tmp_path / "emb.pickle")
+    with open(emb, "wb") as f:
+        pickle.dump({"embedding": E, "ind2label": list(range(100)), "label2ind": {i: i for i in range(100)}}, f)
+    want = torch.from_numpy(E.astype(np.float32))
+    _, _, wts, _ = _cli(lcl, tmp_path, "fixed", "--epochs", "1", "--centroids", emb, "--no_progress")
+    got = torch.load(wts)["cls_centroids.weight"].cpu()
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))
+    capsys.readouterr()
+    _, _, wts2, _ = _cli(lcl, tmp_path, "finetune", "--epochs", "1", "--centroids", emb, "--finetune", wts, "--finetune_init", "1",
+                         "--no_progress")
+    out = capsys.readouterr().out
+    assert "trains the --centroids table" in out and "Pre-training new layers" in out and "Average Accuracy:" in out
+    moved = torch.load(wts2)["cls_centroids.weight"].cpu()
+    assert torch.isfinite(moved).all() and not torch.equal(moved, want)
+
+
+def _center_dp_worker(rank, world, port, out):
+    import torch.distributed as dist
+    for p in (os.path.join(ROOT, "semantic-embeddings_amd"), ROOT):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)     # RCCL refuses two ranks on one device; gloo all-reduces CUDA tensors
+    torch.cuda.set_device(0)
+    import utils
+    import learn_center_loss as lcl
+    from datasets import SyntheticGenerator
+    from engine import Trainer
+    torch.manual_seed(0)
+    model = lcl.CenterLossModel(utils.build_network(64, "resnet-32", classification=True, no_softmax=True, input_channels=3), 100).cuda()
+    losses, metrics = lcl.build_losses(model, 0.1)
+    tr = Trainer(model, losses, metrics, lr=0.05, clipnorm=10.0, autocast_dtype=None, memory_format=torch.contiguous_format)
+    assert tr.world == 2 and tr.reducer.enabled
+    gen = SyntheticGenerator(100, 32, 3, 256, 32)
+    seq = gen.train_sequence(32, shuffle=False, rank=rank, world_size=world, batch_transform=lcl.transform_inputs,
+                             batch_transform_kwargs={"num_classes": 100})
+    before = model.cls_centroids.weight.detach().cpu().clone()
+    ok = tr.enable_graphs(*seq[0])
+    for i in range(4):
+        tr.train_step(*seq[i % len(seq)], {})
+    torch.cuda.synchronize()
+    table = model.cls_centroids.weight.detach().cpu()
+    both = [None, None]
+    dist.all_gather_object(both, table.numpy().tobytes())
+    if rank == 0:
+        torch.save({"ok": ok, "same": both[0] == both[1], "before": before, "after": table}, out)
+    dist.destroy_process_group()
+
+
+def test_world2_centroid_tables_stay_identical(tmp_path):
+    """Two processes (gloo) on the one GPU, 4 graph-mode steps: both ranks hold the same centroid table, and a class that only rank
+    0's half-batches contain has moved on rank 1 too -- its gradient went through the all-reduce.  (A single process on the whole
+    batch is no reference: BatchNorm statistics are per rank, as they are per tower in the reference.)"""
+    import torch.multiprocessing as mp
+    from datasets import SyntheticGenerator
+    out = str(tmp_path / "c.pt")
+    mp.spawn(_center_dp_worker, args=(2, 29641, out), nprocs=2, join=True)
+    got = torch.load(out)
+    assert got["ok"] and got["same"], {k: got[k] for k in ("ok", "same")}
+    y = np.asarray(SyntheticGenerator(100, 32, 3, 256, 32).y_train)
+    rank0 = set(np.concatenate([y[32 * i:32 * (i + 1)][0::2] for i in range(4)]).tolist())
+    rank1 = set(np.concatenate([y[32 * i:32 * (i + 1)][1::2] for i in range(4)]).tolist())
+    only0 = sorted(rank0 - rank1)
+    assert only0
+    moved = (got["after"] != got["before"]).any(dim=1)
+    assert bool(moved[only0].all())
+    never = sorted(set(range(100)) - rank0 - rank1)
+    assert not bool(moved[never].any())                # no gradient ever: not even momentum moves them

@@ -5,7 +5,9 @@
     python tools/bench_kernels.py svm            (margin + reduction kernels and whole LinearSVC fits: 50,000 x 100 x 100 and
                                                   1,281,167 x 1000 x 1000; --n / --d are not used; --svm-sizes small skips the large one)
     python tools/bench_kernels.py classemb       (class pair tables and fp64 Cholesky at C = 1000 (ILSVRC WordNet DAG) and 8,142 (iNat
-                                                  2018), and the whole compute_class_embedding.py run on the iNat hierarchy)"""
+                                                  2018), and the whole compute_class_embedding.py run on the iNat hierarchy)
+    python tools/bench_kernels.py center         (center loss forward / input gradient / centroid gradient at D = 100, and the
+                                                  ResNet-110-fc center-loss training step next to the cosine-loss one)"""
 import argparse
 import os
 import sys
@@ -32,7 +34,8 @@ def timeit(fn, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb"])
+    ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
+                                     "center"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -43,6 +46,8 @@ def main():
     args = ap.parse_args()
     if args.what == "classemb":
         return bench_classemb(args.reps)
+    if args.what == "center":
+        return bench_center()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -321,6 +326,82 @@ def bench_classemb(reps):
             e = pickle.load(f)["embedding"]
         print("compute_class_embedding.py iNat 2018 (8,142 classes, unitsphere): %.1f s wall (process start to exit), finite %s"
               % (wall, bool(np.isfinite(e).all())))
+
+
+def bench_center(reps=200, steps=200):
+    """Center loss (learn_center_loss.py): forward (se_sqdist_loss_fwd + the halving), input gradient (se_sqdist_loss_bwd) and
+    centroid gradient (se_center_loss_centroid_grad) at D = 100, then one ResNet-110-fc training step (batch 128, fp32, HIP-graph
+    replay) with the center-loss model next to the cosine-loss model, the two timed alternately."""
+    from sehip._lib import call
+    sys.path.insert(0, os.path.join(ROOT, "semantic-embeddings_amd"))
+    D = 100
+    for B in (128, 1024):
+        for C in (100, 1000, 8142):
+            rng = np.random.default_rng(B + C)
+            x = torch.from_numpy(rng.standard_normal((B, D)).astype(np.float32)).cuda()
+            c = torch.from_numpy(rng.uniform(-0.05, 0.05, (C, D)).astype(np.float32)).cuda()
+            y = torch.from_numpy(rng.integers(0, C, B)).cuda()
+            g = torch.full((B,), 0.1 / B, device="cuda")
+            loss_i, dx, dc = torch.empty(B, device="cuda"), torch.empty(B, D, device="cuda"), torch.empty(C, D, device="cuda")
+
+            def fwd():
+                call("se_sqdist_loss_fwd", x, 0, D, y, c, D, B, D, C, loss_i, None, None)
+                loss_i.mul_(0.5)
+
+            def bwd_x():
+                call("se_sqdist_loss_bwd", x, 0, D, y, c, D, g, 0.0, B, D, C, dx, 0, D)
+
+            def bwd_c():
+                call("se_center_loss_centroid_grad", x, 0, D, y, c, D, g, 0.0, B, D, C, dc, D)
+            t = [timeit(f, reps)[0] * 1e3 for f in (fwd, bwd_x, bwd_c)]
+            print("center loss B=%d D=%d C=%d: forward %.1f us, input gradient %.1f us, centroid gradient %.1f us "
+                  "(median of %d; HIP events around one call)" % (B, D, C, t[0], t[1], t[2], reps))
+
+    import utils
+    import learn_center_loss as lcl
+    from datasets import SyntheticGenerator
+    from engine import Trainer
+    E = np.load(os.path.join(ROOT, "tests", "golden", "embeddings.npz"))["cifar100_unitsphere"]
+    Ed = torch.from_numpy(E.astype(np.float32)).cuda()
+    trainers = {}
+    for name in ("cosine", "center"):
+        torch.manual_seed(0)
+        model = utils.build_network(100, "resnet-110-fc", input_channels=3).cuda()
+        l2_of = {id(p): model.regularizer for p in model.regularized_parameters()}
+        if name == "cosine":
+            tr = Trainer(model, {"l2norm": (utils.CosineEmbeddingLoss(Ed), 1.0)}, {"l2norm": [utils.nn_accuracy(Ed, dot_prod_sim=True)]},
+                         lr=0.1, momentum=0.9, clipnorm=10.0, l2_of=l2_of, autocast_dtype=None, memory_format=torch.contiguous_format)
+            transform, kw = None, {}
+        else:
+            model = lcl.CenterLossModel(model, 100).cuda()
+            losses, metrics = lcl.build_losses(model, 0.1)
+            tr = Trainer(model, losses, metrics, lr=0.1, momentum=0.9, clipnorm=10.0, l2_of=l2_of, autocast_dtype=None,
+                         memory_format=torch.contiguous_format)
+            transform, kw = lcl.transform_inputs, {"num_classes": 100}
+        seq = SyntheticGenerator(100, 32, 3, 128 * 8, 128).train_sequence(128, shuffle=False, batch_transform=transform,
+                                                                          batch_transform_kwargs=kw)
+        batches = [seq[i] for i in range(8)]
+        assert tr.enable_graphs(*batches[0]), name
+        for i in range(10):
+            tr.train_step(*batches[i % 8], {})
+        trainers[name] = (tr, batches)
+    ms = {name: [] for name in trainers}
+    for _ in range(3):                       # alternate the two models: the same machine state for both
+        for name, (tr, batches) in trainers.items():
+            logs = {}
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(steps):
+                tr.train_step(*batches[i % 8], logs)
+            b.record()
+            torch.cuda.synchronize()
+            assert np.isfinite(float(logs["loss"]))
+            ms[name].append(a.elapsed_time(b) / steps)
+    for name in trainers:
+        step = float(np.median(ms[name]))
+        print("ResNet-110-fc %s-loss step, batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d steps; %s), "
+              "%.0f images/s" % (name, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
 
 
 if __name__ == "__main__":
