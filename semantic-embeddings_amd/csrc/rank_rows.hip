@@ -797,7 +797,9 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
 #pragma unroll
                 for (int s = 0; s < ITEMS; s++) below_l += ((int32_t)key[s] < lo) ? 1u : 0u;        // v_cmp + v_addc
                 // padding slots read as 0 (range-checked buffer loads), which lies below the window because lo >= 1: take them out
-                // again (only the wave(s) that have any)
+                // again (only the wave(s) that have any).  The 0 comes from the range check, not from memory: what lies behind the
+                // row's end -- the next row, or a pitch padding that holds NaN or -inf -- never reaches a key.  Held to that by the
+                // padded-input cases (inp = NAN / NINF) of tests/test_gpu_rank_matrix.py, the first tests whose padding is not zero.
                 // (`lo_b`, `lo_c` below: opaque copies -- hipcc otherwise shares the 98 compare masks between the three loops and spills the
                 // SGPR pairs to VGPR lanes, ~600 v_writelane / v_readlane per row)
                 if (wave_s * (ITEMS * WAVE) + ITEMS * WAVE > n_row) {
