@@ -221,6 +221,49 @@ int se_center_loss_centroid_grad(const void *x, int x_dtype, int64_t ldx, const 
                                  int64_t ldc, const float *grad_loss_i, float grad_scale, int64_t B, int64_t D, int64_t C,
                                  float *dcent, int64_t lddc, se_stream_t stream);
 
+/*
+ * Categorical cross-entropy of the softmax classifier on LOGITS, with label smoothing, Keras 2.2's probability clip and the
+ * accuracy / top-k metrics of the same scores; forward and backward.
+ * Replaces: transform_inputs (learn_classifier.py:17-22: to_categorical + label smoothing on the host), the
+ *           'categorical_crossentropy' loss and the 'accuracy' metric of both compile() calls (learn_classifier.py:116-117, 146-147),
+ *           utils.top_k_acc (utils.py:49-54), and what TF autodiff derives from the loss with respect to the logits.
+ *   logits [B, C] f32 / bf16 (ldz), labels [B] int64 (clamped to [0, C - 1] like the gather of the other loss kernels).
+ *   Per row z with label y:  m = max z,  lse = m + log(sum_c exp(z_c - m)),  t_c = lse - z_c  (= -log softmax(z)_c).
+ *   Target: Y_c = 1 - s for c == y and s / (C - 1) otherwise when 0 < s < 1 (s = smoothing); one-hot for ANY other s, the reference's
+ *   rule.  0 < s < 1 with C < 2 is SE_ERR_INVALID.
+ *   Keras 2.2's categorical_crossentropy on a softmax output is -sum_c Y_c log(clip(p_c / sum p, eps, 1 - eps)), eps = float32(1e-7).
+ *   In the log domain, with LO = -log(1 - eps) = 1.1920929e-7f and HI = -log(eps) = 16.118095f:
+ *       loss_i = sum_c Y_c * min(max(t_c, LO), HI)
+ *       a_c    = Y_c where LO <= t_c <= HI, else 0            A_i = sum_c a_c
+ *       dz_k   = w_i * (A_i * exp(z_k - lse_i) - a_k)         w_i = grad_loss_i[i] (NULL: grad_scale for every row)
+ *   The renormalisation p / sum p is exact in this form (sum p = 1 up to rounding).  The clip caps a sample's loss at HI and gives
+ *   ZERO gradient to a class whose probability left [eps, 1 - eps]: with s = 0 a confidently wrong row has loss_i == HI and dz == 0.
+ *   t_c is evaluated as (m - z_c) + log(sum): for the arg-max class that is log(sum) itself at full relative precision, so the upper
+ *   clip (p > 1 - eps) is decided by the last bit of the float32 sum, as it would be on probabilities; lse - z_c would round t to a
+ *   multiple of ulp(lse).  bwd recomputes the forward's t_c bit for bit, so a_k and A_i always agree.
+ *   fwd outputs: loss_i [B];  aux: se_softmax_xent_aux_floats(B) = 3 B floats, caller-owned, read by bwd: m_i [B], log(sum)_i [B]
+ *        (lse_i = m_i + log(sum)_i, kept apart for the reason above) and A_i [B];
+ *        best [B] int32 = arg-max class of the logits, lowest index on ties (np.argmax; Keras' categorical_accuracy is best == y);
+ *        above [B] int32 = number of classes whose logit is strictly greater than z_y: tf.nn.in_top_k(k) is above < k (ties in
+ *        favour of the target), so one forward pass serves every --top_k_acc;
+ *        loss_mean [1] = sum of loss_i / B: thread j of 256 adds loss_i[j], loss_i[j + 256], ... in order, then a binary tree over
+ *        the 256 partial sums.  best, above and loss_mean may be NULL.
+ *   A row that holds a NaN or +inf: loss_i and its whole dz row are NaN; best is the index of the first NaN, or of the first +inf
+ *   if there is no NaN (np.argmax); above = C (never in the top k: TF's rule for a non-finite target score).  -inf logits are legal
+ *   (probability 0, clipped); a row of nothing but -inf has no softmax: NaN like a row with a NaN, best = 0.  B = 0 is accepted;
+ *   loss_mean is then +0.
+ *   bwd: one pass over [B, C]; dz [B, C] f32 / bf16 (lddz).
+ *   Asynchronous on `stream`, no allocation, no atomics, no host synchronisation: capturable in a HIP graph, and the same inputs
+ *   give the same bits.  Any row pitch; 16-byte loads / stores when pointers and pitches are 16-byte aligned.
+ */
+int64_t se_softmax_xent_aux_floats(int64_t B);
+int se_softmax_xent_fwd(const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, int64_t B, int64_t C,
+                        float smoothing, float *loss_i, float *aux, int32_t *best, int32_t *above, float *loss_mean,
+                        se_stream_t stream);
+int se_softmax_xent_bwd(const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, const float *aux,
+                        const float *grad_loss_i, float grad_scale, int64_t B, int64_t C, float smoothing, void *dz,
+                        int dz_dtype, int64_t lddz, se_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Retrieval side  (evaluate_retrieval.pairwise_retrieval, evaluate_retrieval.py:22-73)
  * ------------------------------------------------------------------------------------------ */

@@ -1,0 +1,507 @@
+// softmax_xent.hip -- categorical cross-entropy of the softmax classifier on LOGITS, with label smoothing, Keras 2.2's clip of the
+// probabilities and the accuracy / top-k metrics of the same scores; forward + backward.
+//
+// Replaces `transform_inputs` (learn_classifier.py:17-22: to_categorical + label smoothing on the host), the
+// 'categorical_crossentropy' loss and the 'accuracy' metric of both compile() calls (learn_classifier.py:116-117, 146-147),
+// utils.top_k_acc (utils.py:49-54) and what TF autodiff derives from the loss with respect to the logits.
+//
+// Per row z with label y (clamped to [0, C - 1]):  m = max z,  lse = m + log sum_c exp(z_c - m),  t_c = lse - z_c = -log softmax(z)_c.
+// Target Y_c = 1 - s (c == y), s / (C - 1) otherwise when 0 < s < 1; one-hot for every other s.  Keras' loss is
+// -sum_c Y_c log(clip(p_c / sum p, eps, 1 - eps)), eps = float32(1e-7); in the log domain, with LO = -log(1 - eps), HI = -log(eps):
+//     loss = sum_c Y_c min(max(t_c, LO), HI)        a_c = Y_c where LO <= t_c <= HI, else 0        A = sum_c a_c
+//     dz_k = w (A exp(z_k - lse) - a_k)
+// t_c is evaluated as (m - z_c) + log(sum): for the arg-max class that is log(sum) itself, at full relative precision, so the upper
+// clip (p > 1 - eps, t < 1.2e-7) is decided by the last bit of the float32 sum as it would be on probabilities -- lse - z_c would
+// round t to a multiple of ulp(lse), ~2e-6 for logits around 30.  aux keeps m and log(sum) apart for the same reason: the backward
+// pass recomputes the forward's t_c bit for bit, so a_k and A always agree.
+// (sum p = 1 up to rounding: the renormalisation is exact in this form.)  best = arg-max class (lowest index on ties; the first NaN
+// if the row holds one), above = number of classes whose logit is strictly greater than z_y (tf.nn.in_top_k(k) == above < k).
+// A row that holds a NaN or +inf, or nothing but -inf: loss, m, log(sum) and A are NaN (so the whole dz row is NaN), above = C.
+//
+// Forward paths, picked by C (xe_launch_fwd):
+//   wave   C <= 1024   one 64-lane wave per row, 16 values per lane in registers, shuffle reductions only (no LDS, no barrier)
+//   block  C <= 8192   one 256-thread workgroup per row, 32 values per thread in registers, 2 (s = 0) or 3 barriers
+//   stream otherwise   one workgroup per row, online max + sum in one read; a smoothed target takes a second read for the clamped sum
+// The row is read from memory once on the register paths (plus one broadcast load of z_y); s = 0 skips the off-target sum.
+// Each path comes with 16-byte loads (pointer and pitch 16-byte aligned) or scalar loads (any pitch).  The backward is one pass
+// over [B, C] (a wave per row up to C = 1024, a workgroup per row above); everything row-wide it needs is in aux.
+// No atomics, no workspace, no host synchronisation: every reduction is a fixed tree, so the same inputs give the same bits.
+#include "se_common.h"
+#include <limits.h>
+
+namespace se {
+
+constexpr float XE_LO = 1.1920929e-7f;     // -log(1 - eps), eps = float32(1e-7)
+constexpr float XE_HI = 16.118095f;        // -log(eps)
+constexpr int XE_WAVE_NV = 16;             // values per lane of the wave path:        C <= 64 * 16
+constexpr int XE_BLOCK_NV = 32;            // values per thread of the workgroup path: C <= 256 * 32
+constexpr int XE_WAVE_MAX_C = 64 * XE_WAVE_NV, XE_BLOCK_MAX_C = 256 * XE_BLOCK_NV;
+
+template <bool BF16>
+__device__ __forceinline__ float xe_ld(const void *row, int64_t c)
+{
+    if constexpr (BF16) return bf16_to_f32(((const uint16_t *)row)[c]);
+    else return ((const float *)row)[c];
+}
+
+// E consecutive values from column c0 (16-byte aligned address): E = 4 or 8 float32 (one or two 16-byte loads), E = 8 bf16 (one)
+template <bool BF16, int E>
+__device__ __forceinline__ void xe_ld_vec(const void *row, int64_t c0, float *v)
+{
+    if constexpr (BF16) {
+        static_assert(E == 8, "bf16 units hold 8 values");
+        const uint4 p = *(const uint4 *)((const uint16_t *)row + c0);
+        const uint32_t w[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            v[2 * k] = __uint_as_float(w[k] << 16);
+            v[2 * k + 1] = __uint_as_float(w[k] & 0xFFFF0000u);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < E; k += 4) {
+            const float4 p = *(const float4 *)((const float *)row + c0 + k);
+            v[k] = p.x; v[k + 1] = p.y; v[k + 2] = p.z; v[k + 3] = p.w;
+        }
+    }
+}
+
+template <bool BF16, int E>
+__device__ __forceinline__ void xe_st_vec(void *row, int64_t c0, const float *v)
+{
+    if constexpr (BF16) {
+        static_assert(E == 8, "bf16 units hold 8 values");
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = (uint32_t)f32_to_bf16(v[2 * k]) | ((uint32_t)f32_to_bf16(v[2 * k + 1]) << 16);
+        *(uint4 *)((uint16_t *)row + c0) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < E; k += 4) *(float4 *)((float *)row + c0 + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
+    }
+}
+
+template <bool BF16>
+__device__ __forceinline__ void xe_st(void *row, int64_t c, float v)
+{
+    if constexpr (BF16) ((uint16_t *)row)[c] = f32_to_bf16(v);
+    else ((float *)row)[c] = v;
+}
+
+__device__ __forceinline__ float xe_wave_max(float v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__device__ __forceinline__ int xe_wave_min(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__device__ __forceinline__ int xe_wave_add(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// sum of a[0 .. N) as a balanced tree (N a power of two); a is consumed
+template <int N>
+__device__ __forceinline__ float xe_tree_sum(float *a)
+{
+#pragma unroll
+    for (int stride = 1; stride < N; stride *= 2)
+#pragma unroll
+        for (int i = 0; i < N; i += 2 * stride) a[i] += a[i + stride];
+    return a[0];
+}
+
+__device__ __forceinline__ float xe_clamp(float t) { return fminf(fmaxf(t, XE_LO), XE_HI); }
+__device__ __forceinline__ bool xe_inside(float t) { return t >= XE_LO && t <= XE_HI; }      // false for NaN
+
+// The values a row statistic needs from every wave of a 256-thread workgroup (slot: one per reduction, never reused within a row)
+struct XeShared {
+    float f[4][4];
+    int i[3][4];
+};
+
+// what the last step of every forward path writes for its row
+__device__ __forceinline__ void xe_write_row(int64_t row, int64_t B, int C, bool bad, float loss, float m, float logsum, float A, int nan_at, int cand,
+                                             int cnt, float *__restrict__ loss_i, float *__restrict__ aux, int32_t *__restrict__ best,
+                                             int32_t *__restrict__ above)
+{
+    const float nan = __uint_as_float(0x7FC00000u);
+    loss_i[row] = bad ? nan : loss;
+    aux[row] = bad ? nan : m;
+    aux[B + row] = bad ? nan : logsum;
+    aux[2 * B + row] = bad ? nan : A;
+    if (best) best[row] = nan_at != INT_MAX ? nan_at : (cand == INT_MAX ? 0 : cand);      // cand == INT_MAX: every logit is -inf
+    if (above) above[row] = bad ? C : cnt;
+}
+
+// E values of a row from column c0, -inf past the row's end
+template <bool BF16, int E>
+__device__ __forceinline__ void xe_ld_unit(const void *zrow, int64_t c0, int C, float *v)
+{
+    if constexpr (E > 1) {
+        if (c0 + E <= C) {
+            xe_ld_vec<BF16, E>(zrow, c0, v);
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < E; k++) v[k] = c0 + k < C ? xe_ld<BF16>(zrow, c0 + k) : -INFINITY;
+}
+
+// Register paths.  G = 64: a wave per row, 4 rows per workgroup; G = 256: a workgroup per row.  Value slot s of thread t is column
+// ((s / E) * G + t) * E + s % E with 16-byte loads (E values each), s * G + t with scalar loads: ascending in s either way.
+template <bool BF16, bool VEC, int G, int NV>
+__global__ __launch_bounds__(256) void xent_fwd_reg_kernel(const void *__restrict__ z, int64_t ldz, const int64_t *__restrict__ labels,
+                                                           int64_t B, int C, float y_on, float y_off, float *__restrict__ loss_i,
+                                                           float *__restrict__ aux, int32_t *__restrict__ best, int32_t *__restrict__ above)
+{
+    constexpr int E = VEC ? (BF16 ? 8 : 4) : 1;
+    static_assert(NV % E == 0, "whole units per thread");
+    const int t = threadIdx.x % G, wave = threadIdx.x >> 6;
+    const int64_t row = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+    if (row >= B) return;                                   // G = 64: the whole wave leaves (this path has no barrier); G = 256: never
+    const void *zrow = BF16 ? (const void *)((const uint16_t *)z + row * ldz) : (const void *)((const float *)z + row * ldz);
+    int64_t yl = labels[row];
+    const int y = (int)(yl < 0 ? 0 : (yl >= C ? C - 1 : yl));
+    const float zy = xe_ld<BF16>(zrow, y);
+    auto col = [&](int s) { return VEC ? ((s / E) * G + t) * E + s % E : s * G + t; };
+
+    float v[NV];
+#pragma unroll
+    for (int j = 0; j < NV / E; j++) {
+        xe_ld_unit<BF16, E>(zrow, col(j * E), C, v + j * E);
+    }
+
+    float m = -INFINITY;
+    int am = INT_MAX, nan_at = INT_MAX, cnt = 0;
+#pragma unroll
+    for (int s = 0; s < NV; s++) {
+        const float x = v[s];
+        const int c = col(s);
+        if (x != x) nan_at = min(nan_at, c);
+        if (x > m) { m = x; am = c; }
+        cnt += x > zy ? 1 : 0;
+    }
+    __shared__ XeShared sh;
+    float M = xe_wave_max(m);
+    nan_at = xe_wave_min(nan_at);
+    if constexpr (G == 256) {
+        if (lane_id() == 0) { sh.f[0][wave] = M; sh.i[0][wave] = nan_at; }
+        wg_barrier();
+        M = fmaxf(fmaxf(sh.f[0][0], sh.f[0][1]), fmaxf(sh.f[0][2], sh.f[0][3]));
+        nan_at = min(min(sh.i[0][0], sh.i[0][1]), min(sh.i[0][2], sh.i[0][3]));
+    }
+    float e[NV];
+#pragma unroll
+    for (int s = 0; s < NV; s++) e[s] = expf(v[s] - M);
+    float S = wave_sum(xe_tree_sum<NV>(e));
+    int cand = xe_wave_min(m == M ? am : INT_MAX);
+    cnt = xe_wave_add(cnt);
+    if constexpr (G == 256) {
+        if (lane_id() == 0) { sh.f[1][wave] = S; sh.i[1][wave] = cand; sh.i[2][wave] = cnt; }
+        wg_barrier();
+        S = (sh.f[1][0] + sh.f[1][1]) + (sh.f[1][2] + sh.f[1][3]);
+        cand = min(min(sh.i[1][0], sh.i[1][1]), min(sh.i[1][2], sh.i[1][3]));
+        cnt = (sh.i[2][0] + sh.i[2][1]) + (sh.i[2][2] + sh.i[2][3]);
+    }
+    const float lS = logf(S);                               // lse = M + lS; t_c = (M - z_c) + lS keeps the arg-max class's t = lS
+    const bool bad = nan_at != INT_MAX || M == INFINITY || M == -INFINITY;      // -inf: nothing but -inf, no softmax
+    float loss, A;
+    if (y_off != 0.f) {                                     // smoothed target: every class contributes
+        float a[NV];
+#pragma unroll
+        for (int s = 0; s < NV; s++) {
+            const int c = col(s);
+            const float tc = (M - v[s]) + lS;
+            const float Y = c < C ? (c == y ? y_on : y_off) : 0.f;
+            e[s] = Y * xe_clamp(tc);
+            a[s] = xe_inside(tc) ? Y : 0.f;
+        }
+        loss = wave_sum(xe_tree_sum<NV>(e));
+        A = wave_sum(xe_tree_sum<NV>(a));
+        if constexpr (G == 256) {
+            if (lane_id() == 0) { sh.f[2][wave] = loss; sh.f[3][wave] = A; }
+            wg_barrier();
+            loss = (sh.f[2][0] + sh.f[2][1]) + (sh.f[2][2] + sh.f[2][3]);
+            A = (sh.f[3][0] + sh.f[3][1]) + (sh.f[3][2] + sh.f[3][3]);
+        }
+    } else {                                                // one-hot: the target class alone
+        const float ty = (M - zy) + lS;
+        loss = y_on * xe_clamp(ty);
+        A = xe_inside(ty) ? y_on : 0.f;
+    }
+    if (t == 0) xe_write_row(row, B, C, bad, loss, M, lS, A, nan_at, cand, cnt, loss_i, aux, best, above);
+}
+
+// Rows too long for registers: one workgroup per row, each thread keeps a running (max, sum of exp) over its units.
+template <bool BF16, bool VEC>
+__global__ __launch_bounds__(256) void xent_fwd_stream_kernel(const void *__restrict__ z, int64_t ldz, const int64_t *__restrict__ labels,
+                                                              int64_t B, int C, float y_on, float y_off, float *__restrict__ loss_i,
+                                                              float *__restrict__ aux, int32_t *__restrict__ best,
+                                                              int32_t *__restrict__ above)
+{
+    constexpr int E = VEC ? (BF16 ? 8 : 4) : 1;
+    const int t = threadIdx.x, wave = threadIdx.x >> 6;
+    const int64_t row = blockIdx.x;
+    const void *zrow = BF16 ? (const void *)((const uint16_t *)z + row * ldz) : (const void *)((const float *)z + row * ldz);
+    int64_t yl = labels[row];
+    const int y = (int)(yl < 0 ? 0 : (yl >= C ? C - 1 : yl));
+    const float zy = xe_ld<BF16>(zrow, y);
+    const int64_t units = ((int64_t)C + E - 1) / E;
+
+    float m = -INFINITY, ssum = 0.f;
+    int am = INT_MAX, nan_at = INT_MAX, cnt = 0;
+    for (int64_t u = t; u < units; u += 256) {
+        const int64_t c0 = u * E;
+        float v[E];
+        xe_ld_unit<BF16, E>(zrow, c0, C, v);
+        float um = -INFINITY;
+        int uam = INT_MAX;
+#pragma unroll
+        for (int k = 0; k < E; k++) {
+            if (v[k] != v[k]) nan_at = min(nan_at, (int)(c0 + k));
+            if (v[k] > um) { um = v[k]; uam = (int)(c0 + k); }
+            cnt += v[k] > zy ? 1 : 0;
+        }
+        if (um > m) {                                       // columns ascend within a thread: the first maximum stays
+            ssum = m == -INFINITY ? 0.f : ssum * expf(m - um);
+            m = um;
+            am = uam;
+        }
+        if (m != -INFINITY) {
+#pragma unroll
+            for (int k = 0; k < E; k++) ssum += expf(v[k] - m);
+        }
+    }
+    __shared__ XeShared sh;
+    float M = xe_wave_max(m);
+    nan_at = xe_wave_min(nan_at);
+    if (lane_id() == 0) { sh.f[0][wave] = M; sh.i[0][wave] = nan_at; }
+    wg_barrier();
+    M = fmaxf(fmaxf(sh.f[0][0], sh.f[0][1]), fmaxf(sh.f[0][2], sh.f[0][3]));
+    nan_at = min(min(sh.i[0][0], sh.i[0][1]), min(sh.i[0][2], sh.i[0][3]));
+    float S = wave_sum(m == -INFINITY ? 0.f : ssum * expf(m - M));
+    int cand = xe_wave_min(m == M ? am : INT_MAX);
+    cnt = xe_wave_add(cnt);
+    if (lane_id() == 0) { sh.f[1][wave] = S; sh.i[1][wave] = cand; sh.i[2][wave] = cnt; }
+    wg_barrier();
+    S = (sh.f[1][0] + sh.f[1][1]) + (sh.f[1][2] + sh.f[1][3]);
+    cand = min(min(sh.i[1][0], sh.i[1][1]), min(sh.i[1][2], sh.i[1][3]));
+    cnt = (sh.i[2][0] + sh.i[2][1]) + (sh.i[2][2] + sh.i[2][3]);
+    const float lS = logf(S);                               // lse = M + lS; t_c = (M - z_c) + lS keeps the arg-max class's t = lS
+    const bool bad = nan_at != INT_MAX || M == INFINITY || M == -INFINITY;      // -inf: nothing but -inf, no softmax
+    float loss, A;
+    if (y_off != 0.f) {                                     // second read of the row (the first left it in the L2)
+        float la[E], aa[E];
+#pragma unroll
+        for (int k = 0; k < E; k++) la[k] = aa[k] = 0.f;
+        for (int64_t u = t; u < units; u += 256) {
+            const int64_t c0 = u * E;
+            float v[E];
+            xe_ld_unit<BF16, E>(zrow, c0, C, v);
+#pragma unroll
+            for (int k = 0; k < E; k++) {
+                const float tc = (M - v[k]) + lS;
+                const float Y = c0 + k < C ? (c0 + k == y ? y_on : y_off) : 0.f;
+                la[k] += Y * xe_clamp(tc);
+                aa[k] += xe_inside(tc) ? Y : 0.f;
+            }
+        }
+        loss = wave_sum(xe_tree_sum<E>(la));
+        A = wave_sum(xe_tree_sum<E>(aa));
+        if (lane_id() == 0) { sh.f[2][wave] = loss; sh.f[3][wave] = A; }
+        wg_barrier();
+        loss = (sh.f[2][0] + sh.f[2][1]) + (sh.f[2][2] + sh.f[2][3]);
+        A = (sh.f[3][0] + sh.f[3][1]) + (sh.f[3][2] + sh.f[3][3]);
+    } else {
+        const float ty = (M - zy) + lS;
+        loss = y_on * xe_clamp(ty);
+        A = xe_inside(ty) ? y_on : 0.f;
+    }
+    if (t == 0) xe_write_row(row, B, C, bad, loss, M, lS, A, nan_at, cand, cnt, loss_i, aux, best, above);
+}
+
+// Deterministic mean of n floats: one 256-thread block, fixed tree; +0 for n = 0.
+__global__ __launch_bounds__(256) void xent_mean_kernel(const float *__restrict__ v, int64_t n, float *__restrict__ out)
+{
+    __shared__ float part[256];
+    float s = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 256) s += v[i];
+    part[threadIdx.x] = s;
+    wg_barrier();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+        wg_barrier();
+    }
+    if (threadIdx.x == 0) out[0] = n > 0 ? part[0] / (float)n : 0.f;
+}
+
+// dz_k = w (A exp(-t_k) - a_k): one pass, G threads per row (64: a wave, 4 rows per workgroup; 256: a workgroup)
+template <bool ZBF, bool DBF, bool VEC, int G>
+__global__ __launch_bounds__(256) void xent_bwd_kernel(const void *__restrict__ z, int64_t ldz, const int64_t *__restrict__ labels,
+                                                       const float *__restrict__ aux, const float *__restrict__ grad_loss_i,
+                                                       float grad_scale, int64_t B, int C, float y_on, float y_off,
+                                                       void *__restrict__ dz, int64_t lddz)
+{
+    constexpr int E = VEC ? ((ZBF || DBF) ? 8 : 4) : 1;
+    const int t = threadIdx.x % G;
+    const int64_t row = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
+    if (row >= B) return;
+    const void *zrow = ZBF ? (const void *)((const uint16_t *)z + row * ldz) : (const void *)((const float *)z + row * ldz);
+    void *drow = DBF ? (void *)((uint16_t *)dz + row * lddz) : (void *)((float *)dz + row * lddz);
+    int64_t yl = labels[row];
+    const int y = (int)(yl < 0 ? 0 : (yl >= C ? C - 1 : yl));
+    const float m = aux[row], lS = aux[B + row], A = aux[2 * B + row];
+    const float w = grad_loss_i ? grad_loss_i[row] : grad_scale;
+    const int64_t units = ((int64_t)C + E - 1) / E;
+    for (int64_t u = t; u < units; u += G) {
+        const int64_t c0 = u * E;
+        const bool full = E > 1 && c0 + E <= C;
+        float v[E], d[E];
+        xe_ld_unit<ZBF, E>(zrow, c0, C, v);
+#pragma unroll
+        for (int k = 0; k < E; k++) {
+            const float tc = (m - v[k]) + lS;               // the forward's t_c, bit for bit
+            const float Y = c0 + k == y ? y_on : y_off;
+            const float a = xe_inside(tc) ? Y : 0.f;
+            const float q = expf(-tc);
+            d[k] = w * (A * q - a);
+        }
+        if constexpr (E > 1) {
+            if (full) {
+                xe_st_vec<DBF, E>(drow, c0, d);
+                continue;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < E; k++)
+            if (c0 + k < C) xe_st<DBF>(drow, c0 + k, d[k]);
+    }
+}
+
+}  // namespace se
+
+using namespace se;
+
+static inline bool xe_aligned16(const void *p, int64_t ld, int elem_bytes) { return (((uintptr_t)p) & 15) == 0 && (ld * elem_bytes) % 16 == 0; }
+
+// target weights: (1 - s, s / (C - 1)) for 0 < s < 1, one-hot otherwise (learn_classifier.py:20)
+static inline void xe_target(float smoothing, int64_t C, float &y_on, float &y_off)
+{
+    const bool smooth = smoothing > 0.f && smoothing < 1.f;
+    y_on = smooth ? (float)(1.0 - (double)smoothing) : 1.0f;
+    y_off = smooth ? (float)((double)smoothing / (double)(C - 1)) : 0.0f;
+}
+
+static int xe_check(const char *who, const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, int64_t B, int64_t C,
+                    float smoothing, const float *aux)
+{
+    if (B < 0 || C < 1) return fail(SE_ERR_INVALID, "%s: bad shape B=%lld C=%lld", who, (long long)B, (long long)C);
+    if (smoothing > 0.f && smoothing < 1.f && C < 2) return fail(SE_ERR_INVALID, "%s: label smoothing %g needs at least 2 classes", who, (double)smoothing);
+    if (z_dtype != SE_DTYPE_F32 && z_dtype != SE_DTYPE_BF16) return fail(SE_ERR_INVALID, "%s: bad dtype %d", who, z_dtype);
+    if (ldz < C) return fail(SE_ERR_INVALID, "%s: leading dimension %lld < C=%lld", who, (long long)ldz, (long long)C);
+    if (C > INT_MAX - 16 || B > INT_MAX) return fail(SE_ERR_UNSUPPORTED, "%s: B or C too large", who);
+    if (B > 0 && (!logits || !labels || !aux)) return fail(SE_ERR_INVALID, "%s: null pointer", who);
+    return SE_OK;
+}
+
+extern "C" int64_t se_softmax_xent_aux_floats(int64_t B) { return B > 0 ? 3 * B : 0; }
+
+template <bool BF16, bool VEC>
+static void xe_launch_fwd(const void *z, int64_t ldz, const int64_t *labels, int64_t B, int C, float y_on, float y_off, float *loss_i,
+                          float *aux, int32_t *best, int32_t *above, hipStream_t s)
+{
+    if (C <= XE_WAVE_MAX_C)
+        hipLaunchKernelGGL((xent_fwd_reg_kernel<BF16, VEC, 64, XE_WAVE_NV>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, z, ldz, labels, B,
+                           C, y_on, y_off, loss_i, aux, best, above);
+    else if (C <= XE_BLOCK_MAX_C)
+        hipLaunchKernelGGL((xent_fwd_reg_kernel<BF16, VEC, 256, XE_BLOCK_NV>), dim3((unsigned)B), dim3(256), 0, s, z, ldz, labels, B, C, y_on,
+                           y_off, loss_i, aux, best, above);
+    else
+        hipLaunchKernelGGL((xent_fwd_stream_kernel<BF16, VEC>), dim3((unsigned)B), dim3(256), 0, s, z, ldz, labels, B, C, y_on, y_off, loss_i,
+                           aux, best, above);
+}
+
+extern "C" int se_softmax_xent_fwd(const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, int64_t B, int64_t C,
+                                   float smoothing, float *loss_i, float *aux, int32_t *best, int32_t *above, float *loss_mean,
+                                   se_stream_t stream)
+{
+    const int rc = xe_check("se_softmax_xent_fwd", logits, z_dtype, ldz, labels, B, C, smoothing, aux);
+    if (rc != SE_OK) return rc;
+    if (B > 0 && !loss_i) return fail(SE_ERR_INVALID, "se_softmax_xent_fwd: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (B > 0) {
+        float y_on, y_off;
+        xe_target(smoothing, C, y_on, y_off);
+        const bool bf = z_dtype == SE_DTYPE_BF16;
+        const bool vec = xe_aligned16(logits, ldz, bf ? 2 : 4);
+        if (bf) {
+            if (vec) xe_launch_fwd<true, true>(logits, ldz, labels, B, (int)C, y_on, y_off, loss_i, aux, best, above, s);
+            else xe_launch_fwd<true, false>(logits, ldz, labels, B, (int)C, y_on, y_off, loss_i, aux, best, above, s);
+        } else {
+            if (vec) xe_launch_fwd<false, true>(logits, ldz, labels, B, (int)C, y_on, y_off, loss_i, aux, best, above, s);
+            else xe_launch_fwd<false, false>(logits, ldz, labels, B, (int)C, y_on, y_off, loss_i, aux, best, above, s);
+        }
+        SE_LAUNCH_CHECK();
+    }
+    if (loss_mean) {
+        hipLaunchKernelGGL(xent_mean_kernel, dim3(1), dim3(256), 0, s, (const float *)loss_i, B, loss_mean);
+        SE_LAUNCH_CHECK();
+    }
+    return SE_OK;
+}
+
+template <bool ZBF, bool DBF, bool VEC>
+static void xe_launch_bwd(const void *z, int64_t ldz, const int64_t *labels, const float *aux, const float *gl, float gs, int64_t B, int C,
+                          float y_on, float y_off, void *dz, int64_t lddz, hipStream_t s)
+{
+    if (C <= XE_WAVE_MAX_C)
+        hipLaunchKernelGGL((xent_bwd_kernel<ZBF, DBF, VEC, 64>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, z, ldz, labels, aux, gl, gs, B,
+                           C, y_on, y_off, dz, lddz);
+    else
+        hipLaunchKernelGGL((xent_bwd_kernel<ZBF, DBF, VEC, 256>), dim3((unsigned)B), dim3(256), 0, s, z, ldz, labels, aux, gl, gs, B, C, y_on,
+                           y_off, dz, lddz);
+}
+
+template <bool ZBF, bool DBF>
+static void xe_launch_bwd_v(bool vec, const void *z, int64_t ldz, const int64_t *labels, const float *aux, const float *gl, float gs,
+                            int64_t B, int C, float y_on, float y_off, void *dz, int64_t lddz, hipStream_t s)
+{
+    if (vec) xe_launch_bwd<ZBF, DBF, true>(z, ldz, labels, aux, gl, gs, B, C, y_on, y_off, dz, lddz, s);
+    else xe_launch_bwd<ZBF, DBF, false>(z, ldz, labels, aux, gl, gs, B, C, y_on, y_off, dz, lddz, s);
+}
+
+extern "C" int se_softmax_xent_bwd(const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, const float *aux,
+                                   const float *grad_loss_i, float grad_scale, int64_t B, int64_t C, float smoothing, void *dz,
+                                   int dz_dtype, int64_t lddz, se_stream_t stream)
+{
+    const int rc = xe_check("se_softmax_xent_bwd", logits, z_dtype, ldz, labels, B, C, smoothing, aux);
+    if (rc != SE_OK) return rc;
+    if (dz_dtype != SE_DTYPE_F32 && dz_dtype != SE_DTYPE_BF16) return fail(SE_ERR_INVALID, "se_softmax_xent_bwd: bad dtype %d", dz_dtype);
+    if (lddz < C) return fail(SE_ERR_INVALID, "se_softmax_xent_bwd: leading dimension %lld < C=%lld", (long long)lddz, (long long)C);
+    if (B == 0) return SE_OK;
+    if (!dz) return fail(SE_ERR_INVALID, "se_softmax_xent_bwd: null pointer");
+    float y_on, y_off;
+    xe_target(smoothing, C, y_on, y_off);
+    const bool zbf = z_dtype == SE_DTYPE_BF16, dbf = dz_dtype == SE_DTYPE_BF16;
+    const bool vec = xe_aligned16(logits, ldz, zbf ? 2 : 4) && xe_aligned16(dz, lddz, dbf ? 2 : 4);
+    hipStream_t s = (hipStream_t)stream;
+    if (zbf) {
+        if (dbf) xe_launch_bwd_v<true, true>(vec, logits, ldz, labels, aux, grad_loss_i, grad_scale, B, (int)C, y_on, y_off, dz, lddz, s);
+        else xe_launch_bwd_v<true, false>(vec, logits, ldz, labels, aux, grad_loss_i, grad_scale, B, (int)C, y_on, y_off, dz, lddz, s);
+    } else {
+        if (dbf) xe_launch_bwd_v<false, true>(vec, logits, ldz, labels, aux, grad_loss_i, grad_scale, B, (int)C, y_on, y_off, dz, lddz, s);
+        else xe_launch_bwd_v<false, false>(vec, logits, ldz, labels, aux, grad_loss_i, grad_scale, B, (int)C, y_on, y_off, dz, lddz, s);
+    }
+    SE_LAUNCH_CHECK();
+    return SE_OK;
+}

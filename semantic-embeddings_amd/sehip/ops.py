@@ -13,7 +13,7 @@ from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, MET
 
 __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
-    "sqdist_loss_backward", "center_loss", "l2norm", "nn_accuracy", "labelembed_loss", "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
+    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "labelembed_loss", "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
@@ -279,6 +279,66 @@ def center_loss(x, labels, centroids, reduction="none"):
     if reduction == "sum":
         return loss_i.sum()
     return loss_i
+
+
+class _SoftmaxCrossEntropy(torch.autograd.Function):
+    """reference: Keras 2.2's 'categorical_crossentropy' on the softmax output against transform_inputs' smoothed one-hot target
+    (learn_classifier.py:17-22, 116-117, 146-147), 'accuracy' and utils.top_k_acc (utils.py:49-54) of the same scores: one
+    se_softmax_xent_fwd; the gradient with respect to the logits is one se_softmax_xent_bwd."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, smoothing, want_mean):
+        require_gpu(logits, labels)
+        if logits.dim() != 2:
+            raise SehipError("logits must be a 2-d [B, C] tensor")
+        B, C = logits.shape
+        z = logits if logits.stride(1) == 1 and (B <= 1 or logits.stride(0) >= C) else logits.contiguous()
+        if labels.dtype != torch.int64 or labels.numel() != B or not labels.is_contiguous():
+            raise SehipError("labels must be a contiguous int64 [B] tensor")
+        if os.environ.get("SEHIP_CHECK_LABELS") == "1" and B and (int(labels.min()) < 0 or int(labels.max()) >= C):
+            raise SehipError("softmax_cross_entropy: labels outside [0, %d)" % C)
+        dev = z.device
+        loss_i = torch.empty((B,), dtype=torch.float32, device=dev)
+        aux = torch.empty((call("se_softmax_xent_aux_floats", B),), dtype=torch.float32, device=dev)
+        best = torch.empty((B,), dtype=torch.int32, device=dev)
+        above = torch.empty((B,), dtype=torch.int32, device=dev)
+        loss_mean = torch.empty((1,), dtype=torch.float32, device=dev) if want_mean else None
+        ldz = z.stride(0) if B > 1 else max(z.stride(0), C)
+        call("se_softmax_xent_fwd", z, _dtype_code(z), ldz, labels, B, C, float(smoothing), loss_i, aux, best, above, loss_mean)
+        ctx.save_for_backward(z, labels, aux)
+        ctx.smoothing, ctx.ldz = float(smoothing), ldz
+        ctx.mark_non_differentiable(best, above)
+        if want_mean:
+            return loss_i, best, above, loss_mean
+        return loss_i, best, above
+
+    @staticmethod
+    def backward(ctx, grad_loss_i, _best, _above, grad_mean=None):
+        z, labels, aux = ctx.saved_tensors
+        B, C = z.shape
+        g = grad_loss_i.to(torch.float32)
+        if grad_mean is not None:           # d mean / d loss_i = 1 / B
+            g = g + grad_mean.to(torch.float32) / max(B, 1)
+        dz = torch.empty((B, C), dtype=z.dtype, device=z.device)
+        call("se_softmax_xent_bwd", z, _dtype_code(z), ctx.ldz, labels, aux, g.contiguous(), 0.0, B, C, ctx.smoothing, dz, _dtype_code(dz), C)
+        return dz, None, None, None
+
+
+def softmax_cross_entropy(logits, labels, label_smoothing=0.0, reduction="none", return_metrics=False):
+    """Differentiable categorical cross-entropy of ``softmax(logits)`` as Keras 2.2 computes it (probabilities clipped to
+    [1e-7, 1 - 1e-7]: a sample's loss is capped at 16.118 and a class whose probability left the range gets no gradient), against the
+    target ``1 - label_smoothing`` for the label and ``label_smoothing / (C - 1)`` for every other class (one-hot unless
+    ``0 < label_smoothing < 1``, the reference's rule): one HIP launch forward, one backward.
+    logits [B, C] float32 or bfloat16 with any row pitch (``d logits`` in the same dtype), labels contiguous int64 [B] (clamped to
+    [0, C - 1]; ``SEHIP_CHECK_LABELS=1`` checks them).  ``reduction``: "none" (per-sample [B]), "mean" (the kernel's fixed-order
+    mean) or "sum".  With ``return_metrics`` the result is ``(loss, best, above)``: int32 [B] arg-max class of every row (lowest
+    index on ties) and the number of classes scoring strictly above the label's -- ``best == labels`` is Keras' accuracy,
+    ``above < k`` is ``tf.nn.in_top_k``."""
+    if reduction not in ("none", "mean", "sum"):
+        raise SehipError("reduction must be none, mean or sum, got %r" % (reduction,))
+    out = _SoftmaxCrossEntropy.apply(logits, labels, float(label_smoothing), reduction == "mean")
+    loss = out[3][0] if reduction == "mean" else (out[0].sum() if reduction == "sum" else out[0])
+    return (loss, out[1], out[2]) if return_metrics else loss
 
 
 class _L2Norm(torch.autograd.Function):

@@ -7,7 +7,9 @@
     python tools/bench_kernels.py classemb       (class pair tables and fp64 Cholesky at C = 1000 (ILSVRC WordNet DAG) and 8,142 (iNat
                                                   2018), and the whole compute_class_embedding.py run on the iNat hierarchy)
     python tools/bench_kernels.py center         (center loss forward / input gradient / centroid gradient at D = 100, and the
-                                                  ResNet-110-fc center-loss training step next to the cosine-loss one)"""
+                                                  ResNet-110-fc center-loss training step next to the cosine-loss one)
+    python tools/bench_kernels.py xent           (softmax cross-entropy forward + backward next to the torch composition the sibling
+                                                  CLIs use, f32 / bf16 logits, s = 0 / 0.1, and the ResNet-110 classifier step)"""
 import argparse
 import os
 import sys
@@ -35,7 +37,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center"])
+                                     "center", "xent"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -48,6 +50,8 @@ def main():
         return bench_classemb(args.reps)
     if args.what == "center":
         return bench_center()
+    if args.what == "xent":
+        return bench_xent()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -402,6 +406,109 @@ def bench_center(reps=200, steps=200):
         step = float(np.median(ms[name]))
         print("ResNet-110-fc %s-loss step, batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d steps; %s), "
               "%.0f images/s" % (name, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
+
+
+def bench_xent(reps=60, batch=20, steps=200):
+    """Softmax cross-entropy (learn_classifier.py): se_softmax_xent_fwd (loss, arg-max, top-k count, mean) + se_softmax_xent_bwd through
+    the C ABI on preallocated buffers, the same through the autograd op, and the torch composition the sibling CLIs use
+    (F.cross_entropy forward + backward, argmax, topk(5)), timed alternately in one process: per shape `reps` windows of `batch`
+    back-to-back calls each (HIP events around a window), median / 10th / 90th percentile of the per-call time.  Bytes: the logits
+    read by the forward and the backward pass and the gradient written, over the kernels' time, against the 6.29 TB/s a float4 copy
+    reaches on MI355X (8 TB/s spec).  Then one ResNet-110 classifier training step (batch 128, fp32, HIP-graph replay) with the
+    fused head next to the torch head."""
+    import torch.nn.functional as F
+    from sehip._lib import call
+    HBM = 6.29e12
+
+    def windows(fns):
+        for f in fns:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(reps):
+            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(batch):
+                    f()
+                b.record()
+                torch.cuda.synchronize()
+                ts[k].append(a.elapsed_time(b) / batch * 1e3)
+        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
+
+    for dtype, dcode, esz in ((torch.float32, 0, 4), (torch.bfloat16, 1, 2)):
+        for B, C in ((128, 100), (128, 1000), (1024, 1000), (256, 8142)):
+            for s in (0.0, 0.1):
+                rng = np.random.default_rng(B + C)
+                z = torch.from_numpy((rng.standard_normal((B, C)) * 3).astype(np.float32)).cuda().to(dtype)
+                y = torch.from_numpy(rng.integers(0, C, B)).cuda()
+                loss_i, aux, mean = torch.empty(B, device="cuda"), torch.empty(3 * B, device="cuda"), torch.empty(1, device="cuda")
+                best, above = torch.empty(B, dtype=torch.int32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+                dz = torch.empty(B, C, dtype=dtype, device="cuda")
+                za, zt = z.clone().requires_grad_(True), z.clone().requires_grad_(True)
+
+                def kernels():
+                    call("se_softmax_xent_fwd", z, dcode, C, y, B, C, s, loss_i, aux, best, above, mean)
+                    call("se_softmax_xent_bwd", z, dcode, C, y, aux, None, 1.0 / B, B, C, s, dz, dcode, C)
+
+                def op():
+                    za.grad = None
+                    loss, _, _ = sehip.softmax_cross_entropy(za, y, s, reduction="mean", return_metrics=True)
+                    loss.backward()
+
+                def composition():
+                    zt.grad = None
+                    F.cross_entropy(zt.float(), y, label_smoothing=s).backward()
+                    zt.argmax(dim=-1)
+                    zt.topk(5, dim=-1)
+                k, o, t = windows((kernels, op, composition))
+                gbs = 3.0 * B * C * esz / (k[0] * 1e-6)
+                print("xent B=%d C=%d %s s=%.1f: kernels %.1f us (%.1f-%.1f), autograd op %.1f us (%.1f-%.1f), torch composition %.1f us "
+                      "(%.1f-%.1f): x%.2f / x%.2f; kernels move %.0f GB/s = %.1f%% of the HBM copy rate"
+                      % (B, C, "bf16" if dcode else "f32", s, k[0], k[1], k[2], o[0], o[1], o[2], t[0], t[1], t[2], t[0] / k[0], t[0] / o[0],
+                         gbs / 1e9, 100.0 * gbs / HBM))
+
+    sys.path.insert(0, os.path.join(ROOT, "semantic-embeddings_amd"))
+    import utils
+    import learn_classifier as lc
+    from learn_image_embeddings import accuracy, categorical_crossentropy
+    from datasets import SyntheticGenerator
+    from engine import Trainer
+    trainers = {}
+    for name in ("fused", "torch"):
+        torch.manual_seed(0)
+        model = lc.build_classifier(100, "resnet-110", input_channels=3).cuda()
+        l2_of = {id(p): model.regularizer for p in model.regularized_parameters()}
+        if name == "fused":
+            losses, metrics = lc.build_losses(0.0, [5])
+        else:
+            losses, metrics = {"prob": (categorical_crossentropy, 1.0)}, {"prob": [accuracy, utils.top_k_acc(5)]}
+        tr = Trainer(model, losses, metrics, lr=0.1, momentum=0.9, clipnorm=10.0, l2_of=l2_of, autocast_dtype=None,
+                     memory_format=torch.contiguous_format)
+        seq = SyntheticGenerator(100, 32, 3, 128 * 8, 128).train_sequence(128, shuffle=False)
+        batches = [seq[i] for i in range(8)]
+        assert tr.enable_graphs(*batches[0]), name
+        for i in range(10):
+            tr.train_step(*batches[i % 8], {})
+        trainers[name] = (tr, batches)
+    ms = {name: [] for name in trainers}
+    for _ in range(3):                       # alternate the two heads: the same machine state for both
+        for name, (tr, batches) in trainers.items():
+            logs = {}
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(steps):
+                tr.train_step(*batches[i % 8], logs)
+            b.record()
+            torch.cuda.synchronize()
+            assert np.isfinite(float(logs["loss"]))
+            ms[name].append(a.elapsed_time(b) / steps)
+    for name in trainers:
+        step = float(np.median(ms[name]))
+        print("ResNet-110 classifier step (%s head: loss + acc + acc5), batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d "
+              "steps; %s), %.0f images/s" % (name, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
 
 
 if __name__ == "__main__":
