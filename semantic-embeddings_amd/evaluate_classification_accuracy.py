@@ -64,6 +64,7 @@ def nn_classification(features, centroids, return_device=False):
 def evaluate(y_pred, data_generator, hierarchy=None):
     """Flat, top-5, class-balanced and hierarchical accuracy (evaluate_classification_accuracy.py:88-108).
     ``y_pred``: ``[N]`` predicted class indices or an ``[N, >= 1]`` class ranking."""
+    from train_cli import average_accuracy      # local like every torch import here: train_cli brings torch and the engine along
     perf = OrderedDict()
     y_true = np.asarray(data_generator.labels_test)
     y_pred = np.asarray(y_pred)
@@ -72,8 +73,7 @@ def evaluate(y_pred, data_generator, hierarchy=None):
         y_pred = y_pred[:, 0]
     hit = (y_pred == y_true)
     perf['Accuracy'] = float(np.mean(hit))
-    class_freq = np.bincount(y_true)
-    perf['Avg. Accuracy'] = float((hit.astype(np.float64) / class_freq[y_true]).sum() / len(class_freq))
+    perf['Avg. Accuracy'] = float(average_accuracy(y_pred, y_true))
     if hierarchy is not None:
         classes = data_generator.classes
         total = 0.0

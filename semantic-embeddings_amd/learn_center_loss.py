@@ -17,21 +17,19 @@ TensorBoard events; the ``prob`` cross-entropy is computed from the logits, with
 [1e-7, 1 - 1e-7] (the same as the ``--cls_weight`` head of learn_image_embeddings.py).
 """
 import argparse
-import os
 import pickle
-from collections import OrderedDict
 
 import numpy as np
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 
 import sehip
+import train_cli
 import utils
 from datasets import get_data_generator
-from engine import Trainer, backbone_mode
-from learn_image_embeddings import JsonLogger, accuracy, categorical_crossentropy
+from learn_image_embeddings import accuracy, categorical_crossentropy
 from models.cifar_resnet import KERAS_BN_EPS, KERAS_BN_MOMENTUM, keras_dense
+from train_cli import read_class_list
 
 NEW_LAYERS = ('embedding_bn', 'prob', 'cls_centroids')    # with the backbone's `embedding` head: what --finetune_init trains first
 
@@ -115,37 +113,12 @@ def build_parser():
     g.add_argument('--center_loss_weight', type=float, default=0.1, help='Weight of the center loss (the softmax loss has weight 1).')
     g = parser.add_argument_group('Training parameters')
     g.add_argument('--architecture', type=str, default='simple', choices=utils.ARCHITECTURES, help='Network architecture.')
-    g.add_argument('--lr_schedule', type=str, default='SGDR', choices=utils.LR_SCHEDULES, help='Learning-rate schedule.')
-    g.add_argument('--clipgrad', type=float, default=10.0, help='Global gradient-norm clip.')
-    g.add_argument('--max_decay', type=float, default=0.0, help='Learning-rate decay reached at the end of training.')
-    g.add_argument('--nesterov', action='store_true', default=False, help='Nesterov momentum.')
-    g.add_argument('--epochs', type=int, default=None, help='Number of training epochs.')
-    g.add_argument('--batch_size', type=int, default=100, help='Global batch size.')
-    g.add_argument('--val_batch_size', type=int, default=None, help='Validation batch size.')
-    g.add_argument('--finetune', type=str, default=None, help='state_dict with pre-trained weights (matched by name, mismatches skipped).')
-    g.add_argument('--finetune_init', type=int, default=3, help='Epochs training only the new layers first.')
-    g.add_argument('--gpus', type=int, default=1, help='Number of GPUs = number of launched processes.')
-    g.add_argument('--read_workers', type=int, default=8, help='Ignored (device-side batches).')
-    g.add_argument('--queue_size', type=int, default=100, help='Ignored (device-side batches).')
-    g.add_argument('--gpu_merge', action='store_true', default=False, help='Ignored (weights always live on the GPUs).')
+    train_cli.add_schedule_arguments(g)
+    train_cli.add_finetune_and_device_arguments(g, 3, 'Epochs training only the new layers first.')
     g = parser.add_argument_group('Output parameters')
-    g.add_argument('--model_dump', type=str, default=None, help='Where to save the whole model (torch.save of the module).')
-    g.add_argument('--weight_dump', type=str, default=None, help='Where to save the state_dict.')
-    g.add_argument('--feature_dump', type=str, default=None, help='Where to save raw test-image embeddings ({"feat": {i: vec}} pickle).')
-    g.add_argument('--log_dir', type=str, default=None, help='Directory for a JSON-lines training log.')
-    g.add_argument('--no_progress', action='store_true', default=False, help='Only print the final performance.')
+    train_cli.add_output_arguments(g, 'Where to save raw test-image embeddings ({"feat": {i: vec}} pickle).')
     utils.add_lr_schedule_arguments(parser)
     return parser
-
-
-def read_class_list(path):
-    """reference: learn_center_loss.py:102-108 (first word of every non-empty line, duplicates dropped, integers if all are)."""
-    with open(path) as class_file:
-        class_list = list(OrderedDict((l.strip().split()[0], None) for l in class_file if l.strip() != '').keys())
-    try:
-        return [int(lbl) for lbl in class_list]
-    except ValueError:
-        return class_list
 
 
 def main(argv=None):
@@ -153,18 +126,7 @@ def main(argv=None):
     if args.val_batch_size is None:
         args.val_batch_size = args.batch_size
 
-    # ---- process group: one process per GPU over RCCL
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    rank = int(os.environ.get('RANK', '0'))
-    if not torch.cuda.is_available():
-        raise RuntimeError('learn_center_loss.py needs a ROCm GPU (no CPU fallback for the HIP loss kernels)')
-    torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
-    if world > 1 and not dist.is_initialized():
-        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-        dist.init_process_group('nccl', rank=rank, world_size=world)
-    if args.gpus != world and rank == 0:
-        print('note: --gpus {} but {} process(es) were launched; using {}'.format(args.gpus, world, world))
-    dev = torch.device('cuda', torch.cuda.current_device())
+    rank, world, dev = train_cli.init_process(args, 'learn_center_loss.py')
 
     # ---- class centroids / class list (learn_center_loss.py:93-108)
     centroids = class_list = None
@@ -181,17 +143,10 @@ def main(argv=None):
     # ---- model (learn_center_loss.py:113-124)
     torch.manual_seed(0)   # identical initial weights on every rank
     embed_model = utils.build_network(embed_dim, args.architecture, input_channels=data_generator.num_channels).to(dev)
-    with torch.no_grad():    # output width of the embedding model (not every architecture ends in a Dense layer)
-        embed_model.eval()
-        width = int(embed_model(torch.zeros((1, data_generator.num_channels, 32, 32), device=dev)).shape[-1])
-        embed_model.train()
+    width = train_cli.output_width(embed_model, data_generator.num_channels, dev)
     model = center_loss_model(embed_model, centroids if centroids is not None else data_generator.num_classes, width=width).to(dev)
     if args.finetune:
-        print('Loading pre-trained weights from {}'.format(args.finetune))
-        state = torch.load(args.finetune, map_location=dev)
-        state = state.get('model', state)
-        own = model.state_dict()
-        model.load_state_dict({k: v for k, v in state.items() if k in own and own[k].shape == v.shape}, strict=False)
+        train_cli.load_pretrained(model, args.finetune, dev)
 
     losses, metrics = build_losses(model, args.center_loss_weight)
     # Keras kernel regulariser of the backbone folded into the update; the head and the centroids carry none
@@ -202,54 +157,30 @@ def main(argv=None):
     train_seq = lambda: data_generator.train_sequence(args.batch_size, batch_transform=transform_inputs, batch_transform_kwargs=kw, **dp)
     val_seq = lambda: data_generator.test_sequence(args.val_batch_size, batch_transform=transform_inputs, batch_transform_kwargs=kw, **dp)
 
-    mode = backbone_mode(args.architecture)       # (autocast dtype, memory format) of the PyTorch-ROCm backbone
     # ---- optional warm-up of the new layers only (learn_center_loss.py:128-148)
     if args.finetune and args.finetune_init > 0:
         if centroids is not None:
             # the reference's layer loops make every layer named cls_centroids trainable here and every layer afterwards
             print('note: --finetune with --finetune_init > 0 trains the --centroids table as well, like the reference')
-        print('Pre-training new layers')
-        pre = Trainer(model, losses, metrics, lr=args.sgd_lr, momentum=0.9, nesterov=args.nesterov, clipnorm=args.clipgrad,
-                      autocast_dtype=mode[0], memory_format=mode[1], l2_of=l2_of,
-                      trainable=lambda n: n.split('.')[0] in NEW_LAYERS or n.startswith('embed_model.embedding.'))
-        pre.fit(train_seq(), val_seq(), epochs=args.finetune_init, verbose=not args.no_progress)
-        pre.close()            # drop its gradient hooks before the second trainer registers its own
-        for p in model.parameters():
-            p.requires_grad_(True)
-        print('Full model training')
+        train_cli.warm_up(args, model, losses, metrics, l2_of, train_seq, val_seq,
+                          lambda n: n.split('.')[0] in NEW_LAYERS or n.startswith('embed_model.embedding.'), 'Pre-training new layers')
 
     # ---- main training (learn_center_loss.py:150-172)
-    sched_args = {k: v for k, v in vars(args).items() if v is not None}
-    callbacks, num_epochs = utils.get_lr_schedule(args.lr_schedule, data_generator.num_train, args.batch_size, schedule_args=sched_args)
-    epochs = args.epochs if args.epochs else num_epochs
-    if args.log_dir:
-        callbacks.append(JsonLogger(args.log_dir))
-    decay = (1.0 / args.max_decay - 1) / ((data_generator.num_train // args.batch_size) * epochs) if args.max_decay > 0 else 0.0
-    trainer = Trainer(model, losses, metrics, lr=args.sgd_lr, momentum=0.9, nesterov=args.nesterov, clipnorm=args.clipgrad,
-                      decay=decay, l2_of=l2_of, autocast_dtype=mode[0], memory_format=mode[1])
-    trainer.fit(train_seq(), val_seq(), epochs=epochs, callbacks=callbacks, verbose=not args.no_progress)
+    trainer = train_cli.fit(args, model, losses, metrics, l2_of, data_generator, train_seq, val_seq, world)
 
     # ---- final evaluation (learn_center_loss.py:174-180)
     final = trainer.evaluate(val_seq())
     logits, feats = trainer.predict(data_generator.test_sequence(args.val_batch_size))      # every test image, on every rank
     if rank == 0:
         print([final[k] for k in sorted(final)], sorted(final))
-        y = np.asarray(data_generator.labels_test)
-        freq = np.bincount(y)
-        print('Average Accuracy: {:.4f}'.format(((logits.argmax(axis=-1) == y).astype(float) / freq[y]).sum() / len(freq)))
+        print('Average Accuracy: {:.4f}'.format(train_cli.average_accuracy(logits.argmax(axis=-1), data_generator.labels_test)))
 
     # ---- dumps (learn_center_loss.py:182-198): the feature dump holds the RAW embeddings
     if rank == 0:
-        if args.weight_dump:
-            torch.save(model.state_dict(), args.weight_dump)
-        if args.model_dump:
-            torch.save(model, args.model_dump)
+        train_cli.dump_model(args, model)
         if args.feature_dump:
-            with open(args.feature_dump, 'wb') as f:
-                pickle.dump({'feat': dict(enumerate(feats))}, f)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+            train_cli.dump_features(args.feature_dump, feats)
+    train_cli.finish_process(world)
     return final
 
 

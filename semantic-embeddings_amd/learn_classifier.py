@@ -19,20 +19,15 @@ composed on the device, weights always live on the GPUs); ``--log_dir`` writes a
 the top-k accuracies are decided on the logits (in favour of the target, like ``tf.nn.in_top_k``), not on the rounded probabilities.
 """
 import argparse
-import os
-import pickle
-from collections import OrderedDict
 
-import numpy as np
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 
 import sehip
+import train_cli
 import utils
 from datasets import get_data_generator
-from engine import Trainer, backbone_mode
-from learn_image_embeddings import JsonLogger
+from train_cli import read_class_list
 
 
 def transform_inputs(X, y, num_classes, label_smoothing=0):
@@ -157,41 +152,14 @@ def build_parser():
     g.add_argument('--architecture', type=str, default='simple', choices=utils.ARCHITECTURES, help='Network architecture.')
     g.add_argument('--label_smoothing', type=float, default=0.0,
                    help='Smooth the target distribution by subtracting this value from the target probability of the ground-truth class.')
-    g.add_argument('--lr_schedule', type=str, default='SGDR', choices=utils.LR_SCHEDULES, help='Learning-rate schedule.')
-    g.add_argument('--clipgrad', type=float, default=10.0, help='Global gradient-norm clip.')
-    g.add_argument('--max_decay', type=float, default=0.0, help='Learning-rate decay reached at the end of training.')
-    g.add_argument('--nesterov', action='store_true', default=False, help='Nesterov momentum.')
-    g.add_argument('--epochs', type=int, default=None, help='Number of training epochs.')
-    g.add_argument('--batch_size', type=int, default=100, help='Global batch size.')
-    g.add_argument('--val_batch_size', type=int, default=None, help='Validation batch size.')
-    g.add_argument('--snapshot', type=str, default=None, help='Checkpoint written after every epoch; resumed from if present.')
-    g.add_argument('--snapshot_best', type=str, nargs='?', default=None, const='val_loss', help='Only keep the best checkpoint w.r.t. this metric.')
-    g.add_argument('--initial_epoch', type=int, default=0, help='First epoch when resuming.')
-    g.add_argument('--finetune', type=str, default=None, help='state_dict with pre-trained weights (matched by name, mismatches skipped).')
-    g.add_argument('--finetune_init', type=int, default=3, help='Epochs training only the last layer first.')
-    g.add_argument('--gpus', type=int, default=1, help='Number of GPUs = number of launched processes.')
-    g.add_argument('--read_workers', type=int, default=8, help='Ignored (device-side batches).')
-    g.add_argument('--queue_size', type=int, default=100, help='Ignored (device-side batches).')
-    g.add_argument('--gpu_merge', action='store_true', default=False, help='Ignored (weights always live on the GPUs).')
+    train_cli.add_schedule_arguments(g)
+    train_cli.add_snapshot_arguments(g)
+    train_cli.add_finetune_and_device_arguments(g, 3, 'Epochs training only the last layer first.')
     g = parser.add_argument_group('Output parameters')
-    g.add_argument('--model_dump', type=str, default=None, help='Where to save the whole model (torch.save of the module).')
-    g.add_argument('--weight_dump', type=str, default=None, help='Where to save the state_dict.')
-    g.add_argument('--feature_dump', type=str, default=None, help='Where to save test-image features ({"feat": {i: vec}} pickle).')
-    g.add_argument('--log_dir', type=str, default=None, help='Directory for a JSON-lines training log.')
+    train_cli.add_output_arguments(g, 'Where to save test-image features ({"feat": {i: vec}} pickle).')
     g.add_argument('--top_k_acc', type=int, nargs='+', default=[], help='Also report these top-k accuracies.')
-    g.add_argument('--no_progress', action='store_true', default=False, help='Only print the final performance.')
     utils.add_lr_schedule_arguments(parser)
     return parser
-
-
-def read_class_list(path):
-    """reference: learn_classifier.py:71-79 (first word of every non-empty line, first occurrence wins, integers if ALL convert)."""
-    with open(path) as class_file:
-        class_list = list(OrderedDict((l.strip().split()[0], None) for l in class_file if l.strip() != '').keys())
-    try:
-        return [int(lbl) for lbl in class_list]
-    except ValueError:
-        return class_list
 
 
 def main(argv=None):
@@ -199,18 +167,7 @@ def main(argv=None):
     if args.val_batch_size is None:
         args.val_batch_size = args.batch_size
 
-    # ---- process group: one process per GPU over RCCL
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    rank = int(os.environ.get('RANK', '0'))
-    if not torch.cuda.is_available():
-        raise RuntimeError('learn_classifier.py needs a ROCm GPU (no CPU fallback for the HIP loss kernels)')
-    torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
-    if world > 1 and not dist.is_initialized():
-        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-        dist.init_process_group('nccl', rank=rank, world_size=world)
-    if args.gpus != world and rank == 0:
-        print('note: --gpus {} but {} process(es) were launched; using {}'.format(args.gpus, world, world))
-    dev = torch.device('cuda', torch.cuda.current_device())
+    rank, world, dev = train_cli.init_process(args, 'learn_classifier.py')
 
     # ---- dataset (learn_classifier.py:70-80)
     class_list = read_class_list(args.class_list) if args.class_list is not None else None
@@ -219,9 +176,7 @@ def main(argv=None):
     # ---- model (learn_classifier.py:83-97)
     torch.manual_seed(0)   # identical initial weights on every rank
     model = build_classifier(data_generator.num_classes, args.architecture, input_channels=data_generator.num_channels).to(dev)
-    if args.snapshot and os.path.exists(args.snapshot):
-        print('Resuming from snapshot {}'.format(args.snapshot))
-        model.load_state_dict(torch.load(args.snapshot, map_location=dev)['model'])
+    train_cli.resume_from_snapshot(model, args.snapshot, dev)
 
     losses, metrics = build_losses(args.label_smoothing, args.top_k_acc)
     # Keras kernel regulariser of the network folded into the update
@@ -232,62 +187,30 @@ def main(argv=None):
     train_seq = lambda: data_generator.train_sequence(args.batch_size, batch_transform=transform_inputs, batch_transform_kwargs=kw, **dp)
     val_seq = lambda: data_generator.test_sequence(args.val_batch_size, batch_transform=transform_inputs, batch_transform_kwargs=kw, **dp)
 
-    mode = backbone_mode(args.architecture)       # (autocast dtype, memory format) of the PyTorch-ROCm backbone
     # ---- pre-trained weights, and the last layer alone for a few epochs (learn_classifier.py:108-125)
     if args.finetune:
-        print('Loading pre-trained weights from {}'.format(args.finetune))
-        state = torch.load(args.finetune, map_location=dev)
-        state = state.get('model', state)
-        own = model.state_dict()
-        model.load_state_dict({k: v for k, v in state.items() if k in own and own[k].shape == v.shape}, strict=False)
+        train_cli.load_pretrained(model, args.finetune, dev)
         if args.finetune_init > 0:
-            print('Pre-training last layer')
             last = {id(p) for p in final_dense(model).parameters()}
             names = {n for n, p in model.named_parameters() if id(p) in last}
-            pre = Trainer(model, losses, metrics, lr=args.sgd_lr, momentum=0.9, nesterov=args.nesterov, clipnorm=args.clipgrad,
-                          autocast_dtype=mode[0], memory_format=mode[1], l2_of=l2_of, trainable=lambda n: n in names)
-            pre.fit(train_seq(), val_seq(), epochs=args.finetune_init, verbose=not args.no_progress)
-            pre.close()            # drop its gradient hooks before the second trainer registers its own
-            for p in model.parameters():
-                p.requires_grad_(True)
-            print('Full model training')
+            train_cli.warm_up(args, model, losses, metrics, l2_of, train_seq, val_seq, lambda n: n in names, 'Pre-training last layer')
 
     # ---- main training (learn_classifier.py:127-155)
-    sched_args = {k: v for k, v in vars(args).items() if v is not None}
-    callbacks, num_epochs = utils.get_lr_schedule(args.lr_schedule, data_generator.num_train, args.batch_size, schedule_args=sched_args)
-    epochs = args.epochs if args.epochs else num_epochs
-    if args.log_dir:
-        callbacks.append(JsonLogger(args.log_dir))
-    if args.snapshot:
-        ck = {'save_best_only': True, 'monitor': args.snapshot_best} if args.snapshot_best else {}
-        callbacks.append(utils.ModelCheckpoint(args.snapshot, **ck) if world <= 1 else utils.TemplateModelCheckpoint(model, args.snapshot, **ck))
-    decay = (1.0 / args.max_decay - 1) / ((data_generator.num_train // args.batch_size) * epochs) if args.max_decay > 0 else 0.0
-    trainer = Trainer(model, losses, metrics, lr=args.sgd_lr, momentum=0.9, nesterov=args.nesterov, clipnorm=args.clipgrad,
-                      decay=decay, l2_of=l2_of, autocast_dtype=mode[0], memory_format=mode[1])
-    trainer.fit(train_seq(), val_seq(), epochs=epochs, initial_epoch=args.initial_epoch, callbacks=callbacks, verbose=not args.no_progress)
+    trainer = train_cli.fit(args, model, losses, metrics, l2_of, data_generator, train_seq, val_seq, world)
 
     # ---- final evaluation (learn_classifier.py:157-163)
     final = trainer.evaluate(val_seq())
     logits = trainer.predict(data_generator.test_sequence(args.val_batch_size))       # every test image, on every rank
     if rank == 0:
         print([final['loss'], final['acc']] + [final['acc{}'.format(k)] for k in args.top_k_acc])
-        y = np.asarray(data_generator.labels_test)
-        freq = np.bincount(y)
-        print('Average Accuracy: {:.4f}'.format(((logits.argmax(axis=-1) == y).astype(float) / freq[y]).sum() / len(freq)))
+        print('Average Accuracy: {:.4f}'.format(train_cli.average_accuracy(logits.argmax(axis=-1), data_generator.labels_test)))
 
     # ---- dumps (learn_classifier.py:165-182)
     if rank == 0:
-        if args.weight_dump:
-            torch.save(model.state_dict(), args.weight_dump)
-        if args.model_dump:
-            torch.save(model, args.model_dump)
+        train_cli.dump_model(args, model)
         if args.feature_dump:
-            feats = predict_features(trainer, data_generator.test_sequence(max(args.val_batch_size, 256)))
-            with open(args.feature_dump, 'wb') as f:
-                pickle.dump({'feat': dict(enumerate(feats))}, f)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+            train_cli.dump_features(args.feature_dump, predict_features(trainer, data_generator.test_sequence(max(args.val_batch_size, 256))))
+    train_cli.finish_process(world)
     return final
 
 

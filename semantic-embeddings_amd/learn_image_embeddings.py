@@ -15,19 +15,17 @@ Keras ``.h5``; ``--read_workers`` / ``--queue_size`` are accepted and ignored (b
 on the device); ``--log_dir`` writes a JSON-lines log instead of TensorBoard events.
 """
 import argparse
-import json
-import os
 import pickle
 
 import numpy as np
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 
+import train_cli
 import utils
 from datasets import get_data_generator
-from engine import Trainer, backbone_mode
 from models.cifar_resnet import keras_bn, keras_dense
+from train_cli import JsonLogger
 
 
 class ClsModel(nn.Module):
@@ -140,43 +138,14 @@ def build_parser():
                         '"unnorm_corr"/"softmax_corr": negated dot product without normalisation / after softmax.')
     g.add_argument('--cls_weight', type=float, default=0.0, help='Weight of an additional softmax classification loss (0 = off).')
     g.add_argument('--cls_base', type=str, default=None, help='Name or index of the layer that the classification layer should be based on. If not specified, the final embedding layer will be used.')
-    g.add_argument('--lr_schedule', type=str, default='SGDR', choices=utils.LR_SCHEDULES, help='Learning-rate schedule.')
-    g.add_argument('--clipgrad', type=float, default=10.0, help='Global gradient-norm clip.')
-    g.add_argument('--max_decay', type=float, default=0.0, help='Learning-rate decay reached at the end of training.')
-    g.add_argument('--nesterov', action='store_true', default=False, help='Nesterov momentum.')
-    g.add_argument('--epochs', type=int, default=None, help='Number of training epochs.')
-    g.add_argument('--batch_size', type=int, default=100, help='Global batch size.')
-    g.add_argument('--val_batch_size', type=int, default=None, help='Validation batch size.')
-    g.add_argument('--snapshot', type=str, default=None, help='Checkpoint written after every epoch; resumed from if present.')
-    g.add_argument('--snapshot_best', type=str, nargs='?', default=None, const='val_loss', help='Only keep the best checkpoint w.r.t. this metric.')
-    g.add_argument('--initial_epoch', type=int, default=0, help='First epoch when resuming.')
-    g.add_argument('--finetune', type=str, default=None, help='state_dict with pre-trained weights (matched by name, mismatches skipped).')
-    g.add_argument('--finetune_init', type=int, default=8, help='Epochs training only the new layers first.')
-    g.add_argument('--gpus', type=int, default=1, help='Number of GPUs = number of launched processes.')
-    g.add_argument('--read_workers', type=int, default=8, help='Ignored (device-side batches).')
-    g.add_argument('--queue_size', type=int, default=100, help='Ignored (device-side batches).')
-    g.add_argument('--gpu_merge', action='store_true', default=False, help='Ignored (weights always live on the GPUs).')
+    train_cli.add_schedule_arguments(g)
+    train_cli.add_snapshot_arguments(g)
+    train_cli.add_finetune_and_device_arguments(g, 8, 'Epochs training only the new layers first.')
     g = parser.add_argument_group('Output parameters')
-    g.add_argument('--model_dump', type=str, default=None, help='Where to save the whole model (torch.save of the module).')
-    g.add_argument('--weight_dump', type=str, default=None, help='Where to save the state_dict.')
-    g.add_argument('--feature_dump', type=str, default=None, help='Where to save test-image embeddings ({"feat": {i: vec}} pickle).')
-    g.add_argument('--log_dir', type=str, default=None, help='Directory for a JSON-lines training log.')
-    g.add_argument('--no_progress', action='store_true', default=False, help='Only print the final performance.')
+    train_cli.add_output_arguments(g, 'Where to save test-image embeddings ({"feat": {i: vec}} pickle).')
     g.add_argument('--top_k_acc', type=int, nargs='+', default=[], help='Also report these top-k accuracies.')
     utils.add_lr_schedule_arguments(parser)
     return parser
-
-
-class JsonLogger(utils.Callback):
-    def __init__(self, log_dir):
-        os.makedirs(log_dir, exist_ok=True)
-        self.path = os.path.join(log_dir, 'training_log.jsonl')
-        open(self.path, 'w').close()
-
-    def on_epoch_end(self, trainer, epoch, logs):
-        if trainer.is_main_process:
-            with open(self.path, 'a') as f:
-                f.write(json.dumps(dict(logs, epoch=epoch + 1)) + '\n')
 
 
 def main(argv=None):
@@ -184,18 +153,7 @@ def main(argv=None):
     if args.val_batch_size is None:
         args.val_batch_size = args.batch_size
 
-    # ---- process group: one process per GPU over RCCL
-    world = int(os.environ.get('WORLD_SIZE', '1'))
-    rank = int(os.environ.get('RANK', '0'))
-    if not torch.cuda.is_available():
-        raise RuntimeError('learn_image_embeddings.py needs a ROCm GPU (no CPU fallback for the HIP loss kernels)')
-    torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
-    if world > 1 and not dist.is_initialized():
-        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-        dist.init_process_group('nccl', rank=rank, world_size=world)
-    if args.gpus != world and rank == 0:
-        print('note: --gpus {} but {} process(es) were launched; using {}'.format(args.gpus, world, world))
-    dev = torch.device('cuda', torch.cuda.current_device())
+    rank, world, dev = train_cli.init_process(args, 'learn_image_embeddings.py')
 
     # ---- class embeddings (learn_image_embeddings.py:105-117)
     if args.embedding == 'onehot':
@@ -214,22 +172,12 @@ def main(argv=None):
     embed_model = utils.build_network(embedding.shape[1], args.architecture, input_channels=data_generator.num_channels).to(dev)
     model = embed_model
     if args.cls_weight > 0:
-        with torch.no_grad():    # output width of the embedding model (not every architecture ends in a Dense layer)
-            was = embed_model.training
-            embed_model.eval()
-            width = int(embed_model(torch.zeros((1, data_generator.num_channels, 32, 32), device=dev)).shape[-1])
-            embed_model.train(was)
+        width = train_cli.output_width(embed_model, data_generator.num_channels, dev)
         model = ClsModel(embed_model, data_generator.num_classes, args.cls_base,
                          head={'inv_corr': 'l2norm', 'softmax_corr': 'softmax'}.get(args.loss), width=width).to(dev)
-    if args.snapshot and os.path.exists(args.snapshot):
-        print('Resuming from snapshot {}'.format(args.snapshot))
-        model.load_state_dict(torch.load(args.snapshot, map_location=dev)['model'])
+    train_cli.resume_from_snapshot(model, args.snapshot, dev)
     if args.finetune:
-        print('Loading pre-trained weights from {}'.format(args.finetune))
-        state = torch.load(args.finetune, map_location=dev)
-        state = state.get('model', state)
-        own = model.state_dict()
-        model.load_state_dict({k: v for k, v in state.items() if k in own and own[k].shape == v.shape}, strict=False)
+        train_cli.load_pretrained(model, args.finetune, dev)
 
     # ---- loss / metrics (learn_image_embeddings.py:160-180)
     onehot_like = (args.loss == 'softmax_corr') or (args.embedding == 'onehot')
@@ -270,31 +218,13 @@ def main(argv=None):
     train_seq = lambda: data_generator.train_sequence(args.batch_size, batch_transform=transform_inputs, batch_transform_kwargs=kw, **dp)
     val_seq = lambda: data_generator.test_sequence(args.val_batch_size, batch_transform=transform_inputs, batch_transform_kwargs=kw, **dp)
 
-    mode = backbone_mode(args.architecture)       # (autocast dtype, memory format) of the PyTorch-ROCm backbone
     # ---- optional warm-up of the new layers only (learn_image_embeddings.py:183-207)
     if args.finetune and args.finetune_init > 0:
-        print('Pre-training new layers')
-        pre = Trainer(model, losses, all_metrics, lr=args.sgd_lr, momentum=0.9, nesterov=args.nesterov, clipnorm=args.clipgrad,
-                      autocast_dtype=mode[0], memory_format=mode[1], l2_of=l2_of, trainable=lambda n: ('embedding' in n) or ('prob' in n))
-        pre.fit(train_seq(), val_seq(), epochs=args.finetune_init, verbose=not args.no_progress)
-        pre.close()            # drop its gradient hooks before the second trainer registers its own
-        for p in model.parameters():
-            p.requires_grad_(True)
-        print('Full model training')
+        train_cli.warm_up(args, model, losses, all_metrics, l2_of, train_seq, val_seq,
+                          lambda n: ('embedding' in n) or ('prob' in n), 'Pre-training new layers')
 
     # ---- main training (learn_image_embeddings.py:209-243)
-    sched_args = {k: v for k, v in vars(args).items() if v is not None}
-    callbacks, num_epochs = utils.get_lr_schedule(args.lr_schedule, data_generator.num_train, args.batch_size, schedule_args=sched_args)
-    epochs = args.epochs if args.epochs else num_epochs
-    if args.log_dir:
-        callbacks.append(JsonLogger(args.log_dir))
-    if args.snapshot:
-        ck = {'save_best_only': True, 'monitor': args.snapshot_best} if args.snapshot_best else {}
-        callbacks.append(utils.ModelCheckpoint(args.snapshot, **ck) if world <= 1 else utils.TemplateModelCheckpoint(model, args.snapshot, **ck))
-    decay = (1.0 / args.max_decay - 1) / ((data_generator.num_train // args.batch_size) * epochs) if args.max_decay > 0 else 0.0
-    trainer = Trainer(model, losses, all_metrics, lr=args.sgd_lr, momentum=0.9, nesterov=args.nesterov, clipnorm=args.clipgrad,
-                      decay=decay, l2_of=l2_of, autocast_dtype=mode[0], memory_format=mode[1])
-    trainer.fit(train_seq(), val_seq(), epochs=epochs, initial_epoch=args.initial_epoch, callbacks=callbacks, verbose=not args.no_progress)
+    trainer = train_cli.fit(args, model, losses, all_metrics, l2_of, data_generator, train_seq, val_seq, world)
 
     # ---- final evaluation (learn_image_embeddings.py:246-255)
     final = trainer.evaluate(val_seq())
@@ -303,17 +233,12 @@ def main(argv=None):
     if (args.cls_weight > 0) or (args.embedding == 'onehot'):
         pred = trainer.predict(data_generator.test_sequence(args.val_batch_size))
         pred = (pred[1] if args.cls_weight > 0 else pred).argmax(axis=-1)
-        y = np.asarray(data_generator.labels_test)
-        freq = np.bincount(y)
         if rank == 0 and world == 1:
-            print('Average Accuracy: {:.4f}'.format(((pred == y).astype(float) / freq[y]).sum() / len(freq)))
+            print('Average Accuracy: {:.4f}'.format(train_cli.average_accuracy(pred, data_generator.labels_test)))
 
     # ---- dumps (learn_image_embeddings.py:258-275)
     if rank == 0:
-        if args.weight_dump:
-            torch.save(model.state_dict(), args.weight_dump)
-        if args.model_dump:
-            torch.save(model, args.model_dump)
+        train_cli.dump_model(args, model)
         if args.feature_dump:
             feats = trainer.predict(data_generator.test_sequence(max(args.val_batch_size, 256)))
             feats = feats[0] if args.cls_weight > 0 else feats
@@ -323,11 +248,8 @@ def main(argv=None):
                 feats = utils.l2norm(torch.from_numpy(feats).to(dev)).cpu().numpy()
             elif args.loss == 'softmax_corr':
                 feats = torch.softmax(torch.from_numpy(feats), -1).numpy()
-            with open(args.feature_dump, 'wb') as f:
-                pickle.dump({'feat': dict(enumerate(feats))}, f)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+            train_cli.dump_features(args.feature_dump, feats)
+    train_cli.finish_process(world)
     return final
 
 

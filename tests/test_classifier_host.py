@@ -173,6 +173,15 @@ def test_parser_has_exactly_the_reference_flags_and_defaults():
     assert p.parse_args(["--dataset", "d", "--data_root", "r", "--snapshot_best", "val_acc"]).snapshot_best == "val_acc"
 
 
+def test_the_scripts_share_one_class_list_reader_and_one_json_logger():
+    import learn_center_loss as lcl
+    import learn_classifier as lc
+    import learn_image_embeddings as lie
+    import train_cli
+    assert lc.read_class_list is train_cli.read_class_list and lcl.read_class_list is train_cli.read_class_list
+    assert lie.JsonLogger is train_cli.JsonLogger
+
+
 def test_transform_inputs_and_losses():
     import learn_classifier as lc
     X, y = lc.transform_inputs("X", "y", 10, label_smoothing=0.1)

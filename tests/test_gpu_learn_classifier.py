@@ -103,16 +103,17 @@ def test_learn_classifier_cli_end_to_end(tmp_path, capsys):
 
 def test_finetune_init_trains_the_last_layer_only(tmp_path, capsys, monkeypatch):
     import learn_classifier as lc
+    import train_cli
     _, _, wts, _ = _cli(lc, tmp_path, "base", "--epochs", "1", "--no_progress", arch="resnet-32")
     loaded = torch.load(wts)
     capsys.readouterr()
     seen = []
 
-    class Recording(lc.Trainer):                 # the state every Trainer of the run starts from
+    class Recording(train_cli.Trainer):          # the state every Trainer of the run starts from
         def __init__(self, model, *a, **k):
             seen.append({n: p.detach().clone() for n, p in model.named_parameters()})
             super().__init__(model, *a, **k)
-    monkeypatch.setattr(lc, "Trainer", Recording)
+    monkeypatch.setattr(train_cli, "Trainer", Recording)
     _, _, wts2, _ = _cli(lc, tmp_path, "ft", "--epochs", "1", "--finetune", wts, "--finetune_init", "1", "--no_progress", arch="resnet-32")
     out = capsys.readouterr().out
     assert "Loading pre-trained weights" in out and "Average Accuracy:" in out
