@@ -601,6 +601,43 @@ int se_class_pair_tables(const int32_t *anc_off, const int32_t *anc_rank, const 
  */
 int se_cholesky_f64(double *a, int64_t lda, int64_t n, int32_t *info, se_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Input pipeline: batches of file-based datasets composed on the device
+ * ------------------------------------------------------------------------------------------ */
+
+/*
+ * One launch composes a batch [B, ch, cw, 3] (NHWC) from variable-sized uint8 RGB images resident in device memory.
+ * Replaces: datasets/common.py:380-581 (FileDatasetGenerator.compose_batch, _load_image, _transform: Pillow's bilinear resize of
+ *           the decoded image, float conversion, normalisation, optional BGR order, random flip, random erasing, random / centre
+ *           crop with reflect padding).  The kernel knows nothing of crop, pad or flip: the host folds them into the tables
+ *           (sehip.resample_tables), which are indexed by OUTPUT coordinate.
+ *   arena    uint8 store of arena_bytes bytes; image b starts at src_off[b], rows packed (src_w * 3 bytes), RGB interleaved
+ *   src_off  [B] int64;  src_hw [B, 2] int32 = (h, w)
+ *   xmap     [B, cw, 3] int32 = (u, xmin, n): u the coordinate of that output column in the zoomed, already flipped image (used
+ *            by the erase test only), xmin the first source column, n the number of taps;  xk [B, cw, Kx] int32: Pillow's 22-bit
+ *            fixed-point weights, zero-padded to Kx
+ *   ymap     [B, ch, 3], yk [B, ch, Ky]: the same for rows
+ *   erase    [B, 4] int32 = (y, x, h, w) in zoomed, flipped coordinates; h == 0: none
+ *   seed     [B] uint32 noise seed of the erase rectangle
+ *   mean, std  [3] f32 (device) in RGB order;  bgr != 0: source channel c is written at position 2 - c
+ *   out      [B, ch, cw, 3] f32 (SE_DTYPE_F32) or bf16 (SE_DTYPE_BF16: the f32 value rounded to nearest even)
+ * For output (b, cy, cx) and source channel c:
+ *     t(r) = clip8((2^21 + sum_i xk[cx, i] * src[r, xmin_x + i, c]) >> 22)        horizontal pass, uint8 result
+ *     v    = clip8((2^21 + sum_j yk[cy, j] * t(ymin_y + j)) >> 22)                vertical pass
+ *     out  = (float(v) - mean[c]) / std[c]                                        IEEE f32 subtract and divide
+ * -- Pillow's 8-bit resampling, bit for bit; an axis whose size does not change takes the single tap 1 << 22.  Where u_y is in
+ * [y, y + h) and u_x in [x, x + w) the value is (U - mean[c']) / std[c'] instead, c' the channel's POSITION in the output (the
+ * reference normalises its noise with the RGB-ordered statistics by position, common.py:538-540) and U uniform in [0, 255) from a
+ * counter-based hash of (seed[b], u_y, u_x, c'): the same arguments give the same noise.
+ * Table entries are clamped to the image (0 <= xmin < w, n <= min(Kx, w - xmin), likewise rows), and a sample whose image does not
+ * lie inside the arena is written as NaN.  SE_ERR_UNSUPPORTED when one output row's taps (Ky rows of cw pixels) and the column
+ * table (cw x Kx weights) exceed the 64 KB of LDS a workgroup owns, or B > 65535.  Asynchronous; no workspace; B = 0 is accepted.
+ */
+int se_image_batch(const void *arena, int64_t arena_bytes, const int64_t *src_off, const int32_t *src_hw, const int32_t *xmap,
+                   const int32_t *xk, const int32_t *ymap, const int32_t *yk, const int32_t *erase, const uint32_t *seed,
+                   const float *mean, const float *std, int bgr, void *out, int out_dtype, int64_t B, int ch, int cw, int Kx, int Ky,
+                   se_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,11 +6,21 @@
 Batches are produced ON THE DEVICE (channels_last float tensors), so images/s is not bound by a
 Python loader: the synthetic generators draw N(0,1) images with fixed seeds (BASELINE.json's
 configs are all measured on synthetic batches), the CIFAR generator keeps the whole pickle-decoded
-dataset in HBM and augments there.  File-based datasets of the reference (ILSVRC, NAB, CUB, ...)
-are out of scope of this build (real-data input path is a "next" row).
+dataset in HBM and augments there, and the file-based generators (NAB / CUB, Cars, Flowers, sub-directory datasets:
+datasets/files.py) keep the DECODED uint8 images of a split in HBM and compose every batch -- Pillow's bilinear resize, normalisation,
+flip, random erasing, crop, reflect padding -- in one launch of se_image_batch (csrc/image_batch.hip).  ILSVRC and iNaturalist stay
+out: their decoded images do not fit a resident store and need a streaming decode tier.
 """
 from .common import DeviceBatchSequence, InMemoryDatasetGenerator, SyntheticGenerator  # noqa: F401
 from .cifar import CifarGenerator  # noqa: F401
+from .files import (CarsGenerator, FileDatasetGenerator, FlowersGenerator, NABGenerator,  # noqa: F401
+                    SubDirectoryGenerator)
+
+# pre-processing statistics of the reference's presets (datasets/__init__.py:4-8), RGB order
+CAFFE_MEAN = [123.68, 116.779, 103.939]
+CAFFE_STD = [1., 1., 1.]
+IMAGENET_MEAN = [122.65435242, 116.6545058, 103.99789959]
+IMAGENET_STD = [71.40583196, 69.56888997, 73.0440314]
 
 SYNTHETIC_PRESETS = {
     # name: (num_classes, height/width, channels, num_train, num_test)
@@ -25,7 +35,10 @@ def get_data_generator(dataset, data_root, classes=None):
 
     Supported names: 'cifar-10', 'cifar-100', 'cifar-100-a', 'cifar-100-b' (python pickles under
     ``data_root``) and 'synthetic-cifar100' / 'synthetic-cub' / 'synthetic-ilsvrc' or the generic
-    'synthetic:<classes>x<size>x<train>x<test>' (``data_root`` ignored)."""
+    'synthetic:<classes>x<size>x<train>x<test>' (``data_root`` ignored); the file-based 'nab', 'cub', 'cub-sub<N>', 'cars',
+    'flowers', 'mit67scenes', 'ucmlu' and 'resisc45' with the reference's presets (datasets/__init__.py:60-162), each optionally
+    followed by '-large' (NAB: target size 512, crops of 448 x 448), then '-ilsvrcmean' (ImageNet statistics) or '-caffe' (BGR,
+    ImageNet mean, no standard deviation).  'ilsvrc' and 'inat*' raise NotImplementedError."""
     name = dataset.lower()
     if name in SYNTHETIC_PRESETS:
         c, hw, ch, ntr, nte = SYNTHETIC_PRESETS[name]
@@ -41,5 +54,44 @@ def get_data_generator(dataset, data_root, classes=None):
         return CifarGenerator(data_root, list(range(50)), reenumerate=name.endswith('-consec'))
     if name.startswith('cifar-100-b'):
         return CifarGenerator(data_root, list(range(50, 100)), reenumerate=name.endswith('-consec'))
-    raise NotImplementedError('dataset "{}": file-based datasets of the reference are outside the scope of this build; '
-                              'use cifar-10/100 or a synthetic-* generator'.format(dataset))
+
+    kwargs = {}
+    if name.endswith('-ilsvrcmean'):
+        kwargs.update(mean=IMAGENET_MEAN, std=IMAGENET_STD)
+        name = name[:-11]
+    elif name.endswith('-caffe'):
+        kwargs.update(mean=CAFFE_MEAN, std=CAFFE_STD, color_mode='bgr')
+        name = name[:-6]
+    if name.endswith('-large'):
+        kwargs.update(cropsize=(448, 448), default_target_size=512)
+        name = name[:-6]
+    if name == 'ilsvrc' or name.startswith('inat'):
+        raise NotImplementedError('dataset "{}": the decoded images of ILSVRC and iNaturalist do not fit the device-resident image '
+                                  'store of this build; they need a streaming decode tier, which is not built'.format(dataset))
+    if name == 'nab':
+        if 'default_target_size' not in kwargs:
+            kwargs['randzoom_range'] = (256, 480)
+        return NABGenerator(data_root, classes, 'images', **kwargs)
+    if name == 'cub' or name.startswith('cub-sub'):
+        kwargs.setdefault('mean', [123.82988033, 127.35116805, 110.25606303])
+        kwargs.setdefault('std', [59.2230949, 58.0736071, 67.80251684])
+        if name.startswith('cub-sub'):
+            samples_per_class = int(name[7:])
+            kwargs['split_file'] = 'train_test_split_{}.txt'.format(samples_per_class)
+            kwargs['train_repeats'] = 30 // samples_per_class
+        kwargs.update(cropsize=(448, 448), default_target_size=512, randzoom_range=None)
+        return NABGenerator(data_root, classes, 'images', **kwargs)
+    if name == 'cars':
+        return CarsGenerator(data_root, classes, **kwargs)
+    if name == 'flowers':
+        return FlowersGenerator(data_root, classes, **kwargs)
+    presets = {'mit67scenes': ([124.62788179, 110.01028625, 94.95780545], [68.56923599, 66.86607736, 67.35944349]),
+               'ucmlu': ([122.65409223, 124.40230701, 114.25659171], [55.74499679, 51.65585669, 50.16527551]),
+               'resisc45': ([94.17769482, 97.40967803, 87.80359702], [51.92246172, 47.22081475, 47.07685676])}
+    if name in presets:
+        if 'mean' not in kwargs and 'std' not in kwargs:
+            kwargs['mean'], kwargs['std'] = presets[name]
+        if name == 'mit67scenes':
+            kwargs.update(img_dir='Images', train_list='TrainImages.txt', test_list='TestImages.txt')
+        return SubDirectoryGenerator(data_root, classes, **kwargs)
+    raise ValueError('Unknown dataset: {}'.format(dataset))

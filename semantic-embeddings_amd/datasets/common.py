@@ -10,10 +10,12 @@ class DeviceBatchSequence(object):
 
     ``rank``/``world_size`` shard every global batch across data-parallel processes: rank r takes
     rows ``r::world_size`` of the global batch, so the union over ranks is the reference's batch.
-    ``batch_transform(X, y, **kwargs)`` is applied last (e.g. learn_image_embeddings.transform_inputs)."""
+    ``batch_transform(X, y, **kwargs)`` is applied last (e.g. learn_image_embeddings.transform_inputs).
+    ``repeats`` sub-epochs make one epoch, each with a permutation of its own (datasets/common.py:87-122: ``len()`` is
+    ``repeats`` x batches per sub-epoch); ``compose_kwargs`` are handed on to ``generator.compose_batch``."""
 
     def __init__(self, generator, indices, labels, batch_size=32, shuffle=False, train=False, augment=False,
-                 batch_transform=None, batch_transform_kwargs={}, rank=0, world_size=1, seed=0):
+                 batch_transform=None, batch_transform_kwargs={}, rank=0, world_size=1, seed=0, repeats=1, compose_kwargs=None):
         self.generator = generator
         self.indices = np.asarray(indices)
         self.labels = np.asarray(labels)
@@ -21,22 +23,28 @@ class DeviceBatchSequence(object):
         self.batch_transform, self.batch_transform_kwargs = batch_transform, batch_transform_kwargs
         self.rank, self.world_size = rank, world_size
         self.rng = np.random.default_rng(seed)      # same seed on every rank -> same permutation
-        self.perm = np.arange(len(self.indices))
+        self.repeats, self.compose_kwargs = int(repeats), dict(compose_kwargs or {})
+        self.epoch_len = int(np.ceil(len(self.indices) / self.batch_size))
+        self.perms = [np.arange(len(self.indices)) for _ in range(self.repeats)]
+        self.perm = self.perms[0]
         self.on_epoch_end()
 
     def __len__(self):
-        return int(np.ceil(len(self.indices) / self.batch_size))
+        return self.repeats * self.epoch_len
 
     def on_epoch_end(self):
         if self.shuffle:
-            self.rng.shuffle(self.perm)
+            for perm in self.perms:
+                self.rng.shuffle(perm)
 
     def __getitem__(self, idx):
-        glob = self.perm[idx * self.batch_size:(idx + 1) * self.batch_size]
+        sub = min(idx // max(self.epoch_len, 1), self.repeats - 1)
+        idx -= sub * self.epoch_len
+        glob = self.perms[sub][idx * self.batch_size:(idx + 1) * self.batch_size]
         sel = glob[self.rank::self.world_size]
         if len(sel) == 0 and len(glob):     # a short last batch with fewer rows than ranks: no rank may see an empty batch (its mean
             sel = glob[[self.rank % len(glob)]]   # would be NaN and the all-reduce would spread it): re-use one of the rows
-        X = self.generator.compose_batch(self.indices[sel], train=self.train, augment=self.augment)
+        X = self.generator.compose_batch(self.indices[sel], train=self.train, augment=self.augment, **self.compose_kwargs)
         y = torch.from_numpy(self.labels[sel].astype(np.int64)).to(X.device, non_blocking=True)
         if self.batch_transform is not None:
             return self.batch_transform(X, y, **self.batch_transform_kwargs)

@@ -7,6 +7,7 @@ the cvjena/semantic-embeddings checkout.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, METRIC_EUCLID, SehipError, call, require_gpu
@@ -18,7 +19,7 @@ __all__ = [
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
     "recall_precision_reduce", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
-    "svm_axpby", "class_pair_tables", "cholesky_lower_",
+    "svm_axpby", "class_pair_tables", "cholesky_lower_", "image_batch", "resample_tables",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
 ]
 
@@ -971,3 +972,102 @@ def cholesky_lower_(a, info=None):
     _i32(info, "info")
     call("se_cholesky_f64", a, a.stride(0) if n > 1 else max(n, 1), n, info)
     return a, info
+
+
+# --------------------------------------------------------------------------------------------
+# input pipeline: batches of file-based datasets composed on the device (image_batch.hip; the generators are datasets/files.py)
+# --------------------------------------------------------------------------------------------
+
+_RESAMPLE_BITS = 22        # Pillow's PRECISION_BITS for 8-bit images (32 - 8 - 2)
+
+
+def _axis_tables(src, dst, crop, offs, pad, flip):
+    """Tables of one axis for a whole batch: ``(map [B, crop, 3] = (u, first source index, taps), weights [B, crop, K])``."""
+    src, dst, offs, pad = (np.asarray(v, dtype=np.int64).reshape(-1) for v in (src, dst, offs, pad))
+    if src.size and (src.min() < 1 or dst.min() < 1):
+        raise SehipError("resample_tables: image sizes must be positive")
+    # output coordinate -> coordinate u in the zoomed, flipped image: crop offset, then np.pad(..., 'reflect') of period 2 (n - 1)
+    p = np.arange(crop, dtype=np.int64)[None, :] + (offs - pad)[:, None]
+    period = np.maximum(2 * (dst - 1), 1)[:, None]
+    m = np.mod(p, period)
+    u = np.where(m < dst[:, None], m, period - m)
+    idx = u if flip is None else np.where(np.asarray(flip, dtype=bool).reshape(-1, 1), dst[:, None] - 1 - u, u)
+    # Pillow's precompute_coeffs (bilinear: support 1), in its order of operations, float64
+    same = src == dst
+    scale = src.astype(np.float64) / dst.astype(np.float64)
+    fs = np.maximum(scale, 1.0)
+    support = fs * 1.0
+    taps = np.ceil(support).astype(np.int64) * 2 + 1
+    K = int(np.max(np.where(same, 1, taps))) if src.size else 1
+    center = (idx + 0.5) * scale[:, None]
+    ss = 1.0 / fs
+    lo = np.maximum((center - support[:, None] + 0.5).astype(np.int64), 0)
+    hi = np.minimum((center + support[:, None] + 0.5).astype(np.int64), src[:, None])
+    n = hi - lo
+    i = np.arange(K, dtype=np.int64)[None, None, :]
+    w = np.abs(((i + lo[:, :, None]) - center[:, :, None] + 0.5) * ss[:, None, None])
+    w = np.where((w < 1.0) & (i < n[:, :, None]), 1.0 - w, 0.0)
+    ww = np.cumsum(w, axis=2)[:, :, -1:]                         # summed in order, like the C loop
+    w = np.divide(w, ww, out=w.copy(), where=ww != 0.0)
+    k = (0.5 + w * float(1 << _RESAMPLE_BITS)).astype(np.int64)
+    # an axis whose size does not change is not resampled by Pillow: the single tap reproduces the pixel
+    sm = same[:, None]
+    lo = np.where(sm, idx, lo)
+    n = np.where(sm, 1, n)
+    one = np.zeros((1, 1, K), dtype=np.int64)
+    one[0, 0, 0] = 1 << _RESAMPLE_BITS
+    k = np.where(sm[:, :, None], one, k)
+    return np.stack((u, lo, n), axis=2).astype(np.int32), np.ascontiguousarray(k.astype(np.int32))
+
+
+def resample_tables(src_sizes, dst_sizes, crop, offsets=None, pads=None, flips=None):
+    """The tables ``se_image_batch`` resamples with, for a whole batch, in vectorised NumPy float64 on the HOST (the device's float64
+    with possible FMA contraction would not reproduce Pillow's quantised weights).
+
+    ``src_sizes`` [B, 2] = (h, w) of the stored images, ``dst_sizes`` [B, 2] = (H', W') of the zoomed images, ``crop`` = (ch, cw),
+    ``offsets`` [B, 2] = (y, x) of the crop window in the zoomed image (an axis larger than the crop), ``pads`` [B, 2] = (y, x) rows /
+    columns of reflect padding in front (an axis smaller than the crop), ``flips`` [B] horizontal flips.  The tables are indexed by
+    OUTPUT coordinate: crop offset, reflect padding (``np.pad(..., 'reflect')``: period 2 (n - 1), a size-1 axis repeats) and flip are
+    applied by gathering rows of Pillow's coefficient table (``PIL.Image.resize(size, BILINEAR)``: ImagingResample's
+    precompute_coeffs + normalize_coeffs_8bpc).  Returns ``(xmap [B, cw, 3], xk [B, cw, Kx], ymap [B, ch, 3], yk [B, ch, Ky])`` int32."""
+    src = np.asarray(src_sizes, dtype=np.int64).reshape(-1, 2)
+    dst = np.asarray(dst_sizes, dtype=np.int64).reshape(-1, 2)
+    B = src.shape[0]
+    offs = np.zeros((B, 2), np.int64) if offsets is None else np.asarray(offsets, dtype=np.int64).reshape(-1, 2)
+    pad = np.zeros((B, 2), np.int64) if pads is None else np.asarray(pads, dtype=np.int64).reshape(-1, 2)
+    if not (dst.shape[0] == offs.shape[0] == pad.shape[0] == B):
+        raise SehipError("resample_tables: one row per sample in every argument")
+    ch, cw = int(crop[0]), int(crop[1])
+    ymap, yk = _axis_tables(src[:, 0], dst[:, 0], ch, offs[:, 0], pad[:, 0], None)
+    xmap, xk = _axis_tables(src[:, 1], dst[:, 1], cw, offs[:, 1], pad[:, 1], flips)
+    return xmap, xk, ymap, yk
+
+
+def image_batch(arena, src_off, src_hw, xmap, xk, ymap, yk, erase, seed, mean, std, bgr=False, dtype=torch.float32, out=None):
+    """``se_image_batch``: one launch composes the batch from the uint8 ``arena`` (see include/sehip.h for every argument; all device
+    tensors: ``src_off`` int64 [B], ``seed`` int32 / uint32 bit patterns [B], ``mean`` / ``std`` float32 [3], the rest int32).
+    Returns ``out`` [B, ch, cw, 3] (NHWC) of ``dtype`` float32 or bfloat16; ``out.permute(0, 3, 1, 2)`` is the channels_last batch."""
+    require_gpu(arena, src_off, src_hw, xmap, xk, ymap, yk, erase, seed, mean, std, out)
+    if arena.dtype != torch.uint8 or not arena.is_contiguous():
+        raise SehipError("image_batch: the arena must be a contiguous uint8 tensor")
+    _i64(src_off, "src_off")
+    for t, name in ((src_hw, "src_hw"), (xmap, "xmap"), (xk, "xk"), (ymap, "ymap"), (yk, "yk"), (erase, "erase")):
+        _i32(t, name)
+    if not seed.is_contiguous() or not mean.is_contiguous() or not std.is_contiguous() or mean.numel() != 3 or std.numel() != 3:
+        raise SehipError("image_batch: seed must be contiguous, mean / std contiguous float32 [3]")
+    B = src_off.numel()
+    if xmap.dim() != 3 or ymap.dim() != 3 or xk.dim() != 3 or yk.dim() != 3 or xmap.shape[2] != 3 or ymap.shape[2] != 3:
+        raise SehipError("image_batch: xmap / ymap must be [B, crop, 3], xk / yk [B, crop, K]")
+    ch, cw, Kx, Ky = ymap.shape[1], xmap.shape[1], xk.shape[2], yk.shape[2]
+    if not (xmap.shape[0] == ymap.shape[0] == xk.shape[0] == yk.shape[0] == B) or xk.shape[1] != cw or yk.shape[1] != ch \
+            or src_hw.numel() != 2 * B or erase.numel() != 4 * B or seed.numel() != B:
+        raise SehipError("image_batch: the tables do not describe one batch of %d samples" % B)
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise SehipError("image_batch: output must be float32 or bfloat16, got %s" % dtype)
+    if out is None:
+        out = torch.empty((B, ch, cw, 3), dtype=dtype, device=arena.device)
+    elif out.dtype != dtype or tuple(out.shape) != (B, ch, cw, 3) or not out.is_contiguous():
+        raise SehipError("image_batch: out must be a contiguous [B, ch, cw, 3] tensor of the requested dtype")
+    call("se_image_batch", arena, arena.numel(), src_off, src_hw, xmap, xk, ymap, yk, erase, seed, mean, std, int(bool(bgr)), out,
+         DTYPE_F32 if dtype == torch.float32 else DTYPE_BF16, B, ch, cw, Kx, Ky)
+    return out

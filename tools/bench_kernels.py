@@ -9,7 +9,10 @@
     python tools/bench_kernels.py center         (center loss forward / input gradient / centroid gradient at D = 100, and the
                                                   ResNet-110-fc center-loss training step next to the cosine-loss one)
     python tools/bench_kernels.py xent           (softmax cross-entropy forward + backward next to the torch composition the sibling
-                                                  CLIs use, f32 / bf16 logits, s = 0 / 0.1, and the ResNet-110 classifier step)"""
+                                                  CLIs use, f32 / bf16 logits, s = 0 / 0.1, and the ResNet-110 classifier step)
+    python tools/bench_kernels.py image          (se_image_batch: a batch of 128 at the CUB preset (375 x 500 sources, shorter side 512,
+                                                  crop 448) and at the NAB preset (about 768 x 1024 sources, random zoom 256-480, crop
+                                                  224): kernel time, host time, bytes over kernel time, next to the ResNet-50 step)"""
 import argparse
 import os
 import sys
@@ -37,7 +40,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent"])
+                                     "center", "xent", "image"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -52,6 +55,8 @@ def main():
         return bench_center()
     if args.what == "xent":
         return bench_xent()
+    if args.what == "image":
+        return bench_image()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -509,6 +514,81 @@ def bench_xent(reps=60, batch=20, steps=200):
         step = float(np.median(ms[name]))
         print("ResNet-110 classifier step (%s head: loss + acc + acc5), batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d "
               "steps; %s), %.0f images/s" % (name, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
+
+
+def bench_image(B=128, reps=20, stored=256):
+    """Composing a batch of a file-based dataset (datasets/files.py): the host part -- drawing the augmentation parameters, building
+    the resampling tables (sehip.resample_tables) and uploading them in one copy, host clock around work that ends in a device
+    synchronise -- and the kernel, se_image_batch, HIP events around one launch on tables that are already on the device, `reps`
+    different batches each, medians.  Bytes: the source pixels inside the row / column span each sample's tables reach + the tables +
+    the batch written, over the kernel time, against the 6.29 TB/s a float4 copy reaches on MI355X.  The store holds `stored` images of
+    uniform noise, float32 and bfloat16 batches.  Last, the ResNet-50 training step of the same batch size (bench.py's configuration:
+    224 x 224, 200 classes, bf16 autocast, channels_last) in the same process: the loader keeps up when host + kernel stay below it."""
+    import argparse as ap
+    import time
+    from datasets.files import DEFAULT_ERASE_PARAMS, FileDatasetGenerator, pack_batch_tables
+    HBM = 6.29e12
+    rng = np.random.default_rng(0)
+    cases = (("CUB preset: 375 x 500 -> shorter side 512, crop 448 x 448", lambda n: np.tile([[375, 500]], (n, 1)),
+              dict(cropsize=(448, 448), default_target_size=512, randzoom_range=None)),
+             ("NAB preset: about 768 x 1024 -> random zoom 256-480, crop 224 x 224",
+              lambda n: np.stack((rng.integers(700, 840, n), rng.integers(950, 1100, n)), axis=1),
+              dict(cropsize=(224, 224), default_target_size=256, randzoom_range=(256, 480))))
+    worst = 0.0
+    for title, make_sizes, kw in cases:
+        gen = FileDatasetGenerator(".", randerase_prob=0.5, randerase_params=DEFAULT_ERASE_PARAMS, **kw)
+        gen._compute_stats([125.30513277, 129.66606421, 118.45121113], [57.0045467, 56.70059436, 68.44430446])
+        sizes = make_sizes(stored).astype(np.int32)
+        nbytes = sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3
+        offsets = np.concatenate(([0], np.cumsum(nbytes)[:-1]))
+        arena = torch.randint(0, 256, (int(nbytes.sum()),), dtype=torch.uint8, device="cuda")
+        mean, std = gen._device_stats()
+        crop = (kw["cropsize"][1], kw["cropsize"][0])
+        host_ms, kern_ms, moved, taps = [], {torch.float32: [], torch.bfloat16: []}, [], None
+        draw = np.random.default_rng(1)
+        for it in range(reps + 2):
+            idx = draw.choice(stored, B, replace=False)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            params = gen.draw_params(sizes[idx], True, True, draw)
+            buf, views = pack_batch_tables(offsets[idx], sizes[idx], params, crop)
+            dbuf = torch.from_numpy(buf).cuda()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            t = {name: (dbuf[a:b].view(torch.int64) if name == "src_off" else dbuf[a:b].view(shape)) for name, (a, b, shape) in views.items()}
+            xmap, ymap = (buf[views[k][0]:views[k][1]].reshape(views[k][2]) for k in ("xmap", "ymap"))
+            span = lambda m: (m[:, :, 1] + m[:, :, 2]).max(axis=1) - m[:, :, 1].min(axis=1)
+            src_bytes = int((span(xmap).astype(np.int64) * span(ymap) * 3).sum())
+            taps = (views["xk"][2][2], views["yk"][2][2])
+            for dtype, esz in ((torch.float32, 4), (torch.bfloat16, 2)):
+                out = torch.empty((B,) + crop + (3,), dtype=dtype, device="cuda")
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                sehip.image_batch(arena, t["src_off"], t["src_hw"], t["xmap"], t["xk"], t["ymap"], t["yk"], t["erase"], t["seed"], mean, std,
+                                  dtype=dtype, out=out)
+                b.record()
+                torch.cuda.synchronize()
+                if it >= 2:                                   # two warm-up batches
+                    kern_ms[dtype].append(a.elapsed_time(b))
+                    if dtype == torch.float32:
+                        moved.append(src_bytes + buf.nbytes + out.numel() * esz)
+            if it >= 2:
+                host_ms.append((t1 - t0) * 1e3)
+        h, k32, k16 = (float(np.median(v)) for v in (host_ms, kern_ms[torch.float32], kern_ms[torch.bfloat16]))
+        gbs = float(np.median(moved)) / (k32 * 1e-3)
+        worst = max(worst, h + k32)
+        print("image batch, B = %d, %s (taps %d x %d): kernel %.3f ms f32 (%.3f-%.3f) / %.3f ms bf16; host (draw + tables + upload of "
+              "%.2f MB) %.3f ms (%.3f-%.3f); host + kernel %.3f ms = %.0f images/s; f32 kernel moves %.1f MB = %.0f GB/s = %.1f%% of the "
+              "HBM copy rate" % (B, title, taps[0], taps[1], k32, min(kern_ms[torch.float32]), max(kern_ms[torch.float32]), k16,
+                                 buf.nbytes / 1e6, h, min(host_ms), max(host_ms), h + k32, B / (h + k32) * 1e3, np.median(moved) / 1e6,
+                                 gbs / 1e9, 100.0 * gbs / HBM), flush=True)
+        del arena
+    sys.path.insert(0, ROOT)
+    import train_bench
+    r = train_bench.bench_train(ap.Namespace(arch="resnet-50", batch=B, steps=30, warmup=5, workload="train", full=False), 0, 1)
+    print("ResNet-50 training step, 224 x 224, 200 classes, batch %d, %s: %.2f ms/step = %.0f images/s; slowest batch composition "
+          "(host + kernel) %.2f ms: the loader %s" % (B, r["dtype"], r["ms_per_step"], r["value"], worst,
+                                                      "keeps up with the network" if worst < r["ms_per_step"] else "DOES NOT keep up: it sets images/s"))
 
 
 if __name__ == "__main__":

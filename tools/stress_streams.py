@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Every retrieval / loss entry point under two-stream contention: result of a call made while a second stream keeps the CUs busy
+"""Every retrieval / loss / input-pipeline entry point under two-stream contention: result of a call made while a second stream keeps the CUs busy
 == result of the same call made alone, bit for bit.
 
 Round 4 found se_topk_rows returning unsorted rows whenever another stream's kernels shared its CUs (a work-group barrier compiled
@@ -46,6 +46,17 @@ xb = dev(f32(4096, 100)); yb = dev(rng.integers(0, C, size=4096).astype(np.int64
 parts = torch.stack([torch.stack([sehip.topk_rows(pd_mid[:, i * 2500:(i + 1) * 2500].contiguous(), 251, col_offset=i * 2500)[j].view(torch.int32)
                                   for j in (0, 1)]) for i in range(8)])     # [8, 2, Q, k] packed lists
 
+# a batch of the file-dataset input pipeline: 32 images of 96 x 128 .. 200 x 260 noise, random zoom 64-120, crop 56 x 56, erasing
+from datasets.files import DEFAULT_ERASE_PARAMS, FileDatasetGenerator, pack_batch_tables
+img_gen = FileDatasetGenerator(".", cropsize=(56, 56), default_target_size=64, randzoom_range=(64, 120), randerase_prob=0.5, randerase_params=DEFAULT_ERASE_PARAMS)
+img_sizes = np.stack((rng.integers(96, 200, 32), rng.integers(128, 260, 32)), axis=1).astype(np.int32)
+img_bytes = img_sizes[:, 0].astype(np.int64) * img_sizes[:, 1] * 3
+img_arena = dev(rng.integers(0, 256, int(img_bytes.sum()), dtype=np.uint8))
+img_buf, img_views = pack_batch_tables(np.concatenate(([0], np.cumsum(img_bytes)[:-1])), img_sizes, img_gen.draw_params(img_sizes, True, True, rng), (56, 56))
+img_dbuf = dev(img_buf)
+img_t = {k: (img_dbuf[a:b].view(torch.int64) if k == "src_off" else img_dbuf[a:b].view(shape)) for k, (a, b, shape) in img_views.items()}
+img_stats = (dev(np.float32([125.3, 129.7, 118.5])), dev(np.float32([57.0, 56.7, 68.4])))
+
 
 def as_tuple(r):
     return tuple(r) if isinstance(r, (tuple, list)) else (r,)
@@ -71,6 +82,8 @@ OPS = {
     "cosine_loss fwd+bwd": lambda: (sehip.cosine_loss_forward(xb, yb, emb)[0], sehip.cosine_loss_backward(xb, yb, emb)),
     "nn_accuracy": lambda: sehip.nn_accuracy(xb, yb, emb, dot_prod_sim=True, k=5),
     "devise_ranking_loss": lambda: sehip.devise_ranking_loss(xb, yb, emb),
+    "image_batch": lambda: sehip.image_batch(img_arena, img_t["src_off"], img_t["src_hw"], img_t["xmap"], img_t["xk"], img_t["ymap"], img_t["yk"],
+                                             img_t["erase"], img_t["seed"], img_stats[0], img_stats[1]),
 }
 SIDE = {
     "distance tiles": lambda: sehip.pairwise_dist(g20[:6000], g20[:6000]),
