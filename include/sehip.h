@@ -264,6 +264,34 @@ int se_softmax_xent_bwd(const void *logits, int z_dtype, int64_t ldz, const int6
                         const float *grad_loss_i, float grad_scale, int64_t B, int64_t C, float smoothing, void *dz,
                         int dz_dtype, int64_t lddz, se_stream_t stream);
 
+/*
+ * Adagrad update of a flat float32 parameter buffer in one launch, gradient scale and L2 regulariser folded in.
+ * Replaces: Keras 2.2 optimizers.Adagrad.get_updates [third party, not in the reference tree] as learn_devise.py:87,114 uses it
+ *           (keras.optimizers.Adagrad(lr=...) in both compile() calls), and the whole-buffer passes that would otherwise scale the
+ *           gradient (the mean over the data-parallel ranks) and add the kernel regulariser's gradient in front of it.
+ *   p [n] in / out, accum [n] in / out (the running sum of squared gradients, zeros before the first step), g [n] in,
+ *   l2 [n] or NULL: the coefficient 2 lambda of every element (0 where a parameter has no regulariser).
+ *   Per element, every operation a separately rounded float32 operation (no FMA contraction; correctly rounded division and square root):
+ *       g1 = grad_scale == 1 ? g : g * grad_scale
+ *       g2 = l2 ? g1 + l2 * p : g1
+ *       a' = a + g2 * g2
+ *       p' = p - (lr * g2) / (sqrt(a') + epsilon)             Keras: p - lr * g / (K.sqrt(new_a) + epsilon)
+ *   lr_dev NULL: the learning rate is the argument lr; otherwise it is read from lr_dev[0] on the device when the kernel runs (lr
+ *   is then ignored), so a captured launch follows a schedule without being captured again.
+ *   g is ONLY READ: after the step it still holds the raw gradient, neither scaled nor regularised.
+ *   An element with g2 = 0 keeps p and accum bit for bit when epsilon > 0 (+0 stays +0); a NaN or Inf in g makes p and accum of that element NaN or
+ *   Inf as the formula says: it is not an error.
+ *   n = 0 returns SE_OK without a launch (every pointer may then be NULL); n < 0, epsilon < 0 or NaN, or a NULL p / accum / g with
+ *   n > 0 is SE_ERR_INVALID.  Any pointer alignment and any n: 16-byte accesses when p, accum, g and l2 are all 16-byte aligned, with
+ *   the n % 4 last elements taken one by one; 4-byte accesses otherwise.  int64 indices.  The grid is capped at
+ *   SE_ADAGRAD_MAX_BLOCKS workgroups of 256 threads that stride over the buffer.
+ *   Asynchronous on `stream`, no allocation, no atomics, no host synchronisation: capturable in a HIP graph, and the same inputs
+ *   give the same bits.
+ */
+#define SE_ADAGRAD_MAX_BLOCKS 2048
+int se_adagrad_step(float *p, float *accum, const float *g, const float *l2, int64_t n, float lr, const float *lr_dev,
+                    float grad_scale, float epsilon, se_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Retrieval side  (evaluate_retrieval.pairwise_retrieval, evaluate_retrieval.py:22-73)
  * ------------------------------------------------------------------------------------------ */

@@ -17,7 +17,8 @@ predict_generator`` + ``multi_gpu_model`` play in the reference (learn_image_emb
 * metrics are accumulated on the device and read back once per epoch (no per-step host sync).
 
 Semantics mirrored from Keras 2.2 [third party, not in the reference tree]: SGD velocity
-``v = m v - lr g; w += v`` (Nesterov: ``w += m v - lr g``), ``clipnorm`` = global-norm clip,
+``v = m v - lr g; w += v`` (Nesterov: ``w += m v - lr g``), Adagrad ``a += g^2; w -= lr g / (sqrt(a) + 1e-7)`` (one fused HIP
+launch over the flat buffers, ``sehip.adagrad_step_``), ``clipnorm`` = global-norm clip,
 per-replica BatchNorm statistics (``multi_gpu_model`` towers == no SyncBN).
 """
 import os
@@ -26,6 +27,8 @@ import time
 import numpy as np
 import torch
 import torch.distributed as dist
+
+import sehip
 
 
 def dist_info():
@@ -188,10 +191,16 @@ class Trainer(object):
     losses:  dict output_name -> (loss_fn(y_true, y_pred) -> [B], weight); outputs of the model
              are matched by position (tuple outputs) in the dict's order.
     metrics: dict output_name -> list of metric fns with ``.name``.
-    A batch from the sequences is ``(X, y)`` or ``(X, [y_1, y_2, ...])``."""
+    A batch from the sequences is ``(X, y)`` or ``(X, [y_1, y_2, ...])``.
+    optimizer: 'sgd' (Keras SGD with ``momentum`` / ``nesterov``) or 'adagrad' (Keras Adagrad with ``epsilon``: ``flat.flat_v`` is the
+             accumulator of squared gradients, ``momentum`` and ``nesterov`` are ignored); both with ``lr / (1 + decay * iterations)``."""
 
     def __init__(self, model, losses, metrics=None, lr=0.1, momentum=0.9, nesterov=False, clipnorm=None, decay=0.0,
-                 l2_of=None, autocast_dtype=torch.bfloat16, bucket_bytes=25 << 20, trainable=None, memory_format=None):
+                 l2_of=None, autocast_dtype=torch.bfloat16, bucket_bytes=25 << 20, trainable=None, memory_format=None,
+                 optimizer='sgd', epsilon=1e-7):
+        if optimizer not in ('sgd', 'adagrad'):
+            raise ValueError("optimizer must be 'sgd' or 'adagrad', got %r" % (optimizer,))
+        self.optimizer, self.epsilon = optimizer, float(epsilon)
         self.model = model
         self.memory_format = memory_format       # None: leave model and batches as they come (channels_last by construction)
         if memory_format is not None:
@@ -261,7 +270,7 @@ class Trainer(object):
 
     def enable_graphs(self, X, y, warmup=3, validate=4, tol=2e-3, max_noise=0.05, allow_autocast=False):
         """Capture the training step into two HIP graphs (``torch.cuda.CUDAGraph``): A = zero grads + forward + fused
-        loss/metric + backward, B = the whole-buffer SGD update; the RCCL all-reduce of the flat gradient buffer stays
+        loss/metric + backward, B = the whole-buffer SGD (or fused Adagrad) update; the RCCL all-reduce of the flat gradient buffer stays
         an eager call between them (one message per step), so 1-GPU and N-GPU runs replay identical graphs.
         A ResNet-110 step is ~1500 small launches and host-launch-bound in eager mode (21.6 -> 15.3 ms on MI355X, fp32).
         Batches of another shape than ``(X, y)`` (a short last batch) run eagerly.
@@ -431,7 +440,10 @@ class Trainer(object):
 
     def apply_update(self, grad_scale=1.0, lr_tensor=None, count=True):
         """Keras-SGD update on the flat buffers (regulariser -> clip -> decayed lr -> momentum).  With ``lr_tensor``
-        (a device scalar) the learning rate is read on the device, so the launches can be captured in a HIP graph."""
+        (a device scalar) the learning rate is read on the device, so the launches can be captured in a HIP graph.
+        ``optimizer='adagrad'``: one ``sehip.adagrad_step_`` launch instead (``_apply_adagrad``)."""
+        if self.optimizer == 'adagrad':
+            return self._apply_adagrad(grad_scale, lr_tensor, count)
         flat = self.flat
         g = flat.flat_g
         if grad_scale != 1.0:
@@ -456,6 +468,28 @@ class Trainer(object):
                 flat.flat_p.add_(v, alpha=self.momentum).add_(g, alpha=-lr)
             else:
                 flat.flat_p.add_(v)
+        if count:
+            self.iterations += 1
+
+    def _apply_adagrad(self, grad_scale, lr_tensor, count):
+        """Keras-Adagrad update (``a += g^2; w -= lr g / (sqrt(a) + epsilon)``, a = ``flat.flat_v``) as ONE launch of the fused kernel,
+        which scales the gradient and adds the regulariser's on the way and leaves ``flat_g`` as backward wrote it.  Only ``clipnorm``
+        needs the regularised gradient in memory first: the whole-buffer lines of the SGD path then run in front of the kernel."""
+        flat = self.flat
+        g, l2 = flat.flat_g, flat.flat_l2 if flat.has_l2 else None
+        if self.clipnorm:
+            if grad_scale != 1.0:
+                g.mul_(grad_scale)
+            if flat.has_l2:
+                g.addcmul_(flat.flat_l2, flat.flat_p)
+            norm = torch.linalg.vector_norm(g)
+            g.mul_(torch.clamp(self.clipnorm / (norm + 1e-12), max=1.0))
+            grad_scale, l2 = 1.0, None
+        if lr_tensor is not None:
+            lr = lr_tensor
+        else:
+            lr = self.lr / (1.0 + self.decay * self.iterations) if self.decay > 0 else self.lr
+        sehip.adagrad_step_(flat.flat_p, flat.flat_v, g, l2, lr=lr, grad_scale=grad_scale, epsilon=self.epsilon)
         if count:
             self.iterations += 1
 

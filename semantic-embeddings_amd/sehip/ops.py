@@ -15,6 +15,7 @@ from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, MET
 __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
     "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "labelembed_loss", "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
+    "adagrad_step_", "ADAGRAD_MAX_BLOCKS",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
@@ -497,6 +498,30 @@ def devise_ranking_loss(y_pred, target, embedding, margin=0.1):
         true_sim = (yt * yp).sum(-1)
         return torch.relu(float(margin) - true_sim[:, None] + yp @ embedding.t()).sum(-1) - float(margin)
     return _DeviseLoss.apply(y_pred, target, embedding, float(margin))
+
+
+ADAGRAD_MAX_BLOCKS = DEFINES["SE_ADAGRAD_MAX_BLOCKS"]     # grid cap of se_adagrad_step: 256 threads per workgroup, 4 elements per thread
+
+
+def adagrad_step_(p, accum, g, l2=None, lr=0.01, grad_scale=1.0, epsilon=1e-7):
+    """In place, one launch (``se_adagrad_step``): Keras 2.2's Adagrad update ``accum += g2 * g2; p -= lr * g2 / (sqrt(accum) + epsilon)``
+    with ``g2 = g * grad_scale + l2 * p`` (keras.optimizers.Adagrad as learn_devise.py:87,114 uses it; every operation a separately
+    rounded float32 operation, include/sehip.h).  ``p``, ``accum``, ``g`` and ``l2`` (None: no regulariser) are contiguous float32
+    device tensors of one size; ``g`` is only read.  ``lr``: a float, or a 0-dim float32 device tensor that is read on the device
+    when the kernel runs (a captured launch then follows the schedule).  Returns ``p``."""
+    require_gpu(p, accum, g, l2)
+    n = p.numel()
+    for t, what in ((p, "p"), (accum, "accum"), (g, "g"), (l2, "l2")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or t.device != p.device):
+            raise SehipError("%s must be a contiguous float32 tensor of %d elements on %s" % (what, n, p.device))
+    lr_dev = None
+    if torch.is_tensor(lr):
+        require_gpu(lr)
+        if lr.dtype != torch.float32 or lr.numel() != 1 or lr.device != p.device:
+            raise SehipError("a learning-rate tensor must hold one float32 value on %s" % (p.device,))
+        lr, lr_dev = 0.0, lr
+    call("se_adagrad_step", p, accum, g, l2, n, float(lr), lr_dev, float(grad_scale), float(epsilon))
+    return p
 
 
 # --------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""What the training command lines (learn_image_embeddings.py, learn_center_loss.py, learn_classifier.py) have in common: the shared
+"""What the training command lines (learn_image_embeddings.py, learn_center_loss.py, learn_classifier.py, learn_devise.py) have in common: the shared
 flag runs, the process group, loading weights, the ``--finetune_init`` warm-up, the main fit and the dumps.  Plain functions that
 each script's ``main()`` calls in order; the model, the losses and what the feature dump holds stay in the scripts."""
 import json
@@ -102,10 +102,15 @@ def resume_from_snapshot(model, snapshot, dev):
 
 
 def load_pretrained(model, path, dev):
-    """``--finetune``: every tensor of the file whose name and shape the model has too."""
+    """``--finetune`` / ``--init_weights``: every tensor of the file whose name and shape the model has too.  The file is a
+    ``state_dict`` (``--weight_dump``), a snapshot, or a whole module as ``--model_dump`` writes it (unpickled, so only from a trusted
+    source -- like ``evaluate_classification_accuracy.py --model``)."""
     print('Loading pre-trained weights from {}'.format(path))
-    state = torch.load(path, map_location=dev)
-    state = state.get('model', state)
+    try:
+        state = torch.load(path, map_location=dev)
+    except pickle.UnpicklingError:          # no plain tensor file: a pickled module
+        state = torch.load(path, map_location=dev, weights_only=False)
+    state = state.state_dict() if isinstance(state, torch.nn.Module) else state.get('model', state)
     own = model.state_dict()
     model.load_state_dict({k: v for k, v in state.items() if k in own and own[k].shape == v.shape}, strict=False)
 
@@ -116,6 +121,22 @@ def _trainer(args, model, losses, metrics, l2_of, **kw):
     mode = backbone_mode(args.architecture)       # (autocast dtype, memory format) of the PyTorch-ROCm backbone
     return Trainer(model, losses, metrics, lr=args.sgd_lr, momentum=0.9, nesterov=args.nesterov, clipnorm=args.clipgrad,
                    l2_of=l2_of, autocast_dtype=mode[0], memory_format=mode[1], **kw)
+
+
+def max_decay_rate(max_decay, num_train, batch_size, epochs):
+    """Keras' ``decay`` that brings ``lr / (1 + decay * iterations)`` down to ``max_decay * lr`` at the last step of ``epochs`` epochs
+    (learn_devise.py:109-112, the formula every trainer of the reference uses); 0 for ``max_decay <= 0``."""
+    return (1.0 / max_decay - 1) / ((num_train // batch_size) * epochs) if max_decay > 0 else 0.0
+
+
+def adagrad_trainer(args, model, losses, metrics, l2_of, lr, max_decay=0.0, num_train=None, epochs=None, **kw):
+    """A trainer like ``keras.optimizers.Adagrad(lr=lr, decay=...)`` compiles (learn_devise.py:87,114): constant ``lr`` apart from
+    the ``max_decay`` decay over ``epochs`` epochs of ``num_train`` images, no gradient clipping, zero accumulators and zero
+    iterations -- what Keras starts from whenever a model is compiled again."""
+    mode = backbone_mode(args.architecture)
+    decay = max_decay_rate(max_decay, num_train, args.batch_size, epochs)
+    return Trainer(model, losses, metrics, lr=lr, decay=decay, clipnorm=None, l2_of=l2_of, autocast_dtype=mode[0],
+                   memory_format=mode[1], optimizer='adagrad', **kw)
 
 
 def warm_up(args, model, losses, metrics, l2_of, train_seq, val_seq, trainable, message):
@@ -152,7 +173,7 @@ def fit(args, model, losses, metrics, l2_of, data_generator, train_seq, val_seq,
     if getattr(args, 'snapshot', None):
         ck = {'save_best_only': True, 'monitor': args.snapshot_best} if args.snapshot_best else {}
         callbacks.append(utils.ModelCheckpoint(args.snapshot, **ck) if world <= 1 else utils.TemplateModelCheckpoint(model, args.snapshot, **ck))
-    decay = (1.0 / args.max_decay - 1) / ((data_generator.num_train // args.batch_size) * epochs) if args.max_decay > 0 else 0.0
+    decay = max_decay_rate(args.max_decay, data_generator.num_train, args.batch_size, epochs)
     trainer = _trainer(args, model, losses, metrics, l2_of, decay=decay)
     trainer.fit(train_seq(), val_seq(), epochs=epochs, initial_epoch=getattr(args, 'initial_epoch', 0), callbacks=callbacks,
                 verbose=not args.no_progress)

@@ -12,7 +12,10 @@
                                                   CLIs use, f32 / bf16 logits, s = 0 / 0.1, and the ResNet-110 classifier step)
     python tools/bench_kernels.py image          (se_image_batch: a batch of 128 at the CUB preset (375 x 500 sources, shorter side 512,
                                                   crop 448) and at the NAB preset (about 768 x 1024 sources, random zoom 256-480, crop
-                                                  224): kernel time, host time, bytes over kernel time, next to the ResNet-50 step)"""
+                                                  224): kernel time, host time, bytes over kernel time, next to the ResNet-50 step)
+    python tools/bench_kernels.py adagrad        (se_adagrad_step over the flat buffers of ResNet-110-fc and ResNet-50, with and without the
+                                                  regulariser, next to the torch composition of the same update, and the ResNet-110-fc
+                                                  DeViSE training step next to the cosine-loss one)"""
 import argparse
 import os
 import sys
@@ -40,7 +43,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image"])
+                                     "center", "xent", "image", "adagrad"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -57,6 +60,8 @@ def main():
         return bench_xent()
     if args.what == "image":
         return bench_image()
+    if args.what == "adagrad":
+        return bench_adagrad()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -589,6 +594,109 @@ def bench_image(B=128, reps=20, stored=256):
     print("ResNet-50 training step, 224 x 224, 200 classes, batch %d, %s: %.2f ms/step = %.0f images/s; slowest batch composition "
           "(host + kernel) %.2f ms: the loader %s" % (B, r["dtype"], r["ms_per_step"], r["value"], worst,
                                                       "keeps up with the network" if worst < r["ms_per_step"] else "DOES NOT keep up: it sets images/s"))
+
+
+def bench_adagrad(reps=40, batch=20, steps=200):
+    """The Adagrad update (learn_devise.py): se_adagrad_step over the flat parameter / accumulator / gradient / L2 buffers engine.FlatState
+    builds for ResNet-110-fc (100 outputs) and ResNet-50 (1000 outputs), with and without the regulariser stream, next to the torch
+    composition of the same update on the same buffers with the learning rate in a device scalar (what a captured step would launch: g +=
+    l2 * p; a += g * g; p -= (g * lr) / (sqrt(a) + eps): 7 launches, 6 without the regulariser), the four timed alternately in one
+    process: `reps` windows of `batch` back-to-back calls each (HIP events around a window) after 3 warm-up calls, median / 10th / 90th
+    percentile of the per-call time.  Bytes: 3 streams in (4 with the regulariser) and 2 out, over the kernel's time, against the 6.29 TB/s
+    a float4 copy reaches on MI355X (8 TB/s spec); the ResNet-110-fc buffers (7 MB each) stay in the on-chip caches between calls, so their
+    rate is not an HBM rate.  Then one ResNet-110-fc training step (batch 128, fp32, HIP-graph replay) under the DeViSE loss with
+    Trainer(optimizer='adagrad') next to the cosine-loss step with SGD, the two timed alternately."""
+    sys.path.insert(0, os.path.join(ROOT, "semantic-embeddings_amd"))
+    import utils
+    import learn_devise as ld
+    from datasets import SyntheticGenerator
+    from engine import FlatState, Trainer
+    HBM = 6.29e12
+    lr, eps = 0.001, 1e-7
+
+    def windows(fns):
+        for f in fns:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(reps):
+            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(batch):
+                    f()
+                b.record()
+                torch.cuda.synchronize()
+                ts[k].append(a.elapsed_time(b) / batch * 1e3)
+        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
+
+    for arch, outputs in (("resnet-110-fc", 100), ("resnet-50", 1000)):
+        torch.manual_seed(0)
+        model = utils.build_network(outputs, arch, input_channels=3).cuda()
+        flat = FlatState(model, {id(p): model.regularizer for p in model.regularized_parameters()})
+        n = flat.total
+        p, a, l2 = flat.flat_p, flat.flat_v, flat.flat_l2
+        g = torch.randn(n, device="cuda") * 1e-2
+        lr_t = torch.full((), lr, device="cuda")
+
+        def kernel(l2):
+            return lambda: sehip.adagrad_step_(p, a, g, l2, lr=lr_t, epsilon=eps)
+
+        def composition(l2):
+            def f():
+                if l2 is not None:
+                    g.addcmul_(l2, p)
+                a.addcmul_(g, g)
+                p.sub_((g * lr_t).div_(a.sqrt().add_(eps)))
+            return f
+        k1, k0, t1, t0 = windows((kernel(l2), kernel(None), composition(l2), composition(None)))
+        assert bool(torch.isfinite(p).all())
+        for what, k, t, streams in (("with the regulariser", k1, t1, 6), ("without", k0, t0, 5)):
+            gbs = streams * 4.0 * n / (k[0] * 1e-6)
+            print("adagrad %s, %d floats per buffer (%.1f MB), %s: kernel %.1f us (%.1f-%.1f), torch composition %.1f us (%.1f-%.1f): x%.2f; "
+                  "the kernel moves %.0f MB = %.0f GB/s = %.1f%% of the HBM copy rate"
+                  % (arch, n, 4.0 * n / 1e6, what, k[0], k[1], k[2], t[0], t[1], t[2], t[0] / k[0], streams * 4.0 * n / 1e6, gbs / 1e9,
+                     100.0 * gbs / HBM), flush=True)
+        del model, flat, p, a, l2, g
+
+    E = np.load(os.path.join(ROOT, "tests", "golden", "embeddings.npz"))["cifar100_unitsphere"]
+    Ed = torch.from_numpy(E.astype(np.float32)).cuda()
+    trainers = {}
+    for name in ("cosine", "devise"):
+        torch.manual_seed(0)
+        model = utils.build_network(100, "resnet-110-fc", input_channels=3).cuda()
+        l2_of = {id(p): model.regularizer for p in model.regularized_parameters()}
+        if name == "cosine":
+            tr = Trainer(model, {"l2norm": (utils.CosineEmbeddingLoss(Ed), 1.0)}, {"l2norm": [utils.nn_accuracy(Ed, dot_prod_sim=True)]},
+                         lr=0.1, momentum=0.9, clipnorm=10.0, l2_of=l2_of, autocast_dtype=None, memory_format=torch.contiguous_format)
+        else:
+            losses, metrics = ld.build_losses(Ed, 0.1)
+            tr = Trainer(model, losses, metrics, lr=0.001, l2_of=l2_of, autocast_dtype=None, memory_format=torch.contiguous_format,
+                         optimizer="adagrad")
+        seq = SyntheticGenerator(100, 32, 3, 128 * 8, 128).train_sequence(128, shuffle=False)
+        batches = [seq[i] for i in range(8)]
+        assert tr.enable_graphs(*batches[0]), name
+        for i in range(10):
+            tr.train_step(*batches[i % 8], {})
+        trainers[name] = (tr, batches)
+    ms = {name: [] for name in trainers}
+    for _ in range(3):                       # alternate the two models: the same machine state for both
+        for name, (tr, batches) in trainers.items():
+            logs = {}
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(steps):
+                tr.train_step(*batches[i % 8], logs)
+            b.record()
+            torch.cuda.synchronize()
+            assert np.isfinite(float(logs["loss"]))
+            ms[name].append(a.elapsed_time(b) / steps)
+    for name, what in (("cosine", "cosine-loss step, SGD"), ("devise", "DeViSE step, fused Adagrad")):
+        step = float(np.median(ms[name]))
+        print("ResNet-110-fc %s, batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d steps; %s), "
+              "%.0f images/s" % (what, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
 
 
 if __name__ == "__main__":

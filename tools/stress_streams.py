@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Every retrieval / loss / input-pipeline entry point under two-stream contention: result of a call made while a second stream keeps the CUs busy
+"""Every retrieval / loss / optimizer / input-pipeline entry point under two-stream contention: result of a call made while a second stream keeps the CUs busy
 == result of the same call made alone, bit for bit.
 
 Round 4 found se_topk_rows returning unsorted rows whenever another stream's kernels shared its CUs (a work-group barrier compiled
@@ -57,6 +57,10 @@ img_dbuf = dev(img_buf)
 img_t = {k: (img_dbuf[a:b].view(torch.int64) if k == "src_off" else img_dbuf[a:b].view(shape)) for k, (a, b, shape) in img_views.items()}
 img_stats = (dev(np.float32([125.3, 129.7, 118.5])), dev(np.float32([57.0, 56.7, 68.4])))
 
+# one Adagrad step over 3,000,005 parameters (two trips of the grid-stride loop and a tail), regulariser and scale folded in
+ag_p, ag_a, ag_g = dev(f32(3000005)), dev(np.abs(f32(3000005))), dev(f32(3000005))
+ag_l2 = dev(np.full(3000005, 4e-4, dtype=np.float32))
+
 
 def as_tuple(r):
     return tuple(r) if isinstance(r, (tuple, list)) else (r,)
@@ -84,6 +88,7 @@ OPS = {
     "devise_ranking_loss": lambda: sehip.devise_ranking_loss(xb, yb, emb),
     "image_batch": lambda: sehip.image_batch(img_arena, img_t["src_off"], img_t["src_hw"], img_t["xmap"], img_t["xk"], img_t["ymap"], img_t["yk"],
                                              img_t["erase"], img_t["seed"], img_stats[0], img_stats[1]),
+    "adagrad_step_": lambda: (lambda p, acc: (sehip.adagrad_step_(p, acc, ag_g, ag_l2, lr=0.01, grad_scale=0.5), acc))(ag_p.clone(), ag_a.clone()),
 }
 SIDE = {
     "distance tiles": lambda: sehip.pairwise_dist(g20[:6000], g20[:6000]),
