@@ -186,6 +186,34 @@ int se_labelembed_loss_bwd(const float *out1, int64_t ld1, const float *out2, in
                            float *d_out2, int64_t ldd2, float *d_tar, int64_t lddt, se_stream_t stream);
 
 /*
+ * The same loss on the learned label-embedding table itself (the `labelembeddings` Embedding of
+ * learn_labelembedding.py:51-52) instead of a materialised gather of its rows, and the table's gradient.
+ *   table [C, C] f32 (ldtab >= C elements between rows); the `tar` row of sample i is
+ *   table + clamp(targets[i], 0, C - 1) * ldtab -- the clamp the loss applies to the label everywhere else.
+ *   fwd: loss_i and aux are bit for bit those of se_labelembed_loss_fwd on tar = table[clamp(targets)].
+ *   bwd: d_out1, d_out2 are bit for bit those of se_labelembed_loss_bwd on that gather; d_table [C, C] (lddtab >= C):
+ *        d_table[k, c] = +0, then, for every i with clamp(targets[i]) == k in INCREASING i, one float32 addition of the
+ *        value se_labelembed_loss_bwd writes to d_tar[i, c] (wt_i (softmax(table[k])_c - softmax(out2_i / tau)_c),
+ *        wt_i = g_i mask_i scale, the same operations and roundings).  Rows with wt_i == 0 are skipped (+0 + +-0 = +0).
+ *        Every row of d_table is written; the rows of classes the batch does not contain are +0.  No atomics, no
+ *        workspace, no host synchronisation: the bits do not depend on the launch geometry or on concurrent work.
+ *        Any of d_out1, d_out2, d_table may be NULL.  B == 0 writes a zero d_table and reads no other array.
+ * SE_LABELEMBED_GRID_CAP: most workgroups (of 4 samples each) the per-sample kernels of all four entry points launch;
+ *        larger batches stride.
+ */
+#define SE_LABELEMBED_GRID_CAP 4096
+int se_labelembed_table_loss_fwd(const float *out1, int64_t ld1, const float *out2, int64_t ld2,
+                                 const float *table, int64_t ldtab, const int64_t *targets, int64_t B,
+                                 int64_t C, float tau, float alpha, float beta, float *loss_i, float *aux,
+                                 se_stream_t stream);
+int se_labelembed_table_loss_bwd(const float *out1, int64_t ld1, const float *out2, int64_t ld2,
+                                 const float *table, int64_t ldtab, const int64_t *targets,
+                                 const float *grad_loss_i, float grad_scale, int64_t B, int64_t C,
+                                 float tau, float alpha, float beta, const float *aux, float *d_out1,
+                                 int64_t ldd1, float *d_out2, int64_t ldd2, float *d_table,
+                                 int64_t lddtab, se_stream_t stream);
+
+/*
  * DeViSE ranking loss on the class-embedding contraction, forward + backward.
  * Replaces: utils.devise_ranking_loss(embedding, margin)(y_true, y_pred)  (utils.py:103-122)
  *           loss_i = sum_c relu(margin - <y_true_i, y_pred_i> + (y_pred . E^T)[i, c]) - margin

@@ -14,7 +14,8 @@ from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, MET
 
 __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
-    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "labelembed_loss", "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
+    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
+    "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
     "adagrad_step_", "ADAGRAD_MAX_BLOCKS",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
@@ -437,6 +438,80 @@ class _LabelEmbedLoss(torch.autograd.Function):
 def labelembed_loss(out1, out2, tar, targets, tau=2.0, alpha=0.9, beta=0.5):
     """Per-sample label-embedding loss [B] (learn_labelembedding.py:21-37), differentiable w.r.t. out1, out2, tar."""
     return _LabelEmbedLoss.apply(out1, out2, tar, targets, tau, alpha, beta)
+
+
+LE_GRID_CAP = DEFINES["SE_LABELEMBED_GRID_CAP"]     # grid cap of the per-sample label-embedding kernels: 4 samples per workgroup
+
+
+class _LabelEmbedTableLoss(torch.autograd.Function):
+    """reference: labelembed_loss on ``tar = labelembeddings(targets)`` (learn_labelembedding.py:21-37, 51-54) and its TF-autodiff
+    backward, the gradient of the Embedding table included: se_labelembed_table_loss_fwd / _bwd read the table row of every sample
+    in place and reduce the table's gradient per class in batch order.  ``out2 is None``: ``out1`` is the packed [B, 2 C] tensor
+    ``out1 | out2`` and its gradient one [B, 2 C] buffer both halves are written into through their pitch."""
+
+    @staticmethod
+    def forward(ctx, out1, out2, table, targets, tau, alpha, beta):
+        require_gpu(out1, out2, table, targets)
+        packed = out2 is None
+        if packed:
+            whole = out1 if out1.dim() != 2 or out1.stride(1) == 1 else out1.contiguous()
+            if whole.dim() != 2 or whole.shape[1] % 2:
+                raise SehipError("the packed logits must be a [B, 2 C] tensor")
+            half = whole.shape[1] // 2
+            out1, out2 = whole[:, :half], whole[:, half:]
+        out1, out2, table = (t if t.dim() != 2 or t.stride(1) == 1 else t.contiguous() for t in (out1, out2, table))
+        ld1, ld2, ldtab = _f32_2d(out1, "out1", 1), _f32_2d(out2, "out2", 1), _f32_2d(table, "table", 1)
+        B, C = out1.shape
+        if out2.shape != (B, C) or table.shape != (C, C):
+            raise SehipError("out1 and out2 must share the shape [B, C] and the table must be [C, C]")
+        if targets.dtype != torch.int64 or targets.numel() != B or not targets.is_contiguous():
+            raise SehipError("targets must be a contiguous int64 [B] tensor")
+        loss_i = torch.empty((B,), dtype=torch.float32, device=out1.device)
+        aux = torch.empty((max(call("se_labelembed_aux_floats", B), 1),), dtype=torch.float32, device=out1.device)
+        call("se_labelembed_table_loss_fwd", out1, ld1, out2, ld2, table, ldtab, targets, B, C, float(tau), float(alpha), float(beta),
+             loss_i, aux)
+        ctx.save_for_backward(out1, out2, table, targets, aux)
+        ctx.hyper = (float(tau), float(alpha), float(beta), ld1, ld2, ldtab, packed)
+        return loss_i
+
+    @staticmethod
+    def backward(ctx, grad):
+        out1, out2, table, targets, aux = ctx.saved_tensors
+        tau, alpha, beta, ld1, ld2, ldtab, packed = ctx.hyper
+        B, C = out1.shape
+        grad = grad.contiguous().to(torch.float32)
+        need = ctx.needs_input_grad
+        both = d1 = d2 = dtab = None
+        ldd = C
+        if packed:
+            if need[0]:
+                both = torch.empty((B, 2 * C), dtype=torch.float32, device=out1.device)
+                d1, d2, ldd = both[:, :C], both[:, C:], 2 * C
+        else:
+            d1 = torch.empty((B, C), dtype=torch.float32, device=out1.device) if need[0] else None
+            d2 = torch.empty((B, C), dtype=torch.float32, device=out1.device) if need[1] else None
+        if need[2]:
+            dtab = torch.empty((C, C), dtype=torch.float32, device=out1.device)
+        call("se_labelembed_table_loss_bwd", out1, ld1, out2, ld2, table, ldtab, targets, grad, 0.0, B, C, tau, alpha, beta, aux,
+             d1, ldd, d2, ldd, dtab, C)
+        return (both if packed else d1), d2 if not packed else None, dtab, None, None, None, None
+
+
+def labelembed_table_loss(out1, out2, table, targets, tau=2.0, alpha=0.9, beta=0.5):
+    """Per-sample label-embedding loss [B] (learn_labelembedding.py:21-37) with ``tar`` read from the learned ``[C, C]`` float32
+    ``table`` (row ``clamp(targets[i], 0, C - 1)`` for sample i) instead of a gathered copy; differentiable w.r.t. ``out1``, ``out2``
+    and ``table``.  ``out1`` / ``out2`` [B, C] float32 need unit stride in the last dimension only (e.g. the column halves of one
+    [B, 2 C] tensor: their row pitch is passed through).  Loss and logit gradients are bit for bit those of ``labelembed_loss`` on
+    ``table[targets]``; the table gradient is the sum of that call's ``d_tar`` rows per class in batch order -- the same inputs give
+    the same bits (torch's embedding backward adds with atomics).  Only the inputs that require a gradient get one."""
+    return _LabelEmbedTableLoss.apply(out1, out2, table, targets, tau, alpha, beta)
+
+
+def labelembed_table_loss_packed(logits2, table, targets, tau=2.0, alpha=0.9, beta=0.5):
+    """``labelembed_table_loss(logits2[:, :C], logits2[:, C:], ...)`` for the packed head output ``logits2 = out1 | out2`` [B, 2 C]:
+    the same bits, but the gradient of ``logits2`` is ONE [B, 2 C] buffer that the kernel writes both halves of through their pitch
+    (slicing first makes autograd pad each half's gradient into a zero [B, 2 C] tensor and add the two)."""
+    return _LabelEmbedTableLoss.apply(logits2, None, table, targets, tau, alpha, beta)
 
 
 class _DeviseLoss(torch.autograd.Function):

@@ -1,4 +1,5 @@
-"""What the training command lines (learn_image_embeddings.py, learn_center_loss.py, learn_classifier.py, learn_devise.py) have in common: the shared
+"""What the training command lines (learn_image_embeddings.py, learn_center_loss.py, learn_classifier.py, learn_devise.py,
+learn_labelembedding.py) have in common: the shared
 flag runs, the process group, loading weights, the ``--finetune_init`` warm-up, the main fit and the dumps.  Plain functions that
 each script's ``main()`` calls in order; the model, the losses and what the feature dump holds stay in the scripts."""
 import json

@@ -15,7 +15,11 @@
                                                   224): kernel time, host time, bytes over kernel time, next to the ResNet-50 step)
     python tools/bench_kernels.py adagrad        (se_adagrad_step over the flat buffers of ResNet-110-fc and ResNet-50, with and without the
                                                   regulariser, next to the torch composition of the same update, and the ResNet-110-fc
-                                                  DeViSE training step next to the cosine-loss one)"""
+                                                  DeViSE training step next to the cosine-loss one)
+    python tools/bench_kernels.py labelembed     (label-embedding loss forward + backward on the learned table next to the composition it
+                                                  replaces -- Embedding gather, loss on the gathered rows, torch's embedding backward -- as
+                                                  bare kernels and through autograd, and the ResNet-110-fc label-embedding training step
+                                                  next to the classifier step)"""
 import argparse
 import os
 import sys
@@ -43,7 +47,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad"])
+                                     "center", "xent", "image", "adagrad", "labelembed"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -62,6 +66,8 @@ def main():
         return bench_image()
     if args.what == "adagrad":
         return bench_adagrad()
+    if args.what == "labelembed":
+        return bench_labelembed()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -519,6 +525,128 @@ def bench_xent(reps=60, batch=20, steps=200):
         step = float(np.median(ms[name]))
         print("ResNet-110 classifier step (%s head: loss + acc + acc5), batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d "
               "steps; %s), %.0f images/s" % (name, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
+
+
+def bench_labelembed(reps=60, batch=20, steps=200):
+    """Label-embedding loss (learn_labelembedding.py) on the learned [C, C] table: se_labelembed_table_loss_fwd / _bwd (loss, both logit
+    gradients and the fixed-order table gradient) next to the composition they replace -- the Embedding gather of the table rows,
+    se_labelembed_loss_fwd / _bwd on the gathered rows and torch's embedding backward into a dense [C, C] gradient (atomic adds) -- both
+    as calls on preallocated buffers and through autograd (forward, mean, backward), timed alternately in one process: per shape `reps`
+    windows of `batch` back-to-back calls each (HIP events around a window), median / 10th / 90th percentile of the per-call time.
+    Every second row has out2 right about its class (mask = 1), so half of the rows contribute to the table gradient.  Then one
+    ResNet-110-fc training step (batch 128, fp32, HIP-graph replay) of the label-embedding model next to the classifier's."""
+    import torch.nn.functional as F
+    from sehip._lib import call
+
+    def windows(fns):
+        for f in fns:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(reps):
+            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(batch):
+                    f()
+                b.record()
+                torch.cuda.synchronize()
+                ts[k].append(a.elapsed_time(b) / batch * 1e3)
+        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
+
+    for B, C in ((128, 100), (128, 1000), (256, 8142)):
+        rng = np.random.default_rng(B + C)
+        o1, o2 = (torch.from_numpy((rng.standard_normal((B, C)) * 2).astype(np.float32)).cuda() for _ in range(2))
+        y = torch.from_numpy(rng.integers(0, C, B)).cuda()
+        o2[torch.arange(0, B, 2, device="cuda"), y[::2]] += 7.0
+        table = torch.eye(C, device="cuda") + 0.1 * torch.randn(C, C, device="cuda")
+        g = torch.full((B,), 1.0 / B, device="cuda")
+        loss_i, aux = torch.empty(B, device="cuda"), torch.empty(call("se_labelembed_aux_floats", B), device="cuda")
+        loss_c, aux_c = torch.empty_like(loss_i), torch.empty_like(aux)
+        d1, d2, dtar, dtab = [torch.empty(B, C, device="cuda") for _ in range(3)] + [torch.empty(C, C, device="cuda")]
+        res = {}
+
+        def kernels():
+            call("se_labelembed_table_loss_fwd", o1, C, o2, C, table, C, y, B, C, 2.0, 0.9, 0.5, loss_i, aux)
+            call("se_labelembed_table_loss_bwd", o1, C, o2, C, table, C, y, g, 0.0, B, C, 2.0, 0.9, 0.5, aux, d1, C, d2, C, dtab, C)
+
+        def composed_kernels():
+            tar = F.embedding(y, table)
+            call("se_labelembed_loss_fwd", o1, C, o2, C, tar, C, y, B, C, 2.0, 0.9, 0.5, loss_c, aux_c)
+            call("se_labelembed_loss_bwd", o1, C, o2, C, tar, C, y, g, 0.0, B, C, 2.0, 0.9, 0.5, aux_c, d1, C, d2, C, dtar, C)
+            res["dtab"] = torch.ops.aten.embedding_dense_backward(dtar, y, C, -1, False)
+
+        a1, a2, ta = o1.clone().requires_grad_(True), o2.clone().requires_grad_(True), table.clone().requires_grad_(True)
+        c1, c2, tc = o1.clone().requires_grad_(True), o2.clone().requires_grad_(True), table.clone().requires_grad_(True)
+
+        def op():
+            a1.grad = a2.grad = ta.grad = None
+            sehip.labelembed_table_loss(a1, a2, ta, y).mean().backward()
+
+        def composed_op():
+            c1.grad = c2.grad = tc.grad = None
+            sehip.labelembed_loss(c1, c2, F.embedding(y, tc), y).mean().backward()
+        k, ck, o, co = windows((kernels, composed_kernels, op, composed_op))
+        parts = [timeit(f, reps)[0] * 1e3 for f in (
+            lambda: call("se_labelembed_table_loss_fwd", o1, C, o2, C, table, C, y, B, C, 2.0, 0.9, 0.5, loss_i, aux),
+            lambda: call("se_labelembed_table_loss_bwd", o1, C, o2, C, table, C, y, g, 0.0, B, C, 2.0, 0.9, 0.5, aux, d1, C, d2, C, None, 0),
+            lambda: call("se_labelembed_table_loss_bwd", o1, C, o2, C, table, C, y, g, 0.0, B, C, 2.0, 0.9, 0.5, aux, None, 0, None, 0, dtab, C))]
+        print("labelembed B=%d C=%d, one call each (median of %d; HIP events around one call): forward %.1f us, logit gradients %.1f us, "
+              "table gradient %.1f us (writes %.1f MB)" % (B, C, reps, parts[0], parts[1], parts[2], 4e-6 * C * C))
+        same = torch.equal(loss_i.view(torch.int32), loss_c.view(torch.int32))
+        diff = float((dtab - res["dtab"]).abs().max())
+        print("labelembed B=%d C=%d: table kernels %.1f us (%.1f-%.1f) vs gather + loss kernels + embedding backward %.1f us (%.1f-%.1f): "
+              "x%.2f; autograd op %.1f us (%.1f-%.1f) vs composed op %.1f us (%.1f-%.1f): x%.2f; loss bits equal %s, table gradients "
+              "differ by at most %.2e" % (B, C, k[0], k[1], k[2], ck[0], ck[1], ck[2], ck[0] / k[0], o[0], o[1], o[2], co[0], co[1], co[2],
+                                          co[0] / o[0], same, diff))
+
+    sys.path.insert(0, os.path.join(ROOT, "semantic-embeddings_amd"))
+    import utils
+    import learn_classifier as lc
+    import learn_labelembedding as ll
+    from datasets import SyntheticGenerator
+    from engine import Trainer
+    trainers = {}
+    for name in ("classifier", "labelembed"):
+        torch.manual_seed(0)
+        if name == "classifier":
+            model = lc.build_classifier(100, "resnet-110-fc", input_channels=3).cuda()
+            l2_of = {id(p): model.regularizer for p in model.regularized_parameters()}
+            losses, metrics = lc.build_losses(0.0)
+            transform, kw = None, {}
+        else:
+            base = utils.build_network(100, "resnet-110-fc", input_channels=3).cuda()
+            l2_of = {id(p): base.regularizer for p in base.regularized_parameters()}
+            model = ll.labelembed_model(base, 100).cuda()
+            losses, metrics = ll.build_losses(model)
+            transform, kw = ll.transform_trainer_inputs, {"num_classes": 100}
+        tr = Trainer(model, losses, metrics, lr=0.1, momentum=0.9, clipnorm=10.0, l2_of=l2_of, autocast_dtype=None,
+                     memory_format=torch.contiguous_format)
+        seq = SyntheticGenerator(100, 32, 3, 128 * 8, 128).train_sequence(128, shuffle=False, batch_transform=transform,
+                                                                          batch_transform_kwargs=kw)
+        batches = [seq[i] for i in range(8)]
+        assert tr.enable_graphs(*batches[0]), name
+        for i in range(10):
+            tr.train_step(*batches[i % 8], {})
+        trainers[name] = (tr, batches)
+    ms = {name: [] for name in trainers}
+    for _ in range(3):                       # alternate the two models: the same machine state for both
+        for name, (tr, batches) in trainers.items():
+            logs = {}
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(steps):
+                tr.train_step(*batches[i % 8], logs)
+            b.record()
+            torch.cuda.synchronize()
+            assert np.isfinite(float(logs["loss"]))
+            ms[name].append(a.elapsed_time(b) / steps)
+    for name in trainers:
+        step = float(np.median(ms[name]))
+        print("ResNet-110-fc %s step, batch 128, 100 classes, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d steps; %s), "
+              "%.0f images/s" % (name, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
 
 
 def bench_image(B=128, reps=20, stored=256):
