@@ -82,8 +82,6 @@ __global__ __launch_bounds__(AG_THREADS) void adagrad_step_kernel(float *__restr
 
 using namespace se;
 
-static inline bool ag_aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
 extern "C" int se_adagrad_step(float *p, float *accum, const float *g, const float *l2, int64_t n, float lr, const float *lr_dev,
                                float grad_scale, float epsilon, se_stream_t stream)
 {
@@ -91,7 +89,7 @@ extern "C" int se_adagrad_step(float *p, float *accum, const float *g, const flo
     if (!(epsilon >= 0.f)) return fail(SE_ERR_INVALID, "se_adagrad_step: epsilon %g must be >= 0", (double)epsilon);
     if (n == 0) return SE_OK;
     if (!p || !accum || !g) return fail(SE_ERR_INVALID, "se_adagrad_step: null pointer");
-    const bool vec = n >= AG_VEC && ag_aligned16(p) && ag_aligned16(accum) && ag_aligned16(g) && (!l2 || ag_aligned16(l2));
+    const bool vec = n >= AG_VEC && aligned16(p) && aligned16(accum) && aligned16(g) && (!l2 || aligned16(l2));
     const int64_t per_block = (int64_t)AG_THREADS * (vec ? AG_VEC : 1);
     int64_t blocks = (n + per_block - 1) / per_block;
     if (blocks > SE_ADAGRAD_MAX_BLOCKS) blocks = SE_ADAGRAD_MAX_BLOCKS;

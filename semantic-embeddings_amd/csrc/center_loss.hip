@@ -20,13 +20,6 @@ constexpr int CL_CHUNKS = 4;       // 64-label chunks whose loads are in flight 
 constexpr int CL_ROWS = 4;         // matched batch rows whose feature loads are in flight together
 
 template <bool BF16>
-__device__ __forceinline__ float cl_load(const void *x, int64_t off)
-{
-    if constexpr (BF16) return bf16_to_f32(((const uint16_t *)x)[off]);
-    else return ((const float *)x)[off];
-}
-
-template <bool BF16>
 __global__ __launch_bounds__(64 * CL_WAVES) void center_loss_centroid_grad_kernel(const void *__restrict__ x, int64_t ldx,
                                                                                   const int64_t *__restrict__ labels,
                                                                                   const float *__restrict__ cent, int64_t ldc,
@@ -57,8 +50,7 @@ __global__ __launch_bounds__(64 * CL_WAVES) void center_loss_centroid_grad_kerne
 #pragma unroll
             for (int j = 0; j < CL_CHUNKS; j++) {
                 const int64_t i = i0 + j * 64 + lane;
-                int64_t y = lab[j];
-                y = y < 0 ? 0 : (y >= C ? C - 1 : y);          // the gather's clamp (se_sqdist_loss_fwd / _bwd)
+                const int64_t y = clamp_label(lab[j], C);      // the gather's clamp (se_sqdist_loss_fwd / _bwd)
                 uint64_t hit = __ballot(i < B && y == k);
                 while (hit) {                                   // matched rows in ascending order, CL_ROWS of them loaded together
                     int64_t row[CL_ROWS];
@@ -76,7 +68,7 @@ __global__ __launch_bounds__(64 * CL_WAVES) void center_loss_centroid_grad_kerne
 #pragma unroll
                         for (int r = 0; r < CL_COLS; r++) {
                             const int64_t d = d0 + r * 64 + lane;
-                            v[q][r] = d < D ? cl_load<BF16>(x, row[q] * ldx + d) : 0.f;
+                            v[q][r] = d < D ? ld_elem<BF16>(x, row[q] * ldx + d) : 0.f;
                         }
                     }
 #pragma unroll
@@ -113,7 +105,7 @@ extern "C" int se_center_loss_centroid_grad(const void *x, int x_dtype, int64_t 
         return fail(SE_ERR_INVALID, "se_center_loss_centroid_grad: bad shape B=%lld D=%lld C=%lld", (long long)B, (long long)D, (long long)C);
     if (!dcent || !centroids || (B > 0 && (!x || !labels))) return fail(SE_ERR_INVALID, "se_center_loss_centroid_grad: null pointer");
     if (ldx < D || ldc < D || lddc < D) return fail(SE_ERR_INVALID, "se_center_loss_centroid_grad: leading dimension < D");
-    if (x_dtype != SE_DTYPE_F32 && x_dtype != SE_DTYPE_BF16) return fail(SE_ERR_INVALID, "se_center_loss_centroid_grad: bad dtype %d", x_dtype);
+    if (!is_float_dtype(x_dtype)) return fail(SE_ERR_INVALID, "se_center_loss_centroid_grad: bad dtype %d", x_dtype);
     const int64_t blocks = (C + CL_WAVES - 1) / CL_WAVES;
     if (blocks > 0x7FFFFFFF) return fail(SE_ERR_UNSUPPORTED, "se_center_loss_centroid_grad: C too large");
     hipStream_t s = (hipStream_t)stream;

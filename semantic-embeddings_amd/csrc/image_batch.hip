@@ -50,13 +50,6 @@ __device__ __forceinline__ float ib_noise(uint32_t seed, int uy, int ux, int c)
 }
 
 template <bool BF16>
-__device__ __forceinline__ void ib_store(void *out, int64_t off, float v)
-{
-    if constexpr (BF16) ((uint16_t *)out)[off] = f32_to_bf16(v);
-    else ((float *)out)[off] = v;
-}
-
-template <bool BF16>
 __global__ __launch_bounds__(IB_THREADS) void image_batch_kernel(const uint8_t *__restrict__ arena, int64_t arena_bytes,
                                                                  const int64_t *__restrict__ src_off, const int32_t *__restrict__ src_hw,
                                                                  const int32_t *__restrict__ xmap, const int32_t *__restrict__ xk,
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(IB_THREADS) void image_batch_kernel(const uint8_t *
     const int64_t off = src_off[b];
     if (h <= 0 || w <= 0 || off < 0 || off > arena_bytes || (int64_t)h * w * 3 > arena_bytes - off) {   // wave-uniform
         for (int idx = tid; idx < nrows * row_elems; idx += IB_THREADS)
-            ib_store<BF16>(out, ((b * ch + cy0) * (int64_t)cw) * 3 + idx, __uint_as_float(0x7FC00000u));
+            st_elem<BF16>(out, ((b * ch + cy0) * (int64_t)cw) * 3 + idx, __uint_as_float(0x7FC00000u));
         return;
     }
     const uint8_t *src = arena + off;
@@ -165,7 +158,7 @@ __global__ __launch_bounds__(IB_THREADS) void image_batch_kernel(const uint8_t *
                 for (int j = 0; j < n; j++) s += k[j] * (int)t[j * row_bytes];
                 val = lut[c * 256 + ib_clip8(s >> 22)];
             }
-            ib_store<BF16>(out, ((b * ch + cy) * (int64_t)cw) * 3 + e, val);
+            st_elem<BF16>(out, ((b * ch + cy) * (int64_t)cw) * 3 + e, val);
         }
         r0 = r1;
         if (r0 < nrows) wg_barrier();          // the next sub-band overwrites the tile
@@ -184,7 +177,7 @@ extern "C" int se_image_batch(const void *arena, int64_t arena_bytes, const int6
     if (B < 0 || ch <= 0 || cw <= 0 || Kx <= 0 || Ky <= 0 || arena_bytes < 0)
         return fail(SE_ERR_INVALID, "se_image_batch: bad shape B=%lld ch=%d cw=%d Kx=%d Ky=%d arena_bytes=%lld", (long long)B, ch, cw, Kx, Ky,
                     (long long)arena_bytes);
-    if (out_dtype != SE_DTYPE_F32 && out_dtype != SE_DTYPE_BF16) return fail(SE_ERR_INVALID, "se_image_batch: bad output dtype %d", out_dtype);
+    if (!is_float_dtype(out_dtype)) return fail(SE_ERR_INVALID, "se_image_batch: bad output dtype %d", out_dtype);
     if (B == 0) return SE_OK;
     if (!arena || !src_off || !src_hw || !xmap || !xk || !ymap || !yk || !erase || !seed || !mean || !std || !out)
         return fail(SE_ERR_INVALID, "se_image_batch: null pointer");

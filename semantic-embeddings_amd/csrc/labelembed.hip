@@ -35,13 +35,6 @@ constexpr int LT_COLS = 4;             // columns per lane: a wave owns 256 colu
 constexpr int LT_CHUNKS = 4;           // 64-label chunks whose loads are in flight together
 constexpr int LT_ROWS = 4;             // matched batch rows whose out2 loads are in flight together
 
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // aux[i] = { lse(out1), lse(out2), lse(tar), lse(out2 / tau), mask, A_i = -sum tau2 * log_softmax(tar), base_i, p2_y,
 //            S1 = sum_j clip(p1_j), R1 = sum_j 1{eps < p1_j < 1 - eps} p1_j, S2, R2 }
 // TABLE: `tar` is the [C, C] table and the row of a sample is the row of its (clamped) label; otherwise the [B, C] gather.
@@ -56,8 +49,7 @@ __global__ __launch_bounds__(256) void labelembed_fwd_kernel(const float *__rest
     const float inv_tau = 1.0f / tau;
     for (int64_t row = (int64_t)blockIdx.x * LE_ROWS_PER_BLOCK + wave; row < B; row += (int64_t)gridDim.x * LE_ROWS_PER_BLOCK) {
         const float *o1 = out1 + row * ld1, *o2 = out2 + row * ld2, *tr = tar + row * ldt;
-        int64_t y = targets[row];
-        y = y < 0 ? 0 : (y >= C ? C - 1 : y);
+        const int64_t y = clamp_label(targets[row], C);
         if constexpr (TABLE) tr = tar + y * ldt;
         // pass 1: maxima and the arg-max of out2 (first maximum, like K.argmax)
         float m1 = -INFINITY, m2 = -INFINITY, mt = -INFINITY;
@@ -71,13 +63,7 @@ __global__ __launch_bounds__(256) void labelembed_fwd_kernel(const float *__rest
         m1 = wave_max(m1);
         mt = wave_max(mt);
         const float m2w = wave_max(m2);
-        // lowest column holding the row maximum
-        int64_t cand = (m2 == m2w) ? am : C;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const int64_t o = __shfl_xor(cand, off, 64);
-            cand = o < cand ? o : cand;
-        }
+        const int64_t cand = wave_min((m2 == m2w) ? am : C);      // lowest column holding the row maximum
         // pass 2: exp-sums and the two weighted sums
         float s1 = 0.f, s2 = 0.f, st = 0.f, s2t = 0.f, w_t_o1 = 0.f, w_tau_t = 0.f;
         for (int64_t c = lane; c < C; c += WAVE) {
@@ -129,13 +115,7 @@ __global__ __launch_bounds__(256) void labelembed_finish_kernel(const float *__r
     __shared__ float part[256];
     float s = 0.f;
     for (int64_t i = threadIdx.x; i < B; i += 256) s += aux[i * LE_AUX + 4];
-    part[threadIdx.x] = s;
-    wg_barrier();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        wg_barrier();
-    }
-    const float scale = (float)B / (part[0] + 1e-8f);
+    const float scale = (float)B / (block_sum_256(s, part) + 1e-8f);
     if (threadIdx.x == 0) scale_out[0] = scale;
     for (int64_t i = threadIdx.x; i < B; i += 256) loss_i[i] = aux[i * LE_AUX + 6] + aux[i * LE_AUX + 5] * aux[i * LE_AUX + 4] * scale;
 }
@@ -158,8 +138,7 @@ __global__ __launch_bounds__(256) void labelembed_bwd_kernel(const float *__rest
     const float inv_tau = 1.0f / tau, sc = scale[0];
     for (int64_t row = (int64_t)blockIdx.x * LE_ROWS_PER_BLOCK + wave; row < B; row += (int64_t)gridDim.x * LE_ROWS_PER_BLOCK) {
         const float *o1 = out1 + row * ld1, *o2 = out2 + row * ld2, *tr = tar + row * ldt;
-        int64_t y = targets[row];
-        y = y < 0 ? 0 : (y >= C ? C - 1 : y);
+        const int64_t y = clamp_label(targets[row], C);
         if constexpr (TABLE) tr = tar + y * ldt;
         const float *r = aux + row * LE_AUX;
         const float lse1 = r[0], lse2 = r[1], lset = r[2], lse2t = r[3], mask = r[4], p2y = r[7];
@@ -211,8 +190,7 @@ __global__ __launch_bounds__(64 * LT_WAVES) void labelembed_table_grad_kernel(co
 #pragma unroll
         for (int j = 0; j < LT_CHUNKS; j++) {
             const int64_t i = i0 + j * 64 + lane;
-            int64_t y = lab[j];
-            y = y < 0 ? 0 : (y >= C ? C - 1 : y);
+            const int64_t y = clamp_label(lab[j], C);
             float wt = 0.f, lset = 0.f, lse2t = 0.f;                            // this lane's row, if it is one of class k
             if (i < B && y == k) {
                 const float *r = aux + i * LE_AUX;

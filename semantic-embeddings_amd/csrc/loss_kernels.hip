@@ -13,18 +13,12 @@
 // The kernels are HBM-bound: algorithmic bytes per row = D*s_x (x) + D*4 (emb row, L2-resident)
 // + D*4 (xhat) + 16.
 #include "se_common.h"
+#include "tile32.h"
 
 namespace se {
 
 constexpr int LOSS_ROWS_PER_BLOCK = 4;  // 4 waves = 256 threads
 constexpr float L2NORM_EPS = 1e-12f;    // tf.nn.l2_normalize default epsilon (TF 1.x)
-
-template <bool BF16>
-__device__ __forceinline__ float load_x(const void *row, int64_t d)
-{
-    if constexpr (BF16) return bf16_to_f32(((const uint16_t *)row)[d]);
-    else return ((const float *)row)[d];
-}
 
 // ss = sum x^2, dt = sum x * t  over one row, all 64 lanes get the totals.
 template <bool BF16>
@@ -40,13 +34,8 @@ __device__ __forceinline__ void row_reduce(const void *xrow, const float *trow, 
             for (int64_t i = lane; i < D / 8; i += WAVE) {
                 uint4 p = xv[i];
                 float4 t0 = tv[2 * i], t1 = tv[2 * i + 1];
-                uint32_t w[4] = {p.x, p.y, p.z, p.w};
                 float xs[8];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    xs[2 * j] = __uint_as_float(w[j] << 16);
-                    xs[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u);
-                }
+                unpack_bf16x8(p, xs);
                 float ts[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
@@ -65,7 +54,7 @@ __device__ __forceinline__ void row_reduce(const void *xrow, const float *trow, 
         }
     } else {
         for (int64_t i = lane; i < D; i += WAVE) {
-            float p = load_x<BF16>(xrow, i);
+            float p = ld_elem<BF16>(xrow, i);
             s = fmaf(p, p, s);
             t = fmaf(p, trow[i], t);
         }
@@ -85,8 +74,7 @@ __global__ __launch_bounds__(256) void cosine_loss_fwd_kernel(
     for (int64_t row = (int64_t)blockIdx.x * LOSS_ROWS_PER_BLOCK + wave; row < B;
          row += (int64_t)gridDim.x * LOSS_ROWS_PER_BLOCK) {
         const char *xrow = (const char *)x + row * ldx * (BF16 ? 2 : 4);
-        int64_t y = labels[row];
-        y = y < 0 ? 0 : (y >= C ? C - 1 : y);  // clamp like a safe gather; host validates
+        const int64_t y = clamp_label(labels[row], C);
         const float *trow = emb + y * lde;
         float ss, dt;
         row_reduce<BF16>(xrow, trow, D, vec_ok != 0, ss, dt);
@@ -105,26 +93,23 @@ __global__ __launch_bounds__(256) void cosine_loss_fwd_kernel(
                     ov[i] = make_float4(p.x * inv, p.y * inv, p.z * inv, p.w * inv);
                 }
             } else {
-                for (int64_t i = lane; i < D; i += WAVE) orow[i] = load_x<BF16>(xrow, i) * inv;
+                for (int64_t i = lane; i < D; i += WAVE) orow[i] = ld_elem<BF16>(xrow, i) * inv;
             }
         }
     }
 }
 
-// Deterministic mean of n floats: one 256-thread block, fixed tree.
+// Deterministic mean of n floats: one 256-thread block, fixed tree; +0 for n = 0.
 __global__ __launch_bounds__(256) void mean_kernel(const float *__restrict__ v, int64_t n, float *__restrict__ out)
 {
     __shared__ float part[256];
     float s = 0.f;
     for (int64_t i = threadIdx.x; i < n; i += 256) s += v[i];
-    part[threadIdx.x] = s;
-    wg_barrier();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        wg_barrier();
-    }
-    if (threadIdx.x == 0) out[0] = part[0] / (float)n;
+    const float total = block_sum_256(s, part);
+    if (threadIdx.x == 0) out[0] = n > 0 ? total / (float)n : 0.f;
 }
+
+void launch_mean(const float *v, int64_t n, float *out, hipStream_t s) { hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, v, n, out); }
 
 template <bool BF16, bool DX_BF16>
 __global__ __launch_bounds__(256) void cosine_loss_bwd_kernel(
@@ -136,8 +121,7 @@ __global__ __launch_bounds__(256) void cosine_loss_bwd_kernel(
     for (int64_t row = (int64_t)blockIdx.x * LOSS_ROWS_PER_BLOCK + wave; row < B;
          row += (int64_t)gridDim.x * LOSS_ROWS_PER_BLOCK) {
         const char *xrow = (const char *)x + row * ldx * (BF16 ? 2 : 4);
-        int64_t y = labels[row];
-        y = y < 0 ? 0 : (y >= C ? C - 1 : y);
+        const int64_t y = clamp_label(labels[row], C);
         const float *trow = emb + y * lde;
         float ss, dt;
         row_reduce<BF16>(xrow, trow, D, vec_ok != 0, ss, dt);
@@ -151,9 +135,8 @@ __global__ __launch_bounds__(256) void cosine_loss_bwd_kernel(
         const float c_x = -inv * proj * inv;
         char *drow = (char *)dx + row * lddx * (DX_BF16 ? 2 : 4);
         for (int64_t i = lane; i < D; i += WAVE) {
-            float v = fmaf(c_t, trow[i], c_x * load_x<BF16>(xrow, i));
-            if constexpr (DX_BF16) ((uint16_t *)drow)[i] = f32_to_bf16(v);
-            else ((float *)drow)[i] = v;
+            float v = fmaf(c_t, trow[i], c_x * ld_elem<BF16>(xrow, i));
+            st_elem<DX_BF16>(drow, i, v);
         }
     }
 }
@@ -169,8 +152,7 @@ __global__ __launch_bounds__(256) void sqdist_loss_fwd_kernel(const void *__rest
     const int wave = threadIdx.x >> 6, lane = lane_id();
     for (int64_t row = (int64_t)blockIdx.x * LOSS_ROWS_PER_BLOCK + wave; row < B; row += (int64_t)gridDim.x * LOSS_ROWS_PER_BLOCK) {
         const char *xrow = (const char *)x + row * ldx * (BF16 ? 2 : 4);
-        int64_t y = labels[row];
-        y = y < 0 ? 0 : (y >= C ? C - 1 : y);
+        const int64_t y = clamp_label(labels[row], C);
         const float *trow = emb + y * lde;
         float s = 0.f;
         if (vec_ok && !BF16) {
@@ -182,7 +164,7 @@ __global__ __launch_bounds__(256) void sqdist_loss_fwd_kernel(const void *__rest
             }
         } else {
             for (int64_t i = lane; i < D; i += WAVE) {
-                const float a = load_x<BF16>(xrow, i) - trow[i];
+                const float a = ld_elem<BF16>(xrow, i) - trow[i];
                 s = fmaf(a, a, s);
             }
         }
@@ -202,15 +184,13 @@ __global__ __launch_bounds__(256) void sqdist_loss_bwd_kernel(const void *__rest
     const int wave = threadIdx.x >> 6, lane = lane_id();
     for (int64_t row = (int64_t)blockIdx.x * LOSS_ROWS_PER_BLOCK + wave; row < B; row += (int64_t)gridDim.x * LOSS_ROWS_PER_BLOCK) {
         const char *xrow = (const char *)x + row * ldx * (BF16 ? 2 : 4);
-        int64_t y = labels[row];
-        y = y < 0 ? 0 : (y >= C ? C - 1 : y);
+        const int64_t y = clamp_label(labels[row], C);
         const float *trow = emb + y * lde;
         const float w2 = 2.0f * (grad_loss_i ? grad_loss_i[row] : grad_scale);
         char *drow = (char *)dx + row * lddx * (DX_BF16 ? 2 : 4);
         for (int64_t i = lane; i < D; i += WAVE) {
-            const float v = w2 * (load_x<BF16>(xrow, i) - trow[i]);
-            if constexpr (DX_BF16) ((uint16_t *)drow)[i] = f32_to_bf16(v);
-            else ((float *)drow)[i] = v;
+            const float v = w2 * (ld_elem<BF16>(xrow, i) - trow[i]);
+            st_elem<DX_BF16>(drow, i, v);
         }
     }
 }
@@ -227,7 +207,7 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const void *__restrict_
          row += (int64_t)gridDim.x * LOSS_ROWS_PER_BLOCK) {
         const char *xrow = (const char *)x + row * ldx * (BF16 ? 2 : 4);
         float s = 0.f;
-        for (int64_t i = lane; i < D; i += WAVE) { const float p = load_x<BF16>(xrow, i); s = fmaf(p, p, s); }
+        for (int64_t i = lane; i < D; i += WAVE) { const float p = ld_elem<BF16>(xrow, i); s = fmaf(p, p, s); }
         s = wave_sum(s);
         const float inv = 1.0f / sqrtf(fmaxf(s, L2NORM_EPS));
         if (lane == 0) {
@@ -235,7 +215,7 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const void *__restrict_
             if (sumsq) sumsq[row] = s;
         }
         float *orow = xhat + row * ldo;
-        for (int64_t i = lane; i < D; i += WAVE) orow[i] = load_x<BF16>(xrow, i) * inv;
+        for (int64_t i = lane; i < D; i += WAVE) orow[i] = ld_elem<BF16>(xrow, i) * inv;
     }
 }
 
@@ -263,6 +243,8 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float *__restrict
 // nn_accuracy: one wave owns a strip of 32 samples and walks all classes in tiles of 32 with
 // v_mfma_f32_32x32x2_f32.  Operands are staged through LDS in K-chunks of 64, stored with even
 // and odd k de-interleaved so that lanes 0-31 (k = 2t) and 32-63 (k = 2t+1) each read 16 B.
+// (The same tile as tile32.h, which the DeViSE kernels use; this kernel keeps its own staging and chunk loop: every spelling
+// through the shared helpers measured 1 - 3 us per call slower, profiles/loss_head_refactor_equivalence.txt section 3.)
 // Instead of materialising top-k, the metric uses the equivalent counting form
 //     acc = (#within >= 1) && (#better < k)
 // with  within = |score - true| < 1e-6,  better = score beyond true by >= 1e-6   (utils.py:84-95).
@@ -338,8 +320,7 @@ __global__ __launch_bounds__(64) void nn_accuracy_kernel(
         const int64_t r = row0 + col;
         float t = 0.f, pn = 0.f;
         if (r < B) {
-            int64_t y = labels[r];
-            y = y < 0 ? 0 : (y >= C ? C - 1 : y);
+            const int64_t y = clamp_label(labels[r], C);
             const float *p = yp + r * ldp, *e = emb + y * lde;
             if (hi == 0) {
                 float s = 0.f;
@@ -414,7 +395,7 @@ __global__ __launch_bounds__(64) void nn_accuracy_kernel(
         const int64_t c = c0 + col;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int lr = (r & 3) + 8 * (r >> 2) + 4 * hi;  // row of this accumulator register
+            const int lr = tile32::acc_row(r, hi);
             float sc = acc[r];
             if (!dot_prod_sim) sc = (sPn[lr] + sCn[col]) - 2.0f * sc;
             const bool valid = (c < C) && (row0 + lr < B);
@@ -442,7 +423,7 @@ __global__ __launch_bounds__(64) void nn_accuracy_kernel(
                                            : (ov < best_v[r] || (ov == best_v[r] && oc < best_c[r]));
             if (take) { best_v[r] = ov; best_c[r] = oc; }
         }
-        const int lr = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        const int lr = tile32::acc_row(r, hi);
         if (col == 0 && row0 + lr < B) {
             if (gridDim.y == 1) {
                 acc_out[row0 + lr] = (n_within[r] >= 1 && n_better[r] < k) ? 1.0f : 0.0f;
@@ -473,8 +454,6 @@ __global__ __launch_bounds__(256) void nn_accuracy_finish_kernel(const uint32_t 
     if (best_out) best_out[r] = 0x7FFFFFFF - (int32_t)(uint32_t)(part_best[r] & 0xFFFFFFFFull);
 }
 
-static inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
-
 }  // namespace se
 
 using namespace se;
@@ -488,19 +467,18 @@ extern "C" int se_cosine_loss_fwd(const void *x, int x_dtype, int64_t ldx, const
     if (B == 0) return SE_OK;
     if (!x || !labels || !emb || !loss_i) return fail(SE_ERR_INVALID, "se_cosine_loss_fwd: null pointer");
     if (ldx < D || lde < D || (xhat && ldxhat < D)) return fail(SE_ERR_INVALID, "se_cosine_loss_fwd: leading dimension < D");
-    if (x_dtype != SE_DTYPE_F32 && x_dtype != SE_DTYPE_BF16) return fail(SE_ERR_INVALID, "se_cosine_loss_fwd: bad dtype %d", x_dtype);
+    if (!is_float_dtype(x_dtype)) return fail(SE_ERR_INVALID, "se_cosine_loss_fwd: bad dtype %d", x_dtype);
     hipStream_t s = (hipStream_t)stream;
     const bool bf = x_dtype == SE_DTYPE_BF16;
     const int vq = bf ? 8 : 4;
     const int vec_ok = (D % vq == 0) && (ldx % vq == 0) && (lde % 4 == 0) && aligned16(x) && aligned16(emb) &&
                        (!xhat || ((ldxhat % 4 == 0) && aligned16(xhat)));
-    int64_t blocks = (B + LOSS_ROWS_PER_BLOCK - 1) / LOSS_ROWS_PER_BLOCK;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (bf) hipLaunchKernelGGL(cosine_loss_fwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, xhat, ldxhat, inv_norm, loss_i, vec_ok);
-    else hipLaunchKernelGGL(cosine_loss_fwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, xhat, ldxhat, inv_norm, loss_i, vec_ok);
+    const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
+    if (bf) hipLaunchKernelGGL(cosine_loss_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, xhat, ldxhat, inv_norm, loss_i, vec_ok);
+    else hipLaunchKernelGGL(cosine_loss_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, xhat, ldxhat, inv_norm, loss_i, vec_ok);
     SE_LAUNCH_CHECK();
     if (loss_mean) {
-        hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, (const float *)loss_i, B, loss_mean);
+        launch_mean(loss_i, B, loss_mean, s);
         SE_LAUNCH_CHECK();
     }
     return SE_OK;
@@ -517,17 +495,13 @@ extern "C" int se_cosine_loss_bwd(const void *x, int x_dtype, int64_t ldx, const
     if (ldx < D || lde < D || lddx < D) return fail(SE_ERR_INVALID, "se_cosine_loss_bwd: leading dimension < D");
     hipStream_t s = (hipStream_t)stream;
     const bool bf = x_dtype == SE_DTYPE_BF16, dbf = dx_dtype == SE_DTYPE_BF16;
-    if ((x_dtype != SE_DTYPE_F32 && !bf) || (dx_dtype != SE_DTYPE_F32 && !dbf)) return fail(SE_ERR_INVALID, "se_cosine_loss_bwd: bad dtype");
+    if (!is_float_dtype(x_dtype) || !is_float_dtype(dx_dtype)) return fail(SE_ERR_INVALID, "se_cosine_loss_bwd: bad dtype");
     const int vq = bf ? 8 : 4;
     const int vec_ok = (D % vq == 0) && (ldx % vq == 0) && (lde % 4 == 0) && aligned16(x) && aligned16(emb);
-    int64_t blocks = (B + LOSS_ROWS_PER_BLOCK - 1) / LOSS_ROWS_PER_BLOCK;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-#define SE_BWD(XB, DB) hipLaunchKernelGGL((cosine_loss_bwd_kernel<XB, DB>), dim3((unsigned)blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, grad_loss_i, grad_scale, B, D, C, dx, lddx, vec_ok)
-    if (bf && dbf) SE_BWD(true, true);
-    else if (bf) SE_BWD(true, false);
-    else if (dbf) SE_BWD(false, true);
-    else SE_BWD(false, false);
-#undef SE_BWD
+    const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
+    dispatch_bools(bf, dbf, [&](auto XB, auto DB) {
+        hipLaunchKernelGGL((cosine_loss_bwd_kernel<XB(), DB()>), dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, grad_loss_i, grad_scale, B, D, C, dx, lddx, vec_ok);
+    });
     SE_LAUNCH_CHECK();
     return SE_OK;
 }
@@ -539,17 +513,16 @@ extern "C" int se_sqdist_loss_fwd(const void *x, int x_dtype, int64_t ldx, const
     if (B == 0) return SE_OK;
     if (!x || !labels || !emb || !loss_i) return fail(SE_ERR_INVALID, "se_sqdist_loss_fwd: null pointer");
     if (ldx < D || lde < D) return fail(SE_ERR_INVALID, "se_sqdist_loss_fwd: leading dimension < D");
-    if (x_dtype != SE_DTYPE_F32 && x_dtype != SE_DTYPE_BF16) return fail(SE_ERR_INVALID, "se_sqdist_loss_fwd: bad dtype %d", x_dtype);
+    if (!is_float_dtype(x_dtype)) return fail(SE_ERR_INVALID, "se_sqdist_loss_fwd: bad dtype %d", x_dtype);
     hipStream_t s = (hipStream_t)stream;
     const bool bf = x_dtype == SE_DTYPE_BF16;
     const int vec_ok = !bf && (D % 4 == 0) && (ldx % 4 == 0) && (lde % 4 == 0) && aligned16(x) && aligned16(emb);
-    int64_t blocks = (B + LOSS_ROWS_PER_BLOCK - 1) / LOSS_ROWS_PER_BLOCK;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (bf) hipLaunchKernelGGL(sqdist_loss_fwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, loss_i, dist_i, vec_ok);
-    else hipLaunchKernelGGL(sqdist_loss_fwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, loss_i, dist_i, vec_ok);
+    const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
+    if (bf) hipLaunchKernelGGL(sqdist_loss_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, loss_i, dist_i, vec_ok);
+    else hipLaunchKernelGGL(sqdist_loss_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, loss_i, dist_i, vec_ok);
     SE_LAUNCH_CHECK();
     if (loss_mean) {
-        hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, s, (const float *)loss_i, B, loss_mean);
+        launch_mean(loss_i, B, loss_mean, s);
         SE_LAUNCH_CHECK();
     }
     return SE_OK;
@@ -565,33 +538,21 @@ extern "C" int se_sqdist_loss_bwd(const void *x, int x_dtype, int64_t ldx, const
     if (ldx < D || lde < D || lddx < D) return fail(SE_ERR_INVALID, "se_sqdist_loss_bwd: leading dimension < D");
     hipStream_t s = (hipStream_t)stream;
     const bool bf = x_dtype == SE_DTYPE_BF16, dbf = dx_dtype == SE_DTYPE_BF16;
-    if ((x_dtype != SE_DTYPE_F32 && !bf) || (dx_dtype != SE_DTYPE_F32 && !dbf)) return fail(SE_ERR_INVALID, "se_sqdist_loss_bwd: bad dtype");
-    int64_t blocks = (B + LOSS_ROWS_PER_BLOCK - 1) / LOSS_ROWS_PER_BLOCK;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-#define SE_BWD(XB, DB) hipLaunchKernelGGL((sqdist_loss_bwd_kernel<XB, DB>), dim3((unsigned)blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, grad_loss_i, grad_scale, B, D, C, dx, lddx)
-    if (bf && dbf) SE_BWD(true, true);
-    else if (bf) SE_BWD(true, false);
-    else if (dbf) SE_BWD(false, true);
-    else SE_BWD(false, false);
-#undef SE_BWD
+    if (!is_float_dtype(x_dtype) || !is_float_dtype(dx_dtype)) return fail(SE_ERR_INVALID, "se_sqdist_loss_bwd: bad dtype");
+    const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
+    dispatch_bools(bf, dbf, [&](auto XB, auto DB) {
+        hipLaunchKernelGGL((sqdist_loss_bwd_kernel<XB(), DB()>), dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, grad_loss_i, grad_scale, B, D, C, dx, lddx);
+    });
     SE_LAUNCH_CHECK();
     return SE_OK;
 }
 
-// class tiles (of 32) one workgroup walks: all of them while that still fills the chip or the class set is small, else slices
-static int nn_acc_tiles_per_block(int64_t B, int64_t C)
-{
-    const int64_t tiles = (C + 31) / 32, sample_blocks = (B + 31) / 32;
-    if (tiles <= 4 || sample_blocks * 1 >= 1024) return (int)tiles;
-    int64_t slices = 1024 / sample_blocks;                  // aim for ~1024 waves
-    if (slices > tiles) slices = tiles;
-    return (int)((tiles + slices - 1) / slices);
-}
+constexpr int NN_ACC_MIN_TILES = 4;     // up to 4 class tiles: one wave walks them all (tile32::tiles_per_block)
 
 extern "C" int64_t se_nn_accuracy_workspace_bytes(int64_t B, int64_t C)
 {
     if (B <= 0 || C <= 0) return 0;
-    return nn_acc_tiles_per_block(B, C) * 32 >= C ? 0 : B * 16;      // per sample: two counters + one ordered word
+    return tile32::tiles_per_block(B, C, NN_ACC_MIN_TILES) * 32 >= C ? 0 : B * 16;      // per sample: two counters + one ordered word
 }
 
 extern "C" int se_nn_accuracy(const float *y_pred, int64_t ldp, const int64_t *labels, const float *emb,
@@ -608,7 +569,7 @@ extern "C" int se_nn_accuracy(const float *y_pred, int64_t ldp, const int64_t *l
     if (need > 0 && (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 7)))
         return fail(SE_ERR_WORKSPACE, "se_nn_accuracy: needs %lld bytes of 8-byte aligned workspace (se_nn_accuracy_workspace_bytes)", (long long)need);
     hipStream_t s = (hipStream_t)stream;
-    const int tpb = nn_acc_tiles_per_block(B, C);
+    const int tpb = tile32::tiles_per_block(B, C, NN_ACC_MIN_TILES);
     const int64_t slices = ((C + 31) / 32 + tpb - 1) / tpb;
     unsigned long long *part_best = (unsigned long long *)workspace;
     uint32_t *part_cnt = need > 0 ? (uint32_t *)((char *)workspace + B * 8) : nullptr;
@@ -629,10 +590,9 @@ extern "C" int se_l2norm_fwd(const void *x, int x_dtype, int64_t ldx, int64_t B,
     if (B < 0 || D <= 0) return fail(SE_ERR_INVALID, "se_l2norm_fwd: bad shape");
     if (B == 0) return SE_OK;
     if (!x || !xhat || ldx < D || ldxhat < D) return fail(SE_ERR_INVALID, "se_l2norm_fwd: bad argument");
-    int64_t blocks = (B + LOSS_ROWS_PER_BLOCK - 1) / LOSS_ROWS_PER_BLOCK;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (x_dtype == SE_DTYPE_BF16) hipLaunchKernelGGL(l2norm_fwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, B, D, xhat, ldxhat, inv_norm, sumsq);
-    else if (x_dtype == SE_DTYPE_F32) hipLaunchKernelGGL(l2norm_fwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, B, D, xhat, ldxhat, inv_norm, sumsq);
+    const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
+    if (x_dtype == SE_DTYPE_BF16) hipLaunchKernelGGL(l2norm_fwd_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, B, D, xhat, ldxhat, inv_norm, sumsq);
+    else if (x_dtype == SE_DTYPE_F32) hipLaunchKernelGGL(l2norm_fwd_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, B, D, xhat, ldxhat, inv_norm, sumsq);
     else return fail(SE_ERR_INVALID, "se_l2norm_fwd: bad dtype %d", x_dtype);
     SE_LAUNCH_CHECK();
     return SE_OK;
@@ -644,9 +604,8 @@ extern "C" int se_l2norm_bwd(const float *grad, int64_t ldg, const float *xhat, 
     if (B < 0 || D <= 0) return fail(SE_ERR_INVALID, "se_l2norm_bwd: bad shape");
     if (B == 0) return SE_OK;
     if (!grad || !xhat || !inv_norm || !sumsq || !dx || ldg < D || ldxhat < D || lddx < D) return fail(SE_ERR_INVALID, "se_l2norm_bwd: bad argument");
-    int64_t blocks = (B + LOSS_ROWS_PER_BLOCK - 1) / LOSS_ROWS_PER_BLOCK;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad, ldg, xhat, ldxhat, inv_norm, sumsq, B, D, dx, lddx);
+    const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
+    hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grad, ldg, xhat, ldxhat, inv_norm, sumsq, B, D, dx, lddx);
     SE_LAUNCH_CHECK();
     return SE_OK;
 }

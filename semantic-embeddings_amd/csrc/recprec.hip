@@ -173,13 +173,6 @@ __global__ __launch_bounds__(RP_THREADS) void relpos_kernel(const RT *__restrict
     }
 }
 
-__device__ __forceinline__ double wave_max_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
 // AP of every query: (1 / R) sum_j j / p_j -- one wave per query, a fixed butterfly
 __global__ __launch_bounds__(RP_THREADS) void rp_ap_kernel(const int32_t *__restrict__ hit_pos, const int64_t *__restrict__ hit_off, int64_t Q,
                                                            double *__restrict__ ap)
@@ -190,8 +183,7 @@ __global__ __launch_bounds__(RP_THREADS) void rp_ap_kernel(const int32_t *__rest
         const int R = (int)(hit_off[q + 1] - off);
         double s = 0.0;
         for (int j = lane + 1; j <= R; j += WAVE) s += (double)j / (double)hit_pos[off + j - 1];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        s = wave_sum(s);
         if (lane == 0) ap[q] = R > 0 ? s / (double)R : 0.0;
     }
 }
@@ -263,7 +255,7 @@ __global__ __launch_bounds__(RP_THREADS) void rp_bin_kernel(const int32_t *__res
             const int end = jhi <= Rq ? jhi : Rq + 1;
             double v = 0.0;
             for (int j = jlo + lane; j < end; j += WAVE) v = fmax(v, (double)j / (double)hit_pos[off + j - 1]);
-            v = wave_max_f64(v);
+            v = wave_max(v);
             const bool has = (end > jlo) || (b == 0 && Rq > 0 && hit_pos[off] > 1);
             if (has) { sum += v; count++; }
         }

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "../../include/sehip.h"
 
@@ -17,6 +18,9 @@ int fail(int code, const char *fmt, ...);
 // compute units of the current device (256 when the query fails), read once per process: one process drives one GPU model.
 // (Hidden: an internal helper, not part of the library's exported symbols.)
 __attribute__((visibility("hidden"))) int num_cus();
+
+// out[0] = mean of v[0 .. n) in a fixed order (one 256-thread block; +0 for n = 0), on stream s (loss_kernels.hip; hidden like num_cus)
+__attribute__((visibility("hidden"))) void launch_mean(const float *v, int64_t n, float *out, hipStream_t s);
 
 // Phase timing (se_phase_timing / se_phase_timing_read, include/sehip.h): when switched on, multi-kernel entry points record a HIP
 // event on their stream behind each phase.  Off (the default): one relaxed atomic load per mark.
@@ -87,14 +91,106 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f)
     return (uint16_t)(u >> 16);
 }
 
-__device__ __forceinline__ float wave_sum(float v)
+// Wave-wide butterflies (every lane gets the result); T = float / int / int64_t / double
+template <class T>
+__device__ __forceinline__ T wave_sum(T v)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
 
+template <class T>
+__device__ __forceinline__ T wave_max(T v)      // floating point: fmax (a NaN loses against a number)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+template <class T>
+__device__ __forceinline__ T wave_min(T v)      // integers
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const T o = __shfl_xor(v, off, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+
+// Sum of one value per thread of a 256-thread workgroup in a fixed order (thread t adds part[t + off], off = 128 ... 1); every thread
+// gets the total.  part: 256 floats of LDS.
+__device__ __forceinline__ float block_sum_256(float v, float *part)
+{
+    part[threadIdx.x] = v;
+    wg_barrier();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+        wg_barrier();
+    }
+    return part[0];
+}
+
+// element i of a float32 / bf16 array as float32, and its store (bf16: round to nearest even)
+template <bool BF16>
+__device__ __forceinline__ float ld_elem(const void *p, int64_t i)
+{
+    if constexpr (BF16) return bf16_to_f32(((const uint16_t *)p)[i]);
+    else return ((const float *)p)[i];
+}
+
+template <bool BF16>
+__device__ __forceinline__ void st_elem(void *p, int64_t i, float v)
+{
+    if constexpr (BF16) ((uint16_t *)p)[i] = f32_to_bf16(v);
+    else ((float *)p)[i] = v;
+}
+
+// the 8 bf16 values of one 16-byte load, in memory order
+__device__ __forceinline__ void unpack_bf16x8(uint4 p, float *v)
+{
+    const uint32_t w[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        v[2 * k] = __uint_as_float(w[k] << 16);
+        v[2 * k + 1] = __uint_as_float(w[k] & 0xFFFF0000u);
+    }
+}
+
+// class label as a safe gather index: clamped to [0, C - 1] (the hosts validate; the kernels never read out of bounds).  C: int or int64_t
+template <class TC>
+__device__ __forceinline__ int64_t clamp_label(int64_t y, TC C) { return y < 0 ? 0 : (y >= C ? C - 1 : y); }
+
+// ---- host helpers of the entry points ----
+inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+inline bool aligned16(const void *p, int64_t ld, int elem_bytes) { return aligned16(p) && (ld * elem_bytes) % 16 == 0; }   // base and row pitch
+inline bool is_float_dtype(int code) { return code == SE_DTYPE_F32 || code == SE_DTYPE_BF16; }
+// grid of a kernel whose workgroups take rows_per_block rows at a time and stride over the rest: ceil(B / rows_per_block), capped
+inline unsigned row_blocks(int64_t B, int rows_per_block, int64_t cap)
+{
+    const int64_t blocks = (B + rows_per_block - 1) / rows_per_block;
+    return (unsigned)(blocks > cap ? cap : blocks);
+}
+// f(std::bool_constant<b0>{}, ...): run-time flags to template arguments, every combination instantiated
+template <class F>
+inline void dispatch_bools(bool b0, F f)
+{
+    if (b0) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+inline void dispatch_bools(bool b0, bool b1, F f)
+{
+    dispatch_bools(b0, [&](auto c0) { dispatch_bools(b1, [&](auto c1) { f(c0, c1); }); });
+}
+template <class F>
+inline void dispatch_bools(bool b0, bool b1, bool b2, F f)
+{
+    dispatch_bools(b0, [&](auto c0) { dispatch_bools(b1, b2, [&](auto c1, auto c2) { f(c0, c1, c2); }); });
+}
 
 // K-block list of the canonical dot product: the FMA chain restarts per block, block sums are added in order
 constexpr int SE_MAX_KB = 16;

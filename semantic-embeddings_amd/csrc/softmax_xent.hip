@@ -37,26 +37,13 @@ constexpr int XE_WAVE_NV = 16;             // values per lane of the wave path: 
 constexpr int XE_BLOCK_NV = 32;            // values per thread of the workgroup path: C <= 256 * 32
 constexpr int XE_WAVE_MAX_C = 64 * XE_WAVE_NV, XE_BLOCK_MAX_C = 256 * XE_BLOCK_NV;
 
-template <bool BF16>
-__device__ __forceinline__ float xe_ld(const void *row, int64_t c)
-{
-    if constexpr (BF16) return bf16_to_f32(((const uint16_t *)row)[c]);
-    else return ((const float *)row)[c];
-}
-
 // E consecutive values from column c0 (16-byte aligned address): E = 4 or 8 float32 (one or two 16-byte loads), E = 8 bf16 (one)
 template <bool BF16, int E>
 __device__ __forceinline__ void xe_ld_vec(const void *row, int64_t c0, float *v)
 {
     if constexpr (BF16) {
         static_assert(E == 8, "bf16 units hold 8 values");
-        const uint4 p = *(const uint4 *)((const uint16_t *)row + c0);
-        const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            v[2 * k] = __uint_as_float(w[k] << 16);
-            v[2 * k + 1] = __uint_as_float(w[k] & 0xFFFF0000u);
-        }
+        unpack_bf16x8(*(const uint4 *)((const uint16_t *)row + c0), v);
     } else {
 #pragma unroll
         for (int k = 0; k < E; k += 4) {
@@ -79,34 +66,6 @@ __device__ __forceinline__ void xe_st_vec(void *row, int64_t c0, const float *v)
 #pragma unroll
         for (int k = 0; k < E; k += 4) *(float4 *)((float *)row + c0 + k) = make_float4(v[k], v[k + 1], v[k + 2], v[k + 3]);
     }
-}
-
-template <bool BF16>
-__device__ __forceinline__ void xe_st(void *row, int64_t c, float v)
-{
-    if constexpr (BF16) ((uint16_t *)row)[c] = f32_to_bf16(v);
-    else ((float *)row)[c] = v;
-}
-
-__device__ __forceinline__ float xe_wave_max(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-__device__ __forceinline__ int xe_wave_min(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-__device__ __forceinline__ int xe_wave_add(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // sum of a[0 .. N) as a balanced tree (N a power of two); a is consumed
@@ -154,7 +113,7 @@ __device__ __forceinline__ void xe_ld_unit(const void *zrow, int64_t c0, int C, 
         }
     }
 #pragma unroll
-    for (int k = 0; k < E; k++) v[k] = c0 + k < C ? xe_ld<BF16>(zrow, c0 + k) : -INFINITY;
+    for (int k = 0; k < E; k++) v[k] = c0 + k < C ? ld_elem<BF16>(zrow, c0 + k) : -INFINITY;
 }
 
 // Register paths.  G = 64: a wave per row, 4 rows per workgroup; G = 256: a workgroup per row.  Value slot s of thread t is column
@@ -170,9 +129,8 @@ __global__ __launch_bounds__(256) void xent_fwd_reg_kernel(const void *__restric
     const int64_t row = (int64_t)blockIdx.x * (256 / G) + threadIdx.x / G;
     if (row >= B) return;                                   // G = 64: the whole wave leaves (this path has no barrier); G = 256: never
     const void *zrow = BF16 ? (const void *)((const uint16_t *)z + row * ldz) : (const void *)((const float *)z + row * ldz);
-    int64_t yl = labels[row];
-    const int y = (int)(yl < 0 ? 0 : (yl >= C ? C - 1 : yl));
-    const float zy = xe_ld<BF16>(zrow, y);
+    const int y = (int)clamp_label(labels[row], C);
+    const float zy = ld_elem<BF16>(zrow, y);
     auto col = [&](int s) { return VEC ? ((s / E) * G + t) * E + s % E : s * G + t; };
 
     float v[NV];
@@ -192,8 +150,8 @@ __global__ __launch_bounds__(256) void xent_fwd_reg_kernel(const void *__restric
         cnt += x > zy ? 1 : 0;
     }
     __shared__ XeShared sh;
-    float M = xe_wave_max(m);
-    nan_at = xe_wave_min(nan_at);
+    float M = wave_max(m);
+    nan_at = wave_min(nan_at);
     if constexpr (G == 256) {
         if (lane_id() == 0) { sh.f[0][wave] = M; sh.i[0][wave] = nan_at; }
         wg_barrier();
@@ -204,8 +162,8 @@ __global__ __launch_bounds__(256) void xent_fwd_reg_kernel(const void *__restric
 #pragma unroll
     for (int s = 0; s < NV; s++) e[s] = expf(v[s] - M);
     float S = wave_sum(xe_tree_sum<NV>(e));
-    int cand = xe_wave_min(m == M ? am : INT_MAX);
-    cnt = xe_wave_add(cnt);
+    int cand = wave_min(m == M ? am : INT_MAX);
+    cnt = wave_sum(cnt);
     if constexpr (G == 256) {
         if (lane_id() == 0) { sh.f[1][wave] = S; sh.i[1][wave] = cand; sh.i[2][wave] = cnt; }
         wg_barrier();
@@ -253,9 +211,8 @@ __global__ __launch_bounds__(256) void xent_fwd_stream_kernel(const void *__rest
     const int t = threadIdx.x, wave = threadIdx.x >> 6;
     const int64_t row = blockIdx.x;
     const void *zrow = BF16 ? (const void *)((const uint16_t *)z + row * ldz) : (const void *)((const float *)z + row * ldz);
-    int64_t yl = labels[row];
-    const int y = (int)(yl < 0 ? 0 : (yl >= C ? C - 1 : yl));
-    const float zy = xe_ld<BF16>(zrow, y);
+    const int y = (int)clamp_label(labels[row], C);
+    const float zy = ld_elem<BF16>(zrow, y);
     const int64_t units = ((int64_t)C + E - 1) / E;
 
     float m = -INFINITY, ssum = 0.f;
@@ -283,15 +240,15 @@ __global__ __launch_bounds__(256) void xent_fwd_stream_kernel(const void *__rest
         }
     }
     __shared__ XeShared sh;
-    float M = xe_wave_max(m);
-    nan_at = xe_wave_min(nan_at);
+    float M = wave_max(m);
+    nan_at = wave_min(nan_at);
     if (lane_id() == 0) { sh.f[0][wave] = M; sh.i[0][wave] = nan_at; }
     wg_barrier();
     M = fmaxf(fmaxf(sh.f[0][0], sh.f[0][1]), fmaxf(sh.f[0][2], sh.f[0][3]));
     nan_at = min(min(sh.i[0][0], sh.i[0][1]), min(sh.i[0][2], sh.i[0][3]));
     float S = wave_sum(m == -INFINITY ? 0.f : ssum * expf(m - M));
-    int cand = xe_wave_min(m == M ? am : INT_MAX);
-    cnt = xe_wave_add(cnt);
+    int cand = wave_min(m == M ? am : INT_MAX);
+    cnt = wave_sum(cnt);
     if (lane_id() == 0) { sh.f[1][wave] = S; sh.i[1][wave] = cand; sh.i[2][wave] = cnt; }
     wg_barrier();
     S = (sh.f[1][0] + sh.f[1][1]) + (sh.f[1][2] + sh.f[1][3]);
@@ -330,21 +287,6 @@ __global__ __launch_bounds__(256) void xent_fwd_stream_kernel(const void *__rest
     if (t == 0) xe_write_row(row, B, C, bad, loss, M, lS, A, nan_at, cand, cnt, loss_i, aux, best, above);
 }
 
-// Deterministic mean of n floats: one 256-thread block, fixed tree; +0 for n = 0.
-__global__ __launch_bounds__(256) void xent_mean_kernel(const float *__restrict__ v, int64_t n, float *__restrict__ out)
-{
-    __shared__ float part[256];
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < n; i += 256) s += v[i];
-    part[threadIdx.x] = s;
-    wg_barrier();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        wg_barrier();
-    }
-    if (threadIdx.x == 0) out[0] = n > 0 ? part[0] / (float)n : 0.f;
-}
-
 // dz_k = w (A exp(-t_k) - a_k): one pass, G threads per row (64: a wave, 4 rows per workgroup; 256: a workgroup)
 template <bool ZBF, bool DBF, bool VEC, int G>
 __global__ __launch_bounds__(256) void xent_bwd_kernel(const void *__restrict__ z, int64_t ldz, const int64_t *__restrict__ labels,
@@ -358,8 +300,7 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const void *__restrict__ 
     if (row >= B) return;
     const void *zrow = ZBF ? (const void *)((const uint16_t *)z + row * ldz) : (const void *)((const float *)z + row * ldz);
     void *drow = DBF ? (void *)((uint16_t *)dz + row * lddz) : (void *)((float *)dz + row * lddz);
-    int64_t yl = labels[row];
-    const int y = (int)(yl < 0 ? 0 : (yl >= C ? C - 1 : yl));
+    const int y = (int)clamp_label(labels[row], C);
     const float m = aux[row], lS = aux[B + row], A = aux[2 * B + row];
     const float w = grad_loss_i ? grad_loss_i[row] : grad_scale;
     const int64_t units = ((int64_t)C + E - 1) / E;
@@ -384,15 +325,13 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const void *__restrict__ 
         }
 #pragma unroll
         for (int k = 0; k < E; k++)
-            if (c0 + k < C) xe_st<DBF>(drow, c0 + k, d[k]);
+            if (c0 + k < C) st_elem<DBF>(drow, c0 + k, d[k]);
     }
 }
 
 }  // namespace se
 
 using namespace se;
-
-static inline bool xe_aligned16(const void *p, int64_t ld, int elem_bytes) { return (((uintptr_t)p) & 15) == 0 && (ld * elem_bytes) % 16 == 0; }
 
 // target weights: (1 - s, s / (C - 1)) for 0 < s < 1, one-hot otherwise (learn_classifier.py:20)
 static inline void xe_target(float smoothing, int64_t C, float &y_on, float &y_off)
@@ -407,7 +346,7 @@ static int xe_check(const char *who, const void *logits, int z_dtype, int64_t ld
 {
     if (B < 0 || C < 1) return fail(SE_ERR_INVALID, "%s: bad shape B=%lld C=%lld", who, (long long)B, (long long)C);
     if (smoothing > 0.f && smoothing < 1.f && C < 2) return fail(SE_ERR_INVALID, "%s: label smoothing %g needs at least 2 classes", who, (double)smoothing);
-    if (z_dtype != SE_DTYPE_F32 && z_dtype != SE_DTYPE_BF16) return fail(SE_ERR_INVALID, "%s: bad dtype %d", who, z_dtype);
+    if (!is_float_dtype(z_dtype)) return fail(SE_ERR_INVALID, "%s: bad dtype %d", who, z_dtype);
     if (ldz < C) return fail(SE_ERR_INVALID, "%s: leading dimension %lld < C=%lld", who, (long long)ldz, (long long)C);
     if (C > INT_MAX - 16 || B > INT_MAX) return fail(SE_ERR_UNSUPPORTED, "%s: B or C too large", who);
     if (B > 0 && (!logits || !labels || !aux)) return fail(SE_ERR_INVALID, "%s: null pointer", who);
@@ -443,18 +382,14 @@ extern "C" int se_softmax_xent_fwd(const void *logits, int z_dtype, int64_t ldz,
         float y_on, y_off;
         xe_target(smoothing, C, y_on, y_off);
         const bool bf = z_dtype == SE_DTYPE_BF16;
-        const bool vec = xe_aligned16(logits, ldz, bf ? 2 : 4);
-        if (bf) {
-            if (vec) xe_launch_fwd<true, true>(logits, ldz, labels, B, (int)C, y_on, y_off, loss_i, aux, best, above, s);
-            else xe_launch_fwd<true, false>(logits, ldz, labels, B, (int)C, y_on, y_off, loss_i, aux, best, above, s);
-        } else {
-            if (vec) xe_launch_fwd<false, true>(logits, ldz, labels, B, (int)C, y_on, y_off, loss_i, aux, best, above, s);
-            else xe_launch_fwd<false, false>(logits, ldz, labels, B, (int)C, y_on, y_off, loss_i, aux, best, above, s);
-        }
+        const bool vec = aligned16(logits, ldz, bf ? 2 : 4);
+        dispatch_bools(bf, vec, [&](auto BF, auto VEC) {
+            xe_launch_fwd<BF(), VEC()>(logits, ldz, labels, B, (int)C, y_on, y_off, loss_i, aux, best, above, s);
+        });
         SE_LAUNCH_CHECK();
     }
     if (loss_mean) {
-        hipLaunchKernelGGL(xent_mean_kernel, dim3(1), dim3(256), 0, s, (const float *)loss_i, B, loss_mean);
+        launch_mean(loss_i, B, loss_mean, s);
         SE_LAUNCH_CHECK();
     }
     return SE_OK;
@@ -472,36 +407,24 @@ static void xe_launch_bwd(const void *z, int64_t ldz, const int64_t *labels, con
                            y_off, dz, lddz);
 }
 
-template <bool ZBF, bool DBF>
-static void xe_launch_bwd_v(bool vec, const void *z, int64_t ldz, const int64_t *labels, const float *aux, const float *gl, float gs,
-                            int64_t B, int C, float y_on, float y_off, void *dz, int64_t lddz, hipStream_t s)
-{
-    if (vec) xe_launch_bwd<ZBF, DBF, true>(z, ldz, labels, aux, gl, gs, B, C, y_on, y_off, dz, lddz, s);
-    else xe_launch_bwd<ZBF, DBF, false>(z, ldz, labels, aux, gl, gs, B, C, y_on, y_off, dz, lddz, s);
-}
-
 extern "C" int se_softmax_xent_bwd(const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, const float *aux,
                                    const float *grad_loss_i, float grad_scale, int64_t B, int64_t C, float smoothing, void *dz,
                                    int dz_dtype, int64_t lddz, se_stream_t stream)
 {
     const int rc = xe_check("se_softmax_xent_bwd", logits, z_dtype, ldz, labels, B, C, smoothing, aux);
     if (rc != SE_OK) return rc;
-    if (dz_dtype != SE_DTYPE_F32 && dz_dtype != SE_DTYPE_BF16) return fail(SE_ERR_INVALID, "se_softmax_xent_bwd: bad dtype %d", dz_dtype);
+    if (!is_float_dtype(dz_dtype)) return fail(SE_ERR_INVALID, "se_softmax_xent_bwd: bad dtype %d", dz_dtype);
     if (lddz < C) return fail(SE_ERR_INVALID, "se_softmax_xent_bwd: leading dimension %lld < C=%lld", (long long)lddz, (long long)C);
     if (B == 0) return SE_OK;
     if (!dz) return fail(SE_ERR_INVALID, "se_softmax_xent_bwd: null pointer");
     float y_on, y_off;
     xe_target(smoothing, C, y_on, y_off);
     const bool zbf = z_dtype == SE_DTYPE_BF16, dbf = dz_dtype == SE_DTYPE_BF16;
-    const bool vec = xe_aligned16(logits, ldz, zbf ? 2 : 4) && xe_aligned16(dz, lddz, dbf ? 2 : 4);
+    const bool vec = aligned16(logits, ldz, zbf ? 2 : 4) && aligned16(dz, lddz, dbf ? 2 : 4);
     hipStream_t s = (hipStream_t)stream;
-    if (zbf) {
-        if (dbf) xe_launch_bwd_v<true, true>(vec, logits, ldz, labels, aux, grad_loss_i, grad_scale, B, (int)C, y_on, y_off, dz, lddz, s);
-        else xe_launch_bwd_v<true, false>(vec, logits, ldz, labels, aux, grad_loss_i, grad_scale, B, (int)C, y_on, y_off, dz, lddz, s);
-    } else {
-        if (dbf) xe_launch_bwd_v<false, true>(vec, logits, ldz, labels, aux, grad_loss_i, grad_scale, B, (int)C, y_on, y_off, dz, lddz, s);
-        else xe_launch_bwd_v<false, false>(vec, logits, ldz, labels, aux, grad_loss_i, grad_scale, B, (int)C, y_on, y_off, dz, lddz, s);
-    }
+    dispatch_bools(zbf, dbf, vec, [&](auto ZBF, auto DBF, auto VEC) {
+        xe_launch_bwd<ZBF(), DBF(), VEC()>(logits, ldz, labels, aux, grad_loss_i, grad_scale, B, (int)C, y_on, y_off, dz, lddz, s);
+    });
     SE_LAUNCH_CHECK();
     return SE_OK;
 }

@@ -1,7 +1,7 @@
 """The training-side kernels (csrc/loss_kernels.hip, devise.hip, labelembed.hip) through every path their host code can choose.
 
 The host entry points pick a kernel instantiation from the feature dtype and the gradient dtype, switch between 16-byte and element
-loads on ``D``, the row pitches and the pointer alignment (``vec_ok``; ``stage_tile32`` decides again per operand inside
+loads on ``D``, the row pitches and the pointer alignment (``vec_ok``; ``stage_tile32`` / ``tile32::load_rows`` decide again per operand inside
 nn_accuracy), cap the grid of the row kernels (8,192 blocks of 4 rows; labelembed's ``le_grid`` at 4,096) and cut large class sets
 into slices whose partial results meet in a finish kernel.  The functions below restate those choices in Python, and CPU tests hold
 the case tables to every tuple of them, so that dropping a case can never silently drop a path.
@@ -94,7 +94,7 @@ def n_slices(tpb, C):
 
 
 def stage_vec(layout, d):
-    """stage_tile32's per-operand choice: ((ld | K) & 3) == 0 and a 16-byte aligned base."""
+    """stage_tile32's and tile32::load_rows' per-operand choice: ((ld | K) & 3) == 0 and a 16-byte aligned base."""
     return pitch(layout, d) % 4 == 0 and d % 4 == 0 and aligned(layout)
 
 
