@@ -694,6 +694,48 @@ int se_image_batch(const void *arena, int64_t arena_bytes, const int64_t *src_of
                    const float *mean, const float *std, int bgr, void *out, int out_dtype, int64_t B, int ch, int cw, int Kx, int Ky,
                    se_stream_t stream);
 
+/*
+ * One launch composes a batch [B, H, W, C] (NHWC) from a store of small float32 images resident in device memory: gather, Keras'
+ * affine random_transform with bilinear interpolation, both flips, standardisation, layout and dtype conversion.
+ * Replaces: datasets/common.py:638-670, 771-796 (TinyDatasetGenerator: ImageDataGenerator.random_transform + standardize per sample
+ *           [third party: keras_preprocessing 1.0.x], i.e. scipy.ndimage.affine_transform(order = 1) channel by channel, the flips,
+ *           then (x - mean) / (std + 1e-6)).
+ *   images   [N, H, W, C] f32, raw un-normalised pixels; C in 1 .. 4, H, W >= 1
+ *   index    [B] int64: the store row of every sample, any order, repeats allowed; a value outside [0, N) writes that sample as NaN
+ *   affine   [B, 6] FLOAT64 = (M00, M01, M02, M10, M11, M12): output (row, col) -> source (row, col)
+ *   flags    [B] int32: bit 0 horizontal flip, bit 1 vertical flip (applied AFTER the transform, as Keras does)
+ *   mean, stdp  [C] f32; stdp already holds std + 1e-6
+ *   fill_mode  SE_FILL_NEAREST / SE_FILL_CONSTANT / SE_FILL_REFLECT;  cval: the value of 'constant' outside the image
+ *   out      [B, H, W, C] f32 (SE_DTYPE_F32) or bf16 (SE_DTYPE_BF16: the f32 value rounded to nearest even)
+ * For output (b, r, c) and channel k, in float64 with every operation separately rounded, in the order of scipy's NI_GeometricTransform:
+ *     r' = vflip ? H - 1 - r : r,   c' = hflip ? W - 1 - c : c
+ *     y  = (r' * M00 + c' * M01) + M02,   x = (r' * M10 + c' * M11) + M12
+ * Per axis of length n with coordinate v:
+ *     nearest   v stays; taps i0 = floor(v) and i0 + 1, each clamped to [0, n - 1] (outside the image both are the edge pixel)
+ *     constant  v < 0 or v > n - 1 on ANY axis: the pixel is cval (no interpolation beyond the edges); otherwise as nearest
+ *     reflect   n == 1: v = 0.  v < 0: p = 2 n; if v < -p: v = p * trunc(-v / p) + v; then v = (v < -n) ? v + p : -v - 1.
+ *               v > n - 1: v = v - p * trunc(v / p); if v >= n: v = p - v - 1.  Taps i0 = floor(v) (may be -1) and i0 + 1, each
+ *               folded: m = mod(i, 2 n); idx = m < n ? m : 2 n - 1 - m
+ * With f = v - floor(v), the weights w0 = 1 - f and w1 = 1 - w0 of each axis and the four taps a00 .. a11 (first digit: row):
+ *     t   = (((0 + (a00 * wy0) * wx0) + (a01 * wy0) * wx1) + (a10 * wy1) * wx0) + (a11 * wy1) * wx1
+ *     out = (float(t) - mean[k]) / stdp[k]                    float(): round to nearest even; IEEE f32 subtract and divide
+ * and float(cval) in the place of float(t) for a 'constant' pixel outside (Keras standardises after the transform) -- bit for bit what
+ * scipy.ndimage.affine_transform(x, M[:2, :2], M[:2, 2], order = 1, mode, cval) into a float32 array, the flips and the float32
+ * standardisation give (tests/golden/tiny_affine.npz).
+ * Every tap is inside its image whatever the matrix holds.  One output element per thread and trip, no LDS, no atomics: the same
+ * bits whatever the launch geometry.  int64 element offsets; the grid is capped at SE_TINY_BATCH_MAX_BLOCKS workgroups of 256
+ * threads that stride over the batch.  B = 0 returns SE_OK without a launch; a negative B or N, H or W < 1, C outside 1 .. 4, an
+ * unknown fill mode or output dtype, or a NULL pointer with B > 0 is SE_ERR_INVALID; H * W * C > 2^30 is SE_ERR_UNSUPPORTED.
+ * Asynchronous; no workspace; capturable in a HIP graph.
+ */
+#define SE_FILL_NEAREST 0
+#define SE_FILL_CONSTANT 1
+#define SE_FILL_REFLECT 2
+#define SE_TINY_BATCH_MAX_BLOCKS 2048
+int se_tiny_batch(const float *images, int64_t N, const int64_t *index, const double *affine, const int32_t *flags, const float *mean,
+                  const float *stdp, int fill_mode, float cval, void *out, int out_dtype, int64_t B, int H, int W, int C,
+                  se_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,12 +6,15 @@
 Batches are produced ON THE DEVICE (channels_last float tensors), so images/s is not bound by a
 Python loader: the synthetic generators draw N(0,1) images with fixed seeds (BASELINE.json's
 configs are all measured on synthetic batches), the CIFAR generator keeps the whole pickle-decoded
-dataset in HBM and augments there, and the file-based generators (NAB / CUB, Cars, Flowers, sub-directory datasets:
+dataset in HBM and augments there -- shift + flip as tensor ops; any other configuration of the reference's train_generator_kwargs
+(the 'cifar-10' preset's zoom, rotation, shear, vertical flip, fill modes) as Keras' affine random_transform in one launch of
+se_tiny_batch (csrc/tiny_batch.hip), bit for bit what scipy.ndimage.affine_transform gives -- and the file-based generators (NAB / CUB, Cars, Flowers, sub-directory datasets:
 datasets/files.py) keep the DECODED uint8 images of a split in HBM and compose every batch -- Pillow's bilinear resize, normalisation,
 flip, random erasing, crop, reflect padding -- in one launch of se_image_batch (csrc/image_batch.hip).  ILSVRC and iNaturalist stay
 out: their decoded images do not fit a resident store and need a streaming decode tier.
 """
-from .common import DeviceBatchSequence, InMemoryDatasetGenerator, SyntheticGenerator  # noqa: F401
+from .common import (DeviceBatchSequence, InMemoryDatasetGenerator, SyntheticGenerator,  # noqa: F401
+                     affine_batch_host, affine_matrices)
 from .cifar import CifarGenerator  # noqa: F401
 from .files import (CarsGenerator, FileDatasetGenerator, FlowersGenerator, NABGenerator,  # noqa: F401
                     SubDirectoryGenerator)
@@ -21,6 +24,9 @@ CAFFE_MEAN = [123.68, 116.779, 103.939]
 CAFFE_STD = [1., 1., 1.]
 IMAGENET_MEAN = [122.65435242, 116.6545058, 103.99789959]
 IMAGENET_STD = [71.40583196, 69.56888997, 73.0440314]
+
+# the reference's 'cifar-10' preset (datasets/__init__.py:80-83)
+CIFAR10_AUGMENTATION = {'horizontal_flip': True, 'width_shift_range': 0.15, 'height_shift_range': 0.15, 'zoom_range': 0.25}
 
 SYNTHETIC_PRESETS = {
     # name: (num_classes, height/width, channels, num_train, num_test)
@@ -47,7 +53,7 @@ def get_data_generator(dataset, data_root, classes=None):
         c, hw, ntr, nte = (int(v) for v in name.split(':', 1)[1].split('x'))
         return SyntheticGenerator(c if classes is None else len(classes), hw, 3, ntr, nte, classes=classes)
     if name == 'cifar-10':
-        return CifarGenerator(data_root, classes, reenumerate=True, cifar10=True)
+        return CifarGenerator(data_root, classes, reenumerate=True, cifar10=True, train_generator_kwargs=dict(CIFAR10_AUGMENTATION))
     if name == 'cifar-100':
         return CifarGenerator(data_root, classes, reenumerate=True)
     if name.startswith('cifar-100-a'):

@@ -21,7 +21,7 @@ __all__ = [
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
     "recall_precision_reduce", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
-    "svm_axpby", "class_pair_tables", "cholesky_lower_", "image_batch", "resample_tables",
+    "svm_axpby", "class_pair_tables", "cholesky_lower_", "image_batch", "resample_tables", "tiny_batch", "TINY_BATCH_MAX_BLOCKS", "FILL_MODES",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
 ]
 
@@ -1170,4 +1170,42 @@ def image_batch(arena, src_off, src_hw, xmap, xk, ymap, yk, erase, seed, mean, s
         raise SehipError("image_batch: out must be a contiguous [B, ch, cw, 3] tensor of the requested dtype")
     call("se_image_batch", arena, arena.numel(), src_off, src_hw, xmap, xk, ymap, yk, erase, seed, mean, std, int(bool(bgr)), out,
          DTYPE_F32 if dtype == torch.float32 else DTYPE_BF16, B, ch, cw, Kx, Ky)
+    return out
+
+
+TINY_BATCH_MAX_BLOCKS = DEFINES["SE_TINY_BATCH_MAX_BLOCKS"]
+FILL_MODES = {"nearest": DEFINES["SE_FILL_NEAREST"], "constant": DEFINES["SE_FILL_CONSTANT"], "reflect": DEFINES["SE_FILL_REFLECT"]}
+
+
+def tiny_batch(images, index, affine, flags, mean, stdp, fill_mode="nearest", cval=0.0, dtype=torch.float32, out=None):
+    """``se_tiny_batch``: one launch composes the batch from the float32 store ``images`` [N, H, W, C] (see include/sehip.h for every
+    argument; all device tensors: ``index`` int64 [B], ``affine`` float64 [B, 6], ``flags`` int32 [B] (bit 0 horizontal, bit 1 vertical
+    flip), ``mean`` / ``stdp`` float32 [C]); ``fill_mode`` 'nearest', 'constant' or 'reflect'.
+    Returns ``out`` [B, H, W, C] (NHWC) of ``dtype`` float32 or bfloat16; ``out.permute(0, 3, 1, 2)`` is the channels_last batch."""
+    require_gpu(images, index, affine, flags, mean, stdp, out)
+    if images.dtype != torch.float32 or images.dim() != 4 or not images.is_contiguous():
+        raise SehipError("tiny_batch: the store must be a contiguous float32 [N, H, W, C] tensor")
+    N, H, W, C = images.shape
+    if not 1 <= C <= 4 or H < 1 or W < 1:
+        raise SehipError("tiny_batch: images of %d x %d x %d: 1 to 4 channels and at least one pixel" % (H, W, C))
+    _i64(index, "index")
+    _i32(flags, "flags")
+    B = index.numel()
+    if affine.dtype != torch.float64 or not affine.is_contiguous() or tuple(affine.shape) != (B, 6):
+        raise SehipError("tiny_batch: affine must be a contiguous float64 [B, 6] tensor")
+    if index.dim() != 1 or tuple(flags.shape) != (B,):
+        raise SehipError("tiny_batch: index and flags must be [B]")
+    for t, name in ((mean, "mean"), (stdp, "stdp")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
+            raise SehipError("tiny_batch: %s must be contiguous float32 [%d]" % (name, C))
+    if fill_mode not in FILL_MODES:
+        raise SehipError("tiny_batch: fill_mode must be one of %s, got %r" % (sorted(FILL_MODES), fill_mode))
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise SehipError("tiny_batch: output must be float32 or bfloat16, got %s" % dtype)
+    if out is None:
+        out = torch.empty((B, H, W, C), dtype=dtype, device=images.device)
+    elif out.dtype != dtype or tuple(out.shape) != (B, H, W, C) or not out.is_contiguous():
+        raise SehipError("tiny_batch: out must be a contiguous [B, H, W, C] tensor of the requested dtype")
+    call("se_tiny_batch", images, N, index, affine, flags, mean, stdp, FILL_MODES[fill_mode], float(cval), out,
+         DTYPE_F32 if dtype == torch.float32 else DTYPE_BF16, B, H, W, C)
     return out

@@ -19,7 +19,10 @@
     python tools/bench_kernels.py labelembed     (label-embedding loss forward + backward on the learned table next to the composition it
                                                   replaces -- Embedding gather, loss on the gathered rows, torch's embedding backward -- as
                                                   bare kernels and through autograd, and the ResNet-110-fc label-embedding training step
-                                                  next to the classifier step)"""
+                                                  next to the classifier step)
+    python tools/bench_kernels.py tiny           (se_tiny_batch: batches of 128 and 512 CIFAR images with the 'cifar-10' preset -- shifts,
+                                                  zoom, flip -- as the bare kernel and as the whole compose_batch, next to the torch
+                                                  composition of the default shift + flip batch)"""
 import argparse
 import os
 import sys
@@ -47,7 +50,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -68,6 +71,8 @@ def main():
         return bench_adagrad()
     if args.what == "labelembed":
         return bench_labelembed()
+    if args.what == "tiny":
+        return bench_tiny()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -722,6 +727,66 @@ def bench_image(B=128, reps=20, stored=256):
     print("ResNet-50 training step, 224 x 224, 200 classes, batch %d, %s: %.2f ms/step = %.0f images/s; slowest batch composition "
           "(host + kernel) %.2f ms: the loader %s" % (B, r["dtype"], r["ms_per_step"], r["value"], worst,
                                                       "keeps up with the network" if worst < r["ms_per_step"] else "DOES NOT keep up: it sets images/s"))
+
+
+def bench_tiny(reps=40, batch=20, stored=10000):
+    """The in-memory batch (datasets/common.py) at 128 x 32 x 32 x 3 and 512 x 32 x 32 x 3 from a store of `stored` CIFAR-sized images:
+    se_tiny_batch with the 'cifar-10' preset (shifts +-15 %, zoom 0.75 .. 1.25, flip) as the bare kernel (parameters already on the
+    device) and as the whole compose_batch (draw_affine + affine_matrices on the host, one upload, one launch), next to the torch
+    composition of the default shift + flip batch (index upload, index_select, device draws, grid_sample, where, channels_last copy) and
+    its device part alone (apply_transform + channels_last copy on a gathered batch with drawn parameters).  The four timed alternately
+    in one process: `reps` windows of `batch` back-to-back calls each (HIP events around a window) after 3 warm-up calls, median / 10th
+    / 90th percentile of the per-call time.  Bytes: the float32 batch out, over the kernel's time (its reads hit the same few images'
+    cache lines four times over)."""
+    sys.path.insert(0, os.path.join(ROOT, "semantic-embeddings_amd"))
+    from datasets import CIFAR10_AUGMENTATION, InMemoryDatasetGenerator
+    from datasets.common import affine_matrices
+
+    def windows(fns):
+        for f in fns:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(reps):
+            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(batch):
+                    f()
+                b.record()
+                torch.cuda.synchronize()
+                ts[k].append(a.elapsed_time(b) / batch * 1e3)
+        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
+
+    rng = np.random.default_rng(0)
+    X = rng.integers(0, 256, (stored, 32, 32, 3)).astype(np.float32)
+    labels = [0] * stored
+    affine = InMemoryDatasetGenerator(X, X[:16], labels, labels[:16], train_generator_kwargs=dict(CIFAR10_AUGMENTATION))
+    plain = InMemoryDatasetGenerator(X, X[:16], labels, labels[:16])
+    assert affine.affine is not None and plain.affine is None
+    for B in (128, 512):
+        idx = rng.permutation(stored)[:B]
+        draws = np.random.default_rng(1)
+        store = affine._raw_store(True)
+        p = affine.draw_affine(B, 32, 32, draws)
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        index, M, flags = dev(idx.astype(np.int64)), dev(affine_matrices(p, 32, 32)), dev(p["hflip"].astype(np.int32))
+        out = torch.empty((B, 32, 32, 3), device="cuda")
+        gathered = plain.compose_batch(idx, train=True, augment=False).contiguous()
+        drawn = plain.draw_transform(B, 32, 32, gathered.device)
+        kernel = lambda: sehip.tiny_batch(store, index, M, flags, affine._stats[0], affine._stats[1], "nearest", 0.0, out=out)
+        whole = lambda: affine.compose_batch(idx, train=True, augment=True, rng=draws)
+        torch_whole = lambda: plain.compose_batch(idx, train=True, augment=True)
+        torch_dev = lambda: plain.apply_transform(gathered, *drawn).contiguous(memory_format=torch.channels_last)
+        k, w, tw, td = windows((kernel, whole, torch_whole, torch_dev))
+        assert bool(torch.isfinite(out).all())
+        nbytes = 4.0 * B * 32 * 32 * 3
+        print("tiny batch %d x 32 x 32 x 3 ('cifar-10' preset): se_tiny_batch %.1f us (%.1f-%.1f), %.2f MB out = %.0f GB/s; whole compose_batch "
+              "(host draws + matrices + upload + launch) %.1f us (%.1f-%.1f); torch composition of the shift + flip batch: device part %.1f us "
+              "(%.1f-%.1f) = x%.2f of the kernel, whole compose_batch %.1f us (%.1f-%.1f) = x%.2f of the affine compose_batch"
+              % (B, k[0], k[1], k[2], nbytes / 1e6, nbytes / (k[0] * 1e-6) / 1e9, w[0], w[1], w[2], td[0], td[1], td[2], td[0] / k[0],
+                 tw[0], tw[1], tw[2], tw[0] / w[0]), flush=True)
 
 
 def bench_adagrad(reps=40, batch=20, steps=200):
