@@ -320,6 +320,46 @@ int se_softmax_xent_bwd(const void *logits, int z_dtype, int64_t ldz, const int6
 int se_adagrad_step(float *p, float *accum, const float *g, const float *l2, int64_t n, float lr, const float *lr_dev,
                     float grad_scale, float epsilon, se_stream_t stream);
 
+/*
+ * The pyramidal residual shortcut in one launch, and the gradient of its pooled operand:
+ *     out = s + ChannelPadding((pad_before, C - Cin - pad_before))(AveragePooling2D(stride)(x))
+ * Replaces: layers.add([s, shortcut(x, n, stride)]) at the end of every block of models/cifar_pyramidnet.py:81-110 (pad_before = 0)
+ *           and the same composition of models/cifar_resnet.py:28-147 (symmetric padding: pad_before = (C - Cin) / 2), which as
+ *           pooling + padding + add write a zero-padded copy of the shortcut as large as s only for the add to read it again.
+ *   s, out  [B, C, H, W] logical;  x [B, Cin, Hx, Wx] logical, Cin + pad_before <= C
+ *   stride  1 (H == Hx, W == Wx) or 2 (H == Hx / 2, W == Wx / 2 rounded down: a trailing odd row or column of x belongs to no
+ *           window, as in Keras' 'valid' pooling and torch's floor mode); any other stride is SE_ERR_UNSUPPORTED
+ *   layout  SE_LAYOUT_NCHW: all tensors dense in the order [B, C, H, W];  SE_LAYOUT_NHWC: dense in the order [B, H, W, C]
+ *           (torch's channels_last).  Operands and output share it.
+ *   dtype   SE_DTYPE_F32 or SE_DTYPE_BF16; operands and output share it
+ * Forward, per element, in float32 with every operation separately rounded (no contraction); bf16 values are widened first:
+ *   channel c in [pad_before, pad_before + Cin), ci = c - pad_before:
+ *       acc    = the window's stride * stride values x[b, ci, stride h + i, stride w + j] added one by one in row-major window order
+ *                (i outer, j inner), starting from the first:  ((x00 + x01) + x10) + x11
+ *       pooled = acc / (float)(stride * stride)
+ *       out    = s + pooled, rounded once to the output dtype (bf16: to nearest even)
+ *   every other channel: out = s, the BITS copied (not "s + 0.0f"): -0.0 and NaN payloads pass through.
+ *   out may be s itself (every element is read before it is written, by the same thread); it must not overlap x.
+ * Backward (se_shortcut_add_bwd), dout [B, C, H, W] and dx [B, Cin, Hx, Wx] in the same layout and dtype:
+ *       dx[b, ci, y, x] = dout[b, pad_before + ci, y / stride, x / stride] / (float)(stride * stride), rounded to the dtype;
+ *       +0 at the positions of a trailing odd row or column.
+ *   The gradient of s is dout itself: there is no kernel for it.  Windows do not overlap, so every dx element has one source.
+ * One launch each, asynchronous on `stream`; no workspace, no allocation, no atomics, no host synchronisation: capturable in a HIP
+ * graph, and the same inputs give the same bits.  Any channel count and image size: accesses are as wide (up to 16 bytes) as the
+ * extents and the pointers' alignment allow, element by element otherwise.  int64 offsets; the grid is capped at
+ * SE_SHORTCUT_MAX_BLOCKS workgroups of 256 threads that stride over the tensor.
+ * B == 0 (or any empty tensor) returns SE_OK without a launch, whatever the pointers.  A bad dtype or layout code, a negative
+ * extent, Cin + pad_before > C, H or W that do not follow from Hx, Wx and stride, or a NULL pointer to a non-empty tensor is
+ * SE_ERR_INVALID.  Every argument is checked before any device work.
+ */
+#define SE_LAYOUT_NCHW 0
+#define SE_LAYOUT_NHWC 1
+#define SE_SHORTCUT_MAX_BLOCKS 2048
+int se_shortcut_add_fwd(const void *s, const void *x, void *out, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W,
+                        int64_t Cin, int64_t Hx, int64_t Wx, int stride, int64_t pad_before, se_stream_t stream);
+int se_shortcut_add_bwd(const void *dout, void *dx, int dtype, int layout, int64_t B, int64_t C, int64_t H, int64_t W, int64_t Cin,
+                        int64_t Hx, int64_t Wx, int stride, int64_t pad_before, se_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Retrieval side  (evaluate_retrieval.pairwise_retrieval, evaluate_retrieval.py:22-73)
  * ------------------------------------------------------------------------------------------ */

@@ -41,8 +41,9 @@ def backbone_mode(architecture):
     """``(autocast_dtype, memory_format)`` for ``Trainer``: how the PyTorch-ROCm backbone of ``architecture`` runs.
     Measured on MI355X, resnet-110-fc, batch 128 (tools/train_variants.py, tools/graph_variants.py): bf16 autocast
     channels_last 31.5 ms/step, fp32 channels_last 23.7, fp32 NCHW 21.6 (eager; all host-launch-bound), fp32 NCHW
-    HIP-graph replay 15.3.  ``SE_TRAIN_DTYPE`` = fp32|bf16 and ``SE_TRAIN_LAYOUT`` = nchw|nhwc override."""
-    small = str(architecture).startswith(('resnet-32', 'resnet-110', 'simple', 'wrn-'))      # CIFAR-sized inputs
+    HIP-graph replay 15.3.  That default of the CIFAR-sized group was measured on ResNet-110 only: Plain-11 (``simple``) and the
+    PyramidNets (``pyramidnet-``) take it over unmeasured.  ``SE_TRAIN_DTYPE`` = fp32|bf16 and ``SE_TRAIN_LAYOUT`` = nchw|nhwc override."""
+    small = str(architecture).startswith(('resnet-32', 'resnet-110', 'simple', 'wrn-', 'pyramidnet-'))      # CIFAR-sized inputs
     dtype = os.environ.get('SE_TRAIN_DTYPE', 'fp32' if small else 'bf16').lower()
     layout = os.environ.get('SE_TRAIN_LAYOUT', 'nchw' if small else 'nhwc').lower()
     if dtype not in ('fp32', 'bf16') or layout not in ('nchw', 'nhwc'):

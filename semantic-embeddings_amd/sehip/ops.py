@@ -16,7 +16,7 @@ __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
     "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
     "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
-    "adagrad_step_", "ADAGRAD_MAX_BLOCKS",
+    "adagrad_step_", "ADAGRAD_MAX_BLOCKS", "shortcut_add", "LAYOUT_NCHW", "LAYOUT_NHWC",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
@@ -597,6 +597,61 @@ def adagrad_step_(p, accum, g, l2=None, lr=0.01, grad_scale=1.0, epsilon=1e-7):
         lr, lr_dev = 0.0, lr
     call("se_adagrad_step", p, accum, g, l2, n, float(lr), lr_dev, float(grad_scale), float(epsilon))
     return p
+
+
+LAYOUT_NCHW, LAYOUT_NHWC = DEFINES["SE_LAYOUT_NCHW"], DEFINES["SE_LAYOUT_NHWC"]
+_LAYOUT_FORMATS = ((LAYOUT_NCHW, torch.contiguous_format), (LAYOUT_NHWC, torch.channels_last))
+
+
+def _common_layout(what, *tensors):
+    """``(layout code, memory format)`` in which every one of the 4-d ``tensors`` is dense; ``SehipError`` when there is none (mixed
+    or strided operands).  Where both hold for all of them -- one channel, 1 x 1 images, or no element at all, which torch calls
+    contiguous whatever the strides -- the two address the same memory, and the strides decide which one the results are allocated
+    in: channels_last when an operand carries its strides (channel stride 1, column stride C), NCHW otherwise."""
+    dense = [(code, fmt) for code, fmt in _LAYOUT_FORMATS if all(t.is_contiguous(memory_format=fmt) for t in tensors)]
+    if not dense:
+        raise SehipError("%s: the operands must share one dense layout, contiguous (NCHW) or channels_last (NHWC); got strides %s"
+                         % (what, ", ".join(str(tuple(t.stride())) for t in tensors)))
+    if len(dense) == 2 and any(t.shape[1] > 1 and t.stride(1) == 1 and t.stride(3) == t.shape[1] for t in tensors):
+        return dense[1]
+    return dense[0]
+
+
+class _ShortcutAdd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, x, stride, pad_before):
+        layout, fmt = _common_layout("shortcut_add", s, x)
+        out = torch.empty(s.shape, dtype=s.dtype, device=s.device, memory_format=fmt)
+        (B, C, H, W), (_, Cin, Hx, Wx) = s.shape, x.shape
+        call("se_shortcut_add_fwd", s, x, out, _dtype_code(s), layout, B, C, H, W, Cin, Hx, Wx, stride, pad_before)
+        ctx.geometry = (x.shape, stride, pad_before, layout, fmt)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x_shape, stride, pad_before, layout, fmt = ctx.geometry
+        dx = None
+        if ctx.needs_input_grad[1]:
+            g = grad_out.contiguous(memory_format=fmt)          # no copy when autograd hands the gradient over in the forward's layout
+            dx = torch.empty(x_shape, dtype=g.dtype, device=g.device, memory_format=fmt)
+            (B, C, H, W), (_, Cin, Hx, Wx) = g.shape, x_shape
+            call("se_shortcut_add_bwd", g, dx, _dtype_code(g), layout, B, C, H, W, Cin, Hx, Wx, stride, pad_before)
+        return grad_out, dx, None, None         # the gradient of s is the incoming tensor itself: no kernel, no copy
+
+
+def shortcut_add(s, x, stride=1, pad_before=0):
+    """``s + ChannelPadding((pad_before, C - Cin - pad_before))(AveragePooling2D(stride)(x))`` in one launch (``se_shortcut_add_fwd``;
+    the residual add at the end of every PyramidNet block, models/cifar_pyramidnet.py:81-110), with autograd: the gradient of ``s`` is
+    the incoming gradient tensor itself, that of ``x`` one launch of ``se_shortcut_add_bwd``.  ``s`` [B, C, H, W] and ``x``
+    [B, Cin, Hx, Wx] are float32 or bfloat16 device tensors of one dtype, both contiguous or both channels_last; ``stride`` 1 or 2
+    (H = Hx // stride, W = Wx // stride).  The arithmetic is fixed in include/sehip.h."""
+    require_gpu(s, x)
+    if s.dim() != 4 or x.dim() != 4 or s.shape[0] != x.shape[0]:
+        raise SehipError("shortcut_add takes s [B, C, H, W] and x [B, Cin, Hx, Wx]; got %s and %s" % (tuple(s.shape), tuple(x.shape)))
+    if s.dtype != x.dtype or s.device != x.device:
+        raise SehipError("shortcut_add: s (%s, %s) and x (%s, %s) must share dtype and device" % (s.dtype, s.device, x.dtype, x.device))
+    _dtype_code(s)
+    return _ShortcutAdd.apply(s, x, int(stride), int(pad_before))
 
 
 # --------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 import sehip
-from models import cifar_resnet, resnet50
+from models import cifar_pyramidnet, cifar_resnet, plainnet, resnet50
 
 ARCHITECTURES = ['simple', 'resnet-32', 'resnet-110', 'resnet-110-fc', 'resnet-110-wfc', 'wrn-28-10',
                  'densenet-100-12', 'densenet-100-24', 'densenet-bc-190-40', 'pyramidnet-272-200', 'pyramidnet-110-270',
@@ -35,7 +35,8 @@ LR_SCHEDULES = ['SGD', 'SGDR', 'CLR', 'ResNet-Schedule']
 
 # architectures with a PyTorch-ROCm body in this build (BASELINE.json configs); the other names are
 # kept so CLI `choices` match the reference but raise NotImplementedError in build_network
-IMPLEMENTED_ARCHITECTURES = ['resnet-32', 'resnet-110', 'resnet-110-fc', 'resnet-110-wfc', 'resnet-50']
+IMPLEMENTED_ARCHITECTURES = ['simple', 'resnet-32', 'resnet-110', 'resnet-110-fc', 'resnet-110-wfc', 'pyramidnet-272-200',
+                             'pyramidnet-110-270', 'resnet-50']
 
 
 def _is_labels(y_true):
@@ -211,6 +212,12 @@ def build_network(num_outputs, architecture, classification=False, no_softmax=Fa
     if architecture == 'resnet-110-wfc':
         return cifar_resnet.SmallResNet(18, filters=[32, 64, 128], activation=activation, include_top=True,
                                         top_activation=top, classes=num_outputs, name=name, input_channels=input_channels)
+    if architecture in ('pyramidnet-272-200', 'pyramidnet-110-270'):        # utils.py:208-216
+        depth, alpha, bottleneck = (272, 200, True) if architecture == 'pyramidnet-272-200' else (110, 270, False)
+        return cifar_pyramidnet.PyramidNet(depth, alpha, bottleneck=bottleneck, activation=activation, classes=num_outputs,
+                                           top_activation=top, name=name, input_channels=input_channels)
+    if architecture == 'simple':                                            # utils.py:218-224
+        return plainnet.PlainNet(num_outputs, activation=activation, final_activation=top, name=name, input_channels=input_channels)
     if architecture == 'resnet-50':
         return resnet50.ResNet50(num_outputs, classification=classification, no_softmax=no_softmax,
                                  input_channels=input_channels or 3, name=name)

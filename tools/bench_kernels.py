@@ -22,7 +22,10 @@
                                                   next to the classifier step)
     python tools/bench_kernels.py tiny           (se_tiny_batch: batches of 128 and 512 CIFAR images with the 'cifar-10' preset -- shifts,
                                                   zoom, flip -- as the bare kernel and as the whole compose_batch, next to the torch
-                                                  composition of the default shift + flip batch)"""
+                                                  composition of the default shift + flip batch)
+    python tools/bench_kernels.py shortcut       (sehip.shortcut_add forward + backward next to the torch composition avg_pool2d + pad + add
+                                                  at PyramidNet-272-200's shapes for batch 128: the widest stride-1 block of each stage and
+                                                  both stride-2 blocks, fp32 NCHW and bf16 NHWC)"""
 import argparse
 import os
 import sys
@@ -50,7 +53,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut"])
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -73,6 +76,8 @@ def main():
         return bench_labelembed()
     if args.what == "tiny":
         return bench_tiny()
+    if args.what == "shortcut":
+        return bench_shortcut()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -890,6 +895,68 @@ def bench_adagrad(reps=40, batch=20, steps=200):
         step = float(np.median(ms[name]))
         print("ResNet-110-fc %s, batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d steps; %s), "
               "%.0f images/s" % (what, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
+
+
+def bench_shortcut(reps=30, batch=10, B=128):
+    """The pyramidal shortcut (models/cifar_pyramidnet.py): sehip.shortcut_add against s + F.pad(F.avg_pool2d(x, stride), ...) at the
+    shapes of PyramidNet-272-200 for batch 128 -- the widest stride-1 block of each stage (blocks 29, 59, 89) and both stride-2 blocks
+    (30, 60) -- in fp32 NCHW (the trainer's default for the CIFAR-sized nets) and bf16 channels_last.  One call = forward + backward
+    through autograd (torch.autograd.grad of the output w.r.t. s and x), so both candidates pay the same autograd bookkeeping; the
+    two are timed alternately in one process: `reps` windows of `batch` back-to-back calls each (HIP events around a window) after 3
+    warm-up calls, median / 10th / 90th percentile of the per-call time.  Bytes the fused pair has to move: s and x in, out out, the
+    shortcut's slice of dout in, dx out; over its time, against the 6.29 TB/s a float4 copy reaches on MI355X."""
+    import torch.nn.functional as F
+    sys.path.insert(0, os.path.join(ROOT, "semantic-embeddings_amd"))
+    from models.cifar_pyramidnet import block_widths
+    HBM = 6.29e12
+    n, widths = block_widths(272, 200, True)
+    shapes = []
+    for k in (n - 1, n, 2 * n - 1, 2 * n, 3 * n - 1):
+        stage, stride = k // n, 2 if k in (n, 2 * n) else 1
+        hw_out = 32 >> stage
+        shapes.append((k, 4 * widths[k - 1], 4 * widths[k], hw_out * stride, stride))
+
+    def windows(fns):
+        for f in fns:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(reps):
+            for j, f in enumerate(fns):                       # alternate: the same machine state for both candidates
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(batch):
+                    f()
+                b.record()
+                torch.cuda.synchronize()
+                ts[j].append(a.elapsed_time(b) / batch * 1e3)
+        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
+
+    for dtype, fmt, label in ((torch.float32, torch.contiguous_format, "fp32 NCHW"), (torch.bfloat16, torch.channels_last, "bf16 NHWC")):
+        for k, cin, c, hx, stride in shapes:
+            h = hx // stride
+            gen = torch.Generator(device="cuda").manual_seed(k)
+            s = torch.randn(B, c, h, h, device="cuda", generator=gen).to(dtype).contiguous(memory_format=fmt).requires_grad_(True)
+            x = torch.randn(B, cin, hx, hx, device="cuda", generator=gen).to(dtype).contiguous(memory_format=fmt).requires_grad_(True)
+            g = torch.randn(B, c, h, h, device="cuda", generator=gen).to(dtype).contiguous(memory_format=fmt)
+
+            def fused():
+                return torch.autograd.grad(sehip.shortcut_add(s, x, stride, 0), (s, x), g)
+
+            def composition():
+                sc = F.avg_pool2d(x, stride) if stride > 1 else x
+                return torch.autograd.grad(s + F.pad(sc, (0, 0, 0, 0, 0, c - cin)), (s, x), g)
+            (fs, fx), (ts_, tx) = fused(), composition()
+            assert torch.equal(fs, ts_) and float((fx.float() - tx.float()).abs().max()) <= 2.0 ** -7 * float(tx.float().abs().max())
+            kf, kt = windows((fused, composition))
+            eb = 4 if dtype == torch.float32 else 2
+            nbytes = eb * (2 * s.numel() + 2 * x.numel() + B * cin * h * h)
+            print("shortcut %s, block %d: s %d x %d x %d x %d, x %d channels at %d x %d, stride %d: fused %.1f us (%.1f-%.1f), torch "
+                  "composition %.1f us (%.1f-%.1f): x%.2f; the fused pair moves %.0f MB = %.0f GB/s = %.1f%% of the HBM copy rate"
+                  % (label, k, B, c, h, h, cin, hx, hx, stride, kf[0], kf[1], kf[2], kt[0], kt[1], kt[2], kt[0] / kf[0], nbytes / 1e6,
+                     nbytes / (kf[0] * 1e-6) / 1e9, 100.0 * nbytes / (kf[0] * 1e-6) / HBM), flush=True)
+            del s, x, g, fs, fx, ts_, tx
 
 
 if __name__ == "__main__":
