@@ -415,8 +415,9 @@ constexpr int RR_TWO_OUT = 256;
 // sorted on a monotone 24-bit IMAGE of the key, q = bits(fl(v + c)) - bits(c / 2) with c = the power of two that puts every |v| of
 // the row below 0.75 c (fl(v + c) lies in [c / 4, 7 c / 4]: rounding is monotone non-decreasing, so the image order never contradicts
 // the key order; below c / 2 the subtraction saturates at 0), again in two 12-bit passes -- and then REPAIRED: keys that share an
-// image (~1.3 % of a 50,000-column cosine row: the image's ulp is c 2^-24 below c and c 2^-23 above it) sit next to each other in index
-// order after the stable sort, and only their true (key, index) order can differ.  To SEE equal images at the final positions the low 8
+// image (~1.3 % of a 50,000-column cosine row: the image's ulp is c 2^-24 below c and c 2^-23 above it) sit next to each other after
+// the sort -- in NO particular order: only the second pass is stable (see RR_IMG_SET_WORDS) -- and the repair puts them into their
+// true (key, index) order.  To SEE equal images at the final positions the low 8
 // image bits are written as a one-byte TAG per COLUMN before the passes (tag plane, column order: consecutive lanes, consecutive
 // bytes -- a linear write under the image arithmetic); after the last pass the tag of final position i is tagb[xbuf[i]]: a scan reads
 // the indices in 16-byte groups, gathers their tags (one random byte read per key: 8 instead of 12 random LDS operations per key in
@@ -434,6 +435,24 @@ constexpr int RR_IMG_RUN = 8;          // longest run the repair sorts (entries)
 constexpr int RR_IMG_WL = 3072;        // worklist entries (run start | length << 16)
 constexpr int RR_IMG_MAX_ITEMS = 98;   // instantiations above this have no room for tags + worklist next to the exchange buffer
 constexpr uint32_t RR_IMG_NAN_PADHI = 0xFF0u;   // most significant image digit of the padding slots (real images end at 0xE00)
+// Pass 0 of a two-pass image row counts on ONE set of 4096 packed counters for the whole workgroup instead of one set per wave: the
+// returning add then hands a key its rank among ALL the workgroup's keys of its digit, in the order the adds were served -- the pass
+// is not stable.  It need not be: stability in pass 0 only decides the order of keys equal in all 24 image bits (keys that differ in
+// the high digit are separated by the stable pass 1), equal images have equal tags, so every such block lies inside a run the repair
+// sorts by (key, index) anyway.  One set: 4 zeroing stores per thread instead of 32 per lane, a counter scan over one set instead of
+// eight, and no aliasing of the exchange buffer (one barrier fewer).
+// LDS reuse of the image build, and the barrier behind each last use:
+//   worklist bytes = the shared set.  Last readers of the worklist: the repair loop (its closing barrier), or -- worklist overflow --
+//     nobody after the tag scan's barrier.  The set is zeroed at the top of the next row attempt, IN FRONT of the barrier of the
+//     maximum search, which therefore also orders the zeroes before every wave's adds.  Last readers of the set: pass 0's destination
+//     look-ups; the worklist is next written by the tag scan, behind the barriers of pass 0's exchanges and all of pass 1.
+//   exchange buffer.  Last readers before pass 0's index scatter: the previous row's write-out (or, a retried row, its scan / repair),
+//     in front of the barrier of the maximum search; pass 0 no longer keeps counters there, so nothing separates its destination
+//     look-ups from its scatter.  Pass 1 zeroes its per-wave sets there behind a barrier of its own (the last exchange read of pass 0
+//     lies in front of it) and keeps the barrier between its look-ups and its scatter.
+//   tag plane.  Written behind the barrier of the maximum search (the previous attempt's repair read it in front of that barrier),
+//     read by the tag scan and the repair.
+constexpr int RR_IMG_SET_WORDS = 2048;
 // Counters are 16 bits wide, two per LDS word (8 waves x 2048 digits x 2 B = 32 KB next to the 100 KB exchange
 // buffer): a wave holds at most 64 x 104 keys and a destination is < 53,248, so neither half can carry into the
 // other.  The returning add is done on the word with the increment shifted into the digit's half.
@@ -520,7 +539,8 @@ struct RRRankHW {
 };
 
 // LDS bytes in front of wave_tot / the exchange buffer: the dedicated per-wave counters, or (image path) the tag plane + worklist,
-// whichever is larger (the two are never live together: the image path's passes both use the counters aliased onto the exchange buffer)
+// whichever is larger (the two are never live together: pass 0 of the image path counts on the shared set in the worklist's bytes, pass 1
+// on the counters aliased onto the exchange buffer)
 template <int ITEMS, bool HWORD, int VAR>
 constexpr size_t rr_region0_bytes()
 {
@@ -720,6 +740,12 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) mb = max(mb, (uint32_t)__shfl_xor((int)mb, off, 64));
                 if (lane == 0) wave_tot[wave] = mb;
+                // pass 0 counts on ONE set of 4096 packed counters for the whole workgroup, in the worklist's bytes (see RR_IMG_SET_WORDS):
+                // 4 words per thread, zeroed here.  The worklist's last readers are the previous attempt's repair loop, which ends in a
+                // barrier, or -- worklist overflow -- nobody after the scan's barrier; the barrier below puts the zeroes in front of
+                // every wave's adds.  (A retried row comes through here again; a row that takes the three passes does not use the set.)
+                static_assert(!IMG || (RR_IMG_SET_WORDS == 4 * RR_THREADS && RR_IMG_SET_WORDS == RR_WIDE_WORDS && RR_IMG_SET_WORDS <= RR_IMG_WL), "one uint4 per thread, inside the worklist");
+                *reinterpret_cast<uint4 *>(wlist + 4 * tid) = make_uint4(0u, 0u, 0u, 0u);
                 wg_barrier();
                 // (behind the barrier: every wave has read the previous row's worklist cursor / give-up flag by now; the next use of either
                 // word lies behind the barriers of the passes)
@@ -860,7 +886,13 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
             // counters of this pass: the wave's slice of the dedicated region, or (wide pass) of the idle exchange buffer
             uint32_t *pcnt = wcnt;              // [RR_WAVES][pcw]
             int pcw = CNT_WORDS;
-            if (wide) {
+            // image path, pass 0 of a two-pass row: ONE counter set for the whole workgroup in the worklist's bytes, zeroed at the top
+            // of the row (wave-uniform).  The pass need not be stable -- see RR_IMG_SET_WORDS.
+            const bool shared0 = IMG && two && p == 0;
+            if (shared0) {
+                pcnt = wlist;
+                pcw = 0;                        // every wave's slice is the one set
+            } else if (wide) {
                 // every wave has finished reading the exchange buffer (previous pass's key exchange).  The FIRST pass of a two-pass row
                 // needs no barrier of its own: the row's qualification (image path: the maximum search; window path: two reductions) put
                 // one between the previous row's write-out -- the last reader of the buffer -- and this point.
@@ -870,11 +902,31 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
             }
             uint32_t *mycnt = pcnt + wave * pcw;
             const uint32_t cb = lds_off(mycnt);                             // this wave's digit counters, byte address
+            // "this pass counts on the one shared set", asked of the stride at every use: a flag kept in a scalar register pair across
+            // the pass costs the image build spills to vector lanes (and code bytes it does not have)
+            auto one_set = [&]() -> bool {
+                if constexpr (!IMG) return false;
+                int z = pcw;
+                asm volatile("" : "+s"(z));
+                return z == 0;
+            };
+            if constexpr (IMG) {
+                // 16 bytes per lane and store (the image build has no code bytes to spare: 8 stores instead of 32)
+                if (!one_set()) {
 #pragma unroll
-            for (int j = 0; j < CNT_WORDS / WAVE; j++) mycnt[j * WAVE + lane] = 0;
-            if (wide) {
+                    for (int j = 0; j < CNT_WORDS / (4 * WAVE); j++) reinterpret_cast<uint4 *>(mycnt)[j * WAVE + lane] = make_uint4(0u, 0u, 0u, 0u);
+                    if (wide) {
 #pragma unroll
-                for (int j = CNT_WORDS / WAVE; j < RR_WIDE_WORDS / WAVE; j++) mycnt[j * WAVE + lane] = 0;
+                        for (int j = CNT_WORDS / (4 * WAVE); j < RR_WIDE_WORDS / (4 * WAVE); j++) reinterpret_cast<uint4 *>(mycnt)[j * WAVE + lane] = make_uint4(0u, 0u, 0u, 0u);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < CNT_WORDS / WAVE; j++) mycnt[j * WAVE + lane] = 0;
+                if (wide) {
+#pragma unroll
+                    for (int j = CNT_WORDS / WAVE; j < RR_WIDE_WORDS / WAVE; j++) mycnt[j * WAVE + lane] = 0;
+                }
             }
             // HWORD digit split: low wlo bits = counter word, the rest (0 or 1 bit) = half
             [[maybe_unused]] const uint32_t wlo = wide ? 11u : 10u, whi = (uint32_t)(end - shift) - wlo, hshift = (uint32_t)(shift + (int)wlo) & 31u;
@@ -918,6 +970,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                 uint32_t T0 = 0, T1 = 0, U0 = 0, U1 = 0;   // per-word totals over the waves (U: second word group of the wide pass)
 #pragma unroll
                 for (int w = 0; w < RR_WAVES; w++) {
+                    if (w == 1 && one_set()) break;   // (the workgroup's one set: the loops of this phase stop behind their first trip)
                     const uint2 v = *reinterpret_cast<const uint2 *>(pcnt + w * pcw + 2 * st);
                     T0 += v.x; T1 += v.y;
                 }
@@ -925,6 +978,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                     __builtin_amdgcn_sched_barrier(0);   // one word group at a time: 2 x ITEMS registers are live across the scan
 #pragma unroll
                     for (int w = 0; w < RR_WAVES; w++) {
+                        if (w == 1 && one_set()) break;
                         const uint2 v = *reinterpret_cast<const uint2 *>(pcnt + w * pcw + CNT_WORDS + 2 * st);
                         U0 += v.x; U1 += v.y;
                     }
@@ -951,6 +1005,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                 uint32_t s0 = ex, s1 = ex + T0;
 #pragma unroll
                 for (int w = 0; w < RR_WAVES; w++) {
+                    if (w == 1 && one_set()) break;
                     uint2 *wp = reinterpret_cast<uint2 *>(pcnt + w * pcw + 2 * tid);
                     const uint2 v = *wp;
                     *wp = make_uint2(s0, s1);
@@ -961,6 +1016,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                     s0 = ex2; s1 = ex2 + U0;
 #pragma unroll
                     for (int w = 0; w < RR_WAVES; w++) {
+                        if (w == 1 && one_set()) break;
                         uint2 *wp = reinterpret_cast<uint2 *>(pcnt + w * pcw + CNT_WORDS + 2 * tid);
                         const uint2 v = *wp;
                         *wp = make_uint2(s0, s1);
@@ -997,7 +1053,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                 __builtin_amdgcn_sched_barrier(0);
             }
             }
-            if (wide) wg_barrier();   // the scatter below overwrites the (aliased) counters other waves may still be looking up
+            if (wide && !one_set()) wg_barrier();   // the scatter below overwrites the (aliased) counters other waves may still be looking up (not the shared set of pass 0: it lies in the worklist)
             RR_T(3)
             if constexpr (LOAD_IN_SCATTER) {
                 if (end >= 32) break;   // the last index scatter follows the loop: it also issues the next row's loads
@@ -1181,8 +1237,8 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                     // tags; the thread whose pair has no such pair in front of it owns the run: it finds the length from the tags behind the
                     // pair (2, 3 or "4 and more"), gathers the true keys from the row (L2 / Infinity Cache; all loads of all its runs in
                     // flight together) and puts runs of 2 and 3 -- nearly all -- into (key, index) order in registers; longer runs take a
-                    // loop (up to RR_IMG_RUN entries; beyond that the row is given up).  Equal keys keep their places: the sort was stable,
-                    // so equal images are already in index order.
+                    // loop (up to RR_IMG_RUN entries; beyond that the row is given up).  Equal keys are ordered by index HERE: pass 0 is
+                    // not stable, so equal images arrive in no particular order.
                     constexpr int GB = 2;
 #pragma unroll 1
                     for (uint32_t e0 = 0; e0 < nwork; e0 += RR_THREADS * GB) {
@@ -1213,6 +1269,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                             }
                             if (three) kc[k] = __float_as_uint(drow_cur[ic[k]]);
                         }
+                        uint32_t rare = 0;   // bit k: entry k owns a run of 4 and more
 #pragma unroll
                         for (int k = 0; k < GB; k++) {
                             if (pp[k] == 0xFFFFFFFFu) continue;
@@ -1220,33 +1277,43 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                             if (p != 0u && tm[k] == t0[k]) continue;                  // the pair in front has equal tags too: its owner takes this run
                             const bool three = (int)p + 2 < n_row && t2[k] == t0[k];
                             const bool more4 = three && (int)p + 3 < n_row && t3[k] == t0[k];
-                            const uint32_t ca = rr_key(ka[k], false, 0u), cb = rr_key(kb[k], false, 0u), cc = rr_key(kc[k], false, 0u);
+                            // (key : index) as one 64-bit number: no two entries compare equal
+                            const uint64_t ca = ((uint64_t)rr_key(ka[k], false, 0u) << 32) | ia[k], cb = ((uint64_t)rr_key(kb[k], false, 0u) << 32) | ib[k],
+                                           cc = ((uint64_t)rr_key(kc[k], false, 0u) << 32) | ic[k];
                             if (!three) {
                                 if (ca > cb) { xbuf[p] = (uint16_t)ib[k]; xbuf[p + 1] = (uint16_t)ia[k]; }
                             } else if (!more4) {
-                                // ranks by counting; ties keep the input order (a before b before c)
-                                const uint32_t ra = (cb < ca) + (cc < ca), rb = (ca <= cb) + (cc < cb), rc = (ca <= cc) + (cb <= cc);
+                                // ranks by counting
+                                const uint32_t ab = ca < cb, ac = ca < cc, bc = cb < cc;
+                                const uint32_t ra = 2u - ab - ac, rb = ab + 1u - bc, rc = ac + bc;
                                 if (ra != 0u || rb != 1u) {
                                     xbuf[p + ra] = (uint16_t)ia[k]; xbuf[p + rb] = (uint16_t)ib[k]; xbuf[p + rc] = (uint16_t)ic[k];
                                 }
-                            } else {
-                                // rare: 4 .. RR_IMG_RUN entries.  Everything in registers (unrolled, predicated); ranks by counting.
-                                int len = 4;
-                                while (len <= RR_IMG_RUN && (int)p + len < n_row && tagb[xbuf[p + len]] == t0[k]) len++;
-                                if (len > RR_IMG_RUN) { ictl[1] = 1u; continue; }
-                                uint32_t idx[RR_IMG_RUN], kk[RR_IMG_RUN];
+                            } else rare |= 1u << k;
+                        }
+                        // rare: 4 .. RR_IMG_RUN entries.  Everything in registers (unrolled, predicated); ranks by counting.  ONE copy of
+                        // this code for the thread's GB entries, behind the unrolled loop: it is cold, and the build has no code bytes to spare.
+                        static_assert(GB == 2, "the entry is picked by one select");
+#pragma unroll 1
+                        for (uint32_t k = 0; k < (uint32_t)GB; k++) {
+                            if (!((rare >> k) & 1u)) continue;
+                            const uint32_t p = k ? pp[1] : pp[0], tg = k ? t0[1] : t0[0];
+                            int len = 4;
+                            while (len <= RR_IMG_RUN && (int)p + len < n_row && tagb[xbuf[p + len]] == tg) len++;
+                            if (len > RR_IMG_RUN) { ictl[1] = 1u; continue; }
+                            uint32_t idx[RR_IMG_RUN];
+                            uint64_t kk[RR_IMG_RUN];   // (key : index)
 #pragma unroll
-                                for (int j = 0; j < RR_IMG_RUN; j++) idx[j] = xbuf[p + (uint32_t)(j < len ? j : 0)];
+                            for (int j = 0; j < RR_IMG_RUN; j++) idx[j] = xbuf[p + (uint32_t)(j < len ? j : 0)];
 #pragma unroll
-                                for (int j = 0; j < RR_IMG_RUN; j++) kk[j] = rr_key(__float_as_uint(drow_cur[idx[j]]), false, 0u);
+                            for (int j = 0; j < RR_IMG_RUN; j++) kk[j] = ((uint64_t)rr_key(__float_as_uint(drow_cur[idx[j]]), false, 0u) << 32) | idx[j];
 #pragma unroll
-                                for (int j = 0; j < RR_IMG_RUN; j++) {
-                                    uint32_t r = 0;
+                            for (int j = 0; j < RR_IMG_RUN; j++) {
+                                uint32_t r = 0;
 #pragma unroll
-                                    for (int i = 0; i < RR_IMG_RUN; i++)
-                                        if (i != j) r += (i < len && (kk[i] < kk[j] || (kk[i] == kk[j] && i < j))) ? 1u : 0u;
-                                    if (j < len) xbuf[p + r] = (uint16_t)idx[j];
-                                }
+                                for (int i = 0; i < RR_IMG_RUN; i++)
+                                    if (i != j) r += (i < len && kk[i] < kk[j]) ? 1u : 0u;
+                                if (j < len) xbuf[p + r] = (uint16_t)idx[j];
                             }
                         }
                     }
