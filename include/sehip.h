@@ -587,6 +587,34 @@ int se_recall_precision_reduce(const int32_t *hit_pos, const int64_t *hit_off, i
                                int bins, double *ap, double *prec_sum, int64_t *first_miss, double *bin_sum,
                                int64_t *bin_count, se_stream_t stream);
 
+/*
+ * Positions of the relevant items WITHOUT a ranking: count, per relevant item, the gallery columns that precede it.
+ * For a gallery that is not the query set (held-out queries against a database) no [q, n] ranking has to exist: the 1-based position
+ * of a relevant item in the canonical order of se_rank_rows is the number of gallery columns in front of it, plus one.
+ * Replaces: `np.argsort` + the relevance list of plot_recall_precision.py:52-79 / class_hierarchy.py:310-314 for
+ *           `hierarchical_precision(retrieved, labels, ..., ignore_qids)` on a query -> gallery mapping that is not all-pairs.
+ * se_count_preceding ACCUMULATES one distance slab (any tile of the gallery's columns, any shard: integer adds commute, the result
+ * does not depend on tiling, launch geometry or call order) into a histogram with the layout of hit_pos:
+ *   pdist     [q, n_cols] f32 distances of the q queries to gallery rows col_offset .. col_offset + n_cols (ldp elements between rows)
+ *   hit_off   [q + 1] int64: query i owns cnt[hit_off[i] .. hit_off[i + 1]), one bin per relevant item (R_i of them)
+ *   rel_d, rel_i [hit_off[q]] f32 / int32: distance and GLOBAL gallery index of every relevant item, per query sorted ascending in
+ *             the canonical order (distance ascending, index ascending, NaN last, -0 == +0); rel_i is only ever compared
+ *   qidx      [q] int32 global gallery index of the query itself (that column is skipped); NULL, or an entry < 0: not in the gallery
+ *   max_rel   an upper bound of R_i the caller knows (sizes the LDS of the launch), 0 = unknown; only the speed depends on it:
+ *             longer key lists, or lists above 5,460 keys, are searched in global memory
+ *   cnt       [hit_off[q]] int32 in/out: for every column j other than the query's own, with p = the number of the query's relevant
+ *             keys strictly before (pdist[i, j], col_offset + j):  cnt[hit_off[i] + p] += 1 if p < R_i.  A relevant column lands
+ *             in its own bin; columns behind the last relevant item are not counted.  Zero it before the first slab.
+ * q == 0 or n_cols == 0: SE_OK, nothing launched.  Asynchronous, no workspace, capturable.
+ * se_count_to_positions: inclusive prefix sum per query, hit_pos[hit_off[i] + s] = sum of cnt[hit_off[i] + p] over p <= s -- the
+ * position (query removed) of the (s + 1)-th relevant item, i.e. what se_relevant_positions writes; se_recall_precision_reduce
+ * consumes it unchanged.  hit_pos may be cnt itself.
+ */
+int se_count_preceding(const float *pdist, int64_t ldp, int64_t q, int64_t n_cols, int64_t col_offset,
+                       const int64_t *hit_off, const float *rel_d, const int32_t *rel_i, const int32_t *qidx,
+                       int64_t max_rel, int32_t *cnt, se_stream_t stream);
+int se_count_to_positions(const int32_t *cnt, const int64_t *hit_off, int64_t q, int32_t *hit_pos, se_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Classification side: linear SVM
  * ------------------------------------------------------------------------------------------ */

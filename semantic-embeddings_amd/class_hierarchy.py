@@ -320,7 +320,8 @@ class ClassHierarchy(object):
 
     def hierarchical_precision_device(self, features, labels, ks=[1, 10, 50, 100], compute_ahp=False, compute_ap=False,
                                       normalize=False, ids=None, tile_rows=None, distributed=False, group=None, kblocks=None,
-                                      gather_per_query=True, kernels=None, per_query=True, head_via_topk=True):
+                                      gather_per_query=True, kernels=None, per_query=True, head_via_topk=True,
+                                      gallery=None, gallery_labels=None, gallery_ids=None, tile_cols=None):
         """``hierarchical_precision(pairwise_retrieval(features, normalize), labels, ...)`` (ignore_qids = True, every
         image is query and gallery item) without leaving the GPU: the rankings stay device tensors
         (``evaluate_retrieval.ranking_tiles``) and the per-query gather + prefix sums run in
@@ -344,7 +345,18 @@ class ClassHierarchy(object):
         path otherwise).  ``kblocks`` (None | 'openblas' | list: the BLAS K-block list for D > 448) reaches BOTH paths -- the
         top-L kernels restart their FMA chain per block exactly like the full-ranking ones, so one process and G processes
         return the same near-tie orders.
-        ``kernels`` (tests): CPU stand-ins ``{'ranking_tiles', 'hierarchical_precision', 'local_topk', 'merge', 'device'}``."""
+        ``kernels`` (tests): CPU stand-ins ``{'ranking_tiles', 'hierarchical_precision', 'local_topk', 'merge', 'device'}``.
+
+        ``gallery`` (features like ``features``; ``gallery_labels`` defaults to ``labels``, ``gallery_ids`` like ``ids``): the rows of
+        ``features`` are QUERIES against this gallery -- the reference's ``hierarchical_precision(retrieved, labels, ...)`` for any
+        ``query id -> ranked gallery ids`` mapping.  A query whose id is a gallery id is dropped from its own ranking
+        (``ignore_qids``), the others keep every item; best-possible curves come from the gallery's class counts.  P@k / AHP@K take
+        the (sharded-gallery) fused top-L path, AP the counting path of ``recall_precision_device(..., gallery=...)``: no ranking of
+        the gallery is made.  Un-clipped AHP needs the whole list and raises ``ValueError`` here (CLI: pass ``--clip_ahp``)."""
+        if gallery is not None:
+            return self._hierarchical_precision_gallery(features, labels, ks, compute_ahp, compute_ap, normalize, ids, tile_rows, tile_cols,
+                                                        distributed, group, kblocks, gather_per_query, kernels, per_query, gallery,
+                                                        gallery_labels, gallery_ids)
         import torch
         from sharded_retrieval import shard_bounds, sharded_topk
         kernels = dict(kernels or {})
@@ -379,20 +391,7 @@ class ClassHierarchy(object):
         # then one float64 prefix sum per row.
         counts = np.bincount(cls_h, minlength=len(class_list))
 
-        def best_curves(table):
-            if torch.is_tensor(table):      # device table: the descending values are the same whatever order ties take
-                vals, order = torch.sort(table, dim=1, descending=True)
-                reps = torch.from_numpy(counts.astype(np.int64)).to(dev)[order]
-                flat = torch.repeat_interleave(vals.reshape(-1), reps.reshape(-1), output_size=len(class_list) * n)
-                return flat.view(len(class_list), n).cumsum(dim=1)
-            table = np.asarray(table, dtype=np.float64)
-            order = np.argsort(-table, axis=1, kind='stable')
-            vals = torch.from_numpy(np.take_along_axis(table, order, axis=1)).to(dev)
-            reps = torch.from_numpy(counts[order].astype(np.int64)).to(dev)
-            flat = torch.repeat_interleave(vals.reshape(-1), reps.reshape(-1), output_size=len(class_list) * n)
-            return flat.view(len(class_list), n).cumsum(dim=1)
-
-        best_w, best_l = best_curves(wup_t), best_curves(lcs_t)
+        best_w, best_l = _best_curves(wup_t, counts, n, dev), _best_curves(lcs_t, counts, n, dev)
 
         import torch.distributed as dist
         world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
@@ -449,6 +448,84 @@ class ClassHierarchy(object):
                 outs.append(kernels['hierarchical_precision'](tile, cls_d, cls_d[r0:r0 + rows].contiguous(), qidx_d[r0:r0 + rows].contiguous(),
                                                              *args_d, ks_d, ahp_len=ahp_len, want_ap=compute_ap, **extra))
         res_d = torch.cat(outs) if outs else torch.zeros((0, ncol), dtype=torch.float64, device=dev)
+        return self._metric_rows_to_results(res_d, n, ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query)
+
+    def _hierarchical_precision_gallery(self, features, labels, ks, compute_ahp, compute_ap, normalize, ids, tile_rows, tile_cols, distributed,
+                                        group, kblocks, gather_per_query, kernels, per_query, gallery, gallery_labels, gallery_ids):
+        """``hierarchical_precision_device`` with a separate gallery (see there)."""
+        import warnings
+        import torch
+        import torch.distributed as dist
+        from evaluate_retrieval import _resolve_kblocks
+        from recall_precision import gallery_problem, recall_precision_device, _to_device_f32
+        from sharded_retrieval import shard_bounds, sharded_topk
+        if compute_ahp is True:
+            raise ValueError('un-clipped AHP needs the whole ranking of the gallery, which a separate gallery never gets: '
+                             'pass compute_ahp=K (--clip_ahp K on the command line)')
+        kernels = dict(kernels or {})
+        stand_ins = bool(kernels)
+        native_metrics = 'hierarchical_precision' not in kernels
+        if native_metrics:
+            import sehip
+            kernels['hierarchical_precision'] = sehip.hierarchical_precision
+        ks = [ks] if isinstance(ks, int) else list(ks)
+        ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
+        qf, gf, q_ids, qcls_h, gcls_h, class_list, qidx_h = gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids)
+        nq, ng = int(qf.shape[0]), int(gf.shape[0])
+        dev = torch.device(kernels.get('device') or torch.device('cuda', torch.cuda.current_device()))
+        if (not stand_ins) and dev.type == 'cuda':
+            wup_t, lcs_t = self.similarity_tables_device(class_list, device=dev)
+        else:
+            wup_t, lcs_t = self.similarity_tables(class_list)
+        counts = np.bincount(gcls_h, minlength=len(class_list))
+        L = min(ng, max(ks + [ahp_clip or 0]) + 1)
+        args_d = [_on_device(a, dev) for a in (wup_t, lcs_t)] + [_best_curves(t, counts, ng, dev)[:, :L + 1].contiguous() for t in (wup_t, lcs_t)]
+        world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
+        rank = dist.get_rank(group) if world > 1 else 0
+        q0, q1 = shard_bounds(nq, world)[rank] if world > 1 else (0, nq)
+        g0, g1 = shard_bounds(ng, world)[rank]
+        fq, fg = _to_device_f32(qf, dev), _to_device_f32(gf, dev)
+        if 'local_topk' not in kernels:
+            import sehip
+            if normalize:
+                sehip.normalize_rows_(fq)
+                sehip.normalize_rows_(fg)
+            metric = sehip.METRIC_COSINE if normalize else sehip.METRIC_EUCLID
+        else:
+            metric = None
+        _, top_i = sharded_topk(fq, fg[g0:g1], L, g0, metric=metric, group=group, local_topk=kernels.get('local_topk'),
+                                merge=kernels.get('merge'), kblocks=_resolve_kblocks(kblocks, int(fq.shape[1])))
+        ncol = 2 * len(ks) + 3
+        res_d = torch.zeros((0, ncol), dtype=torch.float64, device=dev)
+        if q1 > q0:
+            extra = {}
+            if native_metrics:
+                import sehip
+                extra = {'curves': sehip.hprec_reciprocal_curves(args_d[2], args_d[3])}
+            res_d = kernels['hierarchical_precision'](
+                top_i[q0:q1].contiguous(), torch.from_numpy(gcls_h).to(dev), torch.from_numpy(qcls_h[q0:q1].copy()).to(dev),
+                torch.from_numpy(qidx_h[q0:q1].copy()).to(dev), *args_d, torch.tensor(ks, dtype=torch.int32, device=dev),
+                ahp_len=-1 if not compute_ahp else ahp_clip, want_ap=False, **extra)
+        if compute_ap:      # counted, not ranked; every rank gets every query's AP
+            rp_names = ('normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows', 'count_preceding', 'count_to_positions',
+                        'recall_precision_reduce', 'device')
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore', RuntimeWarning)      # queries without a relevant item: AP 0, as in the reference
+                aps = recall_precision_device(features, labels, normalize=normalize, ids=ids, kblocks=kblocks, tile_rows=tile_rows,
+                                              tile_cols=tile_cols, kernels={k: v for k, v in kernels.items() if k in rp_names},
+                                              gallery=gallery, gallery_labels=gallery_labels, gallery_ids=gallery_ids,
+                                              distributed=distributed, group=group)[3]
+            res_d[:, 2 * len(ks) + 2] = torch.from_numpy(aps[q0:q1]).to(dev)
+        return self._metric_rows_to_results(res_d, nq, q_ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query)
+
+    def _metric_rows_to_results(self, res_d, n, ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query):
+        """``(means, per_query)`` from this rank's rows ``q0 .. q1`` of se_hierarchical_precision's output (all-gathered, or only their
+        sums all-reduced, under several ranks)."""
+        import torch
+        import torch.distributed as dist
+        from sharded_retrieval import shard_bounds
+        ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
+        ncol, dev = 2 * len(ks) + 3, res_d.device
         sums = None
         if world > 1:
             if gather_per_query and per_query:    # ragged all-gather: pad every shard to the largest one
@@ -487,6 +564,24 @@ class ClassHierarchy(object):
             sums = sums.cpu().numpy()
             return {name: float(sums[c]) / n for name, c in col.items()}, prec
         return {metric: sum(values.values()) / len(values) for metric, values in prec.items()}, prec
+
+
+def _best_curves(table, counts, n, dev):
+    """[C, n] float64 device curves: per query class the C similarity values in descending order, each repeated by the gallery's count
+    of its class (``counts``, n items in all), then one prefix sum per row."""
+    import torch
+    C = len(counts)
+    if torch.is_tensor(table):      # device table: the descending values are the same whatever order ties take
+        vals, order = torch.sort(table, dim=1, descending=True)
+        reps = torch.from_numpy(counts.astype(np.int64)).to(dev)[order]
+        flat = torch.repeat_interleave(vals.reshape(-1), reps.reshape(-1), output_size=C * n)
+        return flat.view(C, n).cumsum(dim=1)
+    table = np.asarray(table, dtype=np.float64)
+    order = np.argsort(-table, axis=1, kind='stable')
+    vals = torch.from_numpy(np.take_along_axis(table, order, axis=1)).to(dev)
+    reps = torch.from_numpy(counts[order].astype(np.int64)).to(dev)
+    flat = torch.repeat_interleave(vals.reshape(-1), reps.reshape(-1), output_size=C * n)
+    return flat.view(C, n).cumsum(dim=1)
 
 
 def _on_device(table, dev):

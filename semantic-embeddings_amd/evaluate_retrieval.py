@@ -15,7 +15,10 @@ reference: evaluate_retrieval.py:22-73 (pairwise_retrieval), :76-151 (reporting 
   metrics are combined with one small all-reduce; rank 0 prints / writes / plots (SURVEY.md section 8e row 2);
 * ``--skip_ap`` (extension) drops the average-precision column; together with ``--clip_ahp`` no metric needs more than the
   head of each ranking, and under several ranks the SHARDED-GALLERY path is taken: per-shard fused distance + top-k,
-  RCCL all-gather of the per-shard lists, k-way merge.
+  RCCL all-gather of the per-shard lists, k-way merge (SURVEY.md section 8e row 3);
+* ``--gallery_feat FILE`` (extension, with ``--gallery_split``): the --feat file at the same position holds QUERIES against this
+  gallery -- held-out images against a database.  The gallery is never ranked in full: P@k / AHP@K read fused top-k lists
+  (``--clip_ahp`` is required), AP counts the gallery items in front of every relevant one (``se_count_preceding``).
 """
 import argparse
 import os.path
@@ -319,7 +322,35 @@ def build_parser():
     g.add_argument('--skip_ap', action='store_true', default=False,
                    help='Do not compute AP; with --clip_ahp only the head of each ranking is needed (sharded-gallery top-k under several ranks).')
     g.add_argument('--kblocks', type=str, default=None, help="'openblas': restart the fp32 dot-product chain per OpenBLAS K block (D > 448).")
+    add_gallery_flags(g)
     return p
+
+
+def add_gallery_flags(group):
+    """--gallery_feat / --gallery_split of evaluate_retrieval.py and plot_recall_precision.py: every --feat file becomes a set of QUERIES
+    against the gallery file at the same position (no --gallery_feat: all-pairs on the --feat file, as the reference does)."""
+    group.add_argument('--gallery_feat', type=str, action='append',
+                       help='Feature pickle of the GALLERY the matching --feat is queried against (not ranked in full: AP is counted, '
+                            'P@k / AHP@K come from top-k lists; needs --clip_ahp); repeatable.')
+    group.add_argument('--gallery_split', type=str, default='train', choices=['train', 'test'],
+                       help='Dataset split the ids of --gallery_feat belong to.')
+
+
+def gallery_arguments(args, i, data_generator, embed_labels):
+    """Keyword arguments ``gallery`` / ``gallery_labels`` / ``gallery_ids`` of the device metric functions for the ``i``-th --feat
+    file: empty without a matching --gallery_feat.  Gallery items of the 'test' split share their ids with the queries (a query that
+    is a gallery item is dropped from its own ranking); items of the 'train' split are other images whatever their number, so
+    their ids are made distinct: ``('train', id)``."""
+    if not args.gallery_feat or i >= len(args.gallery_feat):
+        return {}
+    features, ind2id, _ = _as_feature_matrix(args.gallery_feat[i])
+    split_labels = data_generator.labels_train if args.gallery_split == 'train' else data_generator.labels_test
+    if embed_labels is not None:
+        split_labels = [embed_labels[lbl] for lbl in split_labels]
+    ids = list(range(len(features))) if ind2id is None else ind2id.tolist()
+    if args.gallery_split == 'test':
+        return {'gallery': features, 'gallery_labels': split_labels, 'gallery_ids': ids}
+    return {'gallery': features, 'gallery_labels': {('train', j): split_labels[j] for j in ids}, 'gallery_ids': [('train', j) for j in ids]}
 
 
 def init_distributed():
@@ -375,7 +406,8 @@ def main(argv=None):
         perf[feat_name] = hierarchy.hierarchical_precision_device(
             features, labels_test, ks, compute_ahp=args.clip_ahp if args.clip_ahp else True, compute_ap=not args.skip_ap,
             normalize=normalize, ids=None if ind2id is None else ind2id.tolist(), distributed=world > 1,
-            kblocks=args.kblocks, per_query=False)[0]      # the tables / plots below use the means only
+            kblocks=args.kblocks, per_query=False,         # the tables / plots below use the means only
+            **gallery_arguments(args, i, data_generator, embed_labels))[0]
     if rank != 0:
         return perf
 

@@ -9,6 +9,8 @@ reference: plot_recall_precision.py:19-86.  Differences a user can observe:
   ``--bins``), with a warning;
 * extensions (own argument group): ``--save FILE`` writes the figure instead of showing it (backend from the extension),
   ``--csv FILE`` writes ``feature,level,mean_precision`` rows, ``--kblocks openblas`` reaches the ranking (D > 448);
+  ``--gallery_feat FILE`` / ``--gallery_split`` (a group of their own): the matching ``--feat`` file holds queries against that
+  gallery, whose relevant items are located by counting instead of by ranking the gallery;
 * matplotlib is only imported when a figure is drawn; with ``--csv`` and without matplotlib the figure is skipped.
 """
 import argparse
@@ -16,7 +18,7 @@ import os.path
 import pickle
 from collections import OrderedDict
 
-from evaluate_retrieval import _as_feature_matrix, str2bool
+from evaluate_retrieval import _as_feature_matrix, add_gallery_flags, gallery_arguments, str2bool
 
 
 def build_parser():
@@ -38,6 +40,7 @@ def build_parser():
     g.add_argument('--save', type=str, default=None, help='Write the figure to this file (format from the extension) instead of showing it.')
     g.add_argument('--csv', type=str, default=None, help='Write "feature,level,mean_precision" rows to this file.')
     g.add_argument('--kblocks', type=str, default=None, help="'openblas': restart the fp32 dot-product chain per OpenBLAS K block (D > 448).")
+    add_gallery_flags(p.add_argument_group('Extensions of this build: queries against a separate gallery (not in the reference)'))
     return p
 
 
@@ -93,7 +96,8 @@ def main(argv=None):
         normalize = args.norm[i] if (args.norm is not None) and (i < len(args.norm)) else False
         features, ind2id, _ = _as_feature_matrix(feat_dump)
         levels, means, mAP, _ = recall_precision_device(features, labels_test, normalize=normalize, bins=args.bins,
-                                                        ids=None if ind2id is None else ind2id.tolist(), kblocks=args.kblocks)
+                                                        ids=None if ind2id is None else ind2id.tolist(), kblocks=args.kblocks,
+                                                        **gallery_arguments(args, i, data_generator, embed_labels))
         curves[feat_name] = (levels, means, mAP)
         print('{}: mAP {:.4f}, {} levels'.format(feat_name, mAP, len(levels)))
     if args.csv:

@@ -20,6 +20,10 @@ Edge cases:
   as in the reference's dict.
 * bin indices are computed as Python does: ``int((j / R) * B)`` in IEEE float64.
 * ties: the device ranking is the canonical (stable) one; nothing here handles ties on its own.
+
+Queries against a separate gallery (``recall_precision_device(..., gallery=...)``): the same statement with ``p_j`` the position in
+the query's ranking of the GALLERY, the query's own gallery item (same id) removed where there is one.  The positions are counted
+(``se_count_preceding`` / ``se_count_to_positions``: gallery columns in front of each relevant item), never read off a ranking.
 """
 import warnings
 
@@ -85,7 +89,53 @@ def recall_precision_host(ranking, labels, bins=None):
     return levels, means, float(np.mean(aps)) if n else float('nan'), aps
 
 
-def recall_precision_device(features, labels, normalize=False, bins=None, ids=None, kblocks=None, tile_rows=None, kernels=None):
+def recall_precision_host_gallery(ranking, query_labels, gallery_labels, qidx=None, bins=None):
+    """``recall_precision_host`` for queries that are not the gallery: ``ranking`` [Q, N] ints, row i is query i's ranking of the
+    gallery items 0 .. N - 1; ``query_labels[i]`` / ``gallery_labels[j]`` their classes; ``qidx[i]`` the gallery item that IS
+    query i (removed from its ranking, the reference's ``ignore_qids``), -1 / None when it is not in the gallery.  A query whose
+    class has no (other) gallery item gets AP 0 and no curve points.  Returns ``(levels, mean_precision, mAP, per_query_ap)``."""
+    ranking = np.asarray(ranking)
+    cls, _ = _class_indices(list(query_labels) + list(gallery_labels))
+    nq = ranking.shape[0]
+    qcls, gcls = cls[:nq], cls[nq:]
+    bins = int(bins) if bins else 0
+    recprec = {}
+    aps = np.zeros(nq, dtype=np.float64)
+    n_single = 0
+    for q in range(nq):
+        row = ranking[q]
+        if qidx is not None and qidx[q] >= 0:
+            row = row[row != qidx[q]]
+        pos = np.flatnonzero(gcls[row] == qcls[q]) + 1
+        R = len(pos)
+        if R == 0:
+            n_single += 1
+            continue
+        j = np.arange(1, R + 1)
+        prec = j / pos
+        aps[q] = prec.sum() / R
+        if bins:
+            b = ((j / R) * bins).astype(np.int64)
+            best = {}
+            if pos[0] > 1:
+                best[0] = 0.0
+            for bi, p in zip(b.tolist(), prec.tolist()):
+                best[bi] = max(best[bi], p) if bi in best else p
+            pts = zip(_bin_keys(list(best), bins).tolist(), best.values())
+        else:
+            pts = list(zip((j / R).tolist(), prec.tolist()))
+            if pos[0] > 1:
+                pts.append((0.0, 0.0))
+        for key, p in pts:
+            recprec.setdefault(key, []).append(p)
+    _warn_singletons(n_single)
+    levels = np.array(sorted(recprec), dtype=np.float64)
+    means = np.array([np.mean(recprec[k]) for k in levels.tolist()], dtype=np.float64)
+    return levels, means, float(np.mean(aps)) if nq else float('nan'), aps
+
+
+def recall_precision_device(features, labels, normalize=False, bins=None, ids=None, kblocks=None, tile_rows=None, kernels=None,
+                            gallery=None, gallery_labels=None, gallery_ids=None, tile_cols=None, distributed=False, group=None):
     """``plot_recall_precision.py``'s per-feature-file computation (lines 52-79) without leaving the GPU: the rankings stay device
     tensors (``evaluate_retrieval.ranking_tiles``; every image is query and gallery item), ``se_relevant_positions`` finds the
     positions of each query's relevant items, ``se_recall_precision_reduce`` turns them into per-query AP and per-class sums
@@ -95,7 +145,18 @@ def recall_precision_device(features, labels, normalize=False, bins=None, ids=No
     ``labels``: class label of image ``ids[i]`` (``ids`` defaults to the dict's keys, else ``range(N)``), a sequence or a mapping.
     ``bins``: None, or the number of recall bins of the reference's ``--bins``.  ``kblocks``: as ``ranking_tiles``.
     ``kernels`` (tests): CPU stand-ins ``{'ranking_tiles', 'relevant_positions', 'recall_precision_reduce', 'device'}``.
-    Returns ``(levels, mean_precision, mAP, per_query_ap)``; see the module docstring for the edge cases."""
+    Returns ``(levels, mean_precision, mAP, per_query_ap)``; see the module docstring for the edge cases.
+
+    ``gallery`` (features in any of the forms above): the rows of ``features`` are QUERIES against this gallery instead of against
+    each other; ``gallery_labels`` (default ``labels``) and ``gallery_ids`` name its items like ``labels`` / ``ids`` do the queries.
+    A query whose id is also a gallery id is removed from its own ranking (the reference's ``ignore_qids``); a gallery given as a plain
+    matrix without ``gallery_ids`` shares no id with the queries.  No ranking of the gallery is made: the positions of the relevant
+    items are counted (``query_gallery_positions``), so the gallery may be far longer than a row ``se_rank_rows`` sorts in registers.
+    ``tile_cols`` (tests): gallery columns per distance slab.  ``distributed``: every rank counts over its shard of the gallery
+    (``sharded_retrieval.shard_bounds``) and ONE integer all-reduce per query tile adds the counts; all ranks return the same values."""
+    if gallery is not None:
+        return _recall_precision_gallery(features, labels, normalize, bins, ids, kblocks, tile_rows, tile_cols, kernels, gallery,
+                                         gallery_labels, gallery_ids, distributed, group)
     import torch
     from evaluate_retrieval import _as_feature_matrix
 
@@ -148,8 +209,14 @@ def recall_precision_device(features, labels, normalize=False, bins=None, ids=No
         kernels['recall_precision_reduce'](hit_pos, hit_off_d, torch.from_numpy(order).to(dev), torch.from_numpy(class_start).to(dev),
                                            class_off_d, bins, ap[r0:r0 + rows], prec_sum, first_miss, bin_sum, bin_count)
 
-    ap_h = ap.cpu().numpy()
     _warn_singletons(int(counts[r_cls == 0].sum()))
+    return _merge_levels(ap.cpu().numpy(), r_cls, counts, class_off, bins, prec_sum, first_miss, bin_sum, bin_count)
+
+
+def _merge_levels(ap_h, r_cls, nq_cls, class_off, bins, prec_sum, first_miss, bin_sum, bin_count):
+    """Per-class device sums -> ``(levels, mean_precision, mAP, per_query_ap)`` in float64: ``r_cls[c]`` relevant items of every query
+    of class c, ``nq_cls[c]`` its queries."""
+    n = len(ap_h)
     if bins:
         bs, bc = bin_sum.cpu().numpy(), bin_count.cpu().numpy()
         tot_s, tot_c = bs.sum(axis=0), bc.sum(axis=0)
@@ -158,11 +225,11 @@ def recall_precision_device(features, labels, normalize=False, bins=None, ids=No
     else:
         S, miss = prec_sum.cpu().numpy(), first_miss.cpu().numpy()
         keys, sums, cnts = [], [], []
-        for c in np.flatnonzero(r_cls > 0):
+        for c in np.flatnonzero((r_cls > 0) & (nq_cls > 0)):
             R = int(r_cls[c])
             keys.append(np.arange(1, R + 1) / R)
             sums.append(S[class_off[c]:class_off[c + 1]])
-            cnts.append(np.full(R, counts[c], dtype=np.int64))
+            cnts.append(np.full(R, nq_cls[c], dtype=np.int64))
             if miss[c] > 0:
                 keys.append(np.zeros(1))
                 sums.append(np.zeros(1))
@@ -174,3 +241,187 @@ def recall_precision_device(features, labels, normalize=False, bins=None, ids=No
             levels, means = np.zeros(0), np.zeros(0)
     return (np.asarray(levels, dtype=np.float64), np.asarray(means, dtype=np.float64),
             float(ap_h.mean()) if n else float('nan'), ap_h)
+
+
+# ---------------------------------------------------------------------------------------------- queries against a separate gallery
+
+def _ids_of(ind2id, ids, n):
+    if ids is None and ind2id is not None:
+        ids = ind2id.tolist()
+    if ids is not None and len(ids) != n:
+        raise ValueError('{} ids for {} feature rows'.format(len(ids), n))
+    return None if ids is None else list(ids)
+
+
+def gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids):
+    """Host bookkeeping of a query-vs-gallery evaluation: ``(query features, gallery features, query ids, qcls, gcls, class list,
+    qidx)`` -- class indices int32 over the sorted union of the classes on either side, ``qidx[i]`` the (first) gallery row whose
+    id equals query i's id, else -1."""
+    from evaluate_retrieval import _as_feature_matrix
+    qf, q_ind2id, _ = _as_feature_matrix(features)
+    gf, g_ind2id, _ = _as_feature_matrix(gallery)
+    if int(qf.shape[1]) != int(gf.shape[1]):
+        raise ValueError('queries have {} feature dimensions, the gallery {}'.format(qf.shape[1], gf.shape[1]))
+    nq, ng = int(qf.shape[0]), int(gf.shape[0])
+    q_ids = _ids_of(q_ind2id, ids, nq)
+    g_ids = _ids_of(g_ind2id, gallery_ids, ng)
+    q_ids = list(range(nq)) if q_ids is None else q_ids
+    gallery_labels = labels if gallery_labels is None else gallery_labels
+    q_lab = [labels[i] for i in q_ids]
+    g_lab = [gallery_labels[i] for i in (range(ng) if g_ids is None else g_ids)]
+    class_list = sorted(set(q_lab) | set(g_lab), key=lambda c: (str(type(c)), c))
+    pos = {c: i for i, c in enumerate(class_list)}
+    qcls = np.array([pos[c] for c in q_lab], dtype=np.int32)
+    gcls = np.array([pos[c] for c in g_lab], dtype=np.int32)
+    qidx = np.full(nq, -1, dtype=np.int32)
+    if g_ids is not None:
+        row_of = {}
+        for j, g in enumerate(g_ids):
+            row_of.setdefault(g, j)
+        qidx = np.array([row_of.get(i, -1) for i in q_ids], dtype=np.int32)
+    return qf, gf, q_ids, qcls, gcls, class_list, qidx
+
+
+def _gallery_kernels(kernels):
+    kernels = dict(kernels or {})
+    names = ('normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows', 'count_preceding', 'count_to_positions', 'recall_precision_reduce')
+    if any(k not in kernels for k in names):
+        import sehip
+
+        def pairwise_dist(a, b, cosine, sqa, sqb, kblocks, out=None):
+            return sehip.pairwise_dist(a, b, metric=sehip.METRIC_COSINE if cosine else sehip.METRIC_EUCLID, sqa=sqa, sqb=sqb,
+                                       kblocks=kblocks, out=out)
+
+        native = {'pairwise_dist': pairwise_dist}
+        for k in names:
+            kernels.setdefault(k, native.get(k) or getattr(sehip, k))
+    return kernels
+
+
+def _to_device_f32(x, dev):
+    import torch
+    if torch.is_tensor(x):
+        return x.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+
+
+def _recall_precision_gallery(features, labels, normalize, bins, ids, kblocks, tile_rows, tile_cols, kernels, gallery, gallery_labels,
+                              gallery_ids, distributed, group):
+    """``recall_precision_device`` with a separate gallery.  Per query tile (queries sorted by class):
+
+    1. relevant keys: per class of the tile, the distances of its queries to the gathered gallery rows of that class
+       (``se_pairwise_dist``: an element's fp32 chain depends on its two rows only, so these are the bits the slabs will hold),
+       each row ordered by ``se_rank_rows``; the query's own gallery row is taken out;
+    2. counting: (tile x gallery tile) distance slabs -> ``se_count_preceding``, over this rank's shard of the gallery, then ONE
+       integer all-reduce of the counts;
+    3. ``se_count_to_positions`` -> the input of ``se_recall_precision_reduce``; scan and reduce run on every rank (they cost a
+       thousandth of the counting), so all ranks hold the same bits without a float64 collective."""
+    import torch
+    import torch.distributed as dist
+    from evaluate_retrieval import _resolve_kblocks
+    from sharded_retrieval import shard_bounds
+
+    kernels = _gallery_kernels(kernels)
+    bins = int(bins) if bins else 0
+    if bins < 0:
+        raise ValueError('bins must be a positive number of recall levels')
+    qf, gf, _, qcls, gcls, class_list, qidx = gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids)
+    nq, ng, C = int(qf.shape[0]), int(gf.shape[0]), len(class_list)
+    dev = torch.device(kernels.get('device') or torch.device('cuda', torch.cuda.current_device()))
+    kb = _resolve_kblocks(kblocks, int(qf.shape[1]))
+    fq, fg = _to_device_f32(qf, dev), _to_device_f32(gf, dev)
+    if normalize:
+        kernels['normalize_rows_'](fq)
+        kernels['normalize_rows_'](fg)
+        sq_q = sq_g = None
+    else:
+        sq_q, sq_g = kernels['row_sqnorm'](fq), kernels['row_sqnorm'](fg)
+    world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
+    g_lo, g_hi = shard_bounds(ng, world)[dist.get_rank(group)] if world > 1 else (0, ng)
+
+    # reduce classes: queries of one class share R only if they agree on being in the gallery -- class 2 c + present
+    gcounts = np.bincount(gcls, minlength=C)
+    present = (qidx >= 0) & (gcls[np.maximum(qidx, 0)] == qcls) if ng else np.zeros(nq, dtype=bool)
+    rc = 2 * qcls.astype(np.int64) + present
+    r_rc = np.repeat(gcounts, 2).astype(np.int64)
+    r_rc[1::2] -= 1
+    r_rc = np.maximum(r_rc, 0)
+    nq_rc = np.bincount(rc, minlength=2 * C)
+    class_off = np.concatenate([[0], np.cumsum(r_rc)]).astype(np.int64)
+    by_class = torch.from_numpy(np.argsort(gcls, kind='stable')).to(dev)                     # gallery rows class by class, ascending inside
+    class_at = np.concatenate([[0], np.cumsum(gcounts)])
+    members = [by_class[class_at[c]:class_at[c + 1]] for c in range(C)]
+
+    class_off_d = torch.from_numpy(class_off).to(dev)
+    ap_sorted = torch.zeros(nq, dtype=torch.float64, device=dev)
+    prec_sum = torch.zeros(max(int(class_off[-1]), 1), dtype=torch.float64, device=dev)[:int(class_off[-1])]
+    first_miss = torch.zeros(2 * C, dtype=torch.int64, device=dev)
+    bin_sum = torch.zeros((2 * C, bins + 1), dtype=torch.float64, device=dev) if bins else None
+    bin_count = torch.zeros((2 * C, bins + 1), dtype=torch.int64, device=dev) if bins else None
+
+    order_q = np.argsort(rc, kind='stable')
+    tile_cols = min(max(ng, 1), int(tile_cols or 65536))
+    tile_rows = min(max(nq, 1), int(tile_rows or max(128, (1 << 30) // (4 * tile_cols))))
+    slab = None
+    if dev.type == 'cuda':       # the grow-only distance buffer ranking_tiles uses: the CLI's next --feat pays no allocation
+        from evaluate_retrieval import _cached_rows
+        slab = _cached_rows('pd', tile_rows, tile_cols, torch.float32, dev)
+    for t0 in range(0, nq, tile_rows):
+        sel = order_q[t0:t0 + tile_rows]
+        rows = len(sel)
+        sel_d = torch.from_numpy(sel).to(dev)
+        q_rows = fq[sel_d]
+        sq_rows = None if sq_q is None else sq_q[sel_d]
+        rc_t = rc[sel]
+        hit_off = np.concatenate([[0], np.cumsum(r_rc[rc_t])]).astype(np.int64)
+        total = int(hit_off[-1])
+        qidx_d = torch.from_numpy(qidx[sel]).to(dev)
+        class_start = np.concatenate([[0], np.cumsum(np.bincount(rc_t, minlength=2 * C))]).astype(np.int32)
+        # ---- 1. the relevant items' keys, class run by class run (the rows of a run are consecutive: the tile is sorted) ----
+        rel_d, rel_i = [], []
+        for k in np.flatnonzero(np.diff(class_start) > 0):
+            if r_rc[k] == 0:
+                continue
+            a, b = int(class_start[k]), int(class_start[k + 1])
+            mem = members[k // 2]
+            pd_c = kernels['pairwise_dist'](q_rows[a:b], fg[mem], normalize, None if sq_rows is None else sq_rows[a:b],
+                                            None if sq_g is None else sq_g[mem], kb)
+            rk = kernels['rank_rows'](pd_c).long()
+            d_sorted, i_sorted = torch.gather(pd_c, 1, rk), mem[rk].to(torch.int32)
+            if k % 2:        # these queries are gallery items of their own class: that one entry leaves every row
+                keep = i_sorted != qidx_d[a:b, None]
+                d_sorted, i_sorted = d_sorted[keep], i_sorted[keep]
+            rel_d.append(d_sorted.reshape(-1))
+            rel_i.append(i_sorted.reshape(-1))
+        rel_d = torch.cat(rel_d) if rel_d else torch.zeros(0, dtype=torch.float32, device=dev)
+        rel_i = torch.cat(rel_i) if rel_i else torch.zeros(0, dtype=torch.int32, device=dev)
+        if int(rel_d.numel()) != total:
+            raise RuntimeError('relevant keys: {} found, {} expected (duplicate gallery ids?)'.format(int(rel_d.numel()), total))
+        pad = max(total, 1)      # the kernels take no NULL: a tile without any relevant item still passes one element
+        rel_d = torch.cat([rel_d, torch.zeros(pad - total, dtype=torch.float32, device=dev)]).contiguous()
+        rel_i = torch.cat([rel_i, torch.zeros(pad - total, dtype=torch.int32, device=dev)]).contiguous()
+        cnt = torch.zeros(pad, dtype=torch.int32, device=dev)
+        hit_off_d = torch.from_numpy(hit_off).to(dev)
+        # ---- 2. counting over this rank's gallery rows ----
+        max_rel = int(r_rc[rc_t].max()) if rows else 0
+        for g0 in range(g_lo, g_hi, tile_cols):
+            g1 = min(g_hi, g0 + tile_cols)
+            pd = kernels['pairwise_dist'](q_rows, fg[g0:g1], normalize, sq_rows, None if sq_g is None else sq_g[g0:g1], kb,
+                                          None if slab is None else slab[:rows, :g1 - g0])
+            kernels['count_preceding'](pd, g0, hit_off_d, rel_d, rel_i, qidx_d, cnt, max_rel)
+        if world > 1:
+            if cnt.is_cuda and dist.get_backend(group) == 'gloo':
+                host = cnt.cpu()
+                dist.all_reduce(host, group=group)
+                cnt.copy_(host)
+            else:
+                dist.all_reduce(cnt, group=group)
+        # ---- 3. positions, AP and the per-class sums ----
+        hit_pos = kernels['count_to_positions'](cnt, hit_off_d)
+        kernels['recall_precision_reduce'](hit_pos, hit_off_d, torch.arange(rows, dtype=torch.int32, device=dev),
+                                           torch.from_numpy(class_start).to(dev), class_off_d, bins, ap_sorted[t0:t0 + rows], prec_sum,
+                                           first_miss, bin_sum, bin_count)
+    ap_h = np.zeros(nq, dtype=np.float64)
+    ap_h[order_q] = ap_sorted.cpu().numpy()
+    _warn_singletons(int(nq_rc[r_rc == 0].sum()))
+    return _merge_levels(ap_h, r_rc, nq_rc, class_off, bins, prec_sum, first_miss, bin_sum, bin_count)

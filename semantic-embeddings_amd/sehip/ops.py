@@ -20,7 +20,7 @@ __all__ = [
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
-    "recall_precision_reduce", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
+    "recall_precision_reduce", "count_preceding", "count_to_positions", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
     "svm_axpby", "class_pair_tables", "cholesky_lower_", "image_batch", "resample_tables", "tiny_batch", "TINY_BATCH_MAX_BLOCKS", "FILL_MODES",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
 ]
@@ -982,6 +982,41 @@ def recall_precision_reduce(hit_pos, hit_off, order, class_start, class_off, bin
     call("se_recall_precision_reduce", hit_pos, hit_off, Q, order, class_start, C, class_off, class_len, bins, ap, prec_sum,
          first_miss, bin_sum if bins > 0 else None, bin_count if bins > 0 else None)
     return ap
+
+
+def count_preceding(pdist, col_offset, hit_off, rel_d, rel_i, qidx, cnt, max_rel=0):
+    """Count one distance slab into the per-relevant-item histogram ``cnt`` (``se_count_preceding``): the positions of a query's
+    relevant items in a gallery it is not ranked against in full.
+
+    pdist [Q, n_cols] f32 (distances to gallery rows ``col_offset ..``), hit_off [Q + 1] int64, rel_d f32 / rel_i int32
+    [hit_off[Q]] (the relevant items' keys, per query ascending in the canonical order), qidx [Q] int32 | None (global gallery index
+    of the query itself, < 0: not in the gallery), cnt int32 [>= hit_off[Q]] in/out (zero before the first slab); ``max_rel``: the
+    longest key list, when the caller knows it.  Slabs and shards accumulate in any order.  Returns ``cnt``."""
+    require_gpu(pdist, hit_off, rel_d, rel_i, qidx, cnt)
+    _f32_rows(pdist, "pdist")
+    _i64(hit_off, "hit_off"); _i32(rel_i, "rel_i"); _i32(cnt, "cnt")
+    if qidx is not None:
+        _i32(qidx, "qidx")
+    if rel_d.dtype != torch.float32 or not rel_d.is_contiguous():
+        raise SehipError("rel_d must be contiguous float32")
+    Q, n_cols = pdist.shape
+    if hit_off.numel() != Q + 1 or (qidx is not None and qidx.numel() != Q) or rel_d.numel() != rel_i.numel() or cnt.numel() < rel_d.numel():
+        raise SehipError("count_preceding: hit_off needs Q + 1 entries, qidx Q, and rel_d / rel_i / cnt one per relevant item")
+    call("se_count_preceding", pdist, pdist.stride(0), Q, n_cols, int(col_offset), hit_off, rel_d, rel_i, qidx, int(max_rel), cnt)
+    return cnt
+
+
+def count_to_positions(cnt, hit_off, out=None):
+    """``se_count_to_positions``: per-query inclusive prefix sum of the bins ``count_preceding`` filled -> the 1-based positions
+    (query removed) ``relevant_positions`` would have read off a full ranking.  ``out`` may be ``cnt`` itself (the default)."""
+    require_gpu(cnt, hit_off, out)
+    _i32(cnt, "cnt"); _i64(hit_off, "hit_off")
+    out = cnt if out is None else out
+    _i32(out, "out")
+    if out.numel() < cnt.numel():
+        raise SehipError("out holds %d positions, cnt %d" % (out.numel(), cnt.numel()))
+    call("se_count_to_positions", cnt, hit_off, hit_off.numel() - 1, out)
+    return out
 
 
 # --------------------------------------------------------------------------------------------

@@ -25,7 +25,14 @@
                                                   composition of the default shift + flip batch)
     python tools/bench_kernels.py shortcut       (sehip.shortcut_add forward + backward next to the torch composition avg_pool2d + pad + add
                                                   at PyramidNet-272-200's shapes for batch 128: the widest stride-1 block of each stage and
-                                                  both stride-2 blocks, fp32 NCHW and bf16 NHWC)"""
+                                                  both stride-2 blocks, fp32 NCHW and bf16 NHWC)
+    python tools/bench_kernels.py qg [--small] [--ranking-path]
+                                                 (one query-vs-gallery AP leg, recall_precision_device(..., gallery=...): 50,000 queries x
+                                                  1,281,167 gallery rows x D = 1000, 1000 classes of ~1281 rows; --small: 2,000 x 60,000 x
+                                                  100, 100 classes; --q / --n / --d override.  Time per phase: relevant keys, distance
+                                                  slabs, counting, scan + reduce.  --ranking-path: the same positions from full rankings of
+                                                  --rank-rows query rows -- se_pairwise_dist + se_rank_rows + se_relevant_positions, the only
+                                                  way before the counting kernel -- scaled to all queries)"""
 import argparse
 import os
 import sys
@@ -53,7 +60,12 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg"])
+    ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
+    ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
+    ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
+    ap.add_argument("--classes", type=int, default=None, help="qg: number of classes")
+    ap.add_argument("--noise", type=float, default=0.7, help="qg: standard deviation of the noise around the class centres (0.7: separable classes, mAP 1)")
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
     ap.add_argument("--n", type=int, default=50000)
     ap.add_argument("--q", type=int, default=None)
@@ -78,6 +90,8 @@ def main():
         return bench_tiny()
     if args.what == "shortcut":
         return bench_shortcut()
+    if args.what == "qg":
+        return bench_qg(args)
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -957,6 +971,91 @@ def bench_shortcut(reps=30, batch=10, B=128):
                   % (label, k, B, c, h, h, cin, hx, hx, stride, kf[0], kf[1], kf[2], kt[0], kt[1], kt[2], kt[0] / kf[0], nbytes / 1e6,
                      nbytes / (kf[0] * 1e-6) / 1e9, 100.0 * nbytes / (kf[0] * 1e-6) / HBM), flush=True)
             del s, x, g, fs, fx, ts_, tx
+
+
+def bench_qg(args):
+    """One query-vs-gallery leg on synthetic unit-norm features (class centre + noise), per phase (HIP events around every kernel call
+    of the driver, summed) and as wall time of the whole call."""
+    import time
+    import warnings
+    from recall_precision import recall_precision_device
+    big = not args.small
+    q = args.q or (50000 if big else 2000)
+    given = {a.split("=")[0] for a in sys.argv[1:]}                          # --n / --d have defaults meant for the other benchmarks
+    n = args.n if "--n" in given else (1281167 if big else 60000)
+    d = args.d if "--d" in given else (1000 if big else 100)
+    C = args.classes or (1000 if big else 100)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    centers = torch.randn((C, d), device="cuda", generator=gen)
+
+    def features(rows, cls):
+        f = torch.empty((rows, d), dtype=torch.float32, device="cuda")
+        for r0 in range(0, rows, 65536):           # in pieces: no second rows x d temporary
+            r1 = min(rows, r0 + 65536)
+            f[r0:r1] = centers[cls[r0:r1]] + args.noise * torch.randn((r1 - r0, d), device="cuda", generator=gen)
+        return sehip.normalize_rows_(f)
+
+    gcls = torch.arange(n, device="cuda") % C                              # ILSVRC's layout: C classes of n / C rows
+    qcls = torch.arange(q, device="cuda") % C
+    fg, fq = features(n, gcls), features(q, qcls)
+    g_lab, q_lab = gcls.cpu().tolist(), qcls.cpu().tolist()
+    print("query-vs-gallery: q=%d n=%d d=%d classes=%d (R = %d per query), noise %.1f, cosine" % (q, n, d, C, n // C, args.noise))
+    if args.ranking_path:
+        rows = min(q, args.rank_rows)
+        pd = sehip.empty_rows(rows, n, torch.float32, "cuda")
+        rk = sehip.empty_rows(rows, n, torch.int32, "cuda")
+        cls_d, qc = gcls.to(torch.int32), qcls[:rows].to(torch.int32).contiguous()
+        hit_off = torch.arange(rows + 1, dtype=torch.int64, device="cuda") * 0
+        hit_off[1:] = torch.cumsum(torch.bincount(gcls, minlength=C)[qcls[:rows]], 0)
+        total = int(hit_off[-1])
+        steps = (("se_pairwise_dist", lambda: sehip.pairwise_dist(fq[:rows], fg, metric=sehip.METRIC_COSINE, out=pd)),
+                 ("se_rank_rows", lambda: sehip.rank_rows(pd, out=rk)),
+                 ("se_relevant_positions", lambda: sehip.relevant_positions(rk, cls_d, qc, None, hit_off, num_classes=C, total=total)))
+        tot = 0.0
+        for name, fn in steps:
+            med, mn = timeit(fn, max(1, min(args.reps, 3)))
+            tot += med
+            print("  %-24s %d rows: median %.2f ms (min %.2f)" % (name, rows, med, mn))
+        print("  ranking path: %.2f ms per %d rows -> %.2f s for all %d queries (scaled by %d / %d)" % (tot, rows, tot * q / rows / 1e3, q, q, rows))
+        return
+    phases = {}
+
+    def timed(phase, fn):
+        def run(*a, **k):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*a, **k)
+            e1.record()
+            phases.setdefault(phase(*a, **k) if callable(phase) else phase, []).append((e0, e1))
+            return out
+        return run
+
+    def pdist(a, b, cosine, sqa, sqb, kblocks, out=None):
+        return sehip.pairwise_dist(a, b, metric=sehip.METRIC_COSINE, kblocks=kblocks, out=out)
+
+    kernels = {"normalize_rows_": lambda x: x,                             # the features are unit-norm already
+               "pairwise_dist": timed(lambda a, b, c, sa, sb, kb, out=None: "distance slabs" if out is not None else "relevant keys", pdist),
+               "rank_rows": timed("relevant keys", sehip.rank_rows), "count_preceding": timed("counting", sehip.count_preceding),
+               "count_to_positions": timed("scan + reduce", sehip.count_to_positions),
+               "recall_precision_reduce": timed("scan + reduce", sehip.recall_precision_reduce)}
+    for rep in range(2):                                                   # the first call pays allocations and the ranking probe
+        phases.clear()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            levels, means, mAP, _ = recall_precision_device(fq, q_lab, normalize=True, gallery=fg, gallery_labels=g_lab, kernels=kernels)
+        torch.cuda.synchronize()
+        wall = time.perf_counter() - t0
+        print("  run %d: wall %.3f s, mAP %.4f, %d levels" % (rep, wall, mAP, len(levels)))
+        for name in ("relevant keys", "distance slabs", "counting", "scan + reduce"):
+            ms = sum(a.elapsed_time(b) for a, b in phases.get(name, []))
+            extra = ""
+            if name == "counting":
+                extra = "  slab read %.1f GB -> %.2f TB/s" % (4.0 * q * n / 1e9, 4.0 * q * n / ms / 1e9) if ms > 0 else ""
+            if name == "distance slabs":
+                extra = "  %.1f TFLOP/s, slab write %.1f GB" % (2.0 * q * n * d / ms / 1e9, 4.0 * q * n / 1e9) if ms > 0 else ""
+            print("    %-15s %10.2f ms in %6d calls%s" % (name, ms, len(phases.get(name, [])), extra))
 
 
 if __name__ == "__main__":
