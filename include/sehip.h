@@ -725,6 +725,45 @@ int se_class_pair_tables(const int32_t *anc_off, const int32_t *anc_rank, const 
  */
 int se_cholesky_f64(double *a, int64_t lda, int64_t n, int32_t *info, se_stream_t stream);
 
+/* info codes of se_eigh_f64 below zero (>= 0: converged, the number of sweeps used) */
+#define SE_EIGH_NOT_CONVERGED (-1) /* off(A) still above the tolerance after max_sweeps sweeps; w / v hold the state reached    */
+#define SE_EIGH_NONFINITE (-2)     /* the input holds a NaN or an infinity (or |A|_F^2 overflows); w / v are NaN                */
+
+/*
+ * Eigendecomposition of a symmetric float64 matrix: A = V diag(w) V^T, eigenvalues ascending, eigenvectors the COLUMNS of V in the
+ * same order (the conventions of numpy.linalg.eigh).
+ * Replaces: the np.linalg.eigh of sim_approx (compute_class_embedding.py:44-72, the eigenvectors of the class similarities scaled
+ *           by the roots of their eigenvalues) and of mds (:134-160, classical multidimensional scaling of the class distances).
+ *   a          [n, n] f64 (lda >= n elements between rows), in; DESTROYED (on return its diagonal holds the unsorted eigenvalues).
+ *              Taken as symmetric: both triangles are read
+ *   w          [n] f64 out, ascending
+ *   v          [n, n] f64 out (ldv >= n elements between rows); v[:, j] belongs to w[j]; elements past column n are not touched
+ *   workspace  se_eigh_f64_workspace_bytes(n) bytes of device memory, 8-byte aligned (n^2 doubles for the unsorted eigenvectors,
+ *              one 64 x 64 rotation per block pair, the reduction scratch); -1 from the size query: n is out of range
+ *   info       [1] int32 out (device): the number of sweeps used (0 for a matrix that is diagonal already), or SE_EIGH_NOT_CONVERGED
+ *              (w / v finite: the diagonal and the rotations reached so far), or SE_EIGH_NONFINITE (w / v all NaN, no sweep run)
+ *   max_sweeps >= 0, the bound of the outer loop (random matrices take 5 to 8 sweeps, the clustered class spectra up to 28)
+ * Two-sided block Jacobi, blocks of 32 columns, round-robin ordering (se_eigh_schedule over nb = 2 ceil(n / 64) blocks, the matrix
+ * padded with zeros that are never stored): per round one workgroup per block pair diagonalises its 64 x 64 sub-block by cyclic
+ * Jacobi in LDS (bounded inner sweeps; a rotation whose entry is exactly 0 is skipped, so the padding never mixes with real rows),
+ * then A[:, pair] J, V[:, pair] J and J^T A[pair, :] run on v_mfma_f64_16x16x4_f64.  The host reads off(A)^2 = sum_{i != j} a_ij^2
+ * once per sweep and stops at off(A) <= sqrt(n) 2^-53 |A|_F: the call SYNCHRONISES the stream (once per sweep and at the end).
+ * Signs, and the basis inside a cluster of equal eigenvalues, are unspecified.  Not bit-equal to LAPACK; eigenvalues, residual
+ * A V - V diag(w) and V^T V - I stay within a few n eps (tests/test_gpu_eigh.py).  n = 0 is accepted (info = 0, nothing else
+ * written); n > 131072 is SE_ERR_UNSUPPORTED.
+ */
+int64_t se_eigh_f64_workspace_bytes(int64_t n);
+int se_eigh_f64(double *a, int64_t lda, int64_t n, double *w, double *v, int64_t ldv, void *workspace, int32_t *info, int max_sweeps,
+                se_stream_t stream);
+
+/*
+ * The rounds of one sweep of se_eigh_f64 over nb blocks (nb even, >= 2), by the circle method: pairs [nb - 1, nb / 2, 2] int32
+ * HOST memory out, pairs[r, k] = (lo, hi) with lo < hi.  Within a round the pairs are disjoint; over the nb - 1 rounds every
+ * unordered pair of blocks occurs exactly once.  Round r pairs block r with block nb - 1 and, for k = 1 .. nb / 2 - 1, block
+ * (r + k) mod (nb - 1) with block (r - k) mod (nb - 1).  Host only (no device work; sehip.eigh_schedule states the same rule).
+ */
+int se_eigh_schedule(int nb, int32_t *pairs);
+
 /* ------------------------------------------------------------------------------------------
  * Input pipeline: batches of file-based datasets composed on the device
  * ------------------------------------------------------------------------------------------ */

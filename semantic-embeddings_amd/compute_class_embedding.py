@@ -12,11 +12,17 @@ Drop-in for the reference's ``compute_class_embedding.py``: the same command lin
 * ``euclidean_embedding`` (:76-130, "spheres"): class 0 at the origin, class c >= 1 at row c - 1 of the Cholesky factor of the
   Gram matrix ``G_ij = (d_0i^2 + d_0j^2 - d_ij^2) / 2`` of the classes 1 .. n - 1 -- the reference's successive hypersphere
   intersections solve exactly these triangular systems.  A failed pivot raises the reference's RuntimeError for that class;
-* ``sim_approx`` / ``mds`` (:44-72, :134-160) stay host NumPy eigendecompositions (``np.linalg.eigh``), fed by the device table.
+* ``sim_approx`` / ``mds`` (:44-72, :134-160): their ``np.linalg.eigh`` is ``se_eigh_f64`` (``sim_approx_factor`` /
+  ``mds_factor``: two-sided block Jacobi in float64 on the matrix cores; the double-centring of mds is formed on the device from
+  the row, column and grand means instead of two n^3 products).  The reference's rules act on the device eigenvalues unchanged:
+  a negative eigenvalue is the RuntimeError of sim_approx, mds keeps ``lam > eps``, the largest eigenvalue comes last in
+  approx_sim and first in mds.  The importable ``sim_approx`` / ``mds`` are the host NumPy forms; ``main`` takes them when no
+  GPU is present and above ``EIGH_DEVICE_MAX_CLASSES`` classes.  The host's LAPACK is measured faster at every size; the
+  constant caps what the device path may cost (see its comment).
 
 The deviation report ("Maximum/Average deviation from target ...") is formed on the device in float64 (an n^3 product at
 n = 8,142 would take minutes of host BLAS).  Results are tolerance-equal to the reference (the factorisation sums in another
-order); the tables are bit-identical.
+order; eigenvectors up to sign and to the basis of a cluster of equal eigenvalues); the tables are bit-identical.
 """
 import argparse
 import pickle
@@ -30,6 +36,13 @@ import numpy as np
 from class_hierarchy import ClassHierarchy
 
 METHODS = ['unitsphere', 'approx_sim', 'spheres', 'mds']
+
+# main() takes the device eigensolver up to this many classes and the host's np.linalg.eigh above it.  This is a cap on what the
+# device path may cost, not a crossover: the block Jacobi solver loses to the host's LAPACK at every measured size
+# (profiles/classemb_eigh_bench.txt: 14 ms against 0.5 ms at n = 100, 46 ms against 1.6 ms at 200, 0.14 s against 0.014 s at 512,
+# 0.72 s against 0.04 s at 1,000, 12.7 s against 4.2 s at 8,142).  Up to 512 classes the loss is at most 0.12 s of a command that
+# takes seconds, and the step stays on the device with the tables and the deviation report; above it the host is taken.
+EIGH_DEVICE_MAX_CLASSES = 512
 
 
 def _square(a, what):
@@ -47,6 +60,11 @@ def _to_device(a):
     if torch.is_tensor(a):
         return a.detach().to(device=torch.device('cuda', torch.cuda.current_device()), dtype=torch.float64).contiguous().clone()
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
+
+
+def _host(a):
+    """NumPy form of an array or tensor."""
+    return a.detach().cpu().numpy() if hasattr(a, 'is_cuda') else a
 
 
 def unitsphere_factor(class_sim):
@@ -105,6 +123,48 @@ def euclidean_embedding(class_dist, solver='general'):
     return emb.cpu().numpy()
 
 
+def _device_eigh(matrix, what):
+    """(ascending eigenvalues, eigenvector columns) of a symmetric device matrix by ``se_eigh_f64``; an input the solver cannot
+    decompose raises."""
+    import sehip
+    lam, vec, info = sehip.eigh(matrix, overwrite_a=True)
+    if info == sehip.EIGH_NONFINITE:
+        raise RuntimeError('Given {} holds NaN or infinite values.'.format(what))
+    if info < 0:
+        raise RuntimeError('The eigendecomposition of {} did not converge.'.format(what))
+    return lam, vec
+
+
+def sim_approx_factor(class_sim, num_dim=None):
+    """Device form of ``sim_approx``: the embedding as a float64 [n, min(n, num_dim)] device tensor.  RuntimeError if an
+    eigenvalue of ``class_sim`` is negative, like the reference."""
+    lam, vec = _device_eigh(_to_device(class_sim), 'class_sim')
+    if bool((lam < 0).any()):
+        raise RuntimeError('Given class_sim is not positive semi-definite.')
+    emb = vec * lam.sqrt()[None, :]
+    if num_dim is not None and num_dim < emb.shape[1]:
+        emb = emb[:, emb.shape[1] - num_dim:]
+    return emb.contiguous()
+
+
+def mds_factor(class_dist, num_dim=None):
+    """Device form of ``mds``: the embedding as a float64 device tensor [n, number of eigenvalues kept].  The double-centred
+    matrix -(D^2 - row means - column means + grand mean) / 2 is formed element-wise; like ``np.linalg.eigh`` only its lower
+    triangle counts."""
+    import torch
+    sq = _to_device(class_dist)
+    sq.mul_(sq)
+    b = (sq - sq.mean(dim=1, keepdim=True) - sq.mean(dim=0, keepdim=True) + sq.mean()).mul_(-0.5)
+    b = b.tril() + b.tril(-1).T
+    lam, vec = _device_eigh(b.contiguous(), 'class_dist')
+    keep = lam > np.finfo(np.float64).eps
+    lam, vec = lam[keep], vec[:, keep]
+    if num_dim is not None:
+        top = torch.argsort(lam, stable=True).flip(0)[:num_dim]
+        lam, vec = lam[top], vec[:, top]
+    return (vec * lam.sqrt()[None, :]).contiguous()
+
+
 def sim_approx(class_sim, num_dim=None):
     """Embedding whose dot products best approximate ``class_sim`` in at most ``num_dim`` dimensions (all n by default): the
     eigenvectors of the similarity matrix scaled by the roots of their eigenvalues, largest last.  Host NumPy ``eigh``."""
@@ -138,10 +198,22 @@ def mds(class_dist, num_dim=None):
 
 
 def deviation(embedding, target, distances):
-    """(max, mean) of |E E^T - target| (``distances`` False) or |pdist(E) - target| on the device, in float64."""
+    """(max, mean) of |E E^T - target| (``distances`` False) or |pdist(E) - target| in float64: on the device, or in NumPy when
+    there is none (the host path of approx_sim / mds)."""
+    import torch
+    if not torch.cuda.is_available():
+        e, t = np.asarray(embedding, dtype=np.float64), np.asarray(target, dtype=np.float64)
+        err_max, err_sum = 0.0, 0.0
+        for r0 in range(0, e.shape[0], 256):                # 256 rows at a time: never more than a [256, n] block
+            est = e[r0:r0 + 256] @ e.T
+            if distances:
+                sq = (e * e).sum(-1)
+                est = np.sqrt(np.maximum(sq[r0:r0 + 256, None] + sq[None, :] - 2.0 * est, 0.0))
+            err = np.abs(est - t[r0:r0 + 256])
+            err_max, err_sum = max(err_max, float(err.max())), err_sum + float(err.sum())
+        return err_max, err_sum / t.size
     e, t = _to_device(embedding), _to_device(target)
     if distances:
-        import torch
         est = torch.cdist(e, e, compute_mode='donot_use_mm_for_euclid_dist')     # direct differences, like scipy's pdist
     else:
         est = e @ e.T
@@ -187,7 +259,8 @@ Default: "unitsphere"''')
 def main(argv=None):
     args = build_parser().parse_args(argv)
     import torch
-    if not torch.cuda.is_available():
+    on_device = torch.cuda.is_available()
+    if not on_device and args.method not in ('approx_sim', 'mds'):
         import sehip
         raise sehip.SehipError('compute_class_embedding.py runs on a ROCm GPU; there is no CPU fallback')
     id_type = str if args.str_ids else int
@@ -196,17 +269,25 @@ def main(argv=None):
     linear_labels = {lbl: i for i, lbl in enumerate(unique_labels)}
 
     # target distances lcs_height(a, b) of every pair, zero on the diagonal
-    _, sem_class_dist = hierarchy.similarity_tables_device(unique_labels, diag_one=True, distance=True, want_wup=False)
+    if on_device:
+        _, sem_class_dist = hierarchy.similarity_tables_device(unique_labels, diag_one=True, distance=True, want_wup=False)
+    else:       # the eigendecomposition methods without a GPU: the host tables (1 - lcs_height off the diagonal)
+        sem_class_dist = 1. - hierarchy.similarity_tables(unique_labels)[1]
+        np.fill_diagonal(sem_class_dist, 0.)
 
+    device_eigh = on_device and len(unique_labels) <= EIGH_DEVICE_MAX_CLASSES
     start_time = time.time()
     if args.method == 'spheres':
         embedding = euclidean_embedding(sem_class_dist)
     elif args.method == 'mds':
-        embedding = mds(sem_class_dist.cpu().numpy(), args.num_dim if args.num_dim else len(unique_labels) - 1)
+        num_dim = args.num_dim if args.num_dim else len(unique_labels) - 1
+        embedding = mds_factor(sem_class_dist, num_dim).cpu().numpy() if device_eigh else mds(_host(sem_class_dist), num_dim)
     elif args.method == 'unitsphere':
         embedding = unitsphere_embedding(1. - sem_class_dist)
+    elif device_eigh:
+        embedding = sim_approx_factor(1. - sem_class_dist, args.num_dim).cpu().numpy()
     else:
-        embedding = sim_approx((1. - sem_class_dist).cpu().numpy(), args.num_dim)
+        embedding = sim_approx(_host(1. - sem_class_dist), args.num_dim)
     stop_time = time.time()
     print('Computed {}-dimensional semantic embeddings for {} classes using the "{}" method in {} seconds.'.format(
         embedding.shape[1], embedding.shape[0], args.method, stop_time - start_time))

@@ -21,7 +21,7 @@ __all__ = [
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
     "recall_precision_reduce", "count_preceding", "count_to_positions", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
-    "svm_axpby", "class_pair_tables", "cholesky_lower_", "image_batch", "resample_tables", "tiny_batch", "TINY_BATCH_MAX_BLOCKS", "FILL_MODES",
+    "svm_axpby", "class_pair_tables", "cholesky_lower_", "eigh", "eigh_schedule", "EIGH_NOT_CONVERGED", "EIGH_NONFINITE", "image_batch", "resample_tables", "tiny_batch", "TINY_BATCH_MAX_BLOCKS", "FILL_MODES",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
 ]
 
@@ -1122,7 +1122,8 @@ def svm_axpby(alpha, x, beta, y, out=None, length=None):
 
 
 # --------------------------------------------------------------------------------------------
-# class embeddings: similarity tables of a hierarchy, Cholesky factor (classemb.hip; the CLI is compute_class_embedding.py)
+# class embeddings: similarity tables of a hierarchy, Cholesky factor, symmetric eigensolver (classemb.hip, eigh.hip; the CLI is
+# compute_class_embedding.py)
 # --------------------------------------------------------------------------------------------
 
 def class_pair_tables(off, rank, spl, depth, height, max_anc, max_height, diag_one=False, distance=False, want_wup=True,
@@ -1162,6 +1163,47 @@ def cholesky_lower_(a, info=None):
     _i32(info, "info")
     call("se_cholesky_f64", a, a.stride(0) if n > 1 else max(n, 1), n, info)
     return a, info
+
+
+EIGH_NOT_CONVERGED, EIGH_NONFINITE = DEFINES["SE_EIGH_NOT_CONVERGED"], DEFINES["SE_EIGH_NONFINITE"]
+
+
+def eigh_schedule(nb):
+    """The rounds of one sweep of ``se_eigh_f64`` over ``nb`` blocks (even, >= 2): a list of nb - 1 rounds, each a list of nb / 2
+    disjoint pairs ``(lo, hi)``, lo < hi, every unordered pair of blocks exactly once per sweep.  The circle method: round r pairs
+    block r with block nb - 1 and, for k = 1 .. nb / 2 - 1, block (r + k) mod (nb - 1) with block (r - k) mod (nb - 1).  Pure
+    Python (the library's ``se_eigh_schedule`` and its kernels follow the same rule; tests/test_eigh_host.py compares them)."""
+    nb = int(nb)
+    if nb < 2 or nb % 2:
+        raise SehipError("eigh_schedule: nb=%d must be even and >= 2" % nb)
+    m = nb - 1
+    return [[(r, m)] + [tuple(sorted(((r + k) % m, (r - k) % m))) for k in range(1, nb // 2)] for r in range(m)]
+
+
+def eigh(a, max_sweeps=60, overwrite_a=False, out_v=None):
+    """``se_eigh_f64`` of a symmetric float64 [n, n] device matrix with contiguous rows (any row pitch): ``(w, v, info)`` with
+    ``w`` [n] ascending, ``v`` [n, n] whose column j belongs to ``w[j]`` (numpy.linalg.eigh's conventions; signs and the basis
+    of a degenerate cluster unspecified) and ``info`` a Python int: the sweeps used, or ``EIGH_NOT_CONVERGED`` (w / v finite,
+    the state after ``max_sweeps``) or ``EIGH_NONFINITE`` (NaN / infinite input; w / v NaN).  ``a`` is copied unless
+    ``overwrite_a``; ``max_sweeps`` bounds the outer loop (random matrices take 5 to 8 sweeps, the clustered class similarities
+    28 at n = 1,000 and 8,142: the default leaves twice that); ``out_v`` may name the [n, n] float64 destination (contiguous rows, any pitch).  Synchronises the stream."""
+    require_gpu(a, out_v)
+    if a.dtype != torch.float64 or a.dim() != 2 or a.shape[0] != a.shape[1] or (a.shape[0] > 1 and a.stride(1) != 1):
+        raise SehipError("eigh takes a square float64 matrix with contiguous rows")
+    n = a.shape[0]
+    if not overwrite_a:
+        a = a.clone(memory_format=torch.contiguous_format)
+    v = torch.empty((n, n), dtype=torch.float64, device=a.device) if out_v is None else out_v
+    if v.dtype != torch.float64 or tuple(v.shape) != (n, n) or (n > 1 and v.stride(1) != 1):
+        raise SehipError("eigh: out_v must be a float64 [n, n] matrix with contiguous rows")
+    w = torch.empty((n,), dtype=torch.float64, device=a.device)
+    info = torch.empty((1,), dtype=torch.int32, device=a.device)
+    nbytes = call("se_eigh_f64_workspace_bytes", n)
+    if nbytes < 0:
+        raise SehipError("eigh: n=%d is out of range" % n)
+    ws = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=a.device)
+    call("se_eigh_f64", a, a.stride(0) if n > 1 else max(n, 1), n, w, v, v.stride(0) if n > 1 else max(n, 1), ws, info, int(max_sweeps))
+    return w, v, int(info.item())
 
 
 # --------------------------------------------------------------------------------------------

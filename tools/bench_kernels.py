@@ -4,8 +4,9 @@
     python tools/bench_kernels.py recprec        (10k x 10k and 50k x 50k, 100 classes; --n is not used)
     python tools/bench_kernels.py svm            (margin + reduction kernels and whole LinearSVC fits: 50,000 x 100 x 100 and
                                                   1,281,167 x 1000 x 1000; --n / --d are not used; --svm-sizes small skips the large one)
-    python tools/bench_kernels.py classemb       (class pair tables and fp64 Cholesky at C = 1000 (ILSVRC WordNet DAG) and 8,142 (iNat
-                                                  2018), and the whole compute_class_embedding.py run on the iNat hierarchy)
+    python tools/bench_kernels.py classemb       (class pair tables, fp64 Cholesky and the fp64 eigensolver (next to np.linalg.eigh) at C = 1000
+                                                  (ILSVRC WordNet DAG) and 8,142 (iNat 2018), and whole compute_class_embedding.py runs on the
+                                                  iNat hierarchy: unitsphere, and approx_sim with the device and the host eigensolver)
     python tools/bench_kernels.py center         (center loss forward / input gradient / centroid gradient at D = 100, and the
                                                   ResNet-110-fc center-loss training step next to the cosine-loss one)
     python tools/bench_kernels.py xent           (softmax cross-entropy forward + backward next to the torch composition the sibling
@@ -319,8 +320,39 @@ def main():
         print("loss fwd B=128 D=100: median %.1f us" % (med * 1e3))
 
 
+def bench_eigh(s, label):
+    """se_eigh_f64 (two-sided block Jacobi) of the symmetric device matrix ``s`` against np.linalg.eigh of the same matrix on this
+    host: wall-clock seconds of whole calls (the device figure includes the input copy, the workspace, every sweep's
+    synchronisation, the sort and the gather), and the accuracy ratios against LAPACK."""
+    import time
+    C = s.shape[0]
+    s_h = s.cpu().numpy()
+    sehip.eigh(s[:65, :65].contiguous())                         # first-call costs (code object load) stay out of the timing
+    torch.cuda.synchronize()
+    runs, hosts = [], []
+    for _ in range(2 if C > 4000 else 3):
+        t0 = time.time()
+        w, v, sweeps = sehip.eigh(s)
+        torch.cuda.synchronize()
+        runs.append(time.time() - t0)
+    for _ in range(1 if C > 4000 else 3):
+        t0 = time.time()
+        lam = np.linalg.eigh(s_h)[0]
+        hosts.append(time.time() - t0)
+    scale = float(np.abs(lam).max())
+    ne = C * 2.0 ** -52
+    e_w = float(np.abs(w.cpu().numpy() - lam).max()) / scale / ne
+    e_r = float((s @ v - v * w[None, :]).abs().max()) / scale / ne
+    e_o = float((v.T @ v - torch.eye(C, dtype=torch.float64, device="cuda")).abs().max()) / ne
+    print("eigh n=%d f64 (%s; block Jacobi, b = 32): %s s, %d sweeps; np.linalg.eigh on this host (%s threads): %s s; "
+          "eigenvalues %.2f residual %.2f orthogonality %.2f (x n eps)"
+          % (C, label, " / ".join("%.4f" % t for t in runs), sweeps, os.environ.get("OMP_NUM_THREADS", "default"),
+             " / ".join("%.4f" % t for t in hosts), e_w, e_r, e_o))
+
+
 def bench_classemb(reps):
-    """se_class_pair_tables (both tables) and se_cholesky_f64 of S = 1 - lcs_height (unit diagonal), plus the full CLI on iNat."""
+    """se_class_pair_tables (both tables), se_cholesky_f64 and se_eigh_f64 of S = 1 - lcs_height (unit diagonal; the eigensolver
+    next to np.linalg.eigh on this host), plus the full CLI on iNat (unitsphere; approx_sim with the device and the host eigensolver)."""
     import pickle
     import subprocess
     import tempfile
@@ -351,6 +383,14 @@ def bench_classemb(reps):
         flop = C ** 3 / 3.0
         print("cholesky n=%d f64: median %.3f ms (min %.3f; %.3f ms of it the copy)  %.2f TFLOP/s"
               % (C, med, mn, cp, flop / ((med - cp) * 1e-3) / 1e12))
+        bench_eigh(s, name)
+        if name == "inat2018":
+            bench_eigh(s[:512, :512].contiguous(), "inat2018, first 512 classes")
+    # the sizes at which compute_class_embedding.main takes the device solver (EIGH_DEVICE_MAX_CLASSES)
+    for name in ("cifar", "cub"):
+        h, classes = load_hierarchy(name)
+        _, s = h.similarity_tables_device(classes, diag_one=True, want_wup=False)
+        bench_eigh(s, name)
     g = np.load(os.path.join(ROOT, "tests", "golden", "hierarchy_inat2018.npz"))
     with tempfile.TemporaryDirectory() as tmp:
         hp, cl, out = os.path.join(tmp, "h.txt"), os.path.join(tmp, "c.txt"), os.path.join(tmp, "e.pickle")
@@ -370,6 +410,21 @@ def bench_classemb(reps):
             e = pickle.load(f)["embedding"]
         print("compute_class_embedding.py iNat 2018 (8,142 classes, unitsphere): %.1f s wall (process start to exit), finite %s"
               % (wall, bool(np.isfinite(e).all())))
+        # --method approx_sim --num_dim 128: the device eigensolver (forced: main() takes the host's eigh above
+        # EIGH_DEVICE_MAX_CLASSES classes) against the command as shipped, which is the host eigendecomposition it took before
+        cli = os.path.join(ROOT, "semantic-embeddings_amd", "compute_class_embedding.py")
+        argv = ["--hierarchy", hp, "--str_ids", "--class_list", cl, "--out", out, "--method", "approx_sim", "--num_dim", "128"]
+        forced = ("import sys; sys.path.insert(0, %r); import compute_class_embedding as cce; "
+                  "cce.EIGH_DEVICE_MAX_CLASSES = 1 << 30; cce.main(sys.argv[1:])" % os.path.dirname(cli))
+        for label, cmd in (("device eigensolver (forced)", [sys.executable, "-c", forced] + argv), ("host np.linalg.eigh (as shipped)", [sys.executable, cli] + argv)):
+            t0 = time.time()
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            wall = time.time() - t0
+            print(r.stdout.strip())
+            if r.returncode != 0:
+                print(r.stderr[-2000:])
+                raise SystemExit(r.returncode)
+            print("compute_class_embedding.py iNat 2018 approx_sim --num_dim 128, %s: %.1f s wall" % (label, wall))
 
 
 def bench_center(reps=200, steps=200):
