@@ -148,7 +148,11 @@ class DeviceBatchSequence(object):
     rows ``r::world_size`` of the global batch, so the union over ranks is the reference's batch.
     ``batch_transform(X, y, **kwargs)`` is applied last (e.g. learn_image_embeddings.transform_inputs).
     ``repeats`` sub-epochs make one epoch, each with a permutation of its own (datasets/common.py:87-122: ``len()`` is
-    ``repeats`` x batches per sub-epoch); ``compose_kwargs`` are handed on to ``generator.compose_batch``."""
+    ``repeats`` x batches per sub-epoch); ``compose_kwargs`` are handed on to ``generator.compose_batch``.
+
+    A generator with a ``prefetch(indices, train)`` method (the streamed store of datasets/files.py) is told, before batch ``i`` is
+    composed, the rows of the next ``generator.prefetch_batches`` batches of the same pass -- this rank's rows, exactly what the
+    later ``compose_batch`` calls will bring.  Never past the end of the current permutation: the next one does not exist yet."""
 
     def __init__(self, generator, indices, labels, batch_size=32, shuffle=False, train=False, augment=False,
                  batch_transform=None, batch_transform_kwargs={}, rank=0, world_size=1, seed=0, repeats=1, compose_kwargs=None):
@@ -173,13 +177,22 @@ class DeviceBatchSequence(object):
             for perm in self.perms:
                 self.rng.shuffle(perm)
 
-    def __getitem__(self, idx):
-        sub = min(idx // max(self.epoch_len, 1), self.repeats - 1)
-        idx -= sub * self.epoch_len
+    def _rows(self, sub, idx):
         glob = self.perms[sub][idx * self.batch_size:(idx + 1) * self.batch_size]
         sel = glob[self.rank::self.world_size]
         if len(sel) == 0 and len(glob):     # a short last batch with fewer rows than ranks: no rank may see an empty batch (its mean
             sel = glob[[self.rank % len(glob)]]   # would be NaN and the all-reduce would spread it): re-use one of the rows
+        return sel
+
+    def __getitem__(self, idx):
+        sub = min(idx // max(self.epoch_len, 1), self.repeats - 1)
+        idx -= sub * self.epoch_len
+        sel = self._rows(sub, idx)
+        announce = getattr(self.generator, 'prefetch', None)
+        if announce is not None:
+            ahead = int(getattr(self.generator, 'prefetch_batches', 0))
+            for nxt in range(idx + 1, min(idx + 1 + ahead, self.epoch_len)):
+                announce(self.indices[self._rows(sub, nxt)], self.train)
         X = self.generator.compose_batch(self.indices[sel], train=self.train, augment=self.augment, **self.compose_kwargs)
         y = torch.from_numpy(self.labels[sel].astype(np.int64)).to(X.device, non_blocking=True)
         if self.batch_transform is not None:

@@ -11,8 +11,44 @@ the host only draws the augmentation parameters (``draw_params``) and builds the
 * ``mean`` / ``std`` given as ``None`` are computed from the training images during their decode pass (``_compute_stats``,
   datasets/common.py:186-207), on first use.
 * The random numbers come from a ``np.random.Generator``, not NumPy's global stream: the reference's distributions, other draws.
+
+Store tiers (``store=``).  ``'resident'`` is the store above; a split larger than ``store_budget_bytes`` is an error.  ``'stream'``
+holds no arena for a split (the ILSVRC training split would take several hundred GB): ``compose_batch`` obtains the decoded images
+of exactly its indices, packs them into a staging arena, uploads it once and launches the same ``se_image_batch`` with offsets
+relative to that arena and the sizes of the decoded images.  ``draw_params`` runs at compose time, in call order, on either tier, so
+the random stream of a (split, rank, seed) does not depend on the tier and the batches of both are bit-identical.  ``'auto'`` decides
+per split at first use, from the header-only size pass: what fits the budget is resident, what does not is streamed.  A streamed
+split is bound by JPEG decoding on the host, not by the device; that is why it is opt-in.
+
+Rules of the streamed store (``_StreamStore``):
+
+* Threads.  Worker threads only decode (Pillow releases the GIL while it does) and hand NumPy arrays back; they are threads, not
+  the reference's worker processes, because a process that has initialised the GPU must not be forked.  Every HIP call -- the upload,
+  the launch -- is issued by the thread that called ``compose_batch``, on its current stream.  A generator has one pool of at most
+  ``decode_threads`` workers for both splits.
+* Look-ahead.  ``prefetch(indices, train)`` announces a batch; its decoding starts at once.  A later ``compose_batch`` finds it by
+  its index tuple; a batch nobody announced is decoded on demand.  At most ``prefetch_batches + 2`` announced batches are kept: when
+  one more arrives, the oldest that was never collected is dropped and its pending decodes are cancelled.
+* Ring.  ``prefetch_batches + 2`` slots, each a pinned host buffer and a device uint8 buffer, taken in turn.  The caller packs the
+  decoded images of a batch into the slot's host buffer only after all of them have arrived, copies it to the slot's device buffer
+  ``non_blocking`` and records the slot's ``uploaded`` event behind that copy; after the launch it records ``consumed``.
+  - A slot's host buffer is not written again until ``uploaded`` has completed (the caller waits on it; with more slots than
+    batches in flight it has long completed).
+  - A slot's device buffer is written again only in stream order behind the launch that read it: same stream, later in the queue;
+    if the caller's current stream has changed since, that stream first waits for ``consumed``.
+  - A slot grows geometrically when a batch needs more bytes.  Before its buffers are replaced, ``uploaded`` and ``consumed`` are
+    synchronised, so that no copy from or to them and no kernel reading them is in flight when they are released.
+* Errors.  Whatever a worker raises for a file surfaces in the caller as ``SehipError`` naming the file.  The futures of a batch are
+  all waited for or cancelled before anything is written, so an error leaves no half-filled slot, and nothing waits on a worker
+  that is not running.
+* Statistics.  With ``mean`` or ``std`` missing, the training split is decoded in file order, a bounded window of images at a time,
+  and fed to the sums of ``_stats_from``: the same float64 operations on the same arrays as the resident tier's, so the results are
+  equal bit for bit.  The variance is taken around the finished float32 mean, so a generator that lacks both makes two passes (one
+  per statistic); no arena is held.
 """
 import os
+import threading
+from collections import OrderedDict
 from concurrent.futures import ThreadPoolExecutor
 from glob import glob
 
@@ -32,27 +68,175 @@ class _Store(object):
     """Decoded images of one split: ``arena`` uint8 (host array until uploaded, then a device tensor), ``offsets`` int64 [N],
     ``sizes`` int32 [N, 2] = (h, w)."""
 
+    tier = 'resident'
+
     def __init__(self, arena, offsets, sizes):
         self.arena, self.offsets, self.sizes = arena, offsets, sizes
         self.device_arena = None
+
+    def images(self):
+        """The decoded images in file order (views of the host arena)."""
+        return (self.arena[o:o + h * w * 3].reshape(h, w, 3) for o, (h, w) in zip(self.offsets, self.sizes))
+
+
+def _decode_rgb(fn):
+    """One file as uint8 [h, w, 3], decoded like the resident store decodes it; any failure names the file."""
+    from PIL import Image
+    try:
+        with Image.open(fn) as im:
+            return np.asarray(im.convert('RGB'), dtype=np.uint8)
+    except Exception as e:
+        raise SehipError('%s: cannot decode: %s: %s' % (fn, type(e).__name__, e))
+
+
+class _Slot(object):
+    """One ring slot: pinned host buffer, device buffer, the event behind the last upload and the one behind the last launch."""
+
+    def __init__(self):
+        self.host = self.dev = self.uploaded = self.consumed = self.stream = None
+
+    def view(self, nbytes):
+        return self.host.numpy()[:nbytes]
+
+
+class _StreamStore(object):
+    """A split that is decoded batch by batch (the module docstring has the rules).  ``pool`` is a callable returning the
+    generator's thread pool."""
+
+    tier = 'stream'
+    STATS_WINDOW = 64          # images decoded ahead of the statistics sums
+
+    def __init__(self, files, pool, prefetch_batches):
+        self.files, self._pool = files, pool
+        self.ring = [_Slot() for _ in range(max(int(prefetch_batches), 0) + 2)]
+        self.turn = 0
+        self.pending = OrderedDict()       # index tuple -> {index: future}
+        self.lock = threading.Lock()
+
+    # -- host half
+
+    def _submit(self, key):
+        pool = self._pool()
+        return {i: pool.submit(_decode_rgb, self.files[i]) for i in dict.fromkeys(key)}
+
+    @staticmethod
+    def _drop(job):
+        for f in job.values():
+            f.cancel()
+
+    def announce(self, indices):
+        key = tuple(int(i) for i in indices)
+        with self.lock:
+            if not key or key in self.pending:
+                return
+            while len(self.pending) >= len(self.ring):
+                self._drop(self.pending.popitem(last=False)[1])
+            self.pending[key] = self._submit(key)
+
+    def collect(self, indices):
+        """The decoded images of ``indices``, {index: array}; announced or not."""
+        key = tuple(int(i) for i in indices)
+        with self.lock:
+            job = self.pending.pop(key, None)
+        if job is None:
+            job = self._submit(key)
+        try:
+            return key, {i: f.result() for i, f in job.items()}
+        except BaseException:
+            self._drop(job)
+            raise
+
+    def stage(self, indices):
+        """Host half of a batch: ``(slot, nbytes, offsets [B] int64, sizes [B, 2] int32)``, the images packed into the host buffer
+        of the next slot of the ring, every distinct index once."""
+        key, images = self.collect(indices)
+        at, total = {}, 0
+        for i, a in images.items():
+            at[i] = total
+            total += a.size
+        slot = self.ring[self.turn % len(self.ring)]
+        self.turn += 1
+        self._reserve(slot, total)
+        host = slot.view(total)
+        for i, a in images.items():
+            host[at[i]:at[i] + a.size] = a.reshape(-1)
+        offsets = np.asarray([at[i] for i in key], dtype=np.int64)
+        sizes = np.asarray([images[i].shape[:2] for i in key], dtype=np.int32).reshape(len(key), 2)
+        return slot, total, offsets, sizes
+
+    def _reserve(self, slot, nbytes):
+        """The slot's host buffer may be written: its last upload has completed, and it holds ``nbytes``."""
+        if slot.uploaded is not None:
+            slot.uploaded.synchronize()
+        if slot.host is None or slot.host.numel() < nbytes:
+            if slot.consumed is not None:
+                slot.consumed.synchronize()
+            cap = max(int(nbytes), 2 * (slot.host.numel() if slot.host is not None else 0), 1 << 16)
+            slot.dev = None
+            slot.host = torch.empty(cap, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+
+    # -- device half: only ever called by the thread that composes the batch
+
+    def upload(self, slot, nbytes, device):
+        """The staged bytes on the device, ordered on the current stream behind the launch that last read this slot."""
+        stream = torch.cuda.current_stream(device)
+        if slot.consumed is not None and slot.stream != stream:
+            stream.wait_event(slot.consumed)
+        if slot.dev is None:
+            slot.dev = torch.empty(slot.host.numel(), dtype=torch.uint8, device=device)
+        if slot.uploaded is None:
+            slot.uploaded, slot.consumed = torch.cuda.Event(), torch.cuda.Event()
+        arena = slot.dev[:max(nbytes, 1)]
+        arena.copy_(slot.host[:max(nbytes, 1)], non_blocking=True)
+        slot.uploaded.record(stream)
+        slot.stream = stream
+        return arena
+
+    def launched(self, slot):
+        slot.consumed.record(slot.stream)
+
+    # -- statistics
+
+    def images(self):
+        """The decoded images in file order, at most STATS_WINDOW of them in flight."""
+        pool, futures = self._pool(), []
+        try:
+            for i in range(len(self.files) + self.STATS_WINDOW):
+                if i < len(self.files):
+                    futures.append(pool.submit(_decode_rgb, self.files[i]))
+                if i >= self.STATS_WINDOW:
+                    yield futures[i - self.STATS_WINDOW].result()
+                    futures[i - self.STATS_WINDOW] = None
+        finally:
+            for f in futures:
+                if f is not None:
+                    f.cancel()
 
 
 class FileDatasetGenerator(_GeneratorBase):
     """Base class of the file-based generators, with the reference's constructor arguments (datasets/common.py:129-162).
 
-    ``cropsize`` is (width, height).  ``store_budget_bytes``: the largest decoded split the store accepts (default: 60 % of the
-    device memory free when the split is decoded); ``dtype``: float32 or bfloat16 batches."""
+    ``cropsize`` is (width, height).  ``store_budget_bytes``: the largest decoded split the resident store accepts (default: 60 % of
+    the device memory free when the split is decoded); ``dtype``: float32 or bfloat16 batches.  ``store``: 'resident' (a split over
+    the budget is an error), 'stream' (no split is held; batches are decoded as they are composed) or 'auto' (per split: resident if
+    it fits the budget, streamed if not).  ``prefetch_batches``: how many batches ahead a sequence announces to a streamed split;
+    ``decode_threads``: the size of the decode pool (the module docstring has the streamed store's rules)."""
 
     def __init__(self, root_dir, cropsize=(224, 224), default_target_size=-1, randzoom_range=None, randrot_max=0,
                  distort_colors=False, colordistort_params={}, randerase_prob=0.0,
                  randerase_params={'sl': 0.02, 'sh': 0.4, 'r1': 0.3, 'r2': 1. / 0.3}, color_mode='rgb',
-                 store_budget_bytes=None, dtype=torch.float32, seed=0):
+                 store_budget_bytes=None, dtype=torch.float32, seed=0, store='resident', prefetch_batches=2,
+                 decode_threads=DECODE_THREADS):
         if distort_colors:
             raise NotImplementedError('distort_colors: colour distortion is not part of the device input pipeline '
                                       '(no preset of the reference turns it on)')
         if randrot_max > 0:
             raise NotImplementedError('randrot_max > 0: random rotation is not part of the device input pipeline '
                                       '(no preset of the reference turns it on)')
+        if store not in ('resident', 'stream', 'auto'):
+            raise ValueError("store=%r: 'resident', 'stream' or 'auto'" % (store,))
+        self.store, self.prefetch_batches, self.decode_threads = store, int(prefetch_batches), int(decode_threads)
+        self._decode_pool = None
         self.root_dir = root_dir
         self.cropsize = cropsize
         self.default_target_size = default_target_size
@@ -114,15 +298,33 @@ class FileDatasetGenerator(_GeneratorBase):
         key = bool(train)
         st = self._stores.get(key)
         if st is None:
-            st = self._stores[key] = self._decode(self.train_img_files if train else self.test_img_files)
+            files = self.train_img_files if train else self.test_img_files
+            st = self._stores[key] = self._stream(files) if self.store == 'stream' else self._decode(files)
             if train and (self._mean is None or self._std is None):
-                self._stats_from(lambda: (st.arena[o:o + h * w * 3].reshape(h, w, 3) for o, (h, w) in zip(st.offsets, st.sizes)))
+                self._stats_from(st.images)
         if (self._mean is None or self._std is None) and not train:
             self._store(True, upload=False)
-        if upload and st.device_arena is None:
+        if upload and st.tier == 'resident' and st.device_arena is None:
             st.device_arena = torch.from_numpy(st.arena).to(self._dev())
             st.arena = None                      # the host copy has served its purpose
         return st
+
+    def _pool(self):
+        """The decode pool of the streamed splits, made at first use: at most 16 workers, whatever ``decode_threads`` asks for."""
+        if self._decode_pool is None:
+            self._decode_pool = ThreadPoolExecutor(max_workers=max(1, min(self.decode_threads, DECODE_THREADS)),
+                                                   thread_name_prefix='sehip-decode')
+        return self._decode_pool
+
+    def _stream(self, files):
+        return _StreamStore(files, self._pool, self.prefetch_batches)
+
+    def prefetch(self, indices, train=True):
+        """Announce a batch that a later ``compose_batch(indices, train)`` will ask for.  Only a streamed split that is already
+        open starts decoding; every other split has its images at hand, and the call does nothing."""
+        st = self._stores.get(bool(train))
+        if st is not None and st.tier == 'stream':
+            st.announce(indices)
 
     def _decode(self, files):
         from PIL import Image
@@ -139,6 +341,8 @@ class FileDatasetGenerator(_GeneratorBase):
             if budget is None and torch.cuda.is_available():
                 budget = int(0.6 * torch.cuda.mem_get_info(self._dev())[0])
             if budget is not None and total > budget:
+                if self.store == 'auto':         # the header pass has decided: this split streams
+                    return self._stream(files)
                 raise SehipError('the decoded images of this split take %d bytes, more than the store budget of %d bytes '
                                  '(store_budget_bytes; default: 60 %% of the free device memory)' % (total, budget))
             arena = np.empty(max(total, 1), dtype=np.uint8)
@@ -229,11 +433,20 @@ class FileDatasetGenerator(_GeneratorBase):
         kernel launch.  ``params``: parameters to use instead of drawing them (the dict of ``draw_params``)."""
         st = self._store(train)
         indices = np.asarray(indices, dtype=np.int64)
+        crop = (int(self.cropsize[1]), int(self.cropsize[0]))
+        if st.tier == 'stream':
+            slot, nbytes, offsets, sizes = st.stage(indices)
+            if params is None:
+                params = self.draw_params(sizes, train, augment, rng, target_size)
+            arena = st.upload(slot, nbytes, self._dev())
+            X = compose_on_device(arena, offsets, sizes, params, crop, self._device_stats(), self.color_mode == 'bgr', self.dtype)
+            st.launched(slot)
+            return (X, params) if return_params else X
         sizes = st.sizes[indices]
         if params is None:
             params = self.draw_params(sizes, train, augment, rng, target_size)
-        X = compose_on_device(st.device_arena, st.offsets[indices], sizes, params, (int(self.cropsize[1]), int(self.cropsize[0])),
-                              self._device_stats(), self.color_mode == 'bgr', self.dtype)
+        X = compose_on_device(st.device_arena, st.offsets[indices], sizes, params, crop, self._device_stats(),
+                              self.color_mode == 'bgr', self.dtype)
         return (X, params) if return_params else X
 
     def _device_stats(self):

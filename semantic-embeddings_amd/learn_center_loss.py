@@ -11,8 +11,9 @@ squared-distance loss head, the gradient of the learned centroid table on a fixe
 
 Differences from the reference a user can observe: ``--gpus N`` expects to be launched with N processes (torchrun); ``--batch_size``
 stays the GLOBAL batch and is split across the ranks like ``multi_gpu_model`` split it across towers; models and weights are torch
-``state_dict`` / ``torch.save`` files, not Keras ``.h5``; ``--read_workers`` / ``--queue_size`` / ``--gpu_merge`` are accepted and
-ignored (batches are composed on the device, weights always live on the GPUs); ``--log_dir`` writes a JSON-lines log instead of
+``state_dict`` / ``torch.save`` files, not Keras ``.h5``; ``--read_workers`` / ``--queue_size`` set the decode threads (at most 16) and
+the batches of look-ahead (at most 4) of a dataset that streams its images (``-stream`` names) and are ignored otherwise (batches are
+composed on the device); ``--gpu_merge`` is accepted and ignored (weights always live on the GPUs); ``--log_dir`` writes a JSON-lines log instead of
 TensorBoard events; the ``prob`` cross-entropy is computed from the logits, without Keras 2.2's clip of the probabilities to
 [1e-7, 1 - 1e-7] (the same as the ``--cls_weight`` head of learn_image_embeddings.py).
 """
@@ -138,7 +139,7 @@ def main(argv=None):
         embed_dim = centroids.shape[1]
     elif args.class_list is not None:
         class_list = read_class_list(args.class_list)
-    data_generator = get_data_generator(args.dataset, args.data_root, classes=class_list)
+    data_generator = train_cli.configure_loader(args, get_data_generator(args.dataset, args.data_root, classes=class_list))
 
     # ---- model (learn_center_loss.py:113-124)
     torch.manual_seed(0)   # identical initial weights on every rank

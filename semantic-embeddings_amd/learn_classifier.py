@@ -14,8 +14,9 @@ metrics, with Keras 2.2's clip of the probabilities to [1e-7, 1 - 1e-7].
 Differences from the reference a user can observe: ``--gpus N`` expects to be launched with N processes (torchrun); ``--batch_size``
 stays the GLOBAL batch and is split across the ranks like ``multi_gpu_model`` split it across towers; models, weights and snapshots
 are torch ``state_dict`` / ``torch.save`` files, not Keras ``.h5`` (the saved model emits logits: its last layer is the dense layer
-``prob`` without the softmax activation); ``--read_workers`` / ``--queue_size`` / ``--gpu_merge`` are accepted and ignored (batches are
-composed on the device, weights always live on the GPUs); ``--log_dir`` writes a JSON-lines log instead of TensorBoard events; ties in
+``prob`` without the softmax activation); ``--read_workers`` / ``--queue_size`` set the decode threads (at most 16) and the
+batches of look-ahead (at most 4) of a dataset that streams its images (``-stream`` names) and are ignored otherwise (batches are
+composed on the device); ``--gpu_merge`` is accepted and ignored (weights always live on the GPUs); ``--log_dir`` writes a JSON-lines log instead of TensorBoard events; ties in
 the top-k accuracies are decided on the logits (in favour of the target, like ``tf.nn.in_top_k``), not on the rounded probabilities.
 """
 import argparse
@@ -171,7 +172,7 @@ def main(argv=None):
 
     # ---- dataset (learn_classifier.py:70-80)
     class_list = read_class_list(args.class_list) if args.class_list is not None else None
-    data_generator = get_data_generator(args.dataset, args.data_root, classes=class_list)
+    data_generator = train_cli.configure_loader(args, get_data_generator(args.dataset, args.data_root, classes=class_list))
 
     # ---- model (learn_classifier.py:83-97)
     torch.manual_seed(0)   # identical initial weights on every rank

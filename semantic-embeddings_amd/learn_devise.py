@@ -17,7 +17,8 @@ launched with N processes (torchrun) and ``--batch_size`` stays the GLOBAL batch
 ``torch.save`` model, not a Keras ``.h5`` model: every tensor that matches the network by name and shape is taken, so a classifier's
 ``prob`` layer is left behind and the dense layer ``embedding`` starts fresh (a network that ends in its pooled features -- resnet-32,
 resnet-110 -- gets that layer appended, like the reference appends it to ``model.layers[-1].input``); models and weights are written
-as torch files; ``--read_workers`` / ``--queue_size`` are accepted and ignored (batches are composed on the device); ``--log_dir``
+as torch files; ``--read_workers`` / ``--queue_size`` set the decode threads (at most 16) and the batches of look-ahead (at most 4) of a
+dataset that streams its images (``-stream`` names) and are ignored otherwise (batches are composed on the device); ``--log_dir``
 writes a JSON-lines log instead of TensorBoard events; the model summary is not printed.
 """
 import argparse
@@ -83,8 +84,10 @@ def build_parser():
     g.add_argument('--val_batch_size', type=int, default=None, help='Validation batch size.')
     g.add_argument('--max_decay', type=float, default=0.0, help='Learning-rate decay reached at the end of training.')
     g.add_argument('--margin', type=float, default=0.1, help='Margin of the hinge ranking loss.')
-    g.add_argument('--read_workers', type=int, default=8, help='Ignored (device-side batches).')
-    g.add_argument('--queue_size', type=int, default=100, help='Ignored (device-side batches).')
+    g.add_argument('--read_workers', type=int, default=8,
+                   help='Decode threads of a dataset that streams its images ("-stream" names), at most 16; ignored otherwise (device-side batches).')
+    g.add_argument('--queue_size', type=int, default=100,
+                   help='Batches a streaming dataset decodes ahead of use, at most 4 (each is a device buffer); ignored otherwise.')
     g.add_argument('--gpus', type=int, default=1, help='Number of GPUs = number of launched processes.')
     g = parser.add_argument_group('Output parameters')
     train_cli.add_output_arguments(g, 'Where to save the embeddings of the test images ({"feat": {i: vec}} pickle).')
@@ -100,7 +103,7 @@ def main(argv=None):
 
     # ---- class embeddings and dataset (learn_devise.py:57-65)
     embed_labels, embedding = load_embedding(args.embedding)
-    data_generator = get_data_generator(args.dataset, args.data_root, classes=embed_labels)
+    data_generator = train_cli.configure_loader(args, get_data_generator(args.dataset, args.data_root, classes=embed_labels))
     emb_dev = torch.from_numpy(embedding).to(dev).contiguous()
 
     # ---- model (learn_devise.py:67-74)

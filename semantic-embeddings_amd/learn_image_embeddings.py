@@ -11,8 +11,9 @@ embeddings (cosine loss on hierarchy-based unit-sphere embeddings by default), s
 Differences from the reference a user can observe: ``--gpus N`` expects to be launched with N
 processes (torchrun); ``--batch_size`` stays the GLOBAL batch and is split across the ranks like
 ``multi_gpu_model`` split it across towers; models / snapshots are torch ``state_dict`` files, not
-Keras ``.h5``; ``--read_workers`` / ``--queue_size`` are accepted and ignored (batches are composed
-on the device); ``--log_dir`` writes a JSON-lines log instead of TensorBoard events.
+Keras ``.h5``; ``--read_workers`` / ``--queue_size`` set the decode threads (at most 16) and the batches of
+look-ahead (at most 4) of a dataset that streams its images (``-stream`` names) and are ignored otherwise
+(batches are composed on the device); ``--log_dir`` writes a JSON-lines log instead of TensorBoard events.
 """
 import argparse
 import pickle
@@ -162,7 +163,7 @@ def main(argv=None):
         with open(args.embedding, 'rb') as pf:
             dump = pickle.load(pf)
         embed_labels, embedding = dump['ind2label'], dump['embedding']
-    data_generator = get_data_generator(args.dataset, args.data_root, classes=embed_labels)
+    data_generator = train_cli.configure_loader(args, get_data_generator(args.dataset, args.data_root, classes=embed_labels))
     if embedding is None:
         embedding = np.eye(data_generator.num_classes)
     emb_dev = torch.from_numpy(np.asarray(embedding, dtype=np.float32)).to(dev).contiguous()   # f64 -> f32 like the TF feed

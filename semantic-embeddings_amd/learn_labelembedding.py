@@ -15,8 +15,9 @@ fixed-order per-class reduction, so a step gives the same bits whenever its inpu
 Differences from the reference a user can observe: ``--gpus N`` expects to be launched with N processes (torchrun); ``--batch_size``
 stays the GLOBAL batch and is split across the ranks like ``multi_gpu_model`` split it across towers -- the loss's batch-wide
 factor ``B / (sum mask + 1e-8)`` is taken over each rank's own sub-batch, as it is over each tower's in the reference; models and
-weights are torch ``state_dict`` / ``torch.save`` files, not Keras ``.h5``; ``--read_workers`` / ``--queue_size`` / ``--gpu_merge``
-are accepted and ignored (batches are composed on the device, weights always live on the GPUs); ``--log_dir`` writes a JSON-lines
+weights are torch ``state_dict`` / ``torch.save`` files, not Keras ``.h5``; ``--read_workers`` / ``--queue_size``
+set the decode threads (at most 16) and the batches of look-ahead (at most 4) of a dataset that streams its images (``-stream`` names)
+and are ignored otherwise (batches are composed on the device); ``--gpu_merge`` is accepted and ignored (weights always live on the GPUs); ``--log_dir`` writes a JSON-lines
 log instead of TensorBoard events.
 """
 import argparse
@@ -165,7 +166,7 @@ def main(argv=None):
 
     # ---- dataset (learn_labelembedding.py:110-119)
     class_list = train_cli.read_class_list(args.class_list) if args.class_list is not None else None
-    data_generator = get_data_generator(args.dataset, args.data_root, classes=class_list)
+    data_generator = train_cli.configure_loader(args, get_data_generator(args.dataset, args.data_root, classes=class_list))
 
     # ---- model (learn_labelembedding.py:122-130)
     torch.manual_seed(0)   # identical initial weights on every rank

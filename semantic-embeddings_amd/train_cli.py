@@ -37,8 +37,10 @@ def add_finetune_and_device_arguments(g, finetune_init, finetune_init_help):
     g.add_argument('--finetune', type=str, default=None, help='state_dict with pre-trained weights (matched by name, mismatches skipped).')
     g.add_argument('--finetune_init', type=int, default=finetune_init, help=finetune_init_help)
     g.add_argument('--gpus', type=int, default=1, help='Number of GPUs = number of launched processes.')
-    g.add_argument('--read_workers', type=int, default=8, help='Ignored (device-side batches).')
-    g.add_argument('--queue_size', type=int, default=100, help='Ignored (device-side batches).')
+    g.add_argument('--read_workers', type=int, default=8,
+                   help='Decode threads of a dataset that streams its images ("-stream" names), at most 16; ignored otherwise (device-side batches).')
+    g.add_argument('--queue_size', type=int, default=100,
+                   help='Batches a streaming dataset decodes ahead of use, at most 4 (each is a device buffer); ignored otherwise.')
     g.add_argument('--gpu_merge', action='store_true', default=False, help='Ignored (weights always live on the GPUs).')
 
 
@@ -59,6 +61,16 @@ def read_class_list(path):
         return [int(lbl) for lbl in class_list]
     except ValueError:
         return class_list
+
+
+def configure_loader(args, data_generator):
+    """``--read_workers`` / ``--queue_size`` for a generator that may stream its images (datasets/files.py, ``store`` other than
+    'resident'): the decode threads, at most 16, and the batches of look-ahead, at most 4 because every slot of the ring is device
+    memory.  Every other generator composes its batches from device-resident data and has nothing to configure."""
+    if getattr(data_generator, 'store', 'resident') != 'resident':
+        data_generator.decode_threads = max(1, min(int(args.read_workers), 16))
+        data_generator.prefetch_batches = max(0, min(int(args.queue_size), 4))
+    return data_generator
 
 
 # ---------------------------------------------------------------- process group: one process per GPU over RCCL

@@ -27,6 +27,10 @@
     python tools/bench_kernels.py shortcut       (sehip.shortcut_add forward + backward next to the torch composition avg_pool2d + pad + add
                                                   at PyramidNet-272-200's shapes for batch 128: the widest stride-1 block of each stage and
                                                   both stride-2 blocks, fp32 NCHW and bf16 NHWC)
+    python tools/bench_kernels.py stream         (the streamed image store, datasets/files.py: 2,048 seeded 500 x 375 JPEGs written to a
+                                                  temporary directory, the ILSVRC preset at batch 128 with 16 decode threads: images/s of
+                                                  streamed composition with look-ahead 0, 2 and 4, its split into decode, packing, upload
+                                                  and tables + se_image_batch, and the resident composition of the same images)
     python tools/bench_kernels.py qg [--small] [--ranking-path]
                                                  (one query-vs-gallery AP leg, recall_precision_device(..., gallery=...): 50,000 queries x
                                                   1,281,167 gallery rows x D = 1000, 1000 classes of ~1281 rows; --small: 2,000 x 60,000 x
@@ -61,7 +65,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -93,6 +97,8 @@ def main():
         return bench_shortcut()
     if args.what == "qg":
         return bench_qg(args)
+    if args.what == "stream":
+        return bench_stream()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -801,6 +807,111 @@ def bench_image(B=128, reps=20, stored=256):
     print("ResNet-50 training step, 224 x 224, 200 classes, batch %d, %s: %.2f ms/step = %.0f images/s; slowest batch composition "
           "(host + kernel) %.2f ms: the loader %s" % (B, r["dtype"], r["ms_per_step"], r["value"], worst,
                                                       "keeps up with the network" if worst < r["ms_per_step"] else "DOES NOT keep up: it sets images/s"))
+
+
+def bench_stream(images=2048, B=128, threads=16, classes=8):
+    """The streamed tier of the file-based datasets (datasets/files.py) at the ILSVRC preset -- shorter side 256 .. 480, crop 224 x 224,
+    batch `B`, `threads` decode threads -- on `images` JPEGs of 500 x 375 (quality 90; smooth content plus noise from a fixed seed)
+    written to a temporary directory in ILSVRC's layout.  Whole epochs of train_sequence(B) (host clock, device synchronised at the
+    end, the second epoch of each generator: the files are in the page cache) with look-ahead 0, 2 and 4, next to the resident tier on
+    the same images.  Then one epoch of un-announced batches taken apart, a device synchronise after every part, medians per batch:
+    decode (the pool), packing into the pinned slot, upload, and draw + tables + their upload + se_image_batch."""
+    import io
+    import tempfile
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import PIL.Image
+    from datasets import ILSVRCGenerator
+    from datasets.files import compose_on_device
+
+    def jpeg(k):
+        rng = np.random.default_rng(k)
+        yy, xx = np.mgrid[0:375, 0:500].astype(np.float64)
+        img = np.stack([128 + 100 * np.sin(xx / (9 + 5 * c) + rng.uniform(0, 6)) * np.cos(yy / (11 + 3 * c) + rng.uniform(0, 6)) for c in range(3)], axis=-1)
+        buf = io.BytesIO()
+        PIL.Image.fromarray(np.clip(img + rng.normal(0, 12, img.shape), 0, 255).astype(np.uint8)).save(buf, format="JPEG", quality=90)
+        return buf.getvalue()
+
+    def epoch(gen):
+        seq = gen.train_sequence(B, shuffle=True)
+        rates = []
+        for _ in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for b in range(len(seq)):
+                seq[b]
+            torch.cuda.synchronize()
+            rates.append(len(seq) * B / (time.perf_counter() - t0))
+            seq.on_epoch_end()
+        return rates
+
+    with tempfile.TemporaryDirectory() as root:
+        t0 = time.perf_counter()
+        with ThreadPoolExecutor(max_workers=threads) as pool:
+            blobs = list(pool.map(jpeg, range(images)))
+        for k, blob in enumerate(blobs):
+            d = os.path.join(root, "ILSVRC2012_img_train", "n%08d" % (k % classes))
+            os.makedirs(d, exist_ok=True)
+            with open(os.path.join(d, "n%08d_%d.JPEG" % (k % classes, k)), "wb") as f:
+                f.write(blob)
+        os.makedirs(os.path.join(root, "ILSVRC2012_img_val"))
+        print("stream: wrote %d JPEGs of 500 x 375, %.1f MB (%.0f KB each), in %.1f s; %d decode threads, batch %d, ILSVRC preset"
+              % (images, sum(map(len, blobs)) / 1e6, np.mean([len(b) for b in blobs]) / 1e3, time.perf_counter() - t0, threads, B), flush=True)
+        del blobs
+        for ahead in (0, 2, 4):
+            gen = ILSVRCGenerator(root, store="stream", prefetch_batches=ahead, decode_threads=threads, dtype=torch.bfloat16)
+            first, second = epoch(gen)
+            print("streamed, look-ahead %d (ring of %d slots): %.0f images/s (first epoch %.0f)" % (ahead, ahead + 2, second, first), flush=True)
+        gen = ILSVRCGenerator(root, store="resident", dtype=torch.bfloat16)
+        t0 = time.perf_counter()
+        st = gen._store(True)
+        built = time.perf_counter() - t0
+        first, second = epoch(gen)
+        print("resident (store of %.2f GB decoded and uploaded in %.1f s = %.0f images/s, once): %.0f images/s (first epoch %.0f)"
+              % (st.device_arena.numel() / 1e9, built, images / built, second, first), flush=True)
+        # one epoch of the streamed tier taken apart
+        gen = ILSVRCGenerator(root, store="stream", prefetch_batches=0, decode_threads=threads, dtype=torch.bfloat16)
+        st, rng, crop = gen._store(True), np.random.default_rng(0), (224, 224)
+        parts = {"decode": [], "pack": [], "upload": [], "tables + se_image_batch": []}
+        for b in range(images // B + 1):
+            idx = rng.choice(images, B, replace=False)
+            torch.cuda.synchronize()
+            t = [time.perf_counter()]
+            key, decoded = st.collect(idx)
+            t.append(time.perf_counter())
+            st.pending[key] = {i: _Done(a) for i, a in decoded.items()}          # stage() finds the batch decoded: what is left is packing
+            slot, nbytes, offsets, sizes = st.stage(idx)
+            t.append(time.perf_counter())
+            arena = st.upload(slot, nbytes, gen._dev())
+            torch.cuda.synchronize()
+            t.append(time.perf_counter())
+            params = gen.draw_params(sizes, True, True, rng)
+            compose_on_device(arena, offsets, sizes, params, crop, gen._device_stats(), False, gen.dtype)
+            st.launched(slot)
+            torch.cuda.synchronize()
+            t.append(time.perf_counter())
+            if b:                                                                 # the first batch warms up
+                for name, dt in zip(parts, np.diff(t)):
+                    parts[name].append(dt * 1e3)
+        med = {name: float(np.median(v)) for name, v in parts.items()}
+        total = sum(med.values())
+        print("one streamed batch of %d taken apart (medians of %d batches, %.1f MB staged): %s; sum %.2f ms = %.0f images/s without overlap"
+              % (B, len(parts["decode"]), nbytes / 1e6, "; ".join("%s %.2f ms (%.0f %%)" % (n, v, 100 * v / total) for n, v in med.items()),
+                 total, B / total * 1e3), flush=True)
+        print("decode alone: %.0f images/s on %d threads = %.2f ms per image and thread" % (B / med["decode"] * 1e3, threads, med["decode"] * threads / B))
+
+
+class _Done(object):
+    """A finished future, for handing already decoded images to _StreamStore.stage."""
+
+    def __init__(self, value):
+        self.value = value
+
+    def result(self):
+        return self.value
+
+    def cancel(self):
+        return False
 
 
 def bench_tiny(reps=40, batch=20, stored=10000):
