@@ -321,7 +321,7 @@ class ClassHierarchy(object):
     def hierarchical_precision_device(self, features, labels, ks=[1, 10, 50, 100], compute_ahp=False, compute_ap=False,
                                       normalize=False, ids=None, tile_rows=None, distributed=False, group=None, kblocks=None,
                                       gather_per_query=True, kernels=None, per_query=True, head_via_topk=True,
-                                      gallery=None, gallery_labels=None, gallery_ids=None, tile_cols=None):
+                                      gallery=None, gallery_labels=None, gallery_ids=None, tile_cols=None, rank_gallery=False):
         """``hierarchical_precision(pairwise_retrieval(features, normalize), labels, ...)`` (ignore_qids = True, every
         image is query and gallery item) without leaving the GPU: the rankings stay device tensors
         (``evaluate_retrieval.ranking_tiles``) and the per-query gather + prefix sums run in
@@ -352,11 +352,30 @@ class ClassHierarchy(object):
         ``query id -> ranked gallery ids`` mapping.  A query whose id is a gallery id is dropped from its own ranking
         (``ignore_qids``), the others keep every item; best-possible curves come from the gallery's class counts.  P@k / AHP@K take
         the (sharded-gallery) fused top-L path, AP the counting path of ``recall_precision_device(..., gallery=...)``: no ranking of
-        the gallery is made.  Un-clipped AHP needs the whole list and raises ``ValueError`` here (CLI: pass ``--clip_ahp``)."""
+        the gallery is made.  Un-clipped AHP needs the whole list and raises ``ValueError`` here (CLI: pass ``--clip_ahp`` or
+        ``--rank_gallery``).
+
+        ``rank_gallery`` (opt-in, with ``gallery``; CLI: ``--rank_gallery``): every query's row is ranked against the WHOLE gallery --
+        ``ranking_tiles(..., gallery=...)``: ``se_pairwise_dist`` + ``se_rank_rows`` on a tile of query rows -- and every requested
+        metric of a query is read from that one ranking by ``se_hierarchical_precision``: P@k, AHP over the whole list
+        (``compute_ahp=True``: ``np.trapz(cumsum(sim) / cum_best, dx=1 / len)``, where ``len`` is the gallery without the query's own
+        item if it has one) or AHP@K, and AP (no counting pass).  8 bytes per (query, gallery item) pass through device memory, tile
+        by tile: before the first launch the tile is sized from the free device memory, after the two ``[C, G]`` float64 best curves,
+        their reciprocal table and the operands; a problem that cannot fit raises a ``ValueError`` naming the estimate (``tile_rows``
+        overrides the size, not the check).  Several ranks: the QUERIES are sharded, the gallery is replicated (a whole ranking needs
+        the whole gallery), rows gathered or sums reduced as above.  No queries at all: the means are NaN, the dictionaries empty.
+        ``kernels`` (tests): ``{'normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows', 'hierarchical_precision', 'device'}``, the
+        names the counting path looks up."""
         if gallery is not None:
+            if rank_gallery:
+                return self._hierarchical_precision_ranked_gallery(features, labels, ks, compute_ahp, compute_ap, normalize, ids, tile_rows,
+                                                                   distributed, group, kblocks, gather_per_query, kernels, per_query, gallery,
+                                                                   gallery_labels, gallery_ids)
             return self._hierarchical_precision_gallery(features, labels, ks, compute_ahp, compute_ap, normalize, ids, tile_rows, tile_cols,
                                                         distributed, group, kblocks, gather_per_query, kernels, per_query, gallery,
                                                         gallery_labels, gallery_ids)
+        if rank_gallery:
+            raise ValueError('rank_gallery=True needs a gallery: without one every image is ranked against all the others already')
         import torch
         from sharded_retrieval import shard_bounds, sharded_topk
         kernels = dict(kernels or {})
@@ -460,8 +479,9 @@ class ClassHierarchy(object):
         from recall_precision import gallery_problem, recall_precision_device, _to_device_f32
         from sharded_retrieval import shard_bounds, sharded_topk
         if compute_ahp is True:
-            raise ValueError('un-clipped AHP needs the whole ranking of the gallery, which a separate gallery never gets: '
-                             'pass compute_ahp=K (--clip_ahp K on the command line)')
+            raise ValueError('un-clipped AHP needs the whole ranking of the gallery, which a separate gallery does not get by default: '
+                             'pass compute_ahp=K (--clip_ahp K on the command line), or opt into that ranking with rank_gallery=True '
+                             '(--rank_gallery)')
         kernels = dict(kernels or {})
         stand_ins = bool(kernels)
         native_metrics = 'hierarchical_precision' not in kernels
@@ -516,6 +536,88 @@ class ClassHierarchy(object):
                                               gallery=gallery, gallery_labels=gallery_labels, gallery_ids=gallery_ids,
                                               distributed=distributed, group=group)[3]
             res_d[:, 2 * len(ks) + 2] = torch.from_numpy(aps[q0:q1]).to(dev)
+        return self._metric_rows_to_results(res_d, nq, q_ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query)
+
+    def _hierarchical_precision_ranked_gallery(self, features, labels, ks, compute_ahp, compute_ap, normalize, ids, tile_rows, distributed,
+                                               group, kblocks, gather_per_query, kernels, per_query, gallery, gallery_labels, gallery_ids):
+        """``hierarchical_precision_device(..., gallery=..., rank_gallery=True)`` (see there)."""
+        import torch
+        import torch.distributed as dist
+        from evaluate_retrieval import ranking_tiles
+        from recall_precision import gallery_problem, _to_device_f32
+        from sharded_retrieval import shard_bounds
+        kernels = dict(kernels or {})
+        stand_ins = bool(kernels)
+        native_metrics = 'hierarchical_precision' not in kernels
+        native_ranking = 'rank_rows' not in kernels
+        if native_metrics or native_ranking:
+            import sehip
+            kernels.setdefault('hierarchical_precision', sehip.hierarchical_precision)
+        ks = [ks] if isinstance(ks, int) else list(ks)
+        ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
+        qf, gf, q_ids, qcls_h, gcls_h, class_list, qidx_h = gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids)
+        nq, ng, d, C = int(qf.shape[0]), int(gf.shape[0]), int(qf.shape[1]), len(class_list)
+        if ng == 0:
+            raise ValueError('the gallery is empty')
+        ncol = 2 * len(ks) + 3
+        if nq == 0:     # nothing to average
+            names = ['P@{} ({})'.format(k, t) for k in ks for t in ('WUP', 'LCS_HEIGHT')]
+            if compute_ahp:
+                names += ['AHP{} ({})'.format('' if ahp_clip is None else '@{}'.format(ahp_clip), t) for t in ('WUP', 'LCS_HEIGHT')]
+            names += ['AP'] if compute_ap else []
+            return {m: float('nan') for m in names}, ({m: {} for m in names} if per_query else None)
+        dev = torch.device(kernels.get('device') or torch.device('cuda', torch.cuda.current_device()))
+        world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
+        rank = dist.get_rank(group) if world > 1 else 0
+        q0, q1 = shard_bounds(nq, world)[rank] if world > 1 else (0, nq)
+
+        # ---- what the evaluation will hold on the device, known before anything is launched: the two [C, G] float64 best curves, their
+        #      reciprocal table (per class two rows of se_hprec_curve_len(G) double2), the operands, and per tile row its distances, its
+        #      ranks (rows of 16-byte pitch) and its metrics, plus the ranking's workspace ----
+        def curve_len(n):
+            return int(sehip._lib.call('se_hprec_curve_len', n)) if native_metrics else 0
+
+        def tile_bytes(rows):
+            ws = int(sehip.rank_rows_workspace_bytes(rows, ng)) if native_ranking else 0
+            return rows * (8 * ((ng + 3) // 4 * 4) + 8 * ncol) + ws
+
+        fixed = 2 * 8 * C * ng + 32 * C * curve_len(ng) + 4 * d * (nq + ng)
+        free = _free_device_bytes(dev)
+        budget = None if free is None else free - free // 10        # a tenth stays free: allocator granularity, the other kernels' scratch
+        rows = max(1, q1 - q0)
+        if tile_rows is not None:
+            rows = max(1, min(rows, int(tile_rows)))
+        elif budget is not None:
+            rows = max(1, min(rows, (budget - fixed) // (8 * ((ng + 3) // 4 * 4) + 8 * ncol)))
+            while rows > 1 and fixed + tile_bytes(rows) > budget:
+                rows = rows * 3 // 4
+            if 128 < rows < q1 - q0:
+                rows = rows // 128 * 128
+        estimate = fixed + tile_bytes(rows)
+        if budget is not None and estimate > budget:
+            raise ValueError('ranking {} queries against a gallery of {} items in {} classes needs an estimated {:,} bytes of device memory '
+                             '({:,} for the best-possible curves, their reciprocal table and the features, {:,} for a tile of {} query row{}), '
+                             '{:,} are free: use the counting path (rank_gallery=False with compute_ahp=K), fewer classes or a smaller gallery'
+                             .format(q1 - q0, ng, C, estimate, fixed, estimate - fixed, rows, '' if rows == 1 else 's', free))
+
+        if (not stand_ins) and dev.type == 'cuda':
+            wup_t, lcs_t = self.similarity_tables_device(class_list, device=dev)
+        else:
+            wup_t, lcs_t = self.similarity_tables(class_list)
+        counts = np.bincount(gcls_h, minlength=C)
+        args_d = [_on_device(a, dev) for a in (wup_t, lcs_t)] + [_best_curves(t, counts, ng, dev) for t in (wup_t, lcs_t)]
+        extra = {'curves': sehip.hprec_reciprocal_curves(args_d[2], args_d[3])} if native_metrics else {}    # once per gallery
+        fq, fg = _to_device_f32(qf, dev), _to_device_f32(gf, dev)
+        gcls_d, qcls_d, qidx_d = (torch.from_numpy(a).to(dev) for a in (gcls_h, qcls_h, qidx_h))
+        ks_d = torch.tensor(ks, dtype=torch.int32, device=dev)
+        ahp_len = -1 if not compute_ahp else (0 if ahp_clip is None else ahp_clip)
+        rank_kernels = {k: kernels[k] for k in ('normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows') if k in kernels}
+        outs = []
+        for r0, tile in ranking_tiles(fq, normalize, tile_rows=rows, queries=(q0, q1), kblocks=kblocks, gallery=fg, kernels=rank_kernels):
+            r1 = r0 + tile.shape[0]     # the tile is consumed here, before the next one overwrites it
+            outs.append(kernels['hierarchical_precision'](tile, gcls_d, qcls_d[r0:r1].contiguous(), qidx_d[r0:r1].contiguous(), *args_d, ks_d,
+                                                         ahp_len=ahp_len, want_ap=compute_ap, **extra))
+        res_d = torch.cat(outs) if outs else torch.zeros((0, ncol), dtype=torch.float64, device=dev)
         return self._metric_rows_to_results(res_d, nq, q_ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query)
 
     def _metric_rows_to_results(self, res_d, n, ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query):
@@ -582,6 +684,16 @@ def _best_curves(table, counts, n, dev):
     reps = torch.from_numpy(counts[order].astype(np.int64)).to(dev)
     flat = torch.repeat_interleave(vals.reshape(-1), reps.reshape(-1), output_size=C * n)
     return flat.view(C, n).cumsum(dim=1)
+
+
+def _free_device_bytes(dev):
+    """Bytes of device memory an allocation on ``dev`` can still get -- free on the device, or held unused by torch's caching
+    allocator; None where there is nothing to size against (the CPU stand-ins of the tests)."""
+    import torch
+    dev = torch.device(dev)
+    if dev.type != 'cuda':
+        return None
+    return int(torch.cuda.mem_get_info(dev)[0]) + int(torch.cuda.memory_reserved(dev)) - int(torch.cuda.memory_allocated(dev))
 
 
 def _on_device(table, dev):

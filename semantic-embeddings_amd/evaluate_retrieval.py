@@ -18,7 +18,11 @@ reference: evaluate_retrieval.py:22-73 (pairwise_retrieval), :76-151 (reporting 
   RCCL all-gather of the per-shard lists, k-way merge (SURVEY.md section 8e row 3);
 * ``--gallery_feat FILE`` (extension, with ``--gallery_split``): the --feat file at the same position holds QUERIES against this
   gallery -- held-out images against a database.  The gallery is never ranked in full: P@k / AHP@K read fused top-k lists
-  (``--clip_ahp`` is required), AP counts the gallery items in front of every relevant one (``se_count_preceding``).
+  (``--clip_ahp`` is required), AP counts the gallery items in front of every relevant one (``se_count_preceding``);
+* ``--rank_gallery`` (extension, with ``--gallery_feat``): every query's row IS ranked against the whole gallery, tile of queries
+  by tile, and every metric is read from that one ranking -- the whole-list ``AHP (WUP)`` / ``AHP (LCS_HEIGHT)`` columns the
+  reference prints by default included, so ``--clip_ahp`` is no longer required (8 bytes per query and gallery item pass through
+  device memory: meant for galleries of CIFAR / CUB / NABirds / Cars size).
 """
 import argparse
 import os.path
@@ -133,8 +137,60 @@ def _cached_rows(kind, rows, n, dtype, device):
     return mat if pitch == n else mat[:, :n]
 
 
+def _rectangular_kernels(kernels):
+    """The four entry points a rectangular ranking takes, under the names the counting path of ``recall_precision_device(...,
+    gallery=...)`` looks up (CPU stand-ins of the tests replace them)."""
+    kernels = dict(kernels or {})
+    names = ('normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows')
+    if any(k not in kernels for k in names):
+        import sehip
+
+        def pairwise_dist(a, b, cosine, sqa, sqb, kblocks, out=None):
+            return sehip.pairwise_dist(a, b, metric=sehip.METRIC_COSINE if cosine else sehip.METRIC_EUCLID, sqa=sqa, sqb=sqb,
+                                       kblocks=kblocks, out=out)
+
+        native = {'pairwise_dist': pairwise_dist}
+        for k in names:
+            kernels.setdefault(k, native.get(k) or getattr(sehip, k))
+    return kernels
+
+
+def _gallery_ranking_tiles(features, gallery, normalize, tile_rows, queries, kblocks, prenormalized, kernels):
+    """``ranking_tiles(..., gallery=...)``: int32 tiles ``[rows, len(gallery)]``."""
+    kernels = _rectangular_kernels(kernels)
+    nq, d = features.shape
+    n = int(gallery.shape[0])
+    if int(gallery.shape[1]) != int(d):
+        raise ValueError('queries have {} feature dimensions, the gallery {}'.format(d, gallery.shape[1]))
+    kblocks = _resolve_kblocks(kblocks, d)
+    if normalize:
+        if not prenormalized:
+            kernels['normalize_rows_'](features)
+            kernels['normalize_rows_'](gallery)
+        sq_q = sq_g = None
+    else:
+        sq_q, sq_g = kernels['row_sqnorm'](features), kernels['row_sqnorm'](gallery)
+    q0, q1 = (0, nq) if queries is None else queries
+    if tile_rows is None:
+        tile_rows = max(128, min(nq, (DEFAULT_TILE_BYTES // (8 * max(n, 1))) // 128 * 128))
+    tile_rows = max(1, int(tile_rows))
+    pd = rk = None
+    if features.is_cuda and q1 > q0:
+        # this iteration's own two buffers, shared by its tiles: nothing of the process-wide tile cache is handed out, so a tile a
+        # caller keeps after the loop is not overwritten by the next evaluation of the process
+        import torch
+        import sehip
+        pd = sehip.empty_rows(min(tile_rows, q1 - q0), n, torch.float32, features.device)
+        rk = sehip.empty_rows(min(tile_rows, q1 - q0), n, torch.int32, features.device)
+    for r0 in range(q0, q1, tile_rows):
+        rows = min(tile_rows, q1 - r0)
+        dist = kernels['pairwise_dist'](features[r0:r0 + rows], gallery, normalize, None if sq_q is None else sq_q[r0:r0 + rows], sq_g,
+                                        kblocks, None if pd is None else pd[:rows])
+        yield r0, (kernels['rank_rows'](dist) if rk is None else kernels['rank_rows'](dist, out=rk[:rows]))
+
+
 def ranking_tiles(features, normalize=False, tile_rows=None, idx64=False, queries=None, kblocks=None, whole_if_fits=True,
-                  prenormalized=False, idx16=False):
+                  prenormalized=False, idx16=False, gallery=None, kernels=None):
     """Generator over ``(first_row, rank_tile)`` with ``rank_tile`` an int32 (int64 if ``idx64``)
     DEVICE tensor ``[rows, N]``: the canonical ranking of queries ``first_row .. first_row+rows``.
     **A tile is valid until the next one is drawn**: distances and ranks live in grow-only per-device buffers that every tile and
@@ -150,7 +206,21 @@ def ranking_tiles(features, normalize=False, tile_rows=None, idx64=False, querie
     ``whole_if_fits`` (default since round 6): rank all queries as ONE tile when distances + ranks (8 N^2 bytes) fit into a third of
     the device memory that is free or already held by the tile cache -- all-pairs then takes the symmetric distance kernel
     (3.2 instead of 5.4 ms at 50k x 50k), i.e. the kernels bench.py times.  The first call on a device pays for the two
-    allocations once (0.24 s for 2 x 10 GB); with the cache later evaluations do not."""
+    allocations once (0.24 s for 2 x 10 GB); with the cache later evaluations do not.
+
+    ``gallery`` (float32 device tensor ``[G, D]``): the rectangular variant -- the rows of ``features`` are QUERIES, every tile is
+    the canonical ranking ``[rows, G]`` (int32) of ``rows`` of them against the whole gallery, with the same (distance, index) order
+    and the same ``kblocks`` chain as the square one; ``queries`` restricts the query rows, ``normalize`` normalises both operands
+    in place.  **Consume each tile before drawing the next**: the tiles of one iteration share two buffers which that iteration
+    owns -- the process-wide cache is not used, so they are not touched again once the iteration has ended.  ``tile_rows`` defaults
+    to ``DEFAULT_TILE_BYTES`` worth of rows (``hierarchical_precision_device(..., rank_gallery=True)`` sizes it from the free device
+    memory instead); ``idx64`` / ``idx16`` / ``whole_if_fits`` do not apply.  ``kernels`` (tests): CPU stand-ins
+    ``{'normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows'}``."""
+    if gallery is not None:
+        if idx64 or idx16:
+            raise ValueError('ranking_tiles(..., gallery=...) writes int32 ranks')
+        yield from _gallery_ranking_tiles(features, gallery, normalize, tile_rows, queries, kblocks, prenormalized, kernels)
+        return
     import torch
     import sehip
 
@@ -323,6 +393,10 @@ def build_parser():
                    help='Do not compute AP; with --clip_ahp only the head of each ranking is needed (sharded-gallery top-k under several ranks).')
     g.add_argument('--kblocks', type=str, default=None, help="'openblas': restart the fp32 dot-product chain per OpenBLAS K block (D > 448).")
     add_gallery_flags(g)
+    # (absent from the namespace unless given -- a run without it parses to exactly what it did before the flag existed)
+    g.add_argument('--rank_gallery', action='store_true', default=argparse.SUPPRESS,
+                   help='With --gallery_feat: rank every query against the WHOLE gallery and read every metric off that ranking; '
+                        'gives the un-clipped AHP columns, so --clip_ahp is not required (with it, AHP@K comes from the same ranking).')
     return p
 
 
@@ -331,9 +405,18 @@ def add_gallery_flags(group):
     against the gallery file at the same position (no --gallery_feat: all-pairs on the --feat file, as the reference does)."""
     group.add_argument('--gallery_feat', type=str, action='append',
                        help='Feature pickle of the GALLERY the matching --feat is queried against (not ranked in full: AP is counted, '
-                            'P@k / AHP@K come from top-k lists; needs --clip_ahp); repeatable.')
+                            'P@k / AHP@K come from top-k lists; needs --clip_ahp or --rank_gallery); repeatable.')
     group.add_argument('--gallery_split', type=str, default='train', choices=['train', 'test'],
                        help='Dataset split the ids of --gallery_feat belong to.')
+
+
+def parse_args(argv=None):
+    """``build_parser().parse_args(argv)`` plus the checks that span several flags."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if getattr(args, 'rank_gallery', False) and not args.gallery_feat:
+        parser.error('--rank_gallery needs --gallery_feat (without a gallery every ranking is a full one already)')
+    return args
 
 
 def gallery_arguments(args, i, data_generator, embed_labels):
@@ -376,7 +459,7 @@ def main(argv=None):
     from datasets import get_data_generator
     from class_hierarchy import ClassHierarchy
 
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     rank, world = init_distributed()
 
     if args.classes_from:
@@ -403,11 +486,14 @@ def main(argv=None):
         features, ind2id, _ = _as_feature_matrix(feat_dump)
         # Several ranks: queries sharded (full rankings), or -- when no metric needs more than the head of a ranking
         # (--skip_ap with --clip_ahp) -- the gallery sharded with an all-gather + merge of per-shard top-k lists.
+        gallery_kw = gallery_arguments(args, i, data_generator, embed_labels)
+        if gallery_kw and getattr(args, 'rank_gallery', False):
+            gallery_kw['rank_gallery'] = True
         perf[feat_name] = hierarchy.hierarchical_precision_device(
             features, labels_test, ks, compute_ahp=args.clip_ahp if args.clip_ahp else True, compute_ap=not args.skip_ap,
             normalize=normalize, ids=None if ind2id is None else ind2id.tolist(), distributed=world > 1,
             kblocks=args.kblocks, per_query=False,         # the tables / plots below use the means only
-            **gallery_arguments(args, i, data_generator, embed_labels))[0]
+            **gallery_kw)[0]
     if rank != 0:
         return perf
 

@@ -37,7 +37,12 @@
                                                   100, 100 classes; --q / --n / --d override.  Time per phase: relevant keys, distance
                                                   slabs, counting, scan + reduce.  --ranking-path: the same positions from full rankings of
                                                   --rank-rows query rows -- se_pairwise_dist + se_rank_rows + se_relevant_positions, the only
-                                                  way before the counting kernel -- scaled to all queries)"""
+                                                  way before the counting kernel -- scaled to all queries.  Then the whole-list phase:
+                                                  hierarchical_precision_device(..., gallery=..., rank_gallery=True) with un-clipped AHP +
+                                                  AP on the CIFAR-100 taxonomy (classes folded onto its 100 leaves) -- distances, ranking
+                                                  and metric kernel per phase -- next to the clipped top-k + counting path (AHP@250 + AP)
+                                                  on the same problem; --whole-rows N ranks only the first N queries and scales, for
+                                                  galleries whose rows take the tiled ranking kernel; --whole-only skips the AP leg)"""
 import argparse
 import os
 import sys
@@ -69,6 +74,8 @@ def main():
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
+    ap.add_argument("--whole-rows", type=int, default=None, help="qg, whole-list phase: rank the first N queries only (times scaled to all)")
+    ap.add_argument("--whole-only", action="store_true", help="qg: the whole-list phase only")
     ap.add_argument("--classes", type=int, default=None, help="qg: number of classes")
     ap.add_argument("--noise", type=float, default=0.7, help="qg: standard deviation of the noise around the class centres (0.7: separable classes, mAP 1)")
     ap.add_argument("--hp-mode", default="all", choices=["all", "whole", "sweep"], help="hprec: every configuration, or whole-list AHP + AP in class order only (profiling)")
@@ -1204,7 +1211,7 @@ def bench_qg(args):
                "rank_rows": timed("relevant keys", sehip.rank_rows), "count_preceding": timed("counting", sehip.count_preceding),
                "count_to_positions": timed("scan + reduce", sehip.count_to_positions),
                "recall_precision_reduce": timed("scan + reduce", sehip.recall_precision_reduce)}
-    for rep in range(2):                                                   # the first call pays allocations and the ranking probe
+    for rep in range(0 if args.whole_only else 2):                         # the first call pays allocations and the ranking probe
         phases.clear()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -1222,6 +1229,79 @@ def bench_qg(args):
             if name == "distance slabs":
                 extra = "  %.1f TFLOP/s, slab write %.1f GB" % (2.0 * q * n * d / ms / 1e9, 4.0 * q * n / 1e9) if ms > 0 else ""
             print("    %-15s %10.2f ms in %6d calls%s" % (name, ms, len(phases.get(name, [])), extra))
+    bench_qg_whole_list(args, fq, fg, q_lab, g_lab, timed, phases)
+
+
+def bench_qg_whole_list(args, fq, fg, q_lab, g_lab, timed, phases):
+    """Whole-list phase of the qg leg: every query ranked against the whole gallery (rank_gallery=True: un-clipped AHP + AP from one
+    ranking), per phase and as wall time, next to the clipped path (fused top-k lists for P@k / AHP@250, counted AP)."""
+    import tempfile
+    from class_hierarchy import ClassHierarchy
+    edges = np.load(os.path.join(ROOT, "tests", "golden", "hierarchy_cifar.npz"))["edges"]
+    with tempfile.NamedTemporaryFile("w", suffix=".txt") as f:
+        for p, c in edges.tolist():
+            f.write("%d %d\n" % (p, c))
+        f.flush()
+        hier = ClassHierarchy.from_file(f.name, id_type=int)
+    q, n = int(fq.shape[0]), int(fg.shape[0])
+    rows = min(q, args.whole_rows or q)
+    scale = q / rows
+    q_lab, g_lab = [c % 100 for c in q_lab[:rows]], [c % 100 for c in g_lab]      # the taxonomy has 100 leaves
+    g_ids = [("g", j) for j in range(n)]
+    kw = dict(ids=list(range(rows)), gallery=fg, gallery_labels=dict(zip(g_ids, g_lab)), gallery_ids=g_ids, normalize=True, per_query=False)
+    ks = [1, 10, 50, 100]
+    print("whole-list phase: %d of %d queries x %d gallery items, %d classes%s" % (rows, q, n, len(set(g_lab)), "" if rows == q else
+                                                                                   " (times below are for %d rows; x %.1f for all)" % (rows, scale)))
+    # both paths run as a user's call runs them (kernels=None): the entry points are timed by wrapping sehip's attributes, which the
+    # host code looks up at call time
+    slab = lambda a, b=None, out=None, **k: "distances" if out is not None else "relevant keys"       # noqa: E731
+    patched = {"pairwise_dist": timed(slab, sehip.pairwise_dist), "rank_rows": timed(lambda pd, **k: "ranking" if k.get("out") is not None else "relevant keys", sehip.rank_rows),
+               "hierarchical_precision": timed("metrics", sehip.hierarchical_precision), "retrieve_topk": timed("fused top-k", sehip.retrieve_topk),
+               "count_preceding": timed("counting", sehip.count_preceding), "count_to_positions": timed("scan + reduce", sehip.count_to_positions),
+               "recall_precision_reduce": timed("scan + reduce", sehip.recall_precision_reduce)}
+    legs = (("whole list, rank_gallery=True (AHP + AP)", dict(compute_ahp=True, rank_gallery=True), ("distances", "ranking", "metrics")),
+            ("clipped, top-k + counting (AHP@250 + AP)", dict(compute_ahp=250),
+             ("fused top-k", "metrics", "relevant keys", "distances", "counting", "scan + reduce")))
+    originals = {k: getattr(sehip, k) for k in patched}
+    for k, v in patched.items():
+        setattr(sehip, k, v)
+    try:
+        _qg_whole_list_legs(legs, hier, fq, rows, n, q_lab, ks, kw, phases)
+    finally:
+        for k, v in originals.items():
+            setattr(sehip, k, v)
+
+
+def _qg_whole_list_legs(legs, hier, fq, rows, n, q_lab, ks, kw, phases):
+    import time
+    import warnings
+    for title, more, names in legs:
+        for rep in range(2):
+            phases.clear()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                try:
+                    means, _ = hier.hierarchical_precision_device(fq[:rows], q_lab, ks, compute_ap=True, **kw, **more)
+                except ValueError as e:                                    # the memory estimate does not admit this shape
+                    print("  %s: refused -- %s" % (title, e))
+                    break
+            torch.cuda.synchronize()
+            wall = time.perf_counter() - t0
+            ahp = [k for k in means if k.startswith("AHP") and k.endswith("(WUP)")][0]
+            print("  %s, run %d: wall %.3f s, %s %.4f, AP %.4f" % (title, rep, wall, ahp, means[ahp], means["AP"]))
+            tot = 0.0
+            for name in names:
+                ms = sum(a.elapsed_time(b) for a, b in phases.get(name, []))
+                tot += ms
+                extra = ""
+                if name == "ranking" and ms > 0:
+                    extra = "  %.1f GB of distances in, as many of ranks out -> %.2f TB/s" % (4.0 * rows * n / 1e9, 8.0 * rows * n / ms / 1e9)
+                if name == "metrics" and ms > 0 and more.get("rank_gallery"):
+                    extra = "  %.1f GB of ranks read -> %.2f TB/s" % (4.0 * rows * n / 1e9, 4.0 * rows * n / ms / 1e9)
+                print("    %-15s %10.2f ms in %6d calls%s" % (name, ms, len(phases.get(name, [])), extra))
+            print("    %-15s %10.2f ms" % ("timed kernels", tot))
 
 
 if __name__ == "__main__":
