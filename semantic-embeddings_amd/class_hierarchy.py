@@ -12,9 +12,9 @@ precision) and every corner of the reference's bookkeeping are kept, so the numb
 reference to float64 round-off (tests/test_class_hierarchy.py checks against values produced by the
 imported reference).
 """
-import types
-
 import os
+import types
+import warnings
 
 import numpy as np
 
@@ -237,15 +237,8 @@ class ClassHierarchy(object):
             kmax = max(kmax, ahp_clip)
         full_lists = compute_ahp is True
 
-        names = ['P@{} ({})'.format(k, t) for k in ks for t in ('WUP', 'LCS_HEIGHT')]
-        ahp_names = ()
-        if compute_ahp:
-            sfx = '' if ahp_clip is None else '@{}'.format(ahp_clip)
-            ahp_names = ('AHP{} (WUP)'.format(sfx), 'AHP{} (LCS_HEIGHT)'.format(sfx))
-        prec = {n: {} for n in names}
-        prec.update({n: {} for n in ahp_names})
-        if compute_ap:
-            prec['AP'] = {}
+        prec = {n: {} for n in _metric_columns(ks, compute_ahp, compute_ap)}
+        ahp_names = [n for n in prec if n.startswith('AHP')]
 
         # label -> row/column index of the similarity tables
         get_label = labels.__getitem__
@@ -366,306 +359,208 @@ class ClassHierarchy(object):
         the whole gallery), rows gathered or sums reduced as above.  No queries at all: the means are NaN, the dictionaries empty.
         ``kernels`` (tests): ``{'normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows', 'hierarchical_precision', 'device'}``, the
         names the counting path looks up."""
-        if gallery is not None:
-            if rank_gallery:
-                return self._hierarchical_precision_ranked_gallery(features, labels, ks, compute_ahp, compute_ap, normalize, ids, tile_rows,
-                                                                   distributed, group, kblocks, gather_per_query, kernels, per_query, gallery,
-                                                                   gallery_labels, gallery_ids)
-            return self._hierarchical_precision_gallery(features, labels, ks, compute_ahp, compute_ap, normalize, ids, tile_rows, tile_cols,
-                                                        distributed, group, kblocks, gather_per_query, kernels, per_query, gallery,
-                                                        gallery_labels, gallery_ids)
-        if rank_gallery:
-            raise ValueError('rank_gallery=True needs a gallery: without one every image is ranked against all the others already')
         import torch
+        import torch.distributed as dist
+        from evaluate_retrieval import RANKING_KERNELS, _resolve_kblocks, resolve_kernels
+        from recall_precision import gallery_problem, recall_precision_device, to_device_f32
         from sharded_retrieval import shard_bounds, sharded_topk
-        kernels = dict(kernels or {})
-        stand_ins = bool(kernels)
-        native_metrics = 'hierarchical_precision' not in kernels
-        native_ranking = 'ranking_tiles' not in kernels
-        if 'ranking_tiles' not in kernels or 'hierarchical_precision' not in kernels:
-            import sehip
-            from evaluate_retrieval import ranking_tiles
-            kernels.setdefault('ranking_tiles', ranking_tiles)
-            kernels.setdefault('hierarchical_precision', sehip.hierarchical_precision)
-
+        if rank_gallery and gallery is None:
+            raise ValueError('rank_gallery=True needs a gallery: without one every image is ranked against all the others already')
+        if gallery is not None and not rank_gallery and compute_ahp is True:
+            raise ValueError('un-clipped AHP needs the whole ranking of the gallery, which a separate gallery does not get by default: '
+                             'pass compute_ahp=K (--clip_ahp K on the command line), or opt into that ranking with rank_gallery=True '
+                             '(--rank_gallery)')
+        # ---- the problem, the device and this rank's queries ----
+        given = dict(kernels or {})
+        native_metrics = 'hierarchical_precision' not in given
+        kernels = resolve_kernels(given, ('hierarchical_precision', 'ranking_tiles', 'device'))
         ks = [ks] if isinstance(ks, int) else list(ks)
         ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
-        n = int(features.shape[0])
-        ids = list(range(n)) if ids is None else list(ids)
-        lab = [labels[i] for i in ids]
-        class_list = sorted(set(lab), key=lambda c: (str(type(c)), c))
-        pos = {c: i for i, c in enumerate(class_list)}
-        cls_h = np.array([pos[c] for c in lab], dtype=np.int32)
-        dev = kernels.get('device') or torch.device('cuda', torch.cuda.current_device())
+        ahp_len = -1 if not compute_ahp else (0 if ahp_clip is None else ahp_clip)
+        ncol = 2 * len(ks) + 3
+        p = gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids)
+        nq, ng, C, dev = int(p.qf.shape[0]), int(p.gf.shape[0]), len(p.class_list), kernels['device']
+        if rank_gallery and ng == 0:
+            raise ValueError('the gallery is empty')
+        if rank_gallery and nq == 0:     # nothing to average
+            names = list(_metric_columns(ks, compute_ahp, compute_ap))
+            return {m: float('nan') for m in names}, ({m: {} for m in names} if per_query else None)
+        world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
+        rank = dist.get_rank(group) if world > 1 else 0
+        q0, q1 = shard_bounds(nq, world)[rank] if world > 1 else (0, nq)
+        # top-L lists are enough when no metric reads past the head of a ranking; a separate gallery is ranked in full on request only
+        head_only = (not compute_ap) and (not compute_ahp or ahp_clip is not None)
+        use_top_lists = (not rank_gallery) if gallery is not None else (head_only and (world > 1 or head_via_topk))
+        if rank_gallery:    # before anything is launched
+            tile_rows = _ranked_gallery_tile_rows(dev, q1 - q0, ng, C, 4 * int(p.qf.shape[1]) * (nq + ng), ncol, tile_rows,
+                                                  native_metrics, 'rank_rows' not in given)
+
+        # ---- class tables and best-possible curves ----
         # with the native kernels the class tables are built on the device as well (se_class_pair_tables: the same bits as
         # similarity_tables, whose double loop costs ~18 us per pair on the host); CPU stand-ins keep the host tables
-        native_tables = (not stand_ins) and torch.device(dev).type == 'cuda'
-        if native_tables:
-            wup_t, lcs_t = self.similarity_tables_device(class_list, device=dev)
+        if (not given) and dev.type == 'cuda':
+            wup_t, lcs_t = self.similarity_tables_device(p.class_list, device=dev)
         else:
-            wup_t, lcs_t = self.similarity_tables(class_list)
+            wup_t, lcs_t = self.similarity_tables(p.class_list)
         # best-possible cumulative similarity per query class: descending-sorted similarities of the whole gallery.  The C x N float64
         # curves are built ON THE DEVICE (round 6: 180 host cumsums of 50,000 entries + 80 MB of host-to-device copies were 25 of the 56 ms
         # of a 50,000-item evaluation): per class the C similarity values in descending order, each repeated by its class count,
         # then one float64 prefix sum per row.
-        counts = np.bincount(cls_h, minlength=len(class_list))
+        counts = np.bincount(p.gcls, minlength=C)
+        best = [_best_curves(t, counts, ng, dev) for t in (wup_t, lcs_t)]
+        L = min(ng, max(ks + [ahp_clip or 0]) + 1)
+        if use_top_lists:
+            best = [b[:, :L + 1].contiguous() for b in best]
+            topk_kblocks = _resolve_kblocks(kblocks, int(p.qf.shape[1]))     # (here: its D > 448 warning names the caller)
+        tables = [_on_device(t, dev) for t in (wup_t, lcs_t)] + best
 
-        best_w, best_l = _best_curves(wup_t, counts, n, dev), _best_curves(lcs_t, counts, n, dev)
-
-        import torch.distributed as dist
-        world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
-        rank = dist.get_rank(group) if world > 1 else 0
-        if torch.is_tensor(features):    # features straight from the network (learn_image_embeddings feature extraction): stay on the device
-            feats = features.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
-        else:
-            feats = torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(dev)
-        cls_d = torch.from_numpy(cls_h).to(dev)
-        qidx_d = torch.arange(n, dtype=torch.int32, device=dev)
-        ks_d = torch.tensor(ks, dtype=torch.int32, device=dev)
-        ahp_len = -1 if not compute_ahp else (0 if ahp_clip is None else ahp_clip)
-        head_only = (not compute_ap) and (not compute_ahp or ahp_clip is not None)
-        q0, q1 = shard_bounds(n, world)[rank] if world > 1 else (0, n)
-        ncol = 2 * len(ks) + 3
-        outs = []
-
-        def curves(args_d):     # the best curves pre-divided for se_hierarchical_precision (the CPU stand-ins of the tests divide themselves)
+        def reciprocal_curves():    # the best curves pre-divided for se_hierarchical_precision (the CPU stand-ins of the tests divide themselves)
             if not native_metrics:
                 return {}
             import sehip
-            return {'curves': sehip.hprec_reciprocal_curves(args_d[2], args_d[3])}
+            return {'curves': sehip.hprec_reciprocal_curves(*best)}
 
-        if head_only and (world > 1 or head_via_topk):
-            # ---- top-L lists are enough for every requested metric: fused distance + top-L (the N x N matrix is never written),
-            #      over this rank's shard of the gallery when there are several ranks ----
-            L = min(n, max(ks + [ahp_clip or 0]) + 1)
-            args_d = [_on_device(a, dev) for a in (wup_t, lcs_t)] + [best_w[:, :L + 1].contiguous(), best_l[:, :L + 1].contiguous()]
-            g0, g1 = shard_bounds(n, world)[rank]
-            if 'local_topk' not in kernels:
+        # ---- operands: ONE device copy of the features when every image is query and gallery item ----
+        fq = to_device_f32(p.qf, dev)
+        fg = fq if p.gf is p.qf else to_device_f32(p.gf, dev)
+        gcls_d = torch.from_numpy(p.gcls).to(dev)
+        if gallery is None:
+            qcls_d, qidx_d = gcls_d, torch.arange(nq, dtype=torch.int32, device=dev)
+        else:
+            qcls_d, qidx_d = torch.from_numpy(p.qcls).to(dev), torch.from_numpy(p.qidx).to(dev)
+        ks_d = torch.tensor(ks, dtype=torch.int32, device=dev)
+
+        def score(ranks, r0, want_ap, extra):       # metric rows of queries r0 .. r0 + len(ranks)
+            r1 = r0 + ranks.shape[0]
+            return kernels['hierarchical_precision'](ranks, gcls_d, qcls_d[r0:r1].contiguous(), qidx_d[r0:r1].contiguous(), *tables, ks_d,
+                                                     ahp_len=ahp_len, want_ap=want_ap, **extra)
+
+        def top_lists():
+            """Fused distance + top-L (the Q x N matrix is never written) over this rank's shard of the gallery, lists merged across the
+            ranks; then the metric rows of this rank's queries."""
+            g0, g1 = shard_bounds(ng, world)[rank]
+            metric = None
+            if 'local_topk' not in given:
                 import sehip
                 if normalize:
-                    sehip.normalize_rows_(feats)
+                    sehip.normalize_rows_(fq)
+                    if fg is not fq:
+                        sehip.normalize_rows_(fg)
                 metric = sehip.METRIC_COSINE if normalize else sehip.METRIC_EUCLID
-            else:
-                metric = None
-            from evaluate_retrieval import _resolve_kblocks
-            _, top_i = sharded_topk(feats, feats[g0:g1], L, g0, metric=metric, group=group,
-                                    local_topk=kernels.get('local_topk'), merge=kernels.get('merge'),
-                                    kblocks=_resolve_kblocks(kblocks, int(feats.shape[1])))
-            if q1 > q0:
-                outs.append(kernels['hierarchical_precision'](top_i[q0:q1].contiguous(), cls_d, cls_d[q0:q1].contiguous(),
-                                                             qidx_d[q0:q1].contiguous(), *args_d, ks_d, ahp_len=ahp_len, want_ap=False,
-                                                             **curves(args_d)))
-        else:
-            args_d = [_on_device(a, dev) for a in (wup_t, lcs_t)] + [best_w, best_l]
-            extra = curves(args_d)      # once per gallery, shared by every tile
+            _, top_i = sharded_topk(fq, fg[g0:g1], L, g0, metric=metric, group=group, local_topk=given.get('local_topk'),
+                                    merge=given.get('merge'), kblocks=topk_kblocks)
+            return [score(top_i[q0:q1].contiguous(), q0, False, reciprocal_curves())] if q1 > q0 else []
+
+        def ranked_tiles():
+            """Full rankings of this rank's queries, tile by tile; each tile is consumed before the next one overwrites it."""
+            extra = reciprocal_curves()     # once per gallery, shared by every tile
+            if gallery is not None:
+                tiles_kw = {'gallery': fg, 'kernels': {k: given[k] for k in RANKING_KERNELS if k in given}}
             # (16-bit ranks between the two kernels -- ranking_tiles(idx16=True), se_hierarchical_precision_r16 -- give the same results
             # from half the bytes, but measured at 50k x 50k the ranking gains 0.24 ms and the metric kernel, which is not bound by its
             # rank stream, loses 0.41 ms to the unpacking: int32 stays the default; SE_EVAL_IDX16=1 switches)
-            tiles_kw = {'idx16': True} if (native_metrics and native_ranking and n <= 53248 and os.environ.get('SE_EVAL_IDX16')) else {}
-            for r0, tile in kernels['ranking_tiles'](feats, normalize, tile_rows=tile_rows, queries=(q0, q1), kblocks=kblocks, **tiles_kw):
-                rows = tile.shape[0]
-                outs.append(kernels['hierarchical_precision'](tile, cls_d, cls_d[r0:r0 + rows].contiguous(), qidx_d[r0:r0 + rows].contiguous(),
-                                                             *args_d, ks_d, ahp_len=ahp_len, want_ap=compute_ap, **extra))
-        res_d = torch.cat(outs) if outs else torch.zeros((0, ncol), dtype=torch.float64, device=dev)
-        return self._metric_rows_to_results(res_d, n, ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query)
+            elif native_metrics and 'ranking_tiles' not in given and ng <= 53248 and os.environ.get('SE_EVAL_IDX16'):
+                tiles_kw = {'idx16': True}
+            else:
+                tiles_kw = {}
+            return [score(tile, r0, compute_ap, extra)
+                    for r0, tile in kernels['ranking_tiles'](fq, normalize, tile_rows=tile_rows, queries=(q0, q1), kblocks=kblocks, **tiles_kw)]
 
-    def _hierarchical_precision_gallery(self, features, labels, ks, compute_ahp, compute_ap, normalize, ids, tile_rows, tile_cols, distributed,
-                                        group, kblocks, gather_per_query, kernels, per_query, gallery, gallery_labels, gallery_ids):
-        """``hierarchical_precision_device`` with a separate gallery (see there)."""
-        import warnings
-        import torch
-        import torch.distributed as dist
-        from evaluate_retrieval import _resolve_kblocks
-        from recall_precision import gallery_problem, recall_precision_device, _to_device_f32
-        from sharded_retrieval import shard_bounds, sharded_topk
-        if compute_ahp is True:
-            raise ValueError('un-clipped AHP needs the whole ranking of the gallery, which a separate gallery does not get by default: '
-                             'pass compute_ahp=K (--clip_ahp K on the command line), or opt into that ranking with rank_gallery=True '
-                             '(--rank_gallery)')
-        kernels = dict(kernels or {})
-        stand_ins = bool(kernels)
-        native_metrics = 'hierarchical_precision' not in kernels
-        if native_metrics:
-            import sehip
-            kernels['hierarchical_precision'] = sehip.hierarchical_precision
-        ks = [ks] if isinstance(ks, int) else list(ks)
-        ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
-        qf, gf, q_ids, qcls_h, gcls_h, class_list, qidx_h = gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids)
-        nq, ng = int(qf.shape[0]), int(gf.shape[0])
-        dev = torch.device(kernels.get('device') or torch.device('cuda', torch.cuda.current_device()))
-        if (not stand_ins) and dev.type == 'cuda':
-            wup_t, lcs_t = self.similarity_tables_device(class_list, device=dev)
-        else:
-            wup_t, lcs_t = self.similarity_tables(class_list)
-        counts = np.bincount(gcls_h, minlength=len(class_list))
-        L = min(ng, max(ks + [ahp_clip or 0]) + 1)
-        args_d = [_on_device(a, dev) for a in (wup_t, lcs_t)] + [_best_curves(t, counts, ng, dev)[:, :L + 1].contiguous() for t in (wup_t, lcs_t)]
-        world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
-        rank = dist.get_rank(group) if world > 1 else 0
-        q0, q1 = shard_bounds(nq, world)[rank] if world > 1 else (0, nq)
-        g0, g1 = shard_bounds(ng, world)[rank]
-        fq, fg = _to_device_f32(qf, dev), _to_device_f32(gf, dev)
-        if 'local_topk' not in kernels:
-            import sehip
-            if normalize:
-                sehip.normalize_rows_(fq)
-                sehip.normalize_rows_(fg)
-            metric = sehip.METRIC_COSINE if normalize else sehip.METRIC_EUCLID
-        else:
-            metric = None
-        _, top_i = sharded_topk(fq, fg[g0:g1], L, g0, metric=metric, group=group, local_topk=kernels.get('local_topk'),
-                                merge=kernels.get('merge'), kblocks=_resolve_kblocks(kblocks, int(fq.shape[1])))
-        ncol = 2 * len(ks) + 3
-        res_d = torch.zeros((0, ncol), dtype=torch.float64, device=dev)
-        if q1 > q0:
-            extra = {}
-            if native_metrics:
-                import sehip
-                extra = {'curves': sehip.hprec_reciprocal_curves(args_d[2], args_d[3])}
-            res_d = kernels['hierarchical_precision'](
-                top_i[q0:q1].contiguous(), torch.from_numpy(gcls_h).to(dev), torch.from_numpy(qcls_h[q0:q1].copy()).to(dev),
-                torch.from_numpy(qidx_h[q0:q1].copy()).to(dev), *args_d, torch.tensor(ks, dtype=torch.int32, device=dev),
-                ahp_len=-1 if not compute_ahp else ahp_clip, want_ap=False, **extra)
-        if compute_ap:      # counted, not ranked; every rank gets every query's AP
-            rp_names = ('normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows', 'count_preceding', 'count_to_positions',
-                        'recall_precision_reduce', 'device')
+        outs = top_lists() if use_top_lists else ranked_tiles()
+        res_d = outs[0] if len(outs) == 1 else (torch.cat(outs) if outs else torch.zeros((0, ncol), dtype=torch.float64, device=dev))
+        columns = _metric_columns(ks, compute_ahp, compute_ap)      # (host work from here on runs under the kernels launched above)
+        if use_top_lists and compute_ap:    # a separate gallery: counted, not ranked; every rank gets every query's AP
             with warnings.catch_warnings():
                 warnings.simplefilter('ignore', RuntimeWarning)      # queries without a relevant item: AP 0, as in the reference
                 aps = recall_precision_device(features, labels, normalize=normalize, ids=ids, kblocks=kblocks, tile_rows=tile_rows,
-                                              tile_cols=tile_cols, kernels={k: v for k, v in kernels.items() if k in rp_names},
-                                              gallery=gallery, gallery_labels=gallery_labels, gallery_ids=gallery_ids,
+                                              tile_cols=tile_cols, kernels=given, gallery=gallery, gallery_labels=gallery_labels, gallery_ids=gallery_ids,
                                               distributed=distributed, group=group)[3]
-            res_d[:, 2 * len(ks) + 2] = torch.from_numpy(aps[q0:q1]).to(dev)
-        return self._metric_rows_to_results(res_d, nq, q_ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query)
+            res_d[:, columns['AP']] = torch.from_numpy(aps[q0:q1]).to(dev)
+        return _metric_rows_to_results(res_d, columns, nq, p.q_ids, q0, q1, world, group, gather_per_query, per_query)
 
-    def _hierarchical_precision_ranked_gallery(self, features, labels, ks, compute_ahp, compute_ap, normalize, ids, tile_rows, distributed,
-                                               group, kblocks, gather_per_query, kernels, per_query, gallery, gallery_labels, gallery_ids):
-        """``hierarchical_precision_device(..., gallery=..., rank_gallery=True)`` (see there)."""
-        import torch
-        import torch.distributed as dist
-        from evaluate_retrieval import ranking_tiles
-        from recall_precision import gallery_problem, _to_device_f32
-        from sharded_retrieval import shard_bounds
-        kernels = dict(kernels or {})
-        stand_ins = bool(kernels)
-        native_metrics = 'hierarchical_precision' not in kernels
-        native_ranking = 'rank_rows' not in kernels
-        if native_metrics or native_ranking:
-            import sehip
-            kernels.setdefault('hierarchical_precision', sehip.hierarchical_precision)
-        ks = [ks] if isinstance(ks, int) else list(ks)
-        ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
-        qf, gf, q_ids, qcls_h, gcls_h, class_list, qidx_h = gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids)
-        nq, ng, d, C = int(qf.shape[0]), int(gf.shape[0]), int(qf.shape[1]), len(class_list)
-        if ng == 0:
-            raise ValueError('the gallery is empty')
-        ncol = 2 * len(ks) + 3
-        if nq == 0:     # nothing to average
-            names = ['P@{} ({})'.format(k, t) for k in ks for t in ('WUP', 'LCS_HEIGHT')]
-            if compute_ahp:
-                names += ['AHP{} ({})'.format('' if ahp_clip is None else '@{}'.format(ahp_clip), t) for t in ('WUP', 'LCS_HEIGHT')]
-            names += ['AP'] if compute_ap else []
-            return {m: float('nan') for m in names}, ({m: {} for m in names} if per_query else None)
-        dev = torch.device(kernels.get('device') or torch.device('cuda', torch.cuda.current_device()))
-        world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
-        rank = dist.get_rank(group) if world > 1 else 0
-        q0, q1 = shard_bounds(nq, world)[rank] if world > 1 else (0, nq)
 
-        # ---- what the evaluation will hold on the device, known before anything is launched: the two [C, G] float64 best curves, their
-        #      reciprocal table (per class two rows of se_hprec_curve_len(G) double2), the operands, and per tile row its distances, its
-        #      ranks (rows of 16-byte pitch) and its metrics, plus the ranking's workspace ----
-        def curve_len(n):
-            return int(sehip._lib.call('se_hprec_curve_len', n)) if native_metrics else 0
+def _metric_columns(ks, compute_ahp, compute_ap):
+    """Metric name -> column of se_hierarchical_precision's ``[Q, 2 len(ks) + 3]`` output, in the order of the result dictionaries:
+    ``P@k (WUP)`` and ``P@k (LCS_HEIGHT)`` per cut-off, ``AHP[@K] (WUP)`` / ``(LCS_HEIGHT)`` (``compute_ahp``: True or K), ``AP``."""
+    nk = len(ks)
+    col = {}
+    for t, k in enumerate(ks):
+        col['P@{} (WUP)'.format(k)] = t
+        col['P@{} (LCS_HEIGHT)'.format(k)] = nk + t
+    if compute_ahp:
+        sfx = '' if isinstance(compute_ahp, bool) else '@{}'.format(int(compute_ahp))
+        col['AHP{} (WUP)'.format(sfx)] = 2 * nk
+        col['AHP{} (LCS_HEIGHT)'.format(sfx)] = 2 * nk + 1
+    if compute_ap:
+        col['AP'] = 2 * nk + 2
+    return col
 
-        def tile_bytes(rows):
-            ws = int(sehip.rank_rows_workspace_bytes(rows, ng)) if native_ranking else 0
-            return rows * (8 * ((ng + 3) // 4 * 4) + 8 * ncol) + ws
 
-        fixed = 2 * 8 * C * ng + 32 * C * curve_len(ng) + 4 * d * (nq + ng)
-        free = _free_device_bytes(dev)
-        budget = None if free is None else free - free // 10        # a tenth stays free: allocator granularity, the other kernels' scratch
-        rows = max(1, q1 - q0)
-        if tile_rows is not None:
-            rows = max(1, min(rows, int(tile_rows)))
-        elif budget is not None:
-            rows = max(1, min(rows, (budget - fixed) // (8 * ((ng + 3) // 4 * 4) + 8 * ncol)))
-            while rows > 1 and fixed + tile_bytes(rows) > budget:
-                rows = rows * 3 // 4
-            if 128 < rows < q1 - q0:
-                rows = rows // 128 * 128
-        estimate = fixed + tile_bytes(rows)
-        if budget is not None and estimate > budget:
-            raise ValueError('ranking {} queries against a gallery of {} items in {} classes needs an estimated {:,} bytes of device memory '
-                             '({:,} for the best-possible curves, their reciprocal table and the features, {:,} for a tile of {} query row{}), '
-                             '{:,} are free: use the counting path (rank_gallery=False with compute_ahp=K), fewer classes or a smaller gallery'
-                             .format(q1 - q0, ng, C, estimate, fixed, estimate - fixed, rows, '' if rows == 1 else 's', free))
+def _ranked_gallery_tile_rows(dev, nq, ng, C, feature_bytes, ncol, tile_rows, native_metrics, native_ranking):
+    """Query rows per tile of ``hierarchical_precision_device(..., rank_gallery=True)`` for this rank's ``nq`` queries, from what the
+    evaluation will hold on the device, known before anything is launched: the two [C, G] float64 best curves, their reciprocal table
+    (per class two rows of se_hprec_curve_len(G) double2), the operands (``feature_bytes``), and per tile row its distances, its ranks
+    (rows of 16-byte pitch) and its metrics, plus the ranking's workspace.  ``tile_rows`` overrides the size, not the check: a
+    problem that cannot fit the free device memory raises ``ValueError``."""
+    if native_metrics or native_ranking:
+        import sehip
+    row_bytes = 8 * ((ng + 3) // 4 * 4) + 8 * ncol
 
-        if (not stand_ins) and dev.type == 'cuda':
-            wup_t, lcs_t = self.similarity_tables_device(class_list, device=dev)
-        else:
-            wup_t, lcs_t = self.similarity_tables(class_list)
-        counts = np.bincount(gcls_h, minlength=C)
-        args_d = [_on_device(a, dev) for a in (wup_t, lcs_t)] + [_best_curves(t, counts, ng, dev) for t in (wup_t, lcs_t)]
-        extra = {'curves': sehip.hprec_reciprocal_curves(args_d[2], args_d[3])} if native_metrics else {}    # once per gallery
-        fq, fg = _to_device_f32(qf, dev), _to_device_f32(gf, dev)
-        gcls_d, qcls_d, qidx_d = (torch.from_numpy(a).to(dev) for a in (gcls_h, qcls_h, qidx_h))
-        ks_d = torch.tensor(ks, dtype=torch.int32, device=dev)
-        ahp_len = -1 if not compute_ahp else (0 if ahp_clip is None else ahp_clip)
-        rank_kernels = {k: kernels[k] for k in ('normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows') if k in kernels}
-        outs = []
-        for r0, tile in ranking_tiles(fq, normalize, tile_rows=rows, queries=(q0, q1), kblocks=kblocks, gallery=fg, kernels=rank_kernels):
-            r1 = r0 + tile.shape[0]     # the tile is consumed here, before the next one overwrites it
-            outs.append(kernels['hierarchical_precision'](tile, gcls_d, qcls_d[r0:r1].contiguous(), qidx_d[r0:r1].contiguous(), *args_d, ks_d,
-                                                         ahp_len=ahp_len, want_ap=compute_ap, **extra))
-        res_d = torch.cat(outs) if outs else torch.zeros((0, ncol), dtype=torch.float64, device=dev)
-        return self._metric_rows_to_results(res_d, nq, q_ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query)
+    def tile_bytes(rows):
+        return rows * row_bytes + (int(sehip.rank_rows_workspace_bytes(rows, ng)) if native_ranking else 0)
 
-    def _metric_rows_to_results(self, res_d, n, ids, q0, q1, ks, compute_ahp, compute_ap, world, group, gather_per_query, per_query):
-        """``(means, per_query)`` from this rank's rows ``q0 .. q1`` of se_hierarchical_precision's output (all-gathered, or only their
-        sums all-reduced, under several ranks)."""
-        import torch
-        import torch.distributed as dist
-        from sharded_retrieval import shard_bounds
-        ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
-        ncol, dev = 2 * len(ks) + 3, res_d.device
-        sums = None
-        if world > 1:
-            if gather_per_query and per_query:    # ragged all-gather: pad every shard to the largest one
-                rows_max = max(e - s for s, e in shard_bounds(n, world))
-                padded = torch.zeros((rows_max, ncol), dtype=torch.float64, device=dev)
-                padded[:res_d.shape[0]] = res_d
-                gathered = torch.empty((world * rows_max, ncol), dtype=torch.float64, device=dev)
-                dist.all_gather_into_tensor(gathered, padded, group=group)
-                res_d = torch.cat([gathered[r * rows_max:r * rows_max + (e - s)] for r, (s, e) in enumerate(shard_bounds(n, world))])
-                q0, q1 = 0, n
-            else:                   # the means only: one all-reduce of ncol sums
-                sums = res_d.sum(dim=0)
-                dist.all_reduce(sums, group=group)
-        nk = len(ks)
-        my_ids = ids[q0:q1]
-        prec = {}
-        col = {}
-        for t, k in enumerate(ks):
-            col['P@{} (WUP)'.format(k)] = t
-            col['P@{} (LCS_HEIGHT)'.format(k)] = nk + t
-        if compute_ahp:
-            sfx = '' if ahp_clip is None else '@{}'.format(ahp_clip)
-            col['AHP{} (WUP)'.format(sfx)] = 2 * nk
-            col['AHP{} (LCS_HEIGHT)'.format(sfx)] = 2 * nk + 1
-        if compute_ap:
-            col['AP'] = 2 * nk + 2
-        if not per_query:
-            if sums is None:        # every row is here (one process, or gathered): the column means
-                sums = res_d.sum(dim=0)
-            sums = sums.cpu().numpy()
-            return {name: float(sums[c]) / n for name, c in col.items()}, None
-        res = res_d.cpu().numpy()
-        for name, c in col.items():
-            prec[name] = dict(zip(my_ids, res[:, c].tolist()))
-        if sums is not None:
-            sums = sums.cpu().numpy()
-            return {name: float(sums[c]) / n for name, c in col.items()}, prec
-        return {metric: sum(values.values()) / len(values) for metric, values in prec.items()}, prec
+    fixed = 2 * 8 * C * ng + 32 * C * (int(sehip._lib.call('se_hprec_curve_len', ng)) if native_metrics else 0) + feature_bytes
+    free = _free_device_bytes(dev)
+    budget = None if free is None else free - free // 10        # a tenth stays free: allocator granularity, the other kernels' scratch
+    rows = max(1, nq)
+    if tile_rows is not None:
+        rows = max(1, min(rows, int(tile_rows)))
+    elif budget is not None:
+        rows = max(1, min(rows, (budget - fixed) // row_bytes))
+        while rows > 1 and fixed + tile_bytes(rows) > budget:
+            rows = rows * 3 // 4
+        if 128 < rows < nq:
+            rows = rows // 128 * 128
+    estimate = fixed + tile_bytes(rows)
+    if budget is not None and estimate > budget:
+        raise ValueError('ranking {} queries against a gallery of {} items in {} classes needs an estimated {:,} bytes of device memory '
+                         '({:,} for the best-possible curves, their reciprocal table and the features, {:,} for a tile of {} query row{}), '
+                         '{:,} are free: use the counting path (rank_gallery=False with compute_ahp=K), fewer classes or a smaller gallery'
+                         .format(nq, ng, C, estimate, fixed, estimate - fixed, rows, '' if rows == 1 else 's', free))
+    return rows
+
+
+def _metric_rows_to_results(res_d, columns, n, ids, q0, q1, world, group, gather_per_query, per_query):
+    """``(means, per_query)`` from this rank's rows ``q0 .. q1`` of se_hierarchical_precision's output (all-gathered, or only their
+    sums all-reduced, under several ranks); ``columns``: ``_metric_columns``."""
+    import torch
+    import torch.distributed as dist
+    from sharded_retrieval import shard_bounds
+    ncol, dev = res_d.shape[1], res_d.device
+    sums = None
+    if world > 1:
+        if gather_per_query and per_query:    # ragged all-gather: pad every shard to the largest one
+            rows_max = max(e - s for s, e in shard_bounds(n, world))
+            padded = torch.zeros((rows_max, ncol), dtype=torch.float64, device=dev)
+            padded[:res_d.shape[0]] = res_d
+            gathered = torch.empty((world * rows_max, ncol), dtype=torch.float64, device=dev)
+            dist.all_gather_into_tensor(gathered, padded, group=group)
+            res_d = torch.cat([gathered[r * rows_max:r * rows_max + (e - s)] for r, (s, e) in enumerate(shard_bounds(n, world))])
+            q0, q1 = 0, n
+        else:                   # the means only: one all-reduce of ncol sums
+            sums = res_d.sum(dim=0)
+            dist.all_reduce(sums, group=group)
+    if not per_query:
+        if sums is None:        # every row is here (one process, or gathered): the column means
+            sums = res_d.sum(dim=0)
+        sums = sums.cpu().numpy()
+        return {name: float(sums[c]) / n for name, c in columns.items()}, None
+    res = res_d.cpu().numpy()
+    prec = {name: dict(zip(ids[q0:q1], res[:, c].tolist())) for name, c in columns.items()}
+    if sums is not None:
+        sums = sums.cpu().numpy()
+        return {name: float(sums[c]) / n for name, c in columns.items()}, prec
+    return {metric: sum(values.values()) / len(values) for metric, values in prec.items()}, prec
 
 
 def _best_curves(table, counts, n, dev):

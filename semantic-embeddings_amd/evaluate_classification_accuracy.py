@@ -282,15 +282,10 @@ def _layer_arg(v):
 def main(argv=None, modes=None):
     """The reference's command line (evaluate_classification_accuracy.py:138-188); returns the table's OrderedDict.
     ``modes`` (tests): a dict overriding 'svm' / 'centroids' / 'prob' with callables of the same signatures."""
-    from datasets import get_data_generator
     from class_hierarchy import ClassHierarchy
+    from evaluate_retrieval import load_labels
     args = build_parser().parse_args(argv)
-    if args.classes_from:
-        with open(args.classes_from, 'rb') as f:
-            embed_labels = pickle.load(f)['ind2label']
-    else:
-        embed_labels = None
-    data_generator = get_data_generator(args.dataset, args.data_root, classes=embed_labels)
+    data_generator = load_labels(args)[0]
     id_type = str if args.str_ids else int
     hierarchy = ClassHierarchy.from_file(args.hierarchy, is_a_relations=args.is_a, id_type=id_type) if args.hierarchy else None
     run = {'svm': train_and_predict, 'centroids': nn_classification_model, 'prob': extract_predictions}

@@ -88,7 +88,6 @@ def _resolve_kblocks(kblocks, d, warn=True):
         return None            # "already resolved to a single chain" (pairwise_retrieval -> ranking_tiles): no second warning
     if kblocks is None:
         if warn and d > 448:
-            import warnings
             warnings.warn("D = {} > 448: the reference's np.dot (evaluate_retrieval.py:59,62) restarts its float32 FMA chain per BLAS "
                           "K block; with kblocks=None distances come from ONE chain and near-tie orders can differ from the "
                           "reference's.  Pass kblocks='openblas' (CLI: --kblocks openblas) for bit-identical rankings."
@@ -121,11 +120,9 @@ def _cached_rows(kind, rows, n, dtype, device):
     """``[rows, n]`` view (row pitch a multiple of 16 bytes, like ``sehip.empty_rows``) of the device's grow-only cached buffer
     ``kind``: a second evaluation in the same process -- the CLI loops over its --feat files -- pays no 10 GB allocation."""
     import torch
-    from sehip.ops import _device_index
-    esz = torch.empty((), dtype=dtype).element_size()
-    per16 = 16 // esz
-    pitch = (n + per16 - 1) // per16 * per16
-    need = rows * pitch * esz
+    from sehip.ops import _device_index, row_pitch
+    pitch = row_pitch(n, dtype)
+    need = rows * pitch * torch.empty((), dtype=dtype).element_size()
     slot = _tile_cache.setdefault(_device_index(device), {})
     buf = slot.get(kind)
     if buf is None or buf.numel() < need:
@@ -137,64 +134,40 @@ def _cached_rows(kind, rows, n, dtype, device):
     return mat if pitch == n else mat[:, :n]
 
 
-def _rectangular_kernels(kernels):
-    """The four entry points a rectangular ranking takes, under the names the counting path of ``recall_precision_device(...,
-    gallery=...)`` looks up (CPU stand-ins of the tests replace them)."""
+RANKING_KERNELS = ('normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows')
+
+
+def _native_pairwise_dist(a, b, cosine, sqa, sqb, kblocks, out=None):
+    import sehip
+    return sehip.pairwise_dist(a, b, metric=sehip.METRIC_COSINE if cosine else sehip.METRIC_EUCLID, sqa=sqa, sqb=sqb, kblocks=kblocks, out=out)
+
+
+def resolve_kernels(kernels, names):
+    """``kernels`` (None, or the CPU stand-ins of the tests) as a new dict in which every one of ``names`` it lacks is the native
+    one: the ``sehip`` function of that name, ``pairwise_dist(a, b, cosine, sqa, sqb, kblocks, out)`` the one adapter of
+    ``sehip.pairwise_dist``, ``'ranking_tiles'`` the generator of this module and ``'device'`` the current ROCm device (a
+    ``torch.device`` either way).  Nothing but ``names`` is looked up."""
     kernels = dict(kernels or {})
-    names = ('normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows')
-    if any(k not in kernels for k in names):
-        import sehip
-
-        def pairwise_dist(a, b, cosine, sqa, sqb, kblocks, out=None):
-            return sehip.pairwise_dist(a, b, metric=sehip.METRIC_COSINE if cosine else sehip.METRIC_EUCLID, sqa=sqa, sqb=sqb,
-                                       kblocks=kblocks, out=out)
-
-        native = {'pairwise_dist': pairwise_dist}
-        for k in names:
-            kernels.setdefault(k, native.get(k) or getattr(sehip, k))
-    return kernels
-
-
-def _gallery_ranking_tiles(features, gallery, normalize, tile_rows, queries, kblocks, prenormalized, kernels):
-    """``ranking_tiles(..., gallery=...)``: int32 tiles ``[rows, len(gallery)]``."""
-    kernels = _rectangular_kernels(kernels)
-    nq, d = features.shape
-    n = int(gallery.shape[0])
-    if int(gallery.shape[1]) != int(d):
-        raise ValueError('queries have {} feature dimensions, the gallery {}'.format(d, gallery.shape[1]))
-    kblocks = _resolve_kblocks(kblocks, d)
-    if normalize:
-        if not prenormalized:
-            kernels['normalize_rows_'](features)
-            kernels['normalize_rows_'](gallery)
-        sq_q = sq_g = None
-    else:
-        sq_q, sq_g = kernels['row_sqnorm'](features), kernels['row_sqnorm'](gallery)
-    q0, q1 = (0, nq) if queries is None else queries
-    if tile_rows is None:
-        tile_rows = max(128, min(nq, (DEFAULT_TILE_BYTES // (8 * max(n, 1))) // 128 * 128))
-    tile_rows = max(1, int(tile_rows))
-    pd = rk = None
-    if features.is_cuda and q1 > q0:
-        # this iteration's own two buffers, shared by its tiles: nothing of the process-wide tile cache is handed out, so a tile a
-        # caller keeps after the loop is not overwritten by the next evaluation of the process
+    if 'device' in names:
         import torch
-        import sehip
-        pd = sehip.empty_rows(min(tile_rows, q1 - q0), n, torch.float32, features.device)
-        rk = sehip.empty_rows(min(tile_rows, q1 - q0), n, torch.int32, features.device)
-    for r0 in range(q0, q1, tile_rows):
-        rows = min(tile_rows, q1 - r0)
-        dist = kernels['pairwise_dist'](features[r0:r0 + rows], gallery, normalize, None if sq_q is None else sq_q[r0:r0 + rows], sq_g,
-                                        kblocks, None if pd is None else pd[:rows])
-        yield r0, (kernels['rank_rows'](dist) if rk is None else kernels['rank_rows'](dist, out=rk[:rows]))
+        kernels['device'] = torch.device(kernels.get('device') or torch.device('cuda', torch.cuda.current_device()))
+    own = {'pairwise_dist': _native_pairwise_dist, 'ranking_tiles': ranking_tiles}
+    for k in names:
+        if k not in kernels and k in own:
+            kernels[k] = own[k]
+        elif k not in kernels:
+            import sehip
+            kernels[k] = getattr(sehip, k)
+    return kernels
 
 
 def ranking_tiles(features, normalize=False, tile_rows=None, idx64=False, queries=None, kblocks=None, whole_if_fits=True,
                   prenormalized=False, idx16=False, gallery=None, kernels=None):
     """Generator over ``(first_row, rank_tile)`` with ``rank_tile`` an int32 (int64 if ``idx64``)
     DEVICE tensor ``[rows, N]``: the canonical ranking of queries ``first_row .. first_row+rows``.
-    **A tile is valid until the next one is drawn**: distances and ranks live in grow-only per-device buffers that every tile and
-    every later call reuses (``release_tile_cache`` frees them).
+    **A tile is valid until the next one is drawn**: the tiles of one iteration share one distance and one rank buffer.  Without a
+    ``gallery`` these are the grow-only per-device buffers of the process-wide tile cache, which every later call reuses
+    (``release_tile_cache`` frees them); with one they belong to the iteration (below).
 
     ``features`` must already be a float32 device tensor ``[N, D]``; it is normalised in place when
     ``normalize`` is set (like the reference mutates its input, evaluate_retrieval.py:58).
@@ -211,50 +184,61 @@ def ranking_tiles(features, normalize=False, tile_rows=None, idx64=False, querie
     ``gallery`` (float32 device tensor ``[G, D]``): the rectangular variant -- the rows of ``features`` are QUERIES, every tile is
     the canonical ranking ``[rows, G]`` (int32) of ``rows`` of them against the whole gallery, with the same (distance, index) order
     and the same ``kblocks`` chain as the square one; ``queries`` restricts the query rows, ``normalize`` normalises both operands
-    in place.  **Consume each tile before drawing the next**: the tiles of one iteration share two buffers which that iteration
-    owns -- the process-wide cache is not used, so they are not touched again once the iteration has ended.  ``tile_rows`` defaults
-    to ``DEFAULT_TILE_BYTES`` worth of rows (``hierarchical_precision_device(..., rank_gallery=True)`` sizes it from the free device
-    memory instead); ``idx64`` / ``idx16`` / ``whole_if_fits`` do not apply.  ``kernels`` (tests): CPU stand-ins
-    ``{'normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows'}``."""
-    if gallery is not None:
-        if idx64 or idx16:
-            raise ValueError('ranking_tiles(..., gallery=...) writes int32 ranks')
-        yield from _gallery_ranking_tiles(features, gallery, normalize, tile_rows, queries, kblocks, prenormalized, kernels)
-        return
-    import torch
-    import sehip
-
-    n, _ = features.shape
-    kblocks = _resolve_kblocks(kblocks, features.shape[1])
+    in place.  The two buffers are this iteration's own -- the process-wide cache is not used, so a tile a caller keeps is not
+    touched again once the iteration has ended.  ``tile_rows`` defaults to ``DEFAULT_TILE_BYTES`` worth of rows
+    (``hierarchical_precision_device(..., rank_gallery=True)`` sizes it from the free device memory instead); ``idx64`` / ``idx16`` /
+    ``whole_if_fits`` do not apply.  ``kernels`` (tests): CPU stand-ins ``{'normalize_rows_', 'row_sqnorm', 'pairwise_dist',
+    'rank_rows'}``."""
+    all_pairs = gallery is None
+    if not all_pairs and (idx64 or idx16):
+        raise ValueError('ranking_tiles(..., gallery=...) writes int32 ranks')
+    kernels = resolve_kernels(kernels, RANKING_KERNELS)
+    if all_pairs:
+        gallery = features
+    nq, d = features.shape
+    n = int(gallery.shape[0])
+    if int(gallery.shape[1]) != int(d):
+        raise ValueError('queries have {} feature dimensions, the gallery {}'.format(d, gallery.shape[1]))
+    kblocks = _resolve_kblocks(kblocks, d)
     if normalize:
         if not prenormalized:
-            sehip.normalize_rows_(features)
-        metric, sq = sehip.METRIC_COSINE, None
+            kernels['normalize_rows_'](features)
+            if not all_pairs:
+                kernels['normalize_rows_'](gallery)
+        sq_q = sq_g = None
     else:
-        metric, sq = sehip.METRIC_EUCLID, sehip.row_sqnorm(features)
-    q0, q1 = (0, n) if queries is None else queries
+        sq_q = kernels['row_sqnorm'](features)
+        sq_g = sq_q if all_pairs else kernels['row_sqnorm'](gallery)
+    q0, q1 = (0, nq) if queries is None else queries
     if tile_rows is None:
-        tile_rows = max(128, min(n, (DEFAULT_TILE_BYTES // (8 * max(n, 1))) // 128 * 128))
-        if whole_if_fits and features.is_cuda:
+        tile_rows = max(128, min(nq, (DEFAULT_TILE_BYTES // (8 * max(n, 1))) // 128 * 128))
+        if whole_if_fits and all_pairs and features.is_cuda:
             # distances + ranks of all queries, plus what the ranking will ask of the (grow-only) workspace cache on top of what that
             # cache already holds -- up to ~3 GB for rows above 53,248 columns
+            import torch
+            import sehip
             extra_ws = max(0, sehip.rank_rows_workspace_bytes(q1 - q0, n) - sehip.workspace_bytes(features.device))
             held = sum(int(b.numel()) for b in _tile_cache.get(sehip.ops._device_index(features.device), {}).values())
             need = (4 + (2 if idx16 else (8 if idx64 else 4))) * n * (q1 - q0)
             if need + extra_ws <= (torch.cuda.mem_get_info(features.device)[0] + held) // 3:
                 tile_rows = max(tile_rows, q1 - q0)
-    rows_max = min(tile_rows, max(q1 - q0, 1))
-    if features.is_cuda:
-        pd = _cached_rows('pd', rows_max, n, torch.float32, features.device)
-        rk = _cached_rows('rk', rows_max, n, torch.int16 if idx16 else (torch.int64 if idx64 else torch.int32), features.device)
-    else:   # (CPU stand-ins of the tests never get here: the kernels need a device)
-        pd = sehip.empty_rows(rows_max, n, torch.float32, features.device)
-        rk = None
+    tile_rows = max(1, int(tile_rows))
+    pd = rk = None          # (CPU stand-ins of the tests allocate their own results)
+    if features.is_cuda and q1 > q0:
+        import torch
+        import sehip
+        rows_max, rk_dtype = min(tile_rows, q1 - q0), torch.int16 if idx16 else (torch.int64 if idx64 else torch.int32)
+        if all_pairs:
+            pd = _cached_rows('pd', rows_max, n, torch.float32, features.device)
+            rk = _cached_rows('rk', rows_max, n, rk_dtype, features.device)
+        else:
+            pd = sehip.empty_rows(rows_max, n, torch.float32, features.device)
+            rk = sehip.empty_rows(rows_max, n, rk_dtype, features.device)
     for r0 in range(q0, q1, tile_rows):
         rows = min(tile_rows, q1 - r0)
-        sehip.pairwise_dist(features[r0:r0 + rows], features, metric=metric,
-                            sqa=None if sq is None else sq[r0:r0 + rows], sqb=sq, kblocks=kblocks, out=pd[:rows])
-        yield r0, sehip.rank_rows(pd[:rows], idx64=idx64, idx16=idx16, out=None if rk is None else rk[:rows])
+        dist = kernels['pairwise_dist'](features[r0:r0 + rows], gallery, normalize, None if sq_q is None else sq_q[r0:r0 + rows], sq_g,
+                                        kblocks, None if pd is None else pd[:rows])
+        yield r0, (kernels['rank_rows'](dist) if rk is None else kernels['rank_rows'](dist, out=rk[:rows]))
 
 
 def pairwise_retrieval(features, normalize=False, return_generator=True, kblocks=None):
@@ -455,20 +439,31 @@ def init_distributed():
     return dist.get_rank(), dist.get_world_size()
 
 
-def main(argv=None):
+def load_labels(args):
+    """``(data generator, ind2label, test labels)`` of --dataset / --data_root: ``ind2label`` from the --classes_from pickle (else
+    None) restricts and orders the classes, and the test split's labels are mapped through it."""
     from datasets import get_data_generator
+    embed_labels = None
+    if args.classes_from:
+        with open(args.classes_from, 'rb') as f:
+            embed_labels = pickle.load(f)['ind2label']
+    data_generator = get_data_generator(args.dataset, args.data_root, classes=embed_labels)
+    labels_test = [embed_labels[lbl] for lbl in data_generator.labels_test] if embed_labels is not None else data_generator.labels_test
+    return data_generator, embed_labels, labels_test
+
+
+def feat_entry(args, i):
+    """``(display name, --norm value)`` of the ``i``-th --feat file: the matching --label, else the file's base name; no."""
+    name = args.label[i] if (args.label is not None) and (i < len(args.label)) else os.path.splitext(os.path.basename(args.feat[i]))[0]
+    return name, (args.norm[i] if (args.norm is not None) and (i < len(args.norm)) else False)
+
+
+def main(argv=None):
     from class_hierarchy import ClassHierarchy
 
     args = parse_args(argv)
     rank, world = init_distributed()
-
-    if args.classes_from:
-        with open(args.classes_from, 'rb') as f:
-            embed_labels = pickle.load(f)['ind2label']
-    else:
-        embed_labels = None
-    data_generator = get_data_generator(args.dataset, args.data_root, classes=embed_labels)
-    labels_test = [embed_labels[lbl] for lbl in data_generator.labels_test] if embed_labels is not None else data_generator.labels_test
+    data_generator, embed_labels, labels_test = load_labels(args)
 
     id_type = str if args.str_ids else int
     hierarchy = ClassHierarchy.from_file(args.hierarchy, is_a_relations=args.is_a, id_type=id_type)
@@ -479,8 +474,7 @@ def main(argv=None):
             ks.append(k)
     perf = OrderedDict()
     for i, feat_dump in tqdm(enumerate(args.feat), total=len(args.feat), disable=rank != 0):
-        feat_name = args.label[i] if (args.label is not None) and (i < len(args.label)) else os.path.splitext(os.path.basename(feat_dump))[0]
-        normalize = args.norm[i] if (args.norm is not None) and (i < len(args.norm)) else False
+        feat_name, normalize = feat_entry(args, i)
         # reference: hierarchy.hierarchical_precision(pairwise_retrieval(feat_dump, normalize), labels_test, ks, ...)
         # (evaluate_retrieval.py:197-201).  Here rankings and metrics stay on the GPU: no N x N Python lists.
         features, ind2id, _ = _as_feature_matrix(feat_dump)

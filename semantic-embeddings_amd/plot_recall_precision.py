@@ -14,11 +14,9 @@ reference: plot_recall_precision.py:19-86.  Differences a user can observe:
 * matplotlib is only imported when a figure is drawn; with ``--csv`` and without matplotlib the figure is skipped.
 """
 import argparse
-import os.path
-import pickle
 from collections import OrderedDict
 
-from evaluate_retrieval import _as_feature_matrix, add_gallery_flags, gallery_arguments, str2bool
+from evaluate_retrieval import _as_feature_matrix, add_gallery_flags, feat_entry, gallery_arguments, load_labels, str2bool
 
 
 def build_parser():
@@ -76,24 +74,16 @@ def plot_curves(curves, save=None):
 
 def main(argv=None):
     """Returns ``{feature name: (levels, mean_precision, mAP)}``."""
-    from datasets import get_data_generator
     from recall_precision import recall_precision_device
 
     args = build_parser().parse_args(argv)
     if args.bins is not None and args.bins <= 0:
         raise SystemExit('--bins must be positive')
-    if args.classes_from:
-        with open(args.classes_from, 'rb') as f:
-            embed_labels = pickle.load(f)['ind2label']
-    else:
-        embed_labels = None
-    data_generator = get_data_generator(args.dataset, args.data_root, classes=embed_labels)
-    labels_test = [embed_labels[lbl] for lbl in data_generator.labels_test] if embed_labels is not None else data_generator.labels_test
+    data_generator, embed_labels, labels_test = load_labels(args)
 
     curves = OrderedDict()
     for i, feat_dump in enumerate(args.feat):
-        feat_name = args.label[i] if (args.label is not None) and (i < len(args.label)) else os.path.splitext(os.path.basename(feat_dump))[0]
-        normalize = args.norm[i] if (args.norm is not None) and (i < len(args.norm)) else False
+        feat_name, normalize = feat_entry(args, i)
         features, ind2id, _ = _as_feature_matrix(feat_dump)
         levels, means, mAP, _ = recall_precision_device(features, labels_test, normalize=normalize, bins=args.bins,
                                                         ids=None if ind2id is None else ind2id.tolist(), kblocks=args.kblocks,

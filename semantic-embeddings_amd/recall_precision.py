@@ -25,25 +25,45 @@ Queries against a separate gallery (``recall_precision_device(..., gallery=...)`
 the query's ranking of the GALLERY, the query's own gallery item (same id) removed where there is one.  The positions are counted
 (``se_count_preceding`` / ``se_count_to_positions``: gallery columns in front of each relevant item), never read off a ranking.
 """
+import collections
 import warnings
 
 import numpy as np
 
+from evaluate_retrieval import RANKING_KERNELS, _as_feature_matrix, _cached_rows, _resolve_kblocks, resolve_kernels
 
-def _class_indices(lab):
-    class_list = sorted(set(lab), key=lambda c: (str(type(c)), c))
+
+def class_indices(*label_lists):
+    """``(class list, [int32 class index of every label] per list)``: the classes of all lists together, sorted (by type name
+    first, so that labels of several types still sort)."""
+    class_list = sorted(set().union(*label_lists), key=lambda c: (str(type(c)), c))
     pos = {c: i for i, c in enumerate(class_list)}
-    return np.array([pos[c] for c in lab], dtype=np.int32), len(class_list)
+    return class_list, [np.array([pos[c] for c in lab], dtype=np.int32) for lab in label_lists]
+
+
+def to_device_f32(x, dev):
+    """A float32 copy of the feature matrix ``x`` (array or tensor) on ``dev`` that the kernels may normalise in place."""
+    import torch
+    if torch.is_tensor(x):      # features straight from the network (learn_image_embeddings feature extraction): stay on the device
+        return x.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
 
 
 def _bin_keys(b, bins):
     return np.asarray(b, dtype=np.int64) / bins + 1 / (2 * bins)
 
 
-def _warn_singletons(n_single):
+def _number_of_bins(bins):
+    bins = int(bins) if bins else 0
+    if bins < 0:
+        raise ValueError('bins must be a positive number of recall levels')
+    return bins
+
+
+def _warn_singletons(n_single, stacklevel=3):
     if n_single:
         warnings.warn('recall-precision: {} quer{} without any other item of their class: AP 0, no curve points'
-                      .format(n_single, 'y' if n_single == 1 else 'ies'), RuntimeWarning, stacklevel=3)
+                      .format(n_single, 'y' if n_single == 1 else 'ies'), RuntimeWarning, stacklevel=stacklevel)
 
 
 def recall_precision_host(ranking, labels, bins=None):
@@ -51,53 +71,18 @@ def recall_precision_host(ranking, labels, bins=None):
 
     ``ranking`` [N, N] ints: row i is query i's ranking of the item indices 0 .. N - 1 (itself included); ``labels[i]`` is the
     class of item i.  Returns ``(levels, mean_precision, mAP, per_query_ap)`` (float64 arrays, float)."""
-    ranking = np.asarray(ranking)
-    cls, _ = _class_indices(list(labels))
-    n = ranking.shape[0]
-    bins = int(bins) if bins else 0
-    recprec = {}
-    aps = np.zeros(n, dtype=np.float64)
-    n_single = 0
-    for q in range(n):
-        row = ranking[q]
-        row = row[row != q]
-        pos = np.flatnonzero(cls[row] == cls[q]) + 1
-        R = len(pos)
-        if R == 0:
-            n_single += 1
-            continue
-        j = np.arange(1, R + 1)
-        prec = j / pos
-        aps[q] = prec.sum() / R
-        if bins:
-            b = ((j / R) * bins).astype(np.int64)
-            best = {}
-            if pos[0] > 1:
-                best[0] = 0.0
-            for bi, p in zip(b.tolist(), prec.tolist()):
-                best[bi] = max(best[bi], p) if bi in best else p
-            pts = zip(_bin_keys(list(best), bins).tolist(), best.values())
-        else:
-            pts = list(zip((j / R).tolist(), prec.tolist()))
-            if pos[0] > 1:
-                pts.append((0.0, 0.0))
-        for key, p in pts:
-            recprec.setdefault(key, []).append(p)
-    _warn_singletons(n_single)
-    levels = np.array(sorted(recprec), dtype=np.float64)
-    means = np.array([np.mean(recprec[k]) for k in levels.tolist()], dtype=np.float64)
-    return levels, means, float(np.mean(aps)) if n else float('nan'), aps
+    return recall_precision_host_gallery(ranking, labels, labels, np.arange(len(ranking)), bins, stacklevel=4)
 
 
-def recall_precision_host_gallery(ranking, query_labels, gallery_labels, qidx=None, bins=None):
+def recall_precision_host_gallery(ranking, query_labels, gallery_labels, qidx=None, bins=None, stacklevel=3):
     """``recall_precision_host`` for queries that are not the gallery: ``ranking`` [Q, N] ints, row i is query i's ranking of the
     gallery items 0 .. N - 1; ``query_labels[i]`` / ``gallery_labels[j]`` their classes; ``qidx[i]`` the gallery item that IS
     query i (removed from its ranking, the reference's ``ignore_qids``), -1 / None when it is not in the gallery.  A query whose
-    class has no (other) gallery item gets AP 0 and no curve points.  Returns ``(levels, mean_precision, mAP, per_query_ap)``."""
+    class has no (other) gallery item gets AP 0 and no curve points.  Returns ``(levels, mean_precision, mAP, per_query_ap)``.
+    (``stacklevel``: of the warning about such queries -- it names the caller of whichever host function was called.)"""
     ranking = np.asarray(ranking)
-    cls, _ = _class_indices(list(query_labels) + list(gallery_labels))
+    _, (qcls, gcls) = class_indices(list(query_labels), list(gallery_labels))
     nq = ranking.shape[0]
-    qcls, gcls = cls[:nq], cls[nq:]
     bins = int(bins) if bins else 0
     recprec = {}
     aps = np.zeros(nq, dtype=np.float64)
@@ -128,10 +113,20 @@ def recall_precision_host_gallery(ranking, query_labels, gallery_labels, qidx=No
                 pts.append((0.0, 0.0))
         for key, p in pts:
             recprec.setdefault(key, []).append(p)
-    _warn_singletons(n_single)
+    _warn_singletons(n_single, stacklevel)
     levels = np.array(sorted(recprec), dtype=np.float64)
     means = np.array([np.mean(recprec[k]) for k in levels.tolist()], dtype=np.float64)
     return levels, means, float(np.mean(aps)) if nq else float('nan'), aps
+
+
+def _accumulators(nq, groups, total, bins, dev):
+    """What ``se_recall_precision_reduce`` adds into, zeroed: ``(ap [nq], prec_sum [total], first_miss [groups], bin_sum, bin_count
+    [groups, bins + 1] -- None without bins)``."""
+    import torch
+    return (torch.zeros(nq, dtype=torch.float64, device=dev), torch.zeros(max(total, 1), dtype=torch.float64, device=dev)[:total],
+            torch.zeros(groups, dtype=torch.int64, device=dev),
+            torch.zeros((groups, bins + 1), dtype=torch.float64, device=dev) if bins else None,
+            torch.zeros((groups, bins + 1), dtype=torch.int64, device=dev) if bins else None)
 
 
 def recall_precision_device(features, labels, normalize=False, bins=None, ids=None, kblocks=None, tile_rows=None, kernels=None,
@@ -158,44 +153,20 @@ def recall_precision_device(features, labels, normalize=False, bins=None, ids=No
         return _recall_precision_gallery(features, labels, normalize, bins, ids, kblocks, tile_rows, tile_cols, kernels, gallery,
                                          gallery_labels, gallery_ids, distributed, group)
     import torch
-    from evaluate_retrieval import _as_feature_matrix
 
-    kernels = dict(kernels or {})
-    if any(k not in kernels for k in ('ranking_tiles', 'relevant_positions', 'recall_precision_reduce')):
-        import sehip
-        from evaluate_retrieval import ranking_tiles
-        kernels.setdefault('ranking_tiles', ranking_tiles)
-        kernels.setdefault('relevant_positions', sehip.relevant_positions)
-        kernels.setdefault('recall_precision_reduce', sehip.recall_precision_reduce)
-    bins = int(bins) if bins else 0
-    if bins < 0:
-        raise ValueError('bins must be a positive number of recall levels')
-
-    features, ind2id, _ = _as_feature_matrix(features)
-    if ids is None and ind2id is not None:
-        ids = ind2id.tolist()
-    n = int(features.shape[0])
-    ids = list(range(n)) if ids is None else list(ids)
-    if len(ids) != n:
-        raise ValueError('{} ids for {} feature rows'.format(len(ids), n))
-    cls_h, C = _class_indices([labels[i] for i in ids])
+    kernels = resolve_kernels(kernels, ('ranking_tiles', 'relevant_positions', 'recall_precision_reduce', 'device'))
+    bins = _number_of_bins(bins)
+    p = gallery_problem(features, labels, ids)
+    n, cls_h, C, dev = len(p.q_ids), p.qcls, len(p.class_list), kernels['device']
     counts = np.bincount(cls_h, minlength=C)
     r_cls = counts - 1                                    # relevant items of a query of class c: the rest of its class
     class_off = np.concatenate([[0], np.cumsum(r_cls)]).astype(np.int64)
-    dev = kernels.get('device') or torch.device('cuda', torch.cuda.current_device())
-    if torch.is_tensor(features):
-        feats = features.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
-    else:
-        feats = torch.from_numpy(np.ascontiguousarray(features, dtype=np.float32)).to(dev)
+    feats = to_device_f32(p.qf, dev)
 
     cls_d = torch.from_numpy(cls_h).to(dev)
     qidx_d = torch.arange(n, dtype=torch.int32, device=dev)
     class_off_d = torch.from_numpy(class_off).to(dev)
-    ap = torch.zeros(n, dtype=torch.float64, device=dev)
-    prec_sum = torch.zeros(max(int(class_off[-1]), 1), dtype=torch.float64, device=dev)[:int(class_off[-1])]
-    first_miss = torch.zeros(C, dtype=torch.int64, device=dev)
-    bin_sum = torch.zeros((C, bins + 1), dtype=torch.float64, device=dev) if bins else None
-    bin_count = torch.zeros((C, bins + 1), dtype=torch.int64, device=dev) if bins else None
+    ap, prec_sum, first_miss, bin_sum, bin_count = _accumulators(n, C, int(class_off[-1]), bins, dev)
     # each tile is consumed before the next one is drawn (ranking_tiles reuses its buffers)
     for r0, tile in kernels['ranking_tiles'](feats, normalize, tile_rows=tile_rows, kblocks=kblocks):
         rows = int(tile.shape[0])
@@ -253,56 +224,38 @@ def _ids_of(ind2id, ids, n):
     return None if ids is None else list(ids)
 
 
-def gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids):
+EvalProblem = collections.namedtuple('EvalProblem', 'qf gf q_ids qcls gcls class_list qidx')
+
+
+def gallery_problem(features, labels, ids=None, gallery=None, gallery_labels=None, gallery_ids=None):
     """Host bookkeeping of a query-vs-gallery evaluation: ``(query features, gallery features, query ids, qcls, gcls, class list,
     qidx)`` -- class indices int32 over the sorted union of the classes on either side, ``qidx[i]`` the (first) gallery row whose
-    id equals query i's id, else -1."""
-    from evaluate_retrieval import _as_feature_matrix
+    id equals query i's id, else -1.  Without a ``gallery`` the all-pairs problem: the gallery IS the queries (``gf is qf``,
+    ``gcls is qcls``) and ``qidx[i] = i``."""
     qf, q_ind2id, _ = _as_feature_matrix(features)
-    gf, g_ind2id, _ = _as_feature_matrix(gallery)
-    if int(qf.shape[1]) != int(gf.shape[1]):
-        raise ValueError('queries have {} feature dimensions, the gallery {}'.format(qf.shape[1], gf.shape[1]))
-    nq, ng = int(qf.shape[0]), int(gf.shape[0])
+    if gallery is not None:
+        gf, g_ind2id, _ = _as_feature_matrix(gallery)
+        if int(qf.shape[1]) != int(gf.shape[1]):
+            raise ValueError('queries have {} feature dimensions, the gallery {}'.format(qf.shape[1], gf.shape[1]))
+    nq = int(qf.shape[0])
     q_ids = _ids_of(q_ind2id, ids, nq)
-    g_ids = _ids_of(g_ind2id, gallery_ids, ng)
     q_ids = list(range(nq)) if q_ids is None else q_ids
-    gallery_labels = labels if gallery_labels is None else gallery_labels
     q_lab = [labels[i] for i in q_ids]
+    if gallery is None:
+        class_list, (cls,) = class_indices(q_lab)
+        return EvalProblem(qf, qf, q_ids, cls, cls, class_list, np.arange(nq, dtype=np.int32))
+    ng = int(gf.shape[0])
+    g_ids = _ids_of(g_ind2id, gallery_ids, ng)
+    gallery_labels = labels if gallery_labels is None else gallery_labels
     g_lab = [gallery_labels[i] for i in (range(ng) if g_ids is None else g_ids)]
-    class_list = sorted(set(q_lab) | set(g_lab), key=lambda c: (str(type(c)), c))
-    pos = {c: i for i, c in enumerate(class_list)}
-    qcls = np.array([pos[c] for c in q_lab], dtype=np.int32)
-    gcls = np.array([pos[c] for c in g_lab], dtype=np.int32)
+    class_list, (qcls, gcls) = class_indices(q_lab, g_lab)
     qidx = np.full(nq, -1, dtype=np.int32)
     if g_ids is not None:
         row_of = {}
         for j, g in enumerate(g_ids):
             row_of.setdefault(g, j)
         qidx = np.array([row_of.get(i, -1) for i in q_ids], dtype=np.int32)
-    return qf, gf, q_ids, qcls, gcls, class_list, qidx
-
-
-def _gallery_kernels(kernels):
-    kernels = dict(kernels or {})
-    names = ('normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows', 'count_preceding', 'count_to_positions', 'recall_precision_reduce')
-    if any(k not in kernels for k in names):
-        import sehip
-
-        def pairwise_dist(a, b, cosine, sqa, sqb, kblocks, out=None):
-            return sehip.pairwise_dist(a, b, metric=sehip.METRIC_COSINE if cosine else sehip.METRIC_EUCLID, sqa=sqa, sqb=sqb,
-                                       kblocks=kblocks, out=out)
-
-        native = {'pairwise_dist': pairwise_dist}
-        for k in names:
-            kernels.setdefault(k, native.get(k) or getattr(sehip, k))
-    return kernels
-
-
-def _to_device_f32(x, dev):
-    import torch
-    if torch.is_tensor(x):
-        return x.detach().to(device=dev, dtype=torch.float32).contiguous().clone()
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+    return EvalProblem(qf, gf, q_ids, qcls, gcls, class_list, qidx)
 
 
 def _recall_precision_gallery(features, labels, normalize, bins, ids, kblocks, tile_rows, tile_cols, kernels, gallery, gallery_labels,
@@ -318,18 +271,14 @@ def _recall_precision_gallery(features, labels, normalize, bins, ids, kblocks, t
        thousandth of the counting), so all ranks hold the same bits without a float64 collective."""
     import torch
     import torch.distributed as dist
-    from evaluate_retrieval import _resolve_kblocks
     from sharded_retrieval import shard_bounds
 
-    kernels = _gallery_kernels(kernels)
-    bins = int(bins) if bins else 0
-    if bins < 0:
-        raise ValueError('bins must be a positive number of recall levels')
+    kernels = resolve_kernels(kernels, RANKING_KERNELS + ('count_preceding', 'count_to_positions', 'recall_precision_reduce', 'device'))
+    bins = _number_of_bins(bins)
     qf, gf, _, qcls, gcls, class_list, qidx = gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids)
-    nq, ng, C = int(qf.shape[0]), int(gf.shape[0]), len(class_list)
-    dev = torch.device(kernels.get('device') or torch.device('cuda', torch.cuda.current_device()))
+    nq, ng, C, dev = int(qf.shape[0]), int(gf.shape[0]), len(class_list), kernels['device']
     kb = _resolve_kblocks(kblocks, int(qf.shape[1]))
-    fq, fg = _to_device_f32(qf, dev), _to_device_f32(gf, dev)
+    fq, fg = to_device_f32(qf, dev), to_device_f32(gf, dev)
     if normalize:
         kernels['normalize_rows_'](fq)
         kernels['normalize_rows_'](fg)
@@ -353,18 +302,13 @@ def _recall_precision_gallery(features, labels, normalize, bins, ids, kblocks, t
     members = [by_class[class_at[c]:class_at[c + 1]] for c in range(C)]
 
     class_off_d = torch.from_numpy(class_off).to(dev)
-    ap_sorted = torch.zeros(nq, dtype=torch.float64, device=dev)
-    prec_sum = torch.zeros(max(int(class_off[-1]), 1), dtype=torch.float64, device=dev)[:int(class_off[-1])]
-    first_miss = torch.zeros(2 * C, dtype=torch.int64, device=dev)
-    bin_sum = torch.zeros((2 * C, bins + 1), dtype=torch.float64, device=dev) if bins else None
-    bin_count = torch.zeros((2 * C, bins + 1), dtype=torch.int64, device=dev) if bins else None
+    ap_sorted, prec_sum, first_miss, bin_sum, bin_count = _accumulators(nq, 2 * C, int(class_off[-1]), bins, dev)
 
     order_q = np.argsort(rc, kind='stable')
     tile_cols = min(max(ng, 1), int(tile_cols or 65536))
     tile_rows = min(max(nq, 1), int(tile_rows or max(128, (1 << 30) // (4 * tile_cols))))
     slab = None
     if dev.type == 'cuda':       # the grow-only distance buffer ranking_tiles uses: the CLI's next --feat pays no allocation
-        from evaluate_retrieval import _cached_rows
         slab = _cached_rows('pd', tile_rows, tile_cols, torch.float32, dev)
     for t0 in range(0, nq, tile_rows):
         sel = order_q[t0:t0 + tile_rows]

@@ -675,12 +675,17 @@ def normalize_rows_(x):
     return x
 
 
+def row_pitch(n, dtype):
+    """Elements per row of an n-column ``dtype`` matrix whose rows start a multiple of 16 bytes apart."""
+    per16 = 16 // torch.empty((), dtype=dtype).element_size()
+    return (n + per16 - 1) // per16 * per16
+
+
 def empty_rows(q, n, dtype, device):
     """[q, n] matrix whose row pitch is a multiple of 16 bytes (a view of a wider buffer when n is not): the distance and ranking
     kernels stream rows out with 16-byte stores and fall back to element stores on unaligned pitches -- 24,633 columns (odd): distances
     1.50 -> 1.18 ms, ranking 3.37 -> 3.01 ms (tools/bench_odd_pitch.py)."""
-    per16 = 16 // torch.empty((), dtype=dtype).element_size()
-    pitch = (n + per16 - 1) // per16 * per16
+    pitch = row_pitch(n, dtype)
     buf = torch.empty((q, pitch), dtype=dtype, device=device)
     return buf if pitch == n else buf[:, :n]
 

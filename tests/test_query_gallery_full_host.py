@@ -111,6 +111,8 @@ def test_rectangular_ranking_tiles():
     rng = np.random.default_rng(3)
     q, g = rng.standard_normal((11, 9)).astype(np.float32), rng.standard_normal((23, 9)).astype(np.float32)
     g[5] = g[17]                                                     # identical gallery rows: the tie goes to the lower index
+    # (empty unless GPU tests ran earlier in this process: their all-pairs evaluations keep their buffers)
+    held = {k: {kk: int(b.numel()) for kk, b in v.items()} for k, v in er._tile_cache.items()}
     for normalize in (True, False):
         for kb in (None, [5, 4]):
             qn, gn = (ro.canon_normalize_rows(q), ro.canon_normalize_rows(g)) if normalize else (q, g)
@@ -120,7 +122,7 @@ def test_rectangular_ranking_tiles():
                                           gallery=torch.from_numpy(g.copy()), kernels=kernels))
             assert [r0 for r0, _ in tiles] == [2, 6, 10] and [t.shape[0] for _, t in tiles] == [4, 4, 1]
             assert np.array_equal(np.concatenate([t.numpy() for _, t in tiles]), want[2:])
-    assert not er._tile_cache
+    assert {k: {kk: int(b.numel()) for kk, b in v.items()} for k, v in er._tile_cache.items()} == held
     with pytest.raises(ValueError, match="feature dimensions"):
         list(er.ranking_tiles(torch.zeros((2, 3)), gallery=torch.zeros((2, 4)), kernels=kernels))
     with pytest.raises(ValueError, match="int32"):

@@ -180,9 +180,17 @@ def test_without_a_gallery_nothing_new_is_reached(monkeypatch):
     def boom(*a, **k):
         raise AssertionError("the query-vs-gallery path was reached without a gallery")
 
-    for mod, name in ((rp, "_recall_precision_gallery"), (rp, "_gallery_kernels"), (sehip, "count_preceding"), (sehip, "count_to_positions"),
+    for mod, name in ((rp, "_recall_precision_gallery"), (sehip, "count_preceding"), (sehip, "count_to_positions"),
                       (sehip.ops, "count_preceding"), (sehip.ops, "count_to_positions")):
         monkeypatch.setattr(mod, name, boom)
+    resolve = rp.resolve_kernels
+
+    def resolve_no_counting(kernels, names):
+        if {"count_preceding", "count_to_positions"} & set(names):
+            boom()
+        return resolve(kernels, names)
+
+    monkeypatch.setattr(rp, "resolve_kernels", resolve_no_counting)
     g = np.load(qg.GOLDEN + "/recprec_d24_euc.npz")
     kernels = _cpu_kernels()
     assert set(kernels) == {"ranking_tiles", "relevant_positions", "recall_precision_reduce", "device"}
