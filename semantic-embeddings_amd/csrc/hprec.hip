@@ -27,9 +27,7 @@
 // trapz of cum / best with dx = 1 / length; AP is the mean over the relevant ranks of precision at that rank.
 // float64 throughout; sums are associated differently from numpy's sequential cumsum and cum / best is cum * (1 / best)
 // (last-bits differences; the tests hold the outputs to 1e-10 of the reference's).
-#include "se_common.h"
-
-#include <type_traits>
+#include "rank_stream.h"
 
 namespace se {
 
@@ -40,44 +38,10 @@ constexpr int HP_THREADS = 256;
 constexpr int HP_WAVES = HP_THREADS / WAVE;
 constexpr int HP_ITEMS = 8;
 constexpr int HP_WAVES_PER_SIMD = 2;
-constexpr int HP_PF = 1;                // chunks of rank look-ahead
 constexpr int HP_CHUNK = HP_THREADS * HP_ITEMS;
 constexpr int HP_MAX_KS = 512;
 constexpr int HP_WS_HEAD = 16;      // order_ws (ints): [0, 8) per-XCD cursors, then one int4 per query in class order: (query, its class, its own gallery index or -1, 0)
 constexpr int HP_ORDER_THREADS = 1024;
-
-// ---- DPP wave scans (no LDS traffic): Kogge-Stone inside the 16-lane rows, then the row totals by row_bcast ----
-template <int CTRL, int ROWS>
-__device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, ROWS, 0xf, true); }
-
-template <int CTRL, int ROWS>
-__device__ __forceinline__ double dpp_f64(double v)
-{
-    const int lo = dpp_i32<CTRL, ROWS>(__double2loint(v)), hi = dpp_i32<CTRL, ROWS>(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double wave_incl_scan_f64(double v)
-{
-    v += dpp_f64<0x111, 0xf>(v);   // row_shr:1
-    v += dpp_f64<0x112, 0xf>(v);   // row_shr:2
-    v += dpp_f64<0x114, 0xf>(v);   // row_shr:4
-    v += dpp_f64<0x118, 0xf>(v);   // row_shr:8
-    v += dpp_f64<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-    v += dpp_f64<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
-__device__ __forceinline__ int wave_incl_scan_i32(int v)
-{
-    v += dpp_i32<0x111, 0xf>(v);
-    v += dpp_i32<0x112, 0xf>(v);
-    v += dpp_i32<0x114, 0xf>(v);
-    v += dpp_i32<0x118, 0xf>(v);
-    v += dpp_i32<0x142, 0xa>(v);
-    v += dpp_i32<0x143, 0xc>(v);
-    return v;
-}
 
 // 1 / x for x = 1 .. 2^31 (AP: precision at a relevant rank): v_rcp_f64 + two Newton steps instead of the IEEE division sequence
 __device__ __forceinline__ double fast_rcp_f64(double x)
@@ -128,7 +92,7 @@ __global__ __launch_bounds__(HP_ORDER_THREADS) void hprec_order_kernel(const int
     const int per = (C + HP_ORDER_THREADS - 1) / HP_ORDER_THREADS, lo = tid * per, hi = (lo + per < C) ? lo + per : C;
     int mine = 0;
     for (int c = lo; c < hi; c++) mine += hp_hist[c];
-    const int incl = wave_incl_scan_i32(mine);
+    const int incl = wave_incl_scan(mine);
     if (lane == 63) s_wt[wave] = incl;
     wg_barrier();
     int run = incl - mine;
@@ -146,9 +110,8 @@ __global__ __launch_bounds__(HP_ORDER_THREADS) void hprec_order_kernel(const int
 }
 
 // out row layout: [P@k WUP x nk][P@k LCS x nk][AHP WUP][AHP LCS][AP]
-// CLSW: where the class of a ranked gallery item comes from -- 1 / 2: a byte / 16-bit copy of `cls` in LDS, filled once per
-// (persistent) workgroup; 0: gathered from global memory (galleries too large for LDS).  The random 4-byte gather costs a
-// 128-byte L2 -> L1 line per rank, 32x the ranking itself, and was what bounded the kernel before the LDS copy.
+// CLSW: where the class of a ranked gallery item comes from (rank_stream.h; the gathers of CLSW = 0 were what bounded the kernel
+// before the LDS copy).
 // RT: element type of the rankings -- int32_t, or uint16_t (se_rank_rows with idx64 == 2: one 16-byte load brings a thread's 8 ranks)
 template <int CLSW, typename RT>
 __global__ __launch_bounds__(HP_THREADS, HP_WAVES_PER_SIMD) void hprec_kernel(const RT *__restrict__ rank, int64_t ldr, int64_t Q, int64_t L,
@@ -168,32 +131,11 @@ __global__ __launch_bounds__(HP_THREADS, HP_WAVES_PER_SIMD) void hprec_kernel(co
     int *s_perm = s_ks + nk;                                       // [nk] their slots in the output row
     int *s_qpos = s_perm + nk;
     int *s_next = s_qpos + 1;                                      // [9]: number of queries drawn, then (query, class, own index, flag) x 2
-    unsigned char *s_cls8 = reinterpret_cast<unsigned char *>(s_qpos + 12);   // [gallery] class of every gallery item (CLSW 1 / 2)
-    unsigned short *s_cls16 = reinterpret_cast<unsigned short *>(s_cls8);
+    unsigned char *s_cls = reinterpret_cast<unsigned char *>(s_qpos + 12);    // [gallery] class of every gallery item as a byte / 16 bits (CLSW 1 / 2)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
     // ---- once per workgroup: the gallery's classes into LDS, the cut-offs sorted (rank by counting; ties keep their order) ----
-    if (CLSW == 1) {
-        unsigned *w = reinterpret_cast<unsigned *>(s_cls8);
-        const int64_t quads = (reinterpret_cast<uintptr_t>(cls) % 16 == 0) ? gallery / 4 : 0;     // 16-byte loads, 8 in flight per thread
-        const int4 *c4 = reinterpret_cast<const int4 *>(cls);
-#pragma unroll 8
-        for (int64_t g = tid; g < quads; g += HP_THREADS) {
-            const int4 v = c4[g];
-            w[g] = ((unsigned)v.x & 0xFFu) | (((unsigned)v.y & 0xFFu) << 8) | (((unsigned)v.z & 0xFFu) << 16) | (((unsigned)v.w & 0xFFu) << 24);
-        }
-        for (int64_t i = quads * 4 + (int64_t)tid * 4; i < gallery; i += HP_THREADS * 4) {
-            unsigned v = 0;
-#pragma unroll
-            for (int e = 0; e < 4; e++) v |= (i + e < gallery ? (unsigned)cls[i + e] & 0xFFu : 0u) << (8 * e);
-            w[i >> 2] = v;
-        }
-    } else if (CLSW == 2) {
-        unsigned *w = reinterpret_cast<unsigned *>(s_cls16);
-#pragma unroll 8
-        for (int64_t i = (int64_t)tid * 2; i < gallery; i += HP_THREADS * 2)
-            w[i >> 1] = ((unsigned)cls[i] & 0xFFFFu) | ((i + 1 < gallery ? (unsigned)cls[i + 1] & 0xFFFFu : 0u) << 16);
-    }
+    fill_class_table<CLSW, HP_THREADS>(cls, gallery, s_cls, tid);
     for (int s = tid; s < nk; s += HP_THREADS) s_perm[s] = ks[s];       // raw cut-offs (LDS copy), ranked below
     wg_barrier();
     int my_k[(HP_MAX_KS + HP_THREADS - 1) / HP_THREADS], my_r[(HP_MAX_KS + HP_THREADS - 1) / HP_THREADS];
@@ -281,35 +223,11 @@ __global__ __launch_bounds__(HP_THREADS, HP_WAVES_PER_SIMD) void hprec_kernel(co
 #pragma unroll
             for (int u = 0; u < NQ; u++) { rrow[u] = rank + qq[u] * ldr; orow[u] = out + qq[u] * ldo; }
             const double2 *rc = rcp + (int64_t)qc * ldc;
-            // The ranks a thread owns in a chunk are requested HP_PF chunks ahead (HP_PF register sets, refilled right after the barrier of
-            // the chunk that consumed them).
-            int r[NQ][HP_PF][HP_ITEMS];
-            auto load_ranks = [&](int (&dst)[HP_ITEMS], const RT *row, int at, int bound) {
-                if (vec_ok && at + HP_ITEMS <= bound) {
-                    if constexpr (sizeof(RT) == 2) {
-                        static_assert(HP_ITEMS % 8 == 0, "16-byte loads of 16-bit ranks");
+            // The ranks a thread owns in a chunk are requested a chunk ahead (refilled as soon as the chunk that consumed them has
+            // looked its classes up).
+            int r[NQ][HP_ITEMS];
 #pragma unroll
-                        for (int v = 0; v < HP_ITEMS / 8; v++) {
-                            const uint4 a = *reinterpret_cast<const uint4 *>(row + at + 8 * v);
-                            dst[8 * v] = (int)(a.x & 0xFFFFu); dst[8 * v + 1] = (int)(a.x >> 16); dst[8 * v + 2] = (int)(a.y & 0xFFFFu); dst[8 * v + 3] = (int)(a.y >> 16);
-                            dst[8 * v + 4] = (int)(a.z & 0xFFFFu); dst[8 * v + 5] = (int)(a.z >> 16); dst[8 * v + 6] = (int)(a.w & 0xFFFFu); dst[8 * v + 7] = (int)(a.w >> 16);
-                        }
-                    } else {
-#pragma unroll
-                    for (int v = 0; v < HP_ITEMS / 4; v++) {
-                        const int4 a = *reinterpret_cast<const int4 *>(row + at + 4 * v);
-                        dst[4 * v] = a.x; dst[4 * v + 1] = a.y; dst[4 * v + 2] = a.z; dst[4 * v + 3] = a.w;
-                    }
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < HP_ITEMS; e++) dst[e] = (at + e < bound) ? (int)row[at + e] : 0;
-                }
-            };
-#pragma unroll
-            for (int u = 0; u < NQ; u++)
-#pragma unroll
-                for (int p = 0; p < HP_PF; p++) load_ranks(r[u][p], rrow[u], tid * HP_ITEMS + p * HP_CHUNK, lp_bound);
+            for (int u = 0; u < NQ; u++) load_ranks(r[u], rrow[u], tid * HP_ITEMS, lp_bound, vec_ok);
             const int32_t self = selfq[0];
             int32_t first = 0;
             if (NQ == 1 && qpos_known < 0) first = (int32_t)rrow[0][0];
@@ -363,8 +281,7 @@ __global__ __launch_bounds__(HP_THREADS, HP_WAVES_PER_SIMD) void hprec_kernel(co
 #pragma unroll
                 for (int e = 0; e < HP_ITEMS; e++) dst[e] = rows[e * HP_THREADS + tid + ((!BEHIND && at + e < qpos) ? half : 0)];
             };
-            auto step = [&](auto slot_c) {
-                constexpr int SLOT = decltype(slot_c)::value;
+            auto step = [&]() {
                 const int i0 = base + tid * HP_ITEMS;
                 const bool cuts = (nk > 0) && (base <= kmax);               // uniform: a cut-off may fall into this chunk
                 // One chunk, in one of three forms (uniform tests below).  FAST: an interior chunk -- every position is live, behind the
@@ -387,10 +304,7 @@ __global__ __launch_bounds__(HP_THREADS, HP_WAVES_PER_SIMD) void hprec_kernel(co
                         for (int e = 0; e < HP_ITEMS; e++) {
                             const int i = i0 + e;
                             const bool live = FAST || ((i < last_pos) && (TAIL || i != qpos));
-                            int c = 0;
-                            if (CLSW == 1) c = s_cls8[r[u][SLOT][e]];
-                            else if (CLSW == 2) c = s_cls16[r[u][SLOT][e]];
-                            else if (live) c = cls[r[u][SLOT][e]];
+                            const int c = class_of<CLSW>(s_cls, cls, r[u][e], live, 0);
                             double2 v = s_sim[c];
                             if (!FAST) { v.x = live ? v.x : 0.0; v.y = live ? v.y : 0.0; }
                             rel[u] |= (live && c == qc) ? (1u << e) : 0u;
@@ -402,15 +316,15 @@ __global__ __launch_bounds__(HP_THREADS, HP_WAVES_PER_SIMD) void hprec_kernel(co
                     // the rank registers are free again: the NEXT chunk's ranks are requested here, in front of the scans and the barrier
                     // (behind the barrier, as in round 5, they had half a chunk to arrive in and the look-ups waited for HBM)
 #pragma unroll
-                    for (int u = 0; u < NQ; u++) load_ranks(r[u][SLOT], rrow[u], i0 + HP_PF * HP_CHUNK, last_pos);
+                    for (int u = 0; u < NQ; u++) load_ranks(r[u], rrow[u], i0 + HP_CHUNK, last_pos, vec_ok);
                     // ---- workgroup exclusive scan of the thread totals: DPP inside the wave, wave totals through LDS ----
                     double iw[NQ], il[NQ];
                     int ir[NQ];
                     double *part = s_part + par * (2 * HP_WAVES * 3);
 #pragma unroll
                     for (int u = 0; u < NQ; u++) {
-                        iw[u] = wave_incl_scan_f64(tw[u]); il[u] = wave_incl_scan_f64(tl[u]);
-                        ir[u] = wave_incl_scan_i32(tr[u]);
+                        iw[u] = wave_incl_scan(tw[u]); il[u] = wave_incl_scan(tl[u]);
+                        ir[u] = wave_incl_scan(tr[u]);
                         if (lane == 63) { part[(u * HP_WAVES + wave) * 3 + 0] = iw[u]; part[(u * HP_WAVES + wave) * 3 + 1] = il[u]; part[(u * HP_WAVES + wave) * 3 + 2] = (double)ir[u]; }
                     }
                     wg_barrier();   // the only barrier of a chunk (of all NQ queries): the other half of s_part is written next time
@@ -491,14 +405,12 @@ __global__ __launch_bounds__(HP_THREADS, HP_WAVES_PER_SIMD) void hprec_kernel(co
                 else chunk(std::integral_constant<int, 0>{});
                 base += HP_CHUNK; par ^= 1; rct += HP_CHUNK;
             };
-            while (base < last_pos) {
-                if (base < last_pos) step(std::integral_constant<int, 0>{});
-            }
+            while (base < last_pos) step();
             // ---- finish: trapezoid and AP (the end points were left in LDS by whichever thread owned ranks 0 and alen - 1) ----
             {
 #pragma unroll
                 for (int u = 0; u < NQ; u++) {
-                    const double f0 = wave_incl_scan_f64(acc_w[u]), f1 = wave_incl_scan_f64(acc_l[u]), f2 = wave_incl_scan_f64(acc_ap[u]);   // lane 63: the wave's sums
+                    const double f0 = wave_incl_scan(acc_w[u]), f1 = wave_incl_scan(acc_l[u]), f2 = wave_incl_scan(acc_ap[u]);   // lane 63: the wave's sums
                     if (lane == 63) { s_fin[(u * HP_WAVES + wave) * 3 + 0] = f0; s_fin[(u * HP_WAVES + wave) * 3 + 1] = f1; s_fin[(u * HP_WAVES + wave) * 3 + 2] = f2; }
                 }
                 wg_barrier();
@@ -558,20 +470,6 @@ extern "C" int se_hprec_reciprocal_curves(const double *best_wup, const double *
 
 extern "C" int64_t se_hprec_order_workspace_bytes(int64_t q) { return q < 0 ? 0 : (int64_t)sizeof(int32_t) * (HP_WS_HEAD + 4 * q); }
 
-namespace se {
-
-struct HpLaunch { int clsw; size_t lds; int grid; };
-
-template <int CLSW, typename RT>
-static hipError_t hp_occupancy(size_t lds, int *blocks_per_cu)
-{
-    hipError_t e = hipFuncSetAttribute((const void *)hprec_kernel<CLSW, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, hprec_kernel<CLSW, RT>, HP_THREADS, lds);
-}
-
-}  // namespace se
-
 template <typename RT>
 static int hp_run(const RT *rank, int64_t ldr, int64_t q, int64_t list_len, const int32_t *cls, int64_t gallery,
                   const int32_t *qcls, const int32_t *qidx, const double *wup, const double *lcs,
@@ -588,21 +486,9 @@ static int hp_run(const RT *rank, int64_t ldr, int64_t q, int64_t list_len, cons
     if (ldr < list_len || ldo < 2 * nk + 3) return fail(SE_ERR_INVALID, "se_hierarchical_precision: leading dimension too small");
     if (rcp_len < list_len) return fail(SE_ERR_INVALID, "se_hierarchical_precision: the reciprocal curves cover %lld positions, the rankings have %lld", (long long)rcp_len, (long long)list_len);
     const size_t fixed = (size_t)num_classes * sizeof(double2) + (size_t)(2 * 2 * HP_WAVES * 3 + 2 * HP_WAVES * 3 + 8) * sizeof(double) + (size_t)(2 * nk + 12) * sizeof(int);
-    const size_t cap = 160 * 1024;
-    if (fixed > cap) return fail(SE_ERR_UNSUPPORTED, "se_hierarchical_precision: %d classes exceed the LDS similarity rows", num_classes);
-    // the gallery's classes as bytes / shorts in LDS when they fit (two workgroups per CU preferred for the byte table), else gathered
-    const size_t tab8 = ((size_t)gallery + 15) / 16 * 16, tab16 = ((size_t)gallery * 2 + 15) / 16 * 16;
-    int clsw = 0;
-    if (list_len * (q < 4096 ? q : 4096) < 8 * gallery) clsw = 0;      // short lists / few queries: filling the table would cost more than the gathers
-    else if (num_classes <= 256 && fixed + tab8 <= cap) clsw = 1;
-    else if (num_classes <= 65536 && fixed + tab16 <= cap) clsw = 2;
-    const size_t lds = fixed + (clsw == 1 ? tab8 : clsw == 2 ? tab16 : 0);
+    if (fixed > CLASS_TABLE_LDS_CAP) return fail(SE_ERR_UNSUPPORTED, "se_hierarchical_precision: %d classes exceed the LDS similarity rows", num_classes);
+    const ClassTable ct = choose_class_table(list_len, q, gallery, num_classes, fixed);
     hipStream_t s = (hipStream_t)stream;
-    int per_cu = 0, dev = 0, cus = 0;
-    SE_HIP_CHECK(clsw == 1 ? (hp_occupancy<1, RT>(lds, &per_cu)) : clsw == 2 ? (hp_occupancy<2, RT>(lds, &per_cu)) : (hp_occupancy<0, RT>(lds, &per_cu)));
-    SE_HIP_CHECK(hipGetDevice(&dev));
-    SE_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (per_cu < 1) per_cu = 1;
     int32_t *ws = static_cast<int32_t *>(order_ws);
     const size_t order_lds = (size_t)(num_classes + HP_ORDER_THREADS / WAVE) * sizeof(int);
     if (ws) {
@@ -611,21 +497,18 @@ static int hp_run(const RT *rank, int64_t ldr, int64_t q, int64_t list_len, cons
         hipLaunchKernelGGL(hprec_order_kernel<RT>, dim3(1), dim3(HP_ORDER_THREADS), order_lds, s, qcls, qidx, q, num_classes, rank, ldr, ws);
         SE_LAUNCH_CHECK();
     }
-    // persistent workgroups (the class table is loaded once each): as many as are resident at once
-    const int64_t resident = (int64_t)per_cu * cus;
-    const int64_t grid = q < resident ? q : resident;
-    const int vec_ok = ((ldr * (int64_t)sizeof(RT)) % 16 == 0) && (reinterpret_cast<uintptr_t>(rank) % 16 == 0);
+    const int vec_ok = ranks_vec_ok<RT, HP_ITEMS>(rank, ldr);
     const double2 *rc = reinterpret_cast<const double2 *>(rcp);
     const int64_t ldc = 2 * se_hprec_curve_len(rcp_len);
-#define SE_HP_LAUNCH(W)                                                                                                                  \
-    hipLaunchKernelGGL((hprec_kernel<W, RT>), dim3((unsigned)grid), dim3(HP_THREADS), lds, s, rank, ldr, q, list_len, cls, gallery, qcls, qidx, \
-                       wup, lcs, num_classes, rc, ldc, ks, nk, ahp_len, want_ap, out, ldo, ws, vec_ok)
-    if (clsw == 1) SE_HP_LAUNCH(1);
-    else if (clsw == 2) SE_HP_LAUNCH(2);
-    else SE_HP_LAUNCH(0);
-#undef SE_HP_LAUNCH
-    SE_LAUNCH_CHECK();
-    return SE_OK;
+    return dispatch_clsw(ct.clsw, [&](auto w) -> int {
+        const auto kernel = hprec_kernel<decltype(w)::value, RT>;
+        int64_t grid = 0;      // persistent workgroups: the class table is loaded once each
+        SE_HIP_CHECK(persistent_grid(kernel, HP_THREADS, ct.lds_bytes, q, &grid));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(HP_THREADS), ct.lds_bytes, s, rank, ldr, q, list_len, cls, gallery, qcls, qidx,
+                           wup, lcs, num_classes, rc, ldc, ks, nk, ahp_len, want_ap, out, ldo, ws, vec_ok);
+        SE_LAUNCH_CHECK();
+        return SE_OK;
+    });
 }
 
 extern "C" int se_hierarchical_precision(const int32_t *rank, int64_t ldr, int64_t q, int64_t list_len, const int32_t *cls, int64_t gallery,

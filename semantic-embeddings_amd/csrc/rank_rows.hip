@@ -43,17 +43,10 @@ struct RankLds {
     uint32_t tidx[RK_TILE];
 };
 
-// Exclusive prefix sum over the 64 lanes with data-parallel primitives (DPP): four row_shr steps scan each row of 16 lanes, row_bcast15 /
-// row_bcast31 carry the row totals on -- six VALU instructions instead of six ds_bpermute round trips (__shfl_up).
+// Exclusive prefix sum over the 64 lanes (the DPP scan of se_common.h) and the wave's total
 __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t &total)
 {
-    uint32_t incl = v;
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, false);   // row_shr:1
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, false);   // row_shr:2
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, false);   // row_shr:4
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, false);   // row_shr:8
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xA, 0xF, false);   // row_bcast15 -> rows 1 and 3
-    incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x143, 0xC, 0xF, false);   // row_bcast31 -> rows 2 and 3
+    const uint32_t incl = wave_incl_scan(v);
     total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     return incl - v;
 }
@@ -374,7 +367,7 @@ struct RRRank {
             uint32_t dlo, dhi;
             differ_mask(d, dlo, dhi);
             // lower lanes with the same digit = lower lanes - lower lanes that differ
-            rnk[g] = (uint32_t)lane - __builtin_amdgcn_mbcnt_hi(dhi, __builtin_amdgcn_mbcnt_lo(dlo, 0u));
+            rnk[g] = (uint32_t)lane - wave_prefix_count(dlo, dhi);
             const uint32_t ca = cb + (d << 2);
             asm volatile("ds_read_b32 %0, %1" : "=v"(base[g]) : "v"(ca) : "memory");
             if (rnk[g] == 0) {   // (lane 0 always leads a group, so the add is issued in every step)
@@ -495,7 +488,7 @@ struct RRRankHW {
                     const uint32_t d = w | (h << 11);   // (w < 2048)
                     const bool in = (d == (uint32_t)__builtin_amdgcn_readfirstlane((int)d));
                     const uint64_t m = __ballot(in);
-                    if (in) g = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                    if (in) g = wave_prefix_count(m);
                     if (lane == 0) inc = (uint32_t)__popcll(m) << shv;
                     part = ~m | 1ull;                // only lane 0 and the lanes outside its group issue the add
                 }
@@ -1154,7 +1147,7 @@ __global__ __launch_bounds__(RR_THREADS, RR_THREADS / 256) void rank_rows_reg_ke
                 // (per-row opaque copies: otherwise hipcc hoists every row-invariant mask / offset of this block out of the row loop and
                 // keeps ~40 of them in scratch -- the reloads cost more than the whole scan)
                 int n_row = row_len(row);
-                int tsc = wave_s * WAVE + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));   // (tid itself lives in scratch by now)
+                int tsc = wave_s * WAVE + (int)wave_prefix_count(~0u, ~0u);   // (tid itself lives in scratch by now)
                 opaque(n_row);
                 opaque(tsc);
                 const float *drow_cur = row_ptr(row);
@@ -1929,7 +1922,7 @@ __global__ __launch_bounds__(RR_THREADS) void rank_order_probe_kernel(uint32_t *
         asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(got) : "v"(ca), "v"(one) : "memory");
         uint32_t dlo, dhi;
         differ_mask(d, dlo, dhi);
-        const uint32_t rnk = (uint32_t)lane - __builtin_amdgcn_mbcnt_hi(dhi, __builtin_amdgcn_mbcnt_lo(dlo, 0u));
+        const uint32_t rnk = (uint32_t)lane - wave_prefix_count(dlo, dhi);
         const uint32_t want = ref[wave][d] + rnk;
         if (rnk == 0) ref[wave][d] += 64u - (uint32_t)(__popc(dlo) + __popc(dhi));   // one lane per digit group
         bad += (got != want);
@@ -1959,7 +1952,7 @@ __global__ __launch_bounds__(RR_THREADS) void rank_order_probe_kernel(uint32_t *
             const uint64_t hb = __ballot(dh[j] != 0);
             const uint64_t hdiff = dh[j] ? ~hb : hb;                                  // lanes whose half differs from mine
             dlo |= (uint32_t)hdiff; dhi |= (uint32_t)(hdiff >> 32);
-            const uint32_t rnk = (uint32_t)lane - __builtin_amdgcn_mbcnt_hi(dhi, __builtin_amdgcn_mbcnt_lo(dlo, 0u));
+            const uint32_t rnk = (uint32_t)lane - wave_prefix_count(dlo, dhi);
             const uint32_t packed = ref[wave][dw[j]];
             const uint32_t want = (dh[j] ? (packed >> 16) : (packed & 0xFFFFu)) + rnk;
             const uint32_t mine = dh[j] ? (got[j] >> 16) : (got[j] & 0xFFFFu);

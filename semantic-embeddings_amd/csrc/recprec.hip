@@ -18,7 +18,7 @@
 //   the buffer -- tiling does not change a bit.  Binned curves: one wave per (class, bin) takes the max of j / p_j over the bin's j
 //   for every query of the class (max is exact in any order) and adds it to the bin's sum.
 // float64 throughout; every j / p_j is an IEEE (correctly rounded) division, like the reference's tp / arange.
-#include "se_common.h"
+#include "rank_stream.h"
 
 #include <limits.h>
 
@@ -33,7 +33,7 @@ constexpr int RP_CHUNK = RP_GSPAN * RP_GROUPS;
 constexpr int RP_HEAD_INTS = 2 * (RP_GROUPS + 1) * RP_WAVES;     // [2][RP_GROUPS][RP_WAVES] hit counts, [2][RP_WAVES] self positions
 constexpr int RP_MAX_BINS = 1 << 20;
 
-// CLSW: where the class of a ranked gallery item comes from -- 1 / 2: a byte / 16-bit copy of `cls` in LDS; 0: global gathers.
+// CLSW: where the class of a ranked gallery item comes from (rank_stream.h) -- 1 / 2: a byte / 16-bit copy of `cls` in LDS; 0: global gathers.
 // RT: element type of the rankings -- int32_t, or uint16_t (se_rank_rows with idx64 == 2).
 template <int CLSW, typename RT>
 __global__ __launch_bounds__(RP_THREADS) void relpos_kernel(const RT *__restrict__ rank, int64_t ldr, int64_t Q, int64_t L,
@@ -44,42 +44,14 @@ __global__ __launch_bounds__(RP_THREADS) void relpos_kernel(const RT *__restrict
     extern __shared__ __attribute__((aligned(16))) unsigned char rp_raw[];
     int *s_cnt = reinterpret_cast<int *>(rp_raw);
     int *s_self = s_cnt + 2 * RP_GROUPS * RP_WAVES;
-    unsigned char *s_cls8 = rp_raw + RP_HEAD_INTS * sizeof(int);
-    unsigned short *s_cls16 = reinterpret_cast<unsigned short *>(s_cls8);
+    unsigned char *s_cls = rp_raw + RP_HEAD_INTS * sizeof(int);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
     // ---- once per workgroup: the gallery's classes into LDS ----
-    if (CLSW == 1) {
-        unsigned *w = reinterpret_cast<unsigned *>(s_cls8);
-        for (int64_t i = (int64_t)tid * 4; i < gallery; i += RP_THREADS * 4) {
-            unsigned v = 0;
-#pragma unroll
-            for (int e = 0; e < 4; e++) v |= (i + e < gallery ? (unsigned)cls[i + e] & 0xFFu : 0u) << (8 * e);
-            w[i >> 2] = v;
-        }
-    } else if (CLSW == 2) {
-        unsigned *w = reinterpret_cast<unsigned *>(s_cls16);
-        for (int64_t i = (int64_t)tid * 2; i < gallery; i += RP_THREADS * 2)
-            w[i >> 1] = ((unsigned)cls[i] & 0xFFFFu) | ((i + 1 < gallery ? (unsigned)cls[i + 1] & 0xFFFFu : 0u) << 16);
-    }
+    fill_class_table<CLSW, RP_THREADS, 2>(cls, gallery, s_cls, tid);
     wg_barrier();
 
     const int Li = (int)L;                 // positions are int32 (checked at the entry point)
-    auto load = [&](int (&dst)[RP_VEC], const RT *row, int at) {
-        if (vec_ok && at + RP_VEC <= Li) {
-            if constexpr (sizeof(RT) == 2) {
-                const uint2 a = *reinterpret_cast<const uint2 *>(row + at);
-                dst[0] = (int)(a.x & 0xFFFFu); dst[1] = (int)(a.x >> 16); dst[2] = (int)(a.y & 0xFFFFu); dst[3] = (int)(a.y >> 16);
-            } else {
-                const int4 a = *reinterpret_cast<const int4 *>(row + at);
-                dst[0] = a.x; dst[1] = a.y; dst[2] = a.z; dst[3] = a.w;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < RP_VEC; e++) dst[e] = (at + e < Li) ? (int)row[at + e] : 0;
-        }
-    };
-
     int par = 0;
     for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
         const int64_t off = hit_off[q];
@@ -91,7 +63,7 @@ __global__ __launch_bounds__(RP_THREADS) void relpos_kernel(const RT *__restrict
         int32_t *out = hit_pos + off;
         int r[RP_GROUPS][RP_VEC];
 #pragma unroll
-        for (int g = 0; g < RP_GROUPS; g++) load(r[g], row, g * RP_GSPAN + tid * RP_VEC);
+        for (int g = 0; g < RP_GROUPS; g++) load_ranks(r[g], row, g * RP_GSPAN + tid * RP_VEC, Li, vec_ok);
         int carry = 0;                                                // hits in the chunks before this one (the same in every thread)
         bool self_before = false;                                     // the query itself was met in an earlier chunk
         for (int base = 0; base < Li; base += RP_CHUNK) {
@@ -106,10 +78,7 @@ __global__ __launch_bounds__(RP_THREADS) void relpos_kernel(const RT *__restrict
                     const int pos = base + g * RP_GSPAN + tid * RP_VEC + k;
                     const bool live = pos < Li;
                     const int v = r[g][k];
-                    int c = -1;
-                    if (CLSW == 1) c = s_cls8[v];
-                    else if (CLSW == 2) c = s_cls16[v];
-                    else if (live) c = cls[v];
+                    const int c = class_of<CLSW>(s_cls, cls, v, live, -1);
                     const bool is_self = live && v == self;
                     bits[g] |= (live && !is_self && c == qc) ? (1u << k) : 0u;
                     if (is_self) { mine_self = true; self_at = pos; }
@@ -117,7 +86,7 @@ __global__ __launch_bounds__(RP_THREADS) void relpos_kernel(const RT *__restrict
             }
             // the rank registers are free: the next chunk's ranks are requested here, in front of the counts and the barrier
 #pragma unroll
-            for (int g = 0; g < RP_GROUPS; g++) load(r[g], row, base + RP_CHUNK + g * RP_GSPAN + tid * RP_VEC);
+            for (int g = 0; g < RP_GROUPS; g++) load_ranks(r[g], row, base + RP_CHUNK + g * RP_GSPAN + tid * RP_VEC, Li, vec_ok);
             // ---- hit index: ballot + mbcnt inside the wave, per-wave totals through LDS ----
             int below[RP_GROUPS];
             int *cnt = s_cnt + par * RP_GROUPS * RP_WAVES;
@@ -128,7 +97,7 @@ __global__ __launch_bounds__(RP_THREADS) void relpos_kernel(const RT *__restrict
 #pragma unroll
                 for (int k = 0; k < RP_VEC; k++) {
                     const uint64_t m = __ballot((bits[g] >> k) & 1u);
-                    below[g] += (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                    below[g] += (int)wave_prefix_count(m);
                     n += __popcll(m);
                 }
                 if (lane == 0) cnt[g * RP_WAVES + wave] = n;
@@ -263,14 +232,6 @@ __global__ __launch_bounds__(RP_THREADS) void rp_bin_kernel(const int32_t *__res
     }
 }
 
-template <int CLSW, typename RT>
-static hipError_t rp_occupancy(size_t lds, int *blocks_per_cu)
-{
-    hipError_t e = hipFuncSetAttribute((const void *)relpos_kernel<CLSW, RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, relpos_kernel<CLSW, RT>, RP_THREADS, lds);
-}
-
 }  // namespace se
 
 using namespace se;
@@ -286,31 +247,17 @@ static int rp_positions(const char *who, const RT *rank, int64_t ldr, int64_t q,
     if (!rank || !cls || !qcls || !hit_off || !hit_pos) return fail(SE_ERR_INVALID, "%s: null pointer", who);
     if (ldr < list_len) return fail(SE_ERR_INVALID, "%s: leading dimension too small", who);
     if (q == 0) return SE_OK;
-    const size_t head = RP_HEAD_INTS * sizeof(int), cap = 160 * 1024;
-    const size_t tab8 = ((size_t)gallery + 15) / 16 * 16, tab16 = ((size_t)gallery * 2 + 15) / 16 * 16;
-    int clsw = 0;
-    if (list_len * (q < 4096 ? q : 4096) < 8 * gallery) clsw = 0;      // few / short rows: filling the table would cost more than the gathers
-    else if (num_classes <= 256 && head + tab8 <= cap) clsw = 1;
-    else if (num_classes <= 65536 && head + tab16 <= cap) clsw = 2;
-    const size_t lds = head + (clsw == 1 ? tab8 : clsw == 2 ? tab16 : 0);
-    hipStream_t s = (hipStream_t)stream;
-    int per_cu = 0, dev = 0, cus = 0;
-    SE_HIP_CHECK(clsw == 1 ? (rp_occupancy<1, RT>(lds, &per_cu)) : clsw == 2 ? (rp_occupancy<2, RT>(lds, &per_cu)) : (rp_occupancy<0, RT>(lds, &per_cu)));
-    SE_HIP_CHECK(hipGetDevice(&dev));
-    SE_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (per_cu < 1) per_cu = 1;
-    const int64_t resident = (int64_t)per_cu * cus;
-    const int64_t grid = q < resident ? q : resident;
-    const int vec_ok = ((ldr * (int64_t)sizeof(RT)) % (RP_VEC * sizeof(RT)) == 0) && (reinterpret_cast<uintptr_t>(rank) % (RP_VEC * sizeof(RT)) == 0);
-#define SE_RP_LAUNCH(W)                                                                                                              \
-    hipLaunchKernelGGL((relpos_kernel<W, RT>), dim3((unsigned)grid), dim3(RP_THREADS), lds, s, rank, ldr, q, list_len, cls, gallery, \
-                       qcls, qidx, hit_off, hit_pos, vec_ok)
-    if (clsw == 1) SE_RP_LAUNCH(1);
-    else if (clsw == 2) SE_RP_LAUNCH(2);
-    else SE_RP_LAUNCH(0);
-#undef SE_RP_LAUNCH
-    SE_LAUNCH_CHECK();
-    return SE_OK;
+    const ClassTable ct = choose_class_table(list_len, q, gallery, num_classes, RP_HEAD_INTS * sizeof(int));
+    const int vec_ok = ranks_vec_ok<RT, RP_VEC>(rank, ldr);
+    return dispatch_clsw(ct.clsw, [&](auto w) -> int {
+        const auto kernel = relpos_kernel<decltype(w)::value, RT>;
+        int64_t grid = 0;
+        SE_HIP_CHECK(persistent_grid(kernel, RP_THREADS, ct.lds_bytes, q, &grid));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(RP_THREADS), ct.lds_bytes, (hipStream_t)stream, rank, ldr, q, list_len, cls, gallery,
+                           qcls, qidx, hit_off, hit_pos, vec_ok);
+        SE_LAUNCH_CHECK();
+        return SE_OK;
+    });
 }
 
 extern "C" int se_relevant_positions(const int32_t *rank, int64_t ldr, int64_t q, int64_t list_len, const int32_t *cls, int64_t gallery,

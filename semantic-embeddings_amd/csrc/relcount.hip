@@ -112,12 +112,7 @@ __global__ __launch_bounds__(RC_THREADS) void relscan_kernel(const int32_t *__re
         int carry = 0;                                                // sum of the steps before this one (the same in every thread)
         for (int64_t base = 0; base < R; base += RC_THREADS) {        // uniform trip count
             const int64_t m = base + tid;
-            int v = m < R ? cnt[off + m] : 0;
-#pragma unroll
-            for (int d = 1; d < WAVE; d <<= 1) {
-                const int t = __shfl_up(v, d, WAVE);
-                if (lane >= d) v += t;
-            }
+            const int v = wave_incl_scan(m < R ? cnt[off + m] : 0);
             if (lane == WAVE - 1) s_tot[par][wave] = v;
             wg_barrier();   // the only barrier of a step: the other half of s_tot is written next time
             int before = carry, total = 0;

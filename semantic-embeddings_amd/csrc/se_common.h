@@ -121,6 +121,37 @@ __device__ __forceinline__ T wave_min(T v)      // integers
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
+// Inclusive prefix sum over the 64 lanes with data-parallel primitives (DPP), T = int / uint32_t / double: four row_shr steps scan
+// each row of 16 lanes, row_bcast15 / row_bcast31 carry the row totals on -- six VALU instructions per 32-bit half instead of six
+// ds_bpermute round trips (__shfl_up), and no LDS traffic.  Lane 63 holds the wave's total.
+template <int CTRL, int ROWS, class T>
+__device__ __forceinline__ T dpp_or_zero(T v)      // v of the lane that CTRL names; 0 where there is none or the row is masked out
+{
+    static_assert(std::is_same<T, int>::value || std::is_same<T, uint32_t>::value || std::is_same<T, double>::value, "int, uint32_t or double");
+    if constexpr (sizeof(T) == 8) {
+        const int lo = dpp_or_zero<CTRL, ROWS>(__double2loint(v)), hi = dpp_or_zero<CTRL, ROWS>(__double2hiint(v));
+        return __hiloint2double(hi, lo);
+    } else {
+        return (T)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWS, 0xf, true);
+    }
+}
+
+template <class T>
+__device__ __forceinline__ T wave_incl_scan(T v)
+{
+    v += dpp_or_zero<0x111, 0xf>(v);   // row_shr:1
+    v += dpp_or_zero<0x112, 0xf>(v);   // row_shr:2
+    v += dpp_or_zero<0x114, 0xf>(v);   // row_shr:4
+    v += dpp_or_zero<0x118, 0xf>(v);   // row_shr:8
+    v += dpp_or_zero<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+    v += dpp_or_zero<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
+// number of set bits of a wave mask (a ballot; or its two halves) below this lane
+__device__ __forceinline__ uint32_t wave_prefix_count(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u)); }
+__device__ __forceinline__ uint32_t wave_prefix_count(uint64_t ballot) { return wave_prefix_count((uint32_t)ballot, (uint32_t)(ballot >> 32)); }
+
 // Sum of one value per thread of a 256-thread workgroup in a fixed order (thread t adds part[t + off], off = 128 ... 1); every thread
 // gets the total.  part: 256 floats of LDS.
 __device__ __forceinline__ float block_sum_256(float v, float *part)
@@ -190,6 +221,16 @@ template <class F>
 inline void dispatch_bools(bool b0, bool b1, bool b2, F f)
 {
     dispatch_bools(b0, [&](auto c0) { dispatch_bools(b1, b2, [&](auto c1, auto c2) { f(c0, c1, c2); }); });
+}
+
+// f(std::integral_constant<int, clsw>{}) for the class-table width clsw = 0 / 1 / 2 of the ranking consumers (rank_stream.h); returns
+// what f returns
+template <class F>
+inline auto dispatch_clsw(int clsw, F f)
+{
+    if (clsw == 1) return f(std::integral_constant<int, 1>{});
+    if (clsw == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 0>{});
 }
 
 // K-block list of the canonical dot product: the FMA chain restarts per block, block sums are added in order

@@ -82,12 +82,7 @@ __device__ __forceinline__ void topk_select_row(const float *__restrict__ drow, 
                 constexpr int PER = TK_NB / WAVE;  // 32 bins per lane
                 uint32_t local = 0;
                 for (int d = 0; d < PER; d++) local += hist[lane * PER + d];
-                uint32_t incl = local;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t v = __shfl_up(incl, off, 64);
-                    if (lane >= off) incl += v;
-                }
+                const uint32_t incl = wave_incl_scan(local);
                 const uint32_t excl = incl - local;
                 if (remaining > excl && remaining <= incl) {  // exactly one lane
                     uint32_t run = excl;
@@ -987,12 +982,7 @@ __global__ __launch_bounds__(RF_WAVES * 64, 3) void pf_refine_kernel(const uint2
             uint32_t run = 0;
             for (int p0 = 0; p0 < parts; p0 += 64) {
                 const uint32_t c = p0 + lane < parts ? cnts[p0 + lane] : 0u;
-                uint32_t incl = c;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t t = __shfl_up(incl, off, 64);
-                    if (lane >= off) incl += t;
-                }
+                const uint32_t incl = wave_incl_scan(c);
                 if (p0 + lane < parts) pre[p0 + lane + 1] = run + incl;
                 run += (uint32_t)__shfl((int)incl, 63, 64);
             }
@@ -1051,12 +1041,7 @@ __global__ __launch_bounds__(RF_WAVES * 64, 3) void pf_refine_kernel(const uint2
                 uint32_t c[4], local = 0;
 #pragma unroll
                 for (int i = 0; i < 4; i++) { c[i] = hist[lane * 4 + i]; local += c[i]; }
-                uint32_t incl = local;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t t = __shfl_up(incl, off, 64);
-                    if (lane >= off) incl += t;
-                }
+                const uint32_t incl = wave_incl_scan(local);
                 uint32_t run = incl - local, digit = 0, rem = 0;
                 const bool mine = remaining > run && remaining <= incl;             // exactly one lane
 #pragma unroll
@@ -1089,7 +1074,7 @@ __global__ __launch_bounds__(RF_WAVES * 64, 3) void pf_refine_kernel(const uint2
                         const uint32_t key = canon_key(__uint_as_float(c.x));
                         const bool take = e < total && (key <= bkey || key == 0xFFFFFFFFu);
                         const uint64_t bm = __ballot(take);
-                        const uint32_t pos = m + __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
+                        const uint32_t pos = m + wave_prefix_count(bm);
                         if (take && pos < (uint32_t)RF_MAX) sel[pos] = c.y;
                         m += (uint32_t)__popcll(bm);
                     }
@@ -1103,7 +1088,7 @@ __global__ __launch_bounds__(RF_WAVES * 64, 3) void pf_refine_kernel(const uint2
                         const uint32_t key = canon_key(__uint_as_float(c.x));
                         const bool take = e < cp && (key <= bkey || key == 0xFFFFFFFFu);
                         const uint64_t bm = __ballot(take);
-                        const uint32_t pos = m + __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u));
+                        const uint32_t pos = m + wave_prefix_count(bm);
                         if (take && pos < (uint32_t)RF_MAX) sel[pos] = c.y;
                         m += (uint32_t)__popcll(bm);
                     }

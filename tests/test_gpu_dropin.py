@@ -125,12 +125,19 @@ def test_training_step_resnet110_fc_uses_hip_loss_and_learns():
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,q,class_order,with_qidx,C", [(3001, 37, True, True, 23), (3001, 37, False, True, 23), (4096, 64, True, False, 23),
                                                          (2048, 9, True, True, 23), (700, 300, True, True, 23), (5000, 40, True, True, 300),
-                                                         (170001, 5, True, True, 23), (90000, 6, False, True, 700)])
+                                                         (170001, 5, True, True, 23), (90000, 6, False, True, 700),
+                                                         (3000, 5, True, True, 23), (3001, 5, True, True, 23)])
 def test_se_hierarchical_precision_general_rankings(n, q, class_order, with_qidx, C):
     """se_hierarchical_precision on rankings where the query sits ANYWHERE in its list (ranks ahead of it divide by the unshifted
     best curve, class_hierarchy.py:280-290), rows that are not 16-byte aligned (n = 3001), no query ids at all, cut-offs in several
     chunks, with and without the class-ordered visit, and all three sources of the gallery classes (byte table in LDS: C <= 256; 16-bit
-    table: C = 300; global gather: tables that do not fit): equal to the NumPy statement of the reference's per-query loop (1e-10)."""
+    table: C = 300; global gather: tables that do not fit, or -- q = 5 -- too few ranks to pay for a table; there n = 3000 has 16-byte
+    aligned uint16 rows and n = 3001 takes the element loads): equal to the NumPy statement of the reference's per-query loop (1e-10)."""
+    _check_hprec_general_rankings(n, q, class_order, with_qidx, C)
+
+
+def _check_hprec_general_rankings(n, q, class_order, with_qidx, C, cls_view=None):
+    """cls_view: device `cls` -> the tensor the kernel is given in its place (the same classes at another address)."""
     import sehip
     from test_dp_gloo import _hprec_standin
     rng = np.random.default_rng(n + q)
@@ -153,6 +160,8 @@ def test_se_hierarchical_precision_general_rankings(n, q, class_order, with_qidx
     dev = [a.cuda() for a in args]
     if not with_qidx:
         dev[3] = None
+    if cls_view is not None:
+        dev[1] = cls_view(dev[1])
     for ahp, ap in ((0, True), (50, False), (2500, True), (-1, False)):
         want = _hprec_standin(*args, ahp_len=ahp, want_ap=ap).numpy()
         got = sehip.hierarchical_precision(*dev, ahp_len=ahp, want_ap=ap, class_order=class_order).cpu().numpy()
@@ -163,6 +172,18 @@ def test_se_hierarchical_precision_general_rankings(n, q, class_order, with_qidx
             dev16 = [dev[0].to(torch.int16)] + dev[1:]
             got16 = sehip.hierarchical_precision(*dev16, ahp_len=ahp, want_ap=ap, class_order=class_order).cpu().numpy()
             assert np.array_equal(got16, got), (ahp, ap, np.abs(got16 - got).max())
+
+
+@pytest.mark.gpu
+def test_se_hierarchical_precision_class_view_off_alignment():
+    """The byte table of the gallery's classes filled from a `cls` that is a view one element into its buffer (4 bytes off the 16-byte
+    loads of the fill: its scalar loads, here for a gallery that is no multiple of 4 either): the same numbers as above."""
+    def view(cls):
+        buf = torch.zeros(cls.numel() + 1, dtype=cls.dtype, device=cls.device)
+        buf[1:].copy_(cls)
+        assert buf[1:].data_ptr() % 16 == 4 and cls.data_ptr() % 16 == 0 and buf[1:].is_contiguous()
+        return buf[1:]
+    _check_hprec_general_rankings(3001, 37, True, True, 23, cls_view=view)
 
 
 @pytest.mark.gpu

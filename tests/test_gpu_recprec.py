@@ -86,6 +86,42 @@ def test_relevant_positions_r16_and_row_subset(n, c):
     assert np.array_equal(got.cpu().numpy(), want)
 
 
+def _misaligned(a):
+    """`a` on the device as a view that starts one element into its buffer: contiguous, 4 bytes off the allocator's alignment."""
+    buf = torch.zeros(a.size + 1, dtype=torch.from_numpy(a).dtype, device="cuda")
+    buf[1:].copy_(torch.from_numpy(a))
+    return buf[1:]
+
+
+# class source of relpos_kernel (csrc/rank_stream.h): (classes, query rows) -- byte table, 16-bit table, global gather (5 rows:
+# list_len * rows < 8 * gallery, no table is filled)
+CLASS_SOURCES = {"byte_table": (3, None), "short_table": (300, None), "gather": (3, 5)}
+
+
+@pytest.mark.parametrize("n", [2047, 2048, 2049])
+@pytest.mark.parametrize("source", sorted(CLASS_SOURCES))
+def test_relevant_positions_every_class_source(n, source):
+    """Every relpos_kernel<CLSW, RT>: one 2048-rank chunk and one rank either side of it (2047 / 2049: a gallery that is no multiple
+    of 4, rows that take the element loads; 2048: the vector loads), int32 and uint16 rankings, `cls` 16-byte aligned (the table
+    fill's 16-byte loads) and as a view one element into its buffer (its scalar loads): the oracle's positions, bit for bit."""
+    import sehip
+    c, rows = CLASS_SOURCES[source]
+    r0 = 0 if rows is None else n // 3
+    rows = n if rows is None else rows
+    rank = _canon(n, 8, True, n)[r0:r0 + rows]
+    cls = np.random.default_rng(n + c).integers(0, c, size=n).astype(np.int32)
+    qcls, qidx = cls[r0:r0 + rows].copy(), np.arange(r0, r0 + rows, dtype=np.int32)
+    hit_off, want = _positions(rank, cls, qcls, qidx)
+    assert (rank.shape[1] * min(rows, 4096) < 8 * n) == (source == "gather")          # the kernel's rule for leaving the table out
+    for cls_dev in (torch.from_numpy(cls).cuda(), _misaligned(cls)):
+        assert (cls_dev.data_ptr() % 16 == 0) == (cls_dev.storage_offset() == 0) and cls_dev.is_contiguous()
+        for r16 in (False, True):
+            rk = torch.from_numpy(rank.astype(np.uint16).view(np.int16) if r16 else rank.astype(np.int32)).cuda()
+            got = sehip.relevant_positions(rk, cls_dev, torch.from_numpy(qcls).cuda(), torch.from_numpy(qidx).cuda(),
+                                           torch.from_numpy(hit_off).cuda(), num_classes=c)
+            assert np.array_equal(got.cpu().numpy(), want), (n, source, cls_dev.storage_offset(), r16)
+
+
 def _hierarchy():
     from class_hierarchy import ClassHierarchy
     g = np.load(os.path.join(GOLDEN, "hierarchy_cifar.npz"))
