@@ -163,6 +163,32 @@ int se_nn_accuracy(const float *y_pred, int64_t ldp, const int64_t *labels, cons
                    int64_t workspace_bytes, se_stream_t stream);
 
 /*
+ * Embedding heads: the loss of `--loss inv_corr` / `--loss mse` AND the nearest-class metric of its batch in one forward launch.
+ * Replaces: utils.inv_correlation on the l2norm head (utils.py:44-46, 125-127) or utils.squared_distance (utils.py:34-36), plus
+ *           utils.nn_accuracy(embedding, dot_prod_sim, k) for every k (utils.py:57-100), which differ only in the last comparison.
+ * The contract is bit identity with the entry points above, on the same inputs:
+ *   mode 0 (cosine head): xhat, inv_norm, loss_i, loss_mean are the bits of se_cosine_loss_fwd (float32 or bf16 x, 1e-12 clamp,
+ *           clamped labels); n_better, n_within, best, scores are what se_nn_accuracy(dot_prod_sim = 1) computes from that xhat.
+ *   mode 1 (squared-distance head): loss_i, dist_i, loss_mean are the bits of se_sqdist_loss_fwd; the metric outputs are those of
+ *           se_nn_accuracy(dot_prod_sim = 0) on x widened to float32.
+ *   n_within [B] int32: classes whose score is within 1e-6 of the label's; n_better [B] int32: classes beyond it by >= 1e-6.
+ *           The accuracy for any k is (n_within >= 1) && (n_better < k): the 0/1 value se_nn_accuracy(..., k, ...) writes.
+ *   xhat, inv_norm (mode 0), dist_i (mode 1), loss_mean, best, scores may be NULL; the outputs of the other mode are ignored.
+ *   The normalised features do not travel through memory between loss and metric: xhat is written only when it is asked for.
+ *   workspace: se_embed_head_workspace_bytes(mode, B, D, C) bytes, 8-byte aligned (0 while one workgroup walks all class tiles of
+ *           its 32 samples); the call zeroes what it needs of it on `stream`, so it can be captured in a HIP graph.
+ *   B == 0 returns SE_OK and touches nothing; a bad mode, dtype, leading dimension, a null required pointer or a missing, short
+ *   or misaligned workspace returns SE_ERR_INVALID.  Results do not depend on the launch geometry or on concurrent work.
+ */
+int64_t se_embed_head_workspace_bytes(int mode, int64_t B, int64_t D, int64_t C);
+int se_embed_head_fwd(int mode, const void *x, int x_dtype, int64_t ldx, const int64_t *labels,
+                      const float *emb, int64_t lde, int64_t B, int64_t D, int64_t C,
+                      float *xhat, int64_t ldxhat, float *inv_norm, float *loss_i, float *dist_i,
+                      float *loss_mean, int32_t *n_better, int32_t *n_within, int32_t *best,
+                      float *scores, int64_t lds, void *workspace, int64_t workspace_bytes,
+                      se_stream_t stream);
+
+/*
  * Label-embedding baseline loss (Sun et al.), forward and backward.
  * Replaces: labelembed_loss(out1, out2, tar, targets, tau, alpha, beta) and cross_entropy
  *           (learn_labelembedding.py:17-37); the backward is what TF autodiff derives from it

@@ -124,6 +124,17 @@ def accuracy(y_true, out):
 accuracy.name = 'acc'
 
 
+def head_by_default(loss, onehot_metrics, num_top_k):
+    """Whether the embedding head (loss and nearest-class metric in one launch, utils.CosineEmbeddingHead / SquaredDistanceHead)
+    replaces the loss object + one utils.nn_accuracy launch per metric.  The logged values are the same bits either way; this only
+    chooses the faster sequence, from profiles/embed_head_bench.txt: the head was not slower at any measured shape (128 x 100 x 100 to
+    256 x 1000 x 1000, float32 and bfloat16 features), for either loss, against one, two or three metric launches (x1.27 at the
+    least), so every such configuration takes it.  One-hot targets use arg-max metrics, which the head does not serve."""
+    if onehot_metrics:
+        return False
+    return True
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description='Learns to map images onto class embeddings (MI355X build).',
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -188,6 +199,9 @@ def main(argv=None):
         loss = lambda y, o: utils.inv_correlation(emb_dev[y], o)
         metrics = [accuracy if onehot_like else utils.nn_accuracy(emb_dev, dot_prod_sim=True)]
         metrics += [utils.top_k_acc(k) if onehot_like else utils.nn_accuracy(emb_dev, dot_prod_sim=True, k=k) for k in args.top_k_acc]
+    elif args.loss == 'inv_corr' and head_by_default('inv_corr', onehot_like, len(args.top_k_acc)):
+        loss = utils.CosineEmbeddingHead(emb_dev)          # fused l2norm + gather + 1 - <.,.> + the metric's counts, one launch
+        metrics = [loss.accuracy()] + [loss.accuracy(k) for k in args.top_k_acc]
     elif args.loss == 'inv_corr':
         loss = utils.CosineEmbeddingLoss(emb_dev)          # fused l2norm + gather + 1 - <.,.>
         metrics = [accuracy if onehot_like else utils.nn_accuracy(emb_dev, dot_prod_sim=True)]
@@ -198,6 +212,9 @@ def main(argv=None):
         loss = lambda y, o: utils.inv_correlation(emb_dev[y], post(o))
         metrics = [accuracy if onehot_like else utils.nn_accuracy(emb_dev, dot_prod_sim=True)]
         metrics += [utils.top_k_acc(k) if onehot_like else utils.nn_accuracy(emb_dev, dot_prod_sim=True, k=k) for k in args.top_k_acc]
+    elif head_by_default('mse', args.embedding == 'onehot', len(args.top_k_acc)):
+        loss = utils.SquaredDistanceHead(emb_dev)          # fused gather + squared distance + the metric's counts, one launch
+        metrics = [loss.accuracy()] + [loss.accuracy(k) for k in args.top_k_acc]
     else:
         loss = utils.SquaredDistanceLoss(emb_dev)          # fused gather + squared distance (se_sqdist_loss_fwd / bwd)
         metrics = [accuracy if args.embedding == 'onehot' else utils.nn_accuracy(emb_dev, dot_prod_sim=False)]

@@ -4,6 +4,7 @@ Every function here calls straight through the C ABI of libsehip.so on the curre
 come from include/sehip.h); PyTorch only provides device memory, streams and autograd plumbing.  Reference citations are into
 the cvjena/semantic-embeddings checkout.
 """
+import collections
 import ctypes
 import os
 
@@ -14,7 +15,7 @@ from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, MET
 
 __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
-    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
+    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "embed_head_forward", "embedding_head", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
     "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
     "adagrad_step_", "ADAGRAD_MAX_BLOCKS", "shortcut_add", "LAYOUT_NCHW", "LAYOUT_NHWC",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
@@ -397,6 +398,85 @@ def nn_accuracy(y_pred, labels, embedding, dot_prod_sim=False, k=1, want_scores=
     if want_best:
         out += (best,)
     return out if len(out) > 1 else acc
+
+
+EMBED_HEAD_MODES = {"cosine": 0, "sqdist": 1}
+EmbedHeadForward = collections.namedtuple("EmbedHeadForward", "loss_i xhat inv_norm dist_i loss_mean n_better n_within best scores")
+EmbeddingHead = collections.namedtuple("EmbeddingHead", "loss_i xhat n_better n_within best scores")
+
+
+def _embed_head_mode(mode):
+    if mode not in EMBED_HEAD_MODES:
+        raise SehipError("mode must be 'cosine' or 'sqdist', got %r" % (mode,))
+    return EMBED_HEAD_MODES[mode]
+
+
+def embed_head_forward(x, labels, embedding, mode="cosine", want_xhat=True, want_inv_norm=False, want_dist=False, want_mean=False,
+                       want_scores=False, want_best=False):
+    """``se_embed_head_fwd``: the loss of ``cosine_loss_forward`` (mode 'cosine') or ``sqdist_loss_forward`` (mode 'sqdist') and the
+    two counts of ``nn_accuracy`` on the same batch, in one launch and bit for bit: ``n_within`` classes score within 1e-6 of the
+    label's, ``n_better`` beyond it, so ``nn_accuracy(k)`` is ``(n_within >= 1) & (n_better < k)`` for every k.
+    Returns an ``EmbedHeadForward`` whose unwanted (or other-mode) fields are None."""
+    require_gpu(x, labels, embedding)
+    code = _embed_head_mode(mode)
+    B, D, C = _class_loss_shapes(x, labels, embedding)
+    dev = x.device
+
+    def f32(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+
+    def i32(*shape):
+        return torch.empty(shape, dtype=torch.int32, device=dev)
+
+    xhat = f32(B, D) if (code == 0 and want_xhat) else None
+    inv_norm = f32(B) if (code == 0 and want_inv_norm) else None
+    dist_i = f32(B) if (code == 1 and want_dist) else None
+    loss_mean = f32(1) if want_mean else None
+    loss_i, n_better, n_within = f32(B), i32(B), i32(B)
+    best = i32(B) if want_best else None
+    scores = f32(B, C) if want_scores else None
+    need = call("se_embed_head_workspace_bytes", code, B, D, C)
+    ws = torch.empty((need // 8,), dtype=torch.int64, device=dev) if need else None     # (fresh: the call may be captured in a HIP graph)
+    call("se_embed_head_fwd", code, x, _dtype_code(x), x.stride(0), labels, embedding, embedding.stride(0), B, D, C, xhat, D, inv_norm,
+         loss_i, dist_i, loss_mean, n_better, n_within, best, scores, C, ws, need)
+    return EmbedHeadForward(loss_i, xhat, inv_norm, dist_i, loss_mean, n_better, n_within, best, scores)
+
+
+class _EmbedHead(torch.autograd.Function):
+    """Per-sample loss of _CosineEmbeddingLoss / _SquaredDistanceLoss with the metric counts of the same batch as non-differentiable
+    by-products of the one forward launch; the backward is the siblings' (se_cosine_loss_bwd / se_sqdist_loss_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, labels, embedding, mode, want_xhat, want_scores, want_best):
+        _check_loss_inputs(labels, embedding, "embedding_head")
+        x = x if x.stride(-1) == 1 else x.contiguous()
+        out = embed_head_forward(x, labels, embedding, mode, want_xhat=want_xhat, want_scores=want_scores, want_best=want_best)
+        ctx.save_for_backward(x, labels, embedding)
+        ctx.mode = mode
+        extras = tuple(out.loss_i.new_empty(0) if t is None else t for t in (out.xhat, out.n_better, out.n_within, out.best, out.scores))
+        ctx.mark_non_differentiable(*extras)
+        return (out.loss_i,) + extras
+
+    @staticmethod
+    def backward(ctx, grad_loss_i, *_unused):
+        x, labels, embedding = ctx.saved_tensors
+        bwd = cosine_loss_backward if ctx.mode == "cosine" else sqdist_loss_backward
+        return bwd(x, labels, embedding, grad_loss_i.contiguous()), None, None, None, None, None, None
+
+
+def embedding_head(x, labels, embedding, mode="cosine", want_normalized=True, want_scores=False, want_best=False):
+    """The loss head of ``--loss inv_corr`` (mode 'cosine': ``cosine_embedding_loss`` on un-normalised features) or ``--loss mse``
+    (mode 'sqdist': ``squared_distance_loss``) together with the nearest-class metric of the batch, in one HIP launch forward.
+
+    Returns ``EmbeddingHead(loss_i, xhat, n_better, n_within, best, scores)``: ``loss_i`` [B] is differentiable with respect to ``x``
+    (the siblings' backward kernels); the rest is not.  ``xhat`` [B, D] are the normalised features (cosine head with
+    ``want_normalized``), ``n_better`` / ``n_within`` int32 [B] the metric's counts -- ``nn_accuracy(..., k)`` of the same batch is
+    ``(n_within >= 1) & (n_better < k)`` for every k --, ``best`` int32 [B] the nearest class and ``scores`` [B, C] the similarity /
+    distance matrix on request; fields not asked for are None.  Every value carries the bits of the separate calls."""
+    _embed_head_mode(mode)
+    want_xhat = bool(want_normalized) and mode == "cosine"
+    loss_i, xhat, n_better, n_within, best, scores = _EmbedHead.apply(x, labels, embedding, mode, want_xhat, bool(want_scores), bool(want_best))
+    return EmbeddingHead(loss_i, xhat if want_xhat else None, n_better, n_within, best if want_best else None, scores if want_scores else None)
 
 
 class _LabelEmbedLoss(torch.autograd.Function):

@@ -173,6 +173,81 @@ def nn_accuracy(embedding, dot_prod_sim=False, k=1):
     return metric
 
 
+class _HeadCounts(object):
+    """What an embedding head keeps of its last loss call: the two metric counts of the batch (``sehip.embedding_head``) and which
+    tensors they belong to.  ``accuracy(k)`` metrics read the counts when they are called on those very tensors -- the same labels
+    storage, the same prediction storage and shape, both unmodified since (tensor version) -- and run ``nn_accuracy`` on any others
+    (a metric called on its own, another batch, CPU tensors, gathered embeddings as ``y_true``): never wrong, only slower."""
+
+    _dot_prod_sim = False
+
+    @staticmethod
+    def _key(t):
+        return (t.data_ptr(), tuple(t.shape), t.dtype, t.device, t._version)
+
+    def _remember(self, y_true, metric_input, n_better, n_within):
+        # the tensors themselves are kept as well: their storage cannot be recycled for another batch while the counts stand
+        self._last = (y_true, metric_input, self._key(y_true), self._key(metric_input), n_better, n_within)
+
+    def _forget(self):
+        self._last = None
+
+    def counts_for(self, y_true, y_pred):
+        """(n_better, n_within) of the last loss call when (y_true, y_pred) are its tensors, else None."""
+        last = getattr(self, '_last', None)
+        if last is None or not (torch.is_tensor(y_true) and torch.is_tensor(y_pred)):
+            return None
+        if self._key(y_true) != last[2] or self._key(y_pred) != last[3]:
+            return None
+        return last[4], last[5]
+
+    def accuracy(self, k=1):
+        """``utils.nn_accuracy(embedding, dot_prod_sim, k)`` under the reference's name, served from the head's last launch."""
+        fallback = nn_accuracy(self.embedding, dot_prod_sim=self._dot_prod_sim, k=k)
+
+        def metric(y_true, y_pred):
+            counts = self.counts_for(y_true, y_pred)
+            if counts is None:
+                return fallback(y_true, y_pred)
+            n_better, n_within = counts
+            return ((n_within >= 1) & (n_better < max(int(k), 1))).float()
+
+        metric.name = fallback.name
+        metric.__name__ = fallback.__name__
+        return metric
+
+
+class CosineEmbeddingHead(_HeadCounts, CosineEmbeddingLoss):
+    """``CosineEmbeddingLoss`` whose forward launch also counts, per sample, the classes scoring within 1e-6 of the label's and beyond
+    it (``se_embed_head_fwd``): ``head.accuracy(k)`` is ``max_sim_acc`` / ``max_sim_acc<k>`` of the batch for every k without a
+    further launch.  Loss, ``last_normalized``, gradient and metric values carry the bits of the separate objects."""
+
+    _dot_prod_sim = True
+
+    def __call__(self, y_true, y_pred):
+        if not _is_labels(y_true):
+            raise ValueError('CosineEmbeddingLoss expects integer class labels as y_true')
+        out = sehip.embedding_head(y_pred, y_true, self.embedding, mode='cosine', want_normalized=True)
+        self.last_normalized = out.xhat
+        self._remember(y_true, out.xhat, out.n_better, out.n_within)
+        return out.loss_i
+
+
+class SquaredDistanceHead(_HeadCounts, SquaredDistanceLoss):
+    """``SquaredDistanceLoss`` with the counts of ``nn_accuracy`` from the same launch (see ``CosineEmbeddingHead``); the metrics are
+    defined on the network's output itself, ``head.accuracy(k)`` is ``nn_accuracy`` / ``nn_accuracy<k>``."""
+
+    _dot_prod_sim = False
+
+    def __call__(self, y_true, y_pred):
+        if _is_labels(y_true) and y_pred.is_cuda and y_pred.dim() == 2 and y_pred.stride(-1) == 1 and y_pred.dtype in (torch.float32, torch.bfloat16):
+            out = sehip.embedding_head(y_pred, y_true, self.embedding, mode='sqdist')
+            self._remember(y_true, y_pred, out.n_better, out.n_within)
+            return out.loss_i
+        self._forget()
+        return SquaredDistanceLoss.__call__(self, y_true, y_pred)
+
+
 def devise_ranking_loss(embedding, margin=0.1):
     """DeViSE ranking loss (utils.py:103-122): fused HIP kernel (MFMA contraction with the hinge, its row sums and the
     active mask in the epilogue; the mask feeds the backward contraction).  ``y_true``: gathered embeddings [B, D] (the

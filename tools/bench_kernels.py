@@ -70,7 +70,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -106,6 +106,8 @@ def main():
         return bench_qg(args)
     if args.what == "stream":
         return bench_stream()
+    if args.what == "head":
+        return bench_head()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -739,6 +741,82 @@ def bench_labelembed(reps=60, batch=20, steps=200):
         step = float(np.median(ms[name]))
         print("ResNet-110-fc %s step, batch 128, 100 classes, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d steps; %s), "
               "%.0f images/s" % (name, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
+
+
+def bench_head(reps=40, batch=20):
+    """Embedding heads (learn_image_embeddings.py --loss inv_corr / mse): se_embed_head_fwd -- loss and the nearest-class metric's counts
+    in one launch -- next to the sequence it replaces for the same outputs, se_cosine_loss_fwd (or se_sqdist_loss_fwd) plus 1, 2 and 3
+    se_nn_accuracy launches (no --top_k_acc, one k, two k), as calls on preallocated buffers, timed alternately in one process: per
+    shape `reps` windows of `batch` back-to-back calls each (HIP events around a window), median / 10th / 90th percentile of the
+    per-call time.  The head is timed with and without the xhat output (the training loop keeps it for feature dumps; the fused
+    contraction does not read it back).  The sequence's xhat always goes through memory: the metric reads it."""
+    from sehip._lib import call
+
+    def windows(fns):
+        for f in fns:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(reps):
+            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(batch):
+                    f()
+                b.record()
+                torch.cuda.synchronize()
+                ts[k].append(a.elapsed_time(b) / batch * 1e3)
+        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
+
+    print("embedding heads: one se_embed_head_fwd vs loss launch + n se_nn_accuracy launches; us per call, median (10th-90th percentile) of "
+          "%d windows of %d calls, candidates alternating" % (reps, batch))
+    for mode, mname in ((0, "cosine"), (1, "sqdist")):
+        for B, D, C in ((128, 100, 100), (128, 200, 200), (128, 555, 555), (128, 1000, 1000), (256, 1000, 1000)):
+            for dtype, dname in ((torch.float32, "f32"), (torch.bfloat16, "bf16")):
+                rng = np.random.default_rng(B + D + C)
+                x = torch.from_numpy(rng.standard_normal((B, D)).astype(np.float32)).cuda().to(dtype)
+                emb = torch.from_numpy(rng.standard_normal((C, D)).astype(np.float32)).cuda()
+                sehip.normalize_rows_(emb)
+                y = torch.from_numpy(rng.integers(0, C, B)).cuda()
+                code = 0 if dtype == torch.float32 else 1
+                f = lambda *s: torch.empty(s, dtype=torch.float32, device="cuda")
+                i = lambda *s: torch.empty(s, dtype=torch.int32, device="cuda")
+                xhat, loss_i, nb, nw = f(B, D), f(B), i(B), i(B)
+                xhat_s, loss_s, accs = f(B, D), f(B), [f(B) for _ in range(3)]
+                need = call("se_embed_head_workspace_bytes", mode, B, D, C)
+                ws = torch.empty(max(need // 8, 1), dtype=torch.int64, device="cuda")
+                need_s = call("se_nn_accuracy_workspace_bytes", B, C)
+                ws_s = torch.empty(max(need_s // 8, 1), dtype=torch.int64, device="cuda")
+
+                def head(with_xhat):
+                    call("se_embed_head_fwd", mode, x, code, D, y, emb, D, B, D, C, xhat if with_xhat else None, D, None, loss_i, None, None,
+                         nb, nw, None, None, C, ws, need)
+
+                def sequence(n):
+                    if mode == 0:
+                        call("se_cosine_loss_fwd", x, code, D, y, emb, D, B, D, C, xhat_s, D, None, loss_s, None)
+                        yp = xhat_s
+                    else:
+                        call("se_sqdist_loss_fwd", x, code, D, y, emb, D, B, D, C, loss_s, None, None)
+                        yp = x if dtype == torch.float32 else x.float()       # the Python path widens bf16 features before the metric
+                    for j in range(n):
+                        call("se_nn_accuracy", yp, D, y, emb, D, B, D, C, 1 - mode, (1, 5, 10)[j], accs[j], None, C, None, ws_s, need_s)
+
+                fns = [lambda: head(True), lambda: head(False)] + [lambda n=n: sequence(n) for n in (1, 2, 3)]
+                if mode == 1:
+                    fns = fns[:1] + fns[2:]
+                t = windows(fns)
+                same = torch.equal(loss_i.view(torch.int32), loss_s.view(torch.int32))
+                for j, k in enumerate((1, 5, 10)):
+                    same = same and torch.equal(((nw >= 1) & (nb < k)).float(), accs[j])
+                if mode == 0:
+                    same = same and torch.equal(xhat.view(torch.int32), xhat_s.view(torch.int32))
+                names = (["head", "head without xhat"] if mode == 0 else ["head"]) + ["loss + 1 metric", "loss + 2 metrics", "loss + 3 metrics"]
+                ref = t[0][0]
+                print("head %-6s %4d x %4d x %4d %-4s: " % (mname, B, D, C, dname) +
+                      "; ".join("%s %.1f (%.1f-%.1f)" % (nm, v[0], v[1], v[2]) for nm, v in zip(names, t)) +
+                      "; head vs 1 / 2 / 3 metrics: x%.2f x%.2f x%.2f; bits equal %s" % (t[-3][0] / ref, t[-2][0] / ref, t[-1][0] / ref, same))
 
 
 def bench_image(B=128, reps=20, stored=256):

@@ -43,6 +43,7 @@ qidx = torch.arange(1024, dtype=torch.int32, device="cuda")
 curves = sehip.hprec_reciprocal_curves(best_d, best_d)
 emb = dev(f32(C, 100)); sehip.normalize_rows_(emb)
 xb = dev(f32(4096, 100)); yb = dev(rng.integers(0, C, size=4096).astype(np.int64))
+emb_wide = dev(f32(1000, 100)); sehip.normalize_rows_(emb_wide)      # 32 class tiles: the embedding head cuts them into slices
 parts = torch.stack([torch.stack([sehip.topk_rows(pd_mid[:, i * 2500:(i + 1) * 2500].contiguous(), 251, col_offset=i * 2500)[j].view(torch.int32)
                                   for j in (0, 1)]) for i in range(8)])     # [8, 2, Q, k] packed lists
 
@@ -85,6 +86,8 @@ OPS = {
                                                                      ahp_len=0, want_ap=True, curves=curves),
     "cosine_loss fwd+bwd": lambda: (sehip.cosine_loss_forward(xb, yb, emb)[0], sehip.cosine_loss_backward(xb, yb, emb)),
     "nn_accuracy": lambda: sehip.nn_accuracy(xb, yb, emb, dot_prod_sim=True, k=5),
+    "embed_head cosine": lambda: sehip.embed_head_forward(xb, yb, emb, mode="cosine", want_best=True),
+    "embed_head sqdist, class slices": lambda: sehip.embed_head_forward(xb[:512], yb[:512], emb_wide, mode="sqdist", want_dist=True, want_best=True),
     "devise_ranking_loss": lambda: sehip.devise_ranking_loss(xb, yb, emb),
     "image_batch": lambda: sehip.image_batch(img_arena, img_t["src_off"], img_t["src_hw"], img_t["xmap"], img_t["xk"], img_t["ymap"], img_t["yk"],
                                              img_t["erase"], img_t["seed"], img_stats[0], img_stats[1]),
