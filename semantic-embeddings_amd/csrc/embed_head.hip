@@ -7,19 +7,19 @@
 // bit for bit, with the metric delivered as its two counts (n_better, n_within) so that every k is read off one contraction.
 //
 // Layout: a workgroup of four waves owns a strip of 32 samples and a slice of the class tiles.
-//   1. loss:   each wave reduces 8 of the strip's rows with the per-lane FMA chains and the wave tree of loss_kernels.hip (its own
-//              copy: the kernels there stay as they are).  The cosine head keeps the 32 inverse norms in LDS; the normalised
-//              features themselves are never read back: every operand chunk of the contraction is rebuilt from x as x * inv_norm,
-//              the very product xhat holds, while it is staged.  xhat goes to global memory only when the caller asks for it.
+//   1. loss:   each wave reduces 8 of the strip's rows with the row chains of loss_head.h, the ones the kernels of loss_kernels.hip
+//              call.  The cosine head keeps the 32 inverse norms in LDS; the normalised features themselves are never read back:
+//              every operand chunk of the contraction is rebuilt from x as x * inv_norm, the very product xhat holds, while it is
+//              staged.  xhat goes to global memory only when the caller asks for it.
 //   2. true:   the label's score per sample, with the arithmetic of the class-tile loop (k-ascending FMA chain; |e|^2 as even + odd
 //              sum), on operands staged through LDS with coalesced loads -- the sibling walks two global rows per lane here.
 //   3. tiles:  the four waves take four class tiles at a time on v_mfma_f32_32x32x2_f32, sharing ONE staged feature chunk; each wave
-//              stages its own class chunk.  Counts and the best class meet in LDS (integer atomics), and, when the class set is cut
-//              into slices, in the workspace; the last slice of a strip to finish writes the strip's results (ticket counter).
+//              stages its own class chunk.  A finished tile goes through the metric epilogue of loss_head.h (se_nn_accuracy's).
+//              Counts and the best class meet in LDS (integer atomics), and, when the class set is cut into slices, in the
+//              workspace; the last slice of a strip to finish writes the strip's results (ticket counter).
 // No floating-point atomics; counts are integer sums and the best class is an ordered-word maximum, so the result does not depend
 // on the launch geometry or on the order in which workgroups finish.
-#include "se_common.h"
-#include "tile32.h"
+#include "loss_head.h"
 
 namespace se {
 namespace head {
@@ -29,72 +29,6 @@ using tile32::f32x16;
 constexpr int THREADS = 256, WAVES = 4;
 constexpr int ROWS_PER_WAVE = 32 / WAVES;
 constexpr int BK = tile32::BK, LD = tile32::LD;
-constexpr float L2NORM_EPS = 1e-12f;    // tf.nn.l2_normalize default epsilon (TF 1.x), as in loss_kernels.hip
-constexpr int NO_CLASS = 0x7FFFFFFF;
-
-// ss = sum x^2, dt = sum x * t over one row: the lane partition, FMA order and wave tree of loss_kernels.hip's row_reduce
-template <bool BF16>
-__device__ __forceinline__ void row_reduce(const void *xrow, const float *trow, int64_t D, bool vec_ok, float &ss, float &dt)
-{
-    const int lane = lane_id();
-    float s = 0.f, t = 0.f;
-    if (vec_ok) {
-        if constexpr (BF16) {
-            const uint4 *xv = (const uint4 *)xrow;  // 8 bf16 per 16 B
-            const float4 *tv = (const float4 *)trow;
-            for (int64_t i = lane; i < D / 8; i += WAVE) {
-                uint4 p = xv[i];
-                float4 t0 = tv[2 * i], t1 = tv[2 * i + 1];
-                float xs[8];
-                unpack_bf16x8(p, xs);
-                float ts[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    s = fmaf(xs[j], xs[j], s);
-                    t = fmaf(xs[j], ts[j], t);
-                }
-            }
-        } else {
-            const float4 *xv = (const float4 *)xrow;
-            const float4 *tv = (const float4 *)trow;
-            for (int64_t i = lane; i < D / 4; i += WAVE) {
-                float4 p = xv[i], q = tv[i];
-                s = fmaf(p.x, p.x, s); s = fmaf(p.y, p.y, s); s = fmaf(p.z, p.z, s); s = fmaf(p.w, p.w, s);
-                t = fmaf(p.x, q.x, t); t = fmaf(p.y, q.y, t); t = fmaf(p.z, q.z, t); t = fmaf(p.w, q.w, t);
-            }
-        }
-    } else {
-        for (int64_t i = lane; i < D; i += WAVE) {
-            float p = ld_elem<BF16>(xrow, i);
-            s = fmaf(p, p, s);
-            t = fmaf(p, trow[i], t);
-        }
-    }
-    ss = wave_sum(s);
-    dt = wave_sum(t);
-}
-
-// sum (x - t)^2 over one row, as sqdist_loss_fwd_kernel forms it
-template <bool BF16>
-__device__ __forceinline__ float row_sqdist(const void *xrow, const float *trow, int64_t D, bool vec_ok)
-{
-    const int lane = lane_id();
-    float s = 0.f;
-    if (vec_ok && !BF16) {
-        const float4 *xv = (const float4 *)xrow, *tv = (const float4 *)trow;
-        for (int64_t i = lane; i < D / 4; i += WAVE) {
-            const float4 p = xv[i], q = tv[i];
-            const float a = p.x - q.x, b = p.y - q.y, c = p.z - q.z, e = p.w - q.w;
-            s = fmaf(a, a, s); s = fmaf(b, b, s); s = fmaf(c, c, s); s = fmaf(e, e, s);
-        }
-    } else {
-        for (int64_t i = lane; i < D; i += WAVE) {
-            const float a = ld_elem<BF16>(xrow, i) - trow[i];
-            s = fmaf(a, a, s);
-        }
-    }
-    return wave_sum(s);
-}
 
 // The strip's feature chunk (32 rows x 64 k) -> LDS by all 256 threads, two (row, 4 consecutive k) items each: the cosine head
 // scales every element by its row's inverse norm (the product xhat holds), the distance head widens it.  Loads are unconditional
@@ -146,7 +80,9 @@ __device__ __forceinline__ void stage_x(float *lds, const void *x, int64_t ldx, 
     }
 }
 
-// the label rows emb[y[r]] of the strip, same chunk, same layout, by all 256 threads (rows outside the batch: zero)
+// the label rows emb[y[r]] of the strip, same chunk, same layout, by all 256 threads (rows outside the batch: zero).
+// This is tile32::load_rows / put_rows spread over 256 threads, kept written out: as a tile32::stage_rows<256> call with a row-pointer
+// functor the squared-distance head measured up to 2.3 us (1.6 %) above the parent's range (profiles/loss_head_dedup.txt section 3).
 __device__ __forceinline__ void stage_label_rows(float *lds, const float *emb, int64_t lde, const int *sY, int64_t k0, int64_t D, bool vec)
 {
     float v[2][4];
@@ -180,17 +116,6 @@ __device__ __forceinline__ void stage_label_rows(float *lds, const float *emb, i
 
 // element k of a staged row (even k in [0, 32), odd k in [32, 64))
 __device__ __forceinline__ float staged(const float *row, int k) { return row[(k & 1) * (BK / 2) + (k >> 1)]; }
-
-// best class of a set as one ordered word: score (larger word = better), then the LOWER class index (nn_accuracy_kernel's word)
-template <int MODE>
-__device__ __forceinline__ unsigned long long best_word(float v, int c)
-{
-    if (v == 0.f) v = 0.f;                                     // -0 ties with +0
-    uint32_t u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);            // ascending with the value
-    if (MODE == 1) u = ~u;                                     // distances: smaller is better
-    return ((unsigned long long)u << 32) | (uint32_t)(NO_CLASS - c);
-}
 
 template <int MODE, bool BF16>
 __global__ __launch_bounds__(THREADS) void embed_head_kernel(
@@ -239,19 +164,7 @@ __global__ __launch_bounds__(THREADS) void embed_head_kernel(
                             if (inv_norm) inv_norm[row] = inv;
                             loss_i[row] = 1.0f - dt * inv;
                         }
-                        if (xhat) {
-                            float *orow = xhat + row * ldxhat;
-                            if (loss_vec && !BF16) {
-                                const float4 *xv = (const float4 *)xrow;
-                                float4 *ov = (float4 *)orow;
-                                for (int64_t i = lane; i < D / 4; i += WAVE) {
-                                    float4 p = xv[i];
-                                    ov[i] = make_float4(p.x * inv, p.y * inv, p.z * inv, p.w * inv);
-                                }
-                            } else {
-                                for (int64_t i = lane; i < D; i += WAVE) orow[i] = ld_elem<BF16>(xrow, i) * inv;
-                            }
-                        }
+                        if (xhat) write_xhat_row<BF16>(xrow, xhat + row * ldxhat, D, loss_vec != 0, inv);
                     }
                 } else {
                     const float s = row_sqdist<BF16>(xrow, trow, D, loss_vec != 0);
@@ -300,15 +213,10 @@ __global__ __launch_bounds__(THREADS) void embed_head_kernel(
     }
 
     // ---- 3. class tiles: four at a time, one per wave, on one shared feature chunk
-    int n_better[16], n_within[16];
-    float best_v[16];
-    int best_c[16];
+    constexpr bool DOT = MODE == 0;
+    metric::Tally tally[16];
 #pragma unroll
-    for (int r = 0; r < 16; r++) {
-        n_better[r] = 0; n_within[r] = 0;
-        best_v[r] = MODE == 0 ? -INFINITY : INFINITY;
-        best_c[r] = NO_CLASS;
-    }
+    for (int r = 0; r < 16; r++) tally[r] = metric::empty_tally(DOT);
 
     const int64_t c_beg = (int64_t)blockIdx.y * tiles_per_block * 32;
     const int64_t c_end = (c_beg + (int64_t)tiles_per_block * 32 < C) ? c_beg + (int64_t)tiles_per_block * 32 : C;
@@ -336,52 +244,27 @@ __global__ __launch_bounds__(THREADS) void embed_head_kernel(
                 if (s + 1 < steps) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
                 if (s + 2 < steps) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
                 if (s + 3 < steps) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
-                if (MODE == 1) {
-                    cn = fmaf(b4.x, b4.x, cn);
-                    if (s + 1 < steps) cn = fmaf(b4.y, b4.y, cn);
-                    if (s + 2 < steps) cn = fmaf(b4.z, b4.z, cn);
-                    if (s + 3 < steps) cn = fmaf(b4.w, b4.w, cn);
-                }
+                if (!DOT) cn = metric::class_norm_steps(cn, b4, s, steps);
             }
         }
         if (!active) continue;
-        if (MODE == 1) cn += __shfl_xor(cn, 32, 64);          // both halves hold even + odd (the sum commutes)
-        const int64_t c = c0 + col;
+        if (!DOT) cn += __shfl_xor(cn, 32, 64);          // both halves hold even + odd (the sum commutes)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int lr = tile32::acc_row(r, hi);
-            float sc = acc[r];
-            if (MODE == 1) sc = (sPn[lr] + cn) - 2.0f * sc;
-            const bool valid = (c < C) && (row0 + lr < B);
-            if (valid) {
-                if (scores) scores[(row0 + lr) * lds_ + c] = sc;
-                const float diff = MODE == 0 ? (sc - sTrue[lr]) : (sTrue[lr] - sc);  // > 0: better than true
-                if (fabsf(diff) < 1e-6f) n_within[r]++;
-                else if (diff >= 1e-6f) n_better[r]++;
-                const bool better = MODE == 0 ? (sc > best_v[r]) : (sc < best_v[r]);
-                if (better) { best_v[r] = sc; best_c[r] = (int)c; }
-            }
+            metric::update(tally[r], DOT, acc[r], sPn, cn, sTrue, lr, row0 + lr, B, c0 + col, C, scores, lds_);
         }
     }
 
     // reduce over the 32 lanes (classes) that share `hi`, then over the four waves in LDS
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-#pragma unroll
-        for (int off = 1; off < 32; off <<= 1) {
-            n_better[r] += __shfl_xor(n_better[r], off, 64);
-            n_within[r] += __shfl_xor(n_within[r], off, 64);
-            const float ov = __shfl_xor(best_v[r], off, 64);
-            const int oc = __shfl_xor(best_c[r], off, 64);
-            const bool take = MODE == 0 ? (ov > best_v[r] || (ov == best_v[r] && oc < best_c[r]))
-                                        : (ov < best_v[r] || (ov == best_v[r] && oc < best_c[r]));
-            if (take) { best_v[r] = ov; best_c[r] = oc; }
-        }
+        metric::reduce32(tally[r], DOT);
         const int lr = tile32::acc_row(r, hi);
         if (col == 0) {
-            atomicAdd(&sCnt[2 * lr], n_better[r]);
-            atomicAdd(&sCnt[2 * lr + 1], n_within[r]);
-            if (best_c[r] != NO_CLASS) atomicMax(&sBest[lr], best_word<MODE>(best_v[r], best_c[r]));
+            atomicAdd(&sCnt[2 * lr], tally[r].n_better);
+            atomicAdd(&sCnt[2 * lr + 1], tally[r].n_within);
+            if (tally[r].best_c != metric::NO_CLASS) atomicMax(&sBest[lr], metric::best_word(tally[r].best_v, tally[r].best_c, DOT));
         }
     }
     wg_barrier();
@@ -392,7 +275,7 @@ __global__ __launch_bounds__(THREADS) void embed_head_kernel(
         if (mine) {
             n_better_out[row] = sCnt[2 * tid];
             n_within_out[row] = sCnt[2 * tid + 1];
-            if (best_out) best_out[row] = NO_CLASS - (int32_t)(uint32_t)(sBest[tid] & 0xFFFFFFFFull);
+            if (best_out) best_out[row] = metric::best_class(sBest[tid]);
         }
         return;
     }
@@ -414,7 +297,7 @@ __global__ __launch_bounds__(THREADS) void embed_head_kernel(
     if (mine) {
         n_better_out[row] = (int32_t)atomicAdd(&part_cnt[2 * row], 0u);          // atomic reads: the other slices' sums live in L2
         n_within_out[row] = (int32_t)atomicAdd(&part_cnt[2 * row + 1], 0u);
-        if (best_out) best_out[row] = NO_CLASS - (int32_t)(uint32_t)(atomicMax(&part_best[row], 0ull) & 0xFFFFFFFFull);
+        if (best_out) best_out[row] = metric::best_class(atomicMax(&part_best[row], 0ull));
     }
 }
 
@@ -442,7 +325,7 @@ extern "C" int64_t se_embed_head_workspace_bytes(int mode, int64_t B, int64_t D,
     if (B <= 0 || C <= 0) return 0;
     if ((int64_t)head::tiles_per_block(B, C) * 32 >= C) return 0;
     const int64_t strips = (B + 31) / 32;
-    return B * 16 + (strips * 4 + 7) / 8 * 8;      // per sample: one ordered word + two counters; per strip: one ticket
+    return metric::workspace_bytes(B, strips);     // per strip: one ticket
 }
 
 extern "C" int se_embed_head_fwd(int mode, const void *x, int x_dtype, int64_t ldx, const int64_t *labels, const float *emb, int64_t lde,
@@ -464,28 +347,18 @@ extern "C" int se_embed_head_fwd(int mode, const void *x, int x_dtype, int64_t l
         return fail(SE_ERR_INVALID, "se_embed_head_fwd: needs %lld bytes of 8-byte aligned workspace (se_embed_head_workspace_bytes)", (long long)need);
     hipStream_t s = (hipStream_t)stream;
     const bool bf = x_dtype == SE_DTYPE_BF16;
-    // the 16-byte paths of the loss rows: the siblings' own predicates (they decide the summation order)
-    int loss_vec;
-    if (mode == 0) {
-        const int vq = bf ? 8 : 4;
-        loss_vec = (D % vq == 0) && (ldx % vq == 0) && (lde % 4 == 0) && aligned16(x) && aligned16(emb) &&
-                   (!xhat || ((ldxhat % 4 == 0) && aligned16(xhat)));
-    } else {
-        loss_vec = !bf && (D % 4 == 0) && (ldx % 4 == 0) && (lde % 4 == 0) && aligned16(x) && aligned16(emb);
-    }
+    const int loss_vec = mode == 0 ? cosine_rows_vec16(x, x_dtype, ldx, emb, lde, D, xhat, ldxhat) : sqdist_rows_vec16(x, x_dtype, ldx, emb, lde, D);
     // staging: four consecutive k per load (any path gives the same values)
     const int x_vec = ((ldx | D) & 3) == 0 && ((((uintptr_t)x) & (bf ? 7 : 15)) == 0);
     const int e_vec = ((lde | D) & 3) == 0 && aligned16(emb);
     const int tpb = head::tiles_per_block(B, C);
     const int64_t strips = (B + 31) / 32, slices = ((C + 31) / 32 + tpb - 1) / tpb;
-    unsigned long long *part_best = (unsigned long long *)workspace;
-    uint32_t *part_cnt = need > 0 ? (uint32_t *)((char *)workspace + B * 8) : nullptr;
-    uint32_t *ticket = need > 0 ? (uint32_t *)((char *)workspace + B * 16) : nullptr;
+    const metric::Workspace ws = metric::workspace(workspace, B, need > 0, true);
     if (need > 0) SE_HIP_CHECK(hipMemsetAsync(workspace, 0, (size_t)need, s));
     dispatch_bools(mode == 1, bf, [&](auto M, auto XB) {
         hipLaunchKernelGGL((head::embed_head_kernel<M() ? 1 : 0, XB()>), dim3((unsigned)strips, (unsigned)slices), dim3(head::THREADS), 0, s,
                            x, ldx, labels, emb, lde, B, D, C, xhat, ldxhat, inv_norm, loss_i, dist_i, n_better, n_within, best, scores, lds,
-                           loss_vec, x_vec, e_vec, tpb, part_best, part_cnt, ticket);
+                           loss_vec, x_vec, e_vec, tpb, ws.part_best, ws.part_cnt, ws.ticket);
     });
     SE_LAUNCH_CHECK();
     if (loss_mean) {

@@ -20,30 +20,25 @@
 // The table form (se_labelembed_table_loss_fwd / _bwd) is the same pair of kernel bodies reading the `tar` row of sample i straight
 // from the learned [C, C] label-embedding table (row clamp(targets[i])) instead of a materialised [B, C] gather, plus the gradient
 // of that table: d_table[k] = sum over {i : clamp(targets[i]) = k} of the d_tar row of sample i, added from +0 in INCREASING i.
-// Layout of that reduction (center_loss.hip's): one wave owns 256 columns of one table row k, scans the labels 64 at a time with a
-// ballot and walks the set bits in ascending order; softmax(table[k]) of its columns is evaluated once, at the first matched row,
-// and stays in registers.  No hand-off between waves, no atomics, no workspace, no LDS.
-#include "se_common.h"
+// Layout of that reduction: one wave owns 256 columns of one table row k and walks its class's batch rows with the fixed-order scan
+// of class_scan.h (the order and constants of the centroid gradient of center_loss.hip); softmax(table[k]) is evaluated once, at the
+// first matched row, and stays in registers.
+#include "class_scan.h"
 
 namespace se {
 
 constexpr int LE_ROWS_PER_BLOCK = 4;   // 4 waves = 256 threads
 constexpr float KERAS_EPS = 1e-7f;     // keras.backend.epsilon(): probabilities are clipped to [eps, 1 - eps]
 constexpr int LE_AUX = 12;             // per-sample record kept for the backward pass
-constexpr int LT_WAVES = 4;            // table gradient: (table row, column block) pairs per 256-thread workgroup, one per wave
-constexpr int LT_COLS = 4;             // columns per lane: a wave owns 256 columns of its row
-constexpr int LT_CHUNKS = 4;           // 64-label chunks whose loads are in flight together
-constexpr int LT_ROWS = 4;             // matched batch rows whose out2 loads are in flight together
+using class_scan::WAVES, class_scan::COLS, class_scan::ROWS;    // table gradient: a wave owns 256 columns of one table row
 
 // aux[i] = { lse(out1), lse(out2), lse(tar), lse(out2 / tau), mask, A_i = -sum tau2 * log_softmax(tar), base_i, p2_y,
 //            S1 = sum_j clip(p1_j), R1 = sum_j 1{eps < p1_j < 1 - eps} p1_j, S2, R2 }
 // TABLE: `tar` is the [C, C] table and the row of a sample is the row of its (clamped) label; otherwise the [B, C] gather.
 template <bool TABLE>
-__global__ __launch_bounds__(256) void labelembed_fwd_kernel(const float *__restrict__ out1, int64_t ld1,
-                                                             const float *__restrict__ out2, int64_t ld2,
-                                                             const float *__restrict__ tar, int64_t ldt,
-                                                             const int64_t *__restrict__ targets, int64_t B, int64_t C,
-                                                             float tau, float alpha, float beta, float *__restrict__ aux)
+__global__ __launch_bounds__(256) void labelembed_fwd_kernel(
+    const float *__restrict__ out1, int64_t ld1, const float *__restrict__ out2, int64_t ld2, const float *__restrict__ tar, int64_t ldt,
+    const int64_t *__restrict__ targets, int64_t B, int64_t C, float tau, float alpha, float beta, float *__restrict__ aux)
 {
     const int wave = threadIdx.x >> 6, lane = lane_id();
     const float inv_tau = 1.0f / tau;
@@ -164,88 +159,71 @@ __global__ __launch_bounds__(256) void labelembed_bwd_kernel(const float *__rest
 // d_table[k, c] = sum over {i : clamp(targets[i]) = k}, in increasing i from +0, of wt_i (softmax(table[k])_c - softmax(out2_i / tau)_c):
 // the value labelembed_bwd_kernel writes to d_tar[i, c], by the same operations (-ffp-contract=off: no fma).  Rows with wt_i == 0
 // (mask_i = 0: most rows early in training) are skipped; they would add +-0 to a sum that starts at +0.
-__global__ __launch_bounds__(64 * LT_WAVES) void labelembed_table_grad_kernel(const float *__restrict__ out2, int64_t ld2,
-                                                                              const float *__restrict__ table, int64_t ldtab,
-                                                                              const int64_t *__restrict__ targets,
-                                                                              const float *__restrict__ grad_loss_i, float grad_scale,
-                                                                              int64_t B, int64_t C, float tau, const float *__restrict__ aux,
-                                                                              float *__restrict__ dtab, int64_t lddtab)
+__global__ __launch_bounds__(64 * WAVES) void labelembed_table_grad_kernel(
+    const float *__restrict__ out2, int64_t ld2, const float *__restrict__ table, int64_t ldtab, const int64_t *__restrict__ targets,
+    const float *__restrict__ grad_loss_i, float grad_scale, int64_t B, int64_t C, float tau, const float *__restrict__ aux,
+    float *__restrict__ dtab, int64_t lddtab)
 {
     const int lane = lane_id();
-    const int64_t k = (int64_t)blockIdx.x * LT_WAVES + (threadIdx.x >> 6);      // wave-uniform
+    const int64_t k = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);      // wave-uniform
     if (k >= C) return;
-    const int64_t c0 = (int64_t)blockIdx.y * (64 * LT_COLS);
+    const int64_t c0 = (int64_t)blockIdx.y * (64 * COLS);
     const float inv_tau = 1.0f / tau, sc = B > 0 ? aux[B * LE_AUX] : 0.f;
-    float acc[LT_COLS], smt[LT_COLS];
+    float acc[COLS], smt[COLS];
 #pragma unroll
-    for (int r = 0; r < LT_COLS; r++) acc[r] = smt[r] = 0.f;
+    for (int r = 0; r < COLS; r++) acc[r] = smt[r] = 0.f;
     bool have_smt = false;
-    for (int64_t i0 = 0; i0 < B; i0 += 64 * LT_CHUNKS) {
-        int64_t lab[LT_CHUNKS];
-#pragma unroll
-        for (int j = 0; j < LT_CHUNKS; j++) {
-            const int64_t i = i0 + j * 64 + lane;
-            lab[j] = i < B ? targets[i] : -1;
-        }
-#pragma unroll
-        for (int j = 0; j < LT_CHUNKS; j++) {
-            const int64_t i = i0 + j * 64 + lane;
-            const int64_t y = clamp_label(lab[j], C);
-            float wt = 0.f, lset = 0.f, lse2t = 0.f;                            // this lane's row, if it is one of class k
-            if (i < B && y == k) {
+    float wt = 0.f, lset = 0.f, lse2t = 0.f;                                                   // this lane's row of the current chunk, if it is one of class k
+    class_scan::scan(
+        targets, B, C, k,
+        [&](int64_t i, bool mine) {
+            wt = 0.f; lset = 0.f; lse2t = 0.f;
+            if (mine) {
                 const float *r = aux + i * LE_AUX;
                 const float g = grad_loss_i ? grad_loss_i[i] : grad_scale;
                 wt = g * r[4] * sc;
                 lset = r[2];
                 lse2t = r[3];
             }
-            uint64_t hit = __ballot(i < B && y == k && wt != 0.f);
-            if (hit && !have_smt) {                                             // softmax(table[k]): once per class, kept in registers
-                const float l = __shfl(lset, __builtin_ctzll(hit), 64);         // every row of the class holds the same lse(table[k])
+            return mine && wt != 0.f;
+        },
+        [&](int first) {
+            if (have_smt) return;                                               // softmax(table[k]): once per class, kept in registers
+            const float l = __shfl(lset, first, 64);                            // every row of the class holds the same lse(table[k])
 #pragma unroll
-                for (int r = 0; r < LT_COLS; r++) {
+            for (int r = 0; r < COLS; r++) {
+                const int64_t c = c0 + r * 64 + lane;
+                smt[r] = c < C ? expf(table[k * ldtab + c] - l) : 0.f;
+            }
+            have_smt = true;
+        },
+        [&](const class_scan::Group &g) {
+            float w[ROWS], l2[ROWS], v[ROWS][COLS];
+#pragma unroll
+            for (int q = 0; q < ROWS; q++) {
+                w[q] = __shfl(wt, g.lane[q], 64);
+                l2[q] = __shfl(lse2t, g.lane[q], 64);
+                const float *o2 = out2 + g.row[q] * ld2;
+#pragma unroll
+                for (int r = 0; r < COLS; r++) {
                     const int64_t c = c0 + r * 64 + lane;
-                    smt[r] = c < C ? expf(table[k * ldtab + c] - l) : 0.f;
+                    v[q][r] = c < C ? o2[c] : 0.f;
                 }
-                have_smt = true;
             }
-            while (hit) {                                   // matched rows in ascending order, LT_ROWS of them loaded together
-                int src[LT_ROWS];
-                int n = 0;
 #pragma unroll
-                for (int q = 0; q < LT_ROWS; q++) {         // slots past the last match load the chunk's first row (< B) unused
-                    src[q] = hit ? __builtin_ctzll(hit) : 0;
-                    n += hit ? 1 : 0;
-                    hit &= hit - 1;
-                }
-                float w[LT_ROWS], l2[LT_ROWS], v[LT_ROWS][LT_COLS];
+            for (int q = 0; q < ROWS; q++) {
+                if (q < g.n) {
 #pragma unroll
-                for (int q = 0; q < LT_ROWS; q++) {
-                    w[q] = __shfl(wt, src[q], 64);
-                    l2[q] = __shfl(lse2t, src[q], 64);
-                    const float *o2 = out2 + (i0 + j * 64 + src[q]) * ld2;
-#pragma unroll
-                    for (int r = 0; r < LT_COLS; r++) {
-                        const int64_t c = c0 + r * 64 + lane;
-                        v[q][r] = c < C ? o2[c] : 0.f;
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < LT_ROWS; q++) {
-                    if (q < n) {
-#pragma unroll
-                        for (int r = 0; r < LT_COLS; r++) {
-                            const float sm2t = expf(v[q][r] * inv_tau - l2[q]);
-                            const float p = w[q] * (smt[r] - sm2t);
-                            acc[r] = acc[r] + p;
-                        }
+                    for (int r = 0; r < COLS; r++) {
+                        const float sm2t = expf(v[q][r] * inv_tau - l2[q]);
+                        const float p = w[q] * (smt[r] - sm2t);
+                        acc[r] = acc[r] + p;
                     }
                 }
             }
-        }
-    }
+        });
 #pragma unroll
-    for (int r = 0; r < LT_COLS; r++) {
+    for (int r = 0; r < COLS; r++) {
         const int64_t c = c0 + r * 64 + lane;
         if (c < C) dtab[k * lddtab + c] = acc[r];
     }
@@ -263,22 +241,63 @@ static int le_grid(int64_t B)
 
 extern "C" int64_t se_labelembed_aux_floats(int64_t B) { return B > 0 ? B * LE_AUX + 4 : 0; }
 
-extern "C" int se_labelembed_loss_fwd(const float *out1, int64_t ld1, const float *out2, int64_t ld2, const float *tar,
-                                      int64_t ldt, const int64_t *targets, int64_t B, int64_t C, float tau, float alpha,
-                                      float beta, float *loss_i, float *aux, se_stream_t stream)
+// The plain and the table entry points differ in where a sample's `tar` row lives (TABLE) and, backwards, in a few checks and in the
+// table's own gradient; `who` names the entry point in the error texts.
+template <bool TABLE>
+static int labelembed_fwd(const char *who, const float *out1, int64_t ld1, const float *out2, int64_t ld2, const float *tar, int64_t ldt,
+                          const int64_t *targets, int64_t B, int64_t C, float tau, float alpha, float beta, float *loss_i, float *aux,
+                          se_stream_t stream)
 {
-    if (B < 0 || C <= 0) return fail(SE_ERR_INVALID, "se_labelembed_loss_fwd: bad shape B=%lld C=%lld", (long long)B, (long long)C);
+    if (B < 0 || C <= 0) return fail(SE_ERR_INVALID, "%s: bad shape B=%lld C=%lld", who, (long long)B, (long long)C);
     if (B == 0) return SE_OK;
-    if (!out1 || !out2 || !tar || !targets || !loss_i || !aux) return fail(SE_ERR_INVALID, "se_labelembed_loss_fwd: null pointer");
-    if (ld1 < C || ld2 < C || ldt < C) return fail(SE_ERR_INVALID, "se_labelembed_loss_fwd: leading dimension too small");
-    if (!(tau > 0.f)) return fail(SE_ERR_INVALID, "se_labelembed_loss_fwd: tau must be positive");
+    if (!out1 || !out2 || !tar || !targets || !loss_i || !aux) return fail(SE_ERR_INVALID, "%s: null pointer", who);
+    if (ld1 < C || ld2 < C || ldt < C) return fail(SE_ERR_INVALID, "%s: leading dimension too small", who);
+    if (!(tau > 0.f)) return fail(SE_ERR_INVALID, "%s: tau must be positive", who);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(labelembed_fwd_kernel<false>, dim3(le_grid(B)), dim3(256), 0, s, out1, ld1, out2, ld2, tar, ldt, targets, B, C, tau,
+    hipLaunchKernelGGL(labelembed_fwd_kernel<TABLE>, dim3(le_grid(B)), dim3(256), 0, s, out1, ld1, out2, ld2, tar, ldt, targets, B, C, tau,
                        alpha, beta, aux);
     SE_LAUNCH_CHECK();
     hipLaunchKernelGGL(labelembed_finish_kernel, dim3(1), dim3(256), 0, s, aux, B, loss_i, aux + B * LE_AUX);
     SE_LAUNCH_CHECK();
     return SE_OK;
+}
+
+// d_tar: the [B, C] gradient of the gather, or (TABLE) the [C, C] gradient of the table.  The plain form has nothing to write at
+// B == 0 and never looked at tau or the input pitches; the table form writes every row of d_tar at any B (all +0 at B == 0).
+template <bool TABLE>
+static int labelembed_bwd(const char *who, const float *out1, int64_t ld1, const float *out2, int64_t ld2, const float *tar, int64_t ldt,
+                          const int64_t *targets, const float *grad_loss_i, float grad_scale, int64_t B, int64_t C, float tau, float alpha,
+                          float beta, const float *aux, float *d_out1, int64_t ldd1, float *d_out2, int64_t ldd2, float *d_tar, int64_t lddt,
+                          se_stream_t stream)
+{
+    if (B < 0 || C <= 0) return fail(SE_ERR_INVALID, "%s: bad shape B=%lld C=%lld", who, (long long)B, (long long)C);
+    if (!TABLE && B == 0) return SE_OK;
+    if (B > 0 && (!out1 || !out2 || !tar || !targets || !aux)) return fail(SE_ERR_INVALID, "%s: null pointer", who);
+    if (TABLE && B > 0 && (ld1 < C || ld2 < C || ldt < C)) return fail(SE_ERR_INVALID, "%s: leading dimension too small", who);
+    if ((d_out1 && ldd1 < C) || (d_out2 && ldd2 < C) || (d_tar && lddt < C)) return fail(SE_ERR_INVALID, "%s: leading dimension too small", who);
+    if (TABLE && !(tau > 0.f)) return fail(SE_ERR_INVALID, "%s: tau must be positive", who);
+    hipStream_t s = (hipStream_t)stream;
+    if (B > 0 && (!TABLE || d_out1 || d_out2)) {
+        hipLaunchKernelGGL(labelembed_bwd_kernel<TABLE>, dim3(le_grid(B)), dim3(256), 0, s, out1, ld1, out2, ld2, tar, ldt, targets, grad_loss_i,
+                           grad_scale, B, C, tau, alpha, beta, aux, aux + B * LE_AUX, d_out1, ldd1, d_out2, ldd2,
+                           TABLE ? (float *)nullptr : d_tar, TABLE ? (int64_t)0 : lddt);
+        SE_LAUNCH_CHECK();
+    }
+    if (TABLE && d_tar) {
+        const int64_t bx = (C + WAVES - 1) / WAVES, by = (C + 64 * COLS - 1) / (64 * COLS);
+        if (bx > 0x7FFFFFFF || by > 65535) return fail(SE_ERR_UNSUPPORTED, "%s: C too large", who);
+        hipLaunchKernelGGL(labelembed_table_grad_kernel, dim3((unsigned)bx, (unsigned)by), dim3(64 * WAVES), 0, s, out2, ld2, tar, ldt,
+                           targets, grad_loss_i, grad_scale, B, C, tau, aux, d_tar, lddt);
+        SE_LAUNCH_CHECK();
+    }
+    return SE_OK;
+}
+
+extern "C" int se_labelembed_loss_fwd(const float *out1, int64_t ld1, const float *out2, int64_t ld2, const float *tar,
+                                      int64_t ldt, const int64_t *targets, int64_t B, int64_t C, float tau, float alpha,
+                                      float beta, float *loss_i, float *aux, se_stream_t stream)
+{
+    return labelembed_fwd<false>("se_labelembed_loss_fwd", out1, ld1, out2, ld2, tar, ldt, targets, B, C, tau, alpha, beta, loss_i, aux, stream);
 }
 
 extern "C" int se_labelembed_loss_bwd(const float *out1, int64_t ld1, const float *out2, int64_t ld2, const float *tar,
@@ -287,33 +306,16 @@ extern "C" int se_labelembed_loss_bwd(const float *out1, int64_t ld1, const floa
                                       float *d_out1, int64_t ldd1, float *d_out2, int64_t ldd2, float *d_tar, int64_t lddt,
                                       se_stream_t stream)
 {
-    if (B < 0 || C <= 0) return fail(SE_ERR_INVALID, "se_labelembed_loss_bwd: bad shape B=%lld C=%lld", (long long)B, (long long)C);
-    if (B == 0) return SE_OK;
-    if (!out1 || !out2 || !tar || !targets || !aux) return fail(SE_ERR_INVALID, "se_labelembed_loss_bwd: null pointer");
-    if ((d_out1 && ldd1 < C) || (d_out2 && ldd2 < C) || (d_tar && lddt < C)) return fail(SE_ERR_INVALID, "se_labelembed_loss_bwd: leading dimension too small");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(labelembed_bwd_kernel<false>, dim3(le_grid(B)), dim3(256), 0, s, out1, ld1, out2, ld2, tar, ldt, targets, grad_loss_i,
-                       grad_scale, B, C, tau, alpha, beta, aux, aux + B * LE_AUX, d_out1, ldd1, d_out2, ldd2, d_tar, lddt);
-    SE_LAUNCH_CHECK();
-    return SE_OK;
+    return labelembed_bwd<false>("se_labelembed_loss_bwd", out1, ld1, out2, ld2, tar, ldt, targets, grad_loss_i, grad_scale, B, C, tau, alpha,
+                                 beta, aux, d_out1, ldd1, d_out2, ldd2, d_tar, lddt, stream);
 }
 
 extern "C" int se_labelembed_table_loss_fwd(const float *out1, int64_t ld1, const float *out2, int64_t ld2, const float *table,
                                             int64_t ldtab, const int64_t *targets, int64_t B, int64_t C, float tau, float alpha,
                                             float beta, float *loss_i, float *aux, se_stream_t stream)
 {
-    if (B < 0 || C <= 0) return fail(SE_ERR_INVALID, "se_labelembed_table_loss_fwd: bad shape B=%lld C=%lld", (long long)B, (long long)C);
-    if (B == 0) return SE_OK;
-    if (!out1 || !out2 || !table || !targets || !loss_i || !aux) return fail(SE_ERR_INVALID, "se_labelembed_table_loss_fwd: null pointer");
-    if (ld1 < C || ld2 < C || ldtab < C) return fail(SE_ERR_INVALID, "se_labelembed_table_loss_fwd: leading dimension too small");
-    if (!(tau > 0.f)) return fail(SE_ERR_INVALID, "se_labelembed_table_loss_fwd: tau must be positive");
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(labelembed_fwd_kernel<true>, dim3(le_grid(B)), dim3(256), 0, s, out1, ld1, out2, ld2, table, ldtab, targets, B, C,
-                       tau, alpha, beta, aux);
-    SE_LAUNCH_CHECK();
-    hipLaunchKernelGGL(labelembed_finish_kernel, dim3(1), dim3(256), 0, s, aux, B, loss_i, aux + B * LE_AUX);
-    SE_LAUNCH_CHECK();
-    return SE_OK;
+    return labelembed_fwd<true>("se_labelembed_table_loss_fwd", out1, ld1, out2, ld2, table, ldtab, targets, B, C, tau, alpha, beta, loss_i, aux,
+                                stream);
 }
 
 extern "C" int se_labelembed_table_loss_bwd(const float *out1, int64_t ld1, const float *out2, int64_t ld2, const float *table,
@@ -322,25 +324,6 @@ extern "C" int se_labelembed_table_loss_bwd(const float *out1, int64_t ld1, cons
                                             float *d_out1, int64_t ldd1, float *d_out2, int64_t ldd2, float *d_table, int64_t lddtab,
                                             se_stream_t stream)
 {
-    if (B < 0 || C <= 0) return fail(SE_ERR_INVALID, "se_labelembed_table_loss_bwd: bad shape B=%lld C=%lld", (long long)B, (long long)C);
-    if (B > 0 && (!out1 || !out2 || !table || !targets || !aux)) return fail(SE_ERR_INVALID, "se_labelembed_table_loss_bwd: null pointer");
-    if (B > 0 && (ld1 < C || ld2 < C || ldtab < C)) return fail(SE_ERR_INVALID, "se_labelembed_table_loss_bwd: leading dimension too small");
-    if ((d_out1 && ldd1 < C) || (d_out2 && ldd2 < C) || (d_table && lddtab < C))
-        return fail(SE_ERR_INVALID, "se_labelembed_table_loss_bwd: leading dimension too small");
-    if (!(tau > 0.f)) return fail(SE_ERR_INVALID, "se_labelembed_table_loss_bwd: tau must be positive");
-    hipStream_t s = (hipStream_t)stream;
-    if (B > 0 && (d_out1 || d_out2)) {
-        hipLaunchKernelGGL(labelembed_bwd_kernel<true>, dim3(le_grid(B)), dim3(256), 0, s, out1, ld1, out2, ld2, table, ldtab, targets,
-                           grad_loss_i, grad_scale, B, C, tau, alpha, beta, aux, aux + B * LE_AUX, d_out1, ldd1, d_out2, ldd2,
-                           (float *)nullptr, (int64_t)0);
-        SE_LAUNCH_CHECK();
-    }
-    if (d_table) {                                          // every row is written, B == 0 included (all +0)
-        const int64_t bx = (C + LT_WAVES - 1) / LT_WAVES, by = (C + 64 * LT_COLS - 1) / (64 * LT_COLS);
-        if (bx > 0x7FFFFFFF || by > 65535) return fail(SE_ERR_UNSUPPORTED, "se_labelembed_table_loss_bwd: C too large");
-        hipLaunchKernelGGL(labelembed_table_grad_kernel, dim3((unsigned)bx, (unsigned)by), dim3(64 * LT_WAVES), 0, s, out2, ld2, table,
-                           ldtab, targets, grad_loss_i, grad_scale, B, C, tau, aux, d_table, lddtab);
-        SE_LAUNCH_CHECK();
-    }
-    return SE_OK;
+    return labelembed_bwd<true>("se_labelembed_table_loss_bwd", out1, ld1, out2, ld2, table, ldtab, targets, grad_loss_i, grad_scale, B, C, tau,
+                                alpha, beta, aux, d_out1, ldd1, d_out2, ldd2, d_table, lddtab, stream);
 }

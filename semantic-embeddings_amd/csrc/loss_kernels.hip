@@ -12,56 +12,12 @@
 // (sum x^2 and x . emb[y]) are done with DPP/shuffle wave reductions -- no LDS, no atomics.
 // The kernels are HBM-bound: algorithmic bytes per row = D*s_x (x) + D*4 (emb row, L2-resident)
 // + D*4 (xhat) + 16.
-#include "se_common.h"
-#include "tile32.h"
+// The row chains, their host predicates and the metric's tile epilogue are in loss_head.h, shared with embed_head.hip.
+#include "loss_head.h"
 
 namespace se {
 
 constexpr int LOSS_ROWS_PER_BLOCK = 4;  // 4 waves = 256 threads
-constexpr float L2NORM_EPS = 1e-12f;    // tf.nn.l2_normalize default epsilon (TF 1.x)
-
-// ss = sum x^2, dt = sum x * t  over one row, all 64 lanes get the totals.
-template <bool BF16>
-__device__ __forceinline__ void row_reduce(const void *xrow, const float *trow, int64_t D, bool vec_ok,
-                                           float &ss, float &dt)
-{
-    const int lane = lane_id();
-    float s = 0.f, t = 0.f;
-    if (vec_ok) {
-        if constexpr (BF16) {
-            const uint4 *xv = (const uint4 *)xrow;  // 8 bf16 per 16 B
-            const float4 *tv = (const float4 *)trow;
-            for (int64_t i = lane; i < D / 8; i += WAVE) {
-                uint4 p = xv[i];
-                float4 t0 = tv[2 * i], t1 = tv[2 * i + 1];
-                float xs[8];
-                unpack_bf16x8(p, xs);
-                float ts[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    s = fmaf(xs[j], xs[j], s);
-                    t = fmaf(xs[j], ts[j], t);
-                }
-            }
-        } else {
-            const float4 *xv = (const float4 *)xrow;
-            const float4 *tv = (const float4 *)trow;
-            for (int64_t i = lane; i < D / 4; i += WAVE) {
-                float4 p = xv[i], q = tv[i];
-                s = fmaf(p.x, p.x, s); s = fmaf(p.y, p.y, s); s = fmaf(p.z, p.z, s); s = fmaf(p.w, p.w, s);
-                t = fmaf(p.x, q.x, t); t = fmaf(p.y, q.y, t); t = fmaf(p.z, q.z, t); t = fmaf(p.w, q.w, t);
-            }
-        }
-    } else {
-        for (int64_t i = lane; i < D; i += WAVE) {
-            float p = ld_elem<BF16>(xrow, i);
-            s = fmaf(p, p, s);
-            t = fmaf(p, trow[i], t);
-        }
-    }
-    ss = wave_sum(s);
-    dt = wave_sum(t);
-}
 
 template <bool BF16>
 __global__ __launch_bounds__(256) void cosine_loss_fwd_kernel(
@@ -83,19 +39,7 @@ __global__ __launch_bounds__(256) void cosine_loss_fwd_kernel(
             if (inv_norm) inv_norm[row] = inv;
             loss_i[row] = 1.0f - dt * inv;
         }
-        if (xhat) {
-            float *orow = xhat + row * ldxhat;
-            if (vec_ok && !BF16) {
-                const float4 *xv = (const float4 *)xrow;
-                float4 *ov = (float4 *)orow;
-                for (int64_t i = lane; i < D / 4; i += WAVE) {
-                    float4 p = xv[i];
-                    ov[i] = make_float4(p.x * inv, p.y * inv, p.z * inv, p.w * inv);
-                }
-            } else {
-                for (int64_t i = lane; i < D; i += WAVE) orow[i] = ld_elem<BF16>(xrow, i) * inv;
-            }
-        }
+        if (xhat) write_xhat_row<BF16>(xrow, xhat + row * ldxhat, D, vec_ok != 0, inv);
     }
 }
 
@@ -154,21 +98,7 @@ __global__ __launch_bounds__(256) void sqdist_loss_fwd_kernel(const void *__rest
         const char *xrow = (const char *)x + row * ldx * (BF16 ? 2 : 4);
         const int64_t y = clamp_label(labels[row], C);
         const float *trow = emb + y * lde;
-        float s = 0.f;
-        if (vec_ok && !BF16) {
-            const float4 *xv = (const float4 *)xrow, *tv = (const float4 *)trow;
-            for (int64_t i = lane; i < D / 4; i += WAVE) {
-                const float4 p = xv[i], q = tv[i];
-                const float a = p.x - q.x, b = p.y - q.y, c = p.z - q.z, e = p.w - q.w;
-                s = fmaf(a, a, s); s = fmaf(b, b, s); s = fmaf(c, c, s); s = fmaf(e, e, s);
-            }
-        } else {
-            for (int64_t i = lane; i < D; i += WAVE) {
-                const float a = ld_elem<BF16>(xrow, i) - trow[i];
-                s = fmaf(a, a, s);
-            }
-        }
-        s = wave_sum(s);
+        const float s = row_sqdist<BF16>(xrow, trow, D, vec_ok != 0);
         if (lane == 0) {
             loss_i[row] = s;
             if (dist_i) dist_i[row] = sqrtf(s);
@@ -245,14 +175,11 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float *__restrict
 // and odd k de-interleaved so that lanes 0-31 (k = 2t) and 32-63 (k = 2t+1) each read 16 B.
 // (The same tile as tile32.h, which the DeViSE kernels use; this kernel keeps its own staging and chunk loop: every spelling
 // through the shared helpers measured 1 - 3 us per call slower, profiles/loss_head_refactor_equivalence.txt section 3.)
-// Instead of materialising top-k, the metric uses the equivalent counting form
-//     acc = (#within >= 1) && (#better < k)
-// with  within = |score - true| < 1e-6,  better = score beyond true by >= 1e-6   (utils.py:84-95).
+// What happens to a finished tile (the counting form of the metric, the best class) is metric:: of loss_head.h.
 // ------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using tile32::f32x16;
 
-constexpr int ACC_BK = 64;            // k per staged chunk
-constexpr int ACC_LD = ACC_BK + 4;    // padded row pitch (floats): conflict-free ds_read_b128
+constexpr int ACC_BK = tile32::BK, ACC_LD = tile32::LD;    // k per staged chunk; padded row pitch (floats)
 
 __device__ __forceinline__ void stage_tile32(float *lds, const float *src, int64_t ld, int64_t row0,
                                              int64_t nrows, int64_t k0, int64_t K)
@@ -310,6 +237,7 @@ __global__ __launch_bounds__(64) void nn_accuracy_kernel(
     const int lane = lane_id();
     const int col = lane & 31, hi = lane >> 5;
     const int64_t row0 = (int64_t)blockIdx.x * 32;
+    const bool dot = dot_prod_sim != 0;
 
     // "true" score per sample.  The reference forms it with a separate elementwise reduction
     // (utils.py:80 / :91) and then needs the 1e-6 band to absorb the float32 noise between that
@@ -326,7 +254,7 @@ __global__ __launch_bounds__(64) void nn_accuracy_kernel(
                 float s = 0.f;
                 for (int64_t d = 0; d < D; d++) s = fmaf(p[d], e[d], s);
                 t = s;                                   // S[r, y]
-            } else if (!dot_prod_sim) {
+            } else if (!dot) {
                 float ce = 0.f, co = 0.f;
                 for (int64_t d = 0; d < D; d += 2) {
                     ce = fmaf(e[d], e[d], ce);
@@ -340,20 +268,14 @@ __global__ __launch_bounds__(64) void nn_accuracy_kernel(
         pn = __shfl_xor(pn, 32, 64);                     // hi==0 lanes receive |p|^2
         if (hi == 0) {
             sPn[col] = pn;
-            sTrue[col] = dot_prod_sim ? t : ((pn + other) - 2.0f * t);
+            sTrue[col] = dot ? t : ((pn + other) - 2.0f * t);
         }
     }
     wg_barrier();
 
-    int n_better[16], n_within[16];
-    float best_v[16];
-    int best_c[16];
+    metric::Tally tally[16];
 #pragma unroll
-    for (int r = 0; r < 16; r++) {
-        n_better[r] = 0; n_within[r] = 0;
-        best_v[r] = dot_prod_sim ? -INFINITY : INFINITY;
-        best_c[r] = 0x7FFFFFFF;
-    }
+    for (int r = 0; r < 16; r++) tally[r] = metric::empty_tally(dot);
 
     const int64_t c_beg = (int64_t)blockIdx.y * tiles_per_block * 32;
     const int64_t c_end = (c_beg + (int64_t)tiles_per_block * 32 < C) ? c_beg + (int64_t)tiles_per_block * 32 : C;
@@ -378,68 +300,36 @@ __global__ __launch_bounds__(64) void nn_accuracy_kernel(
                 if (s + 1 < steps) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc, 0, 0, 0);
                 if (s + 2 < steps) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc, 0, 0, 0);
                 if (s + 3 < steps) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc, 0, 0, 0);
-                if (!dot_prod_sim) {
-                    cn = fmaf(b4.x, b4.x, cn);
-                    if (s + 1 < steps) cn = fmaf(b4.y, b4.y, cn);
-                    if (s + 2 < steps) cn = fmaf(b4.z, b4.z, cn);
-                    if (s + 3 < steps) cn = fmaf(b4.w, b4.w, cn);
-                }
+                if (!dot) cn = metric::class_norm_steps(cn, b4, s, steps);
             }
         }
-        if (!dot_prod_sim) {
+        if (!dot) {
             cn += __shfl_xor(cn, 32, 64);
             wg_barrier();
             if (hi == 0) sCn[col] = cn;
             wg_barrier();
         }
-        const int64_t c = c0 + col;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int lr = tile32::acc_row(r, hi);
-            float sc = acc[r];
-            if (!dot_prod_sim) sc = (sPn[lr] + sCn[col]) - 2.0f * sc;
-            const bool valid = (c < C) && (row0 + lr < B);
-            if (valid) {
-                if (scores) scores[(row0 + lr) * lds_ + c] = sc;
-                const float diff = dot_prod_sim ? (sc - sTrue[lr]) : (sTrue[lr] - sc);  // > 0: better than true
-                if (fabsf(diff) < 1e-6f) n_within[r]++;
-                else if (diff >= 1e-6f) n_better[r]++;
-                const bool better = dot_prod_sim ? (sc > best_v[r]) : (sc < best_v[r]);
-                if (better) { best_v[r] = sc; best_c[r] = (int)c; }
-            }
+            metric::update(tally[r], dot, acc[r], sPn, sCn[col], sTrue, lr, row0 + lr, B, c0 + col, C, scores, lds_);
         }
     }
 
     // reduce over the 32 lanes (classes) that share `hi`
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-#pragma unroll
-        for (int off = 1; off < 32; off <<= 1) {
-            n_better[r] += __shfl_xor(n_better[r], off, 64);
-            n_within[r] += __shfl_xor(n_within[r], off, 64);
-            const float ov = __shfl_xor(best_v[r], off, 64);
-            const int oc = __shfl_xor(best_c[r], off, 64);
-            const bool take = dot_prod_sim ? (ov > best_v[r] || (ov == best_v[r] && oc < best_c[r]))
-                                           : (ov < best_v[r] || (ov == best_v[r] && oc < best_c[r]));
-            if (take) { best_v[r] = ov; best_c[r] = oc; }
-        }
+        metric::reduce32(tally[r], dot);
         const int lr = tile32::acc_row(r, hi);
         if (col == 0 && row0 + lr < B) {
             if (gridDim.y == 1) {
-                acc_out[row0 + lr] = (n_within[r] >= 1 && n_better[r] < k) ? 1.0f : 0.0f;
-                if (best_out) best_out[row0 + lr] = best_c[r];
+                acc_out[row0 + lr] = (tally[r].n_within >= 1 && tally[r].n_better < k) ? 1.0f : 0.0f;
+                if (best_out) best_out[row0 + lr] = tally[r].best_c;
             } else {
-                atomicAdd(&part_cnt[2 * (row0 + lr)], (uint32_t)n_better[r]);
-                atomicAdd(&part_cnt[2 * (row0 + lr) + 1], (uint32_t)n_within[r]);
-                if (best_c[r] != 0x7FFFFFFF) {
-                    // best class of this slice as one ordered word: score (larger = better), then LOWER class index
-                    float v = best_v[r];
-                    if (v == 0.f) v = 0.f;                                     // -0 ties with +0
-                    uint32_t u = __float_as_uint(v);
-                    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);            // ascending with the value
-                    if (!dot_prod_sim) u = ~u;                                 // distances: smaller is better
-                    atomicMax(&part_best[row0 + lr], ((unsigned long long)u << 32) | (uint32_t)(0x7FFFFFFF - best_c[r]));
-                }
+                atomicAdd(&part_cnt[2 * (row0 + lr)], (uint32_t)tally[r].n_better);
+                atomicAdd(&part_cnt[2 * (row0 + lr) + 1], (uint32_t)tally[r].n_within);
+                if (tally[r].best_c != metric::NO_CLASS)
+                    atomicMax(&part_best[row0 + lr], metric::best_word(tally[r].best_v, tally[r].best_c, dot));
             }
         }
     }
@@ -451,7 +341,7 @@ __global__ __launch_bounds__(256) void nn_accuracy_finish_kernel(const uint32_t 
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= B) return;
     acc_out[r] = (part_cnt[2 * r + 1] >= 1u && part_cnt[2 * r] < (uint32_t)k) ? 1.0f : 0.0f;
-    if (best_out) best_out[r] = 0x7FFFFFFF - (int32_t)(uint32_t)(part_best[r] & 0xFFFFFFFFull);
+    if (best_out) best_out[r] = metric::best_class(part_best[r]);
 }
 
 }  // namespace se
@@ -469,13 +359,11 @@ extern "C" int se_cosine_loss_fwd(const void *x, int x_dtype, int64_t ldx, const
     if (ldx < D || lde < D || (xhat && ldxhat < D)) return fail(SE_ERR_INVALID, "se_cosine_loss_fwd: leading dimension < D");
     if (!is_float_dtype(x_dtype)) return fail(SE_ERR_INVALID, "se_cosine_loss_fwd: bad dtype %d", x_dtype);
     hipStream_t s = (hipStream_t)stream;
-    const bool bf = x_dtype == SE_DTYPE_BF16;
-    const int vq = bf ? 8 : 4;
-    const int vec_ok = (D % vq == 0) && (ldx % vq == 0) && (lde % 4 == 0) && aligned16(x) && aligned16(emb) &&
-                       (!xhat || ((ldxhat % 4 == 0) && aligned16(xhat)));
+    const int vec_ok = cosine_rows_vec16(x, x_dtype, ldx, emb, lde, D, xhat, ldxhat);
     const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
-    if (bf) hipLaunchKernelGGL(cosine_loss_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, xhat, ldxhat, inv_norm, loss_i, vec_ok);
-    else hipLaunchKernelGGL(cosine_loss_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, xhat, ldxhat, inv_norm, loss_i, vec_ok);
+    dispatch_bools(x_dtype == SE_DTYPE_BF16, [&](auto XB) {
+        hipLaunchKernelGGL(cosine_loss_fwd_kernel<XB()>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, xhat, ldxhat, inv_norm, loss_i, vec_ok);
+    });
     SE_LAUNCH_CHECK();
     if (loss_mean) {
         launch_mean(loss_i, B, loss_mean, s);
@@ -496,8 +384,7 @@ extern "C" int se_cosine_loss_bwd(const void *x, int x_dtype, int64_t ldx, const
     hipStream_t s = (hipStream_t)stream;
     const bool bf = x_dtype == SE_DTYPE_BF16, dbf = dx_dtype == SE_DTYPE_BF16;
     if (!is_float_dtype(x_dtype) || !is_float_dtype(dx_dtype)) return fail(SE_ERR_INVALID, "se_cosine_loss_bwd: bad dtype");
-    const int vq = bf ? 8 : 4;
-    const int vec_ok = (D % vq == 0) && (ldx % vq == 0) && (lde % 4 == 0) && aligned16(x) && aligned16(emb);
+    const int vec_ok = cosine_rows_vec16(x, x_dtype, ldx, emb, lde, D);
     const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
     dispatch_bools(bf, dbf, [&](auto XB, auto DB) {
         hipLaunchKernelGGL((cosine_loss_bwd_kernel<XB(), DB()>), dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, grad_loss_i, grad_scale, B, D, C, dx, lddx, vec_ok);
@@ -515,11 +402,11 @@ extern "C" int se_sqdist_loss_fwd(const void *x, int x_dtype, int64_t ldx, const
     if (ldx < D || lde < D) return fail(SE_ERR_INVALID, "se_sqdist_loss_fwd: leading dimension < D");
     if (!is_float_dtype(x_dtype)) return fail(SE_ERR_INVALID, "se_sqdist_loss_fwd: bad dtype %d", x_dtype);
     hipStream_t s = (hipStream_t)stream;
-    const bool bf = x_dtype == SE_DTYPE_BF16;
-    const int vec_ok = !bf && (D % 4 == 0) && (ldx % 4 == 0) && (lde % 4 == 0) && aligned16(x) && aligned16(emb);
+    const int vec_ok = sqdist_rows_vec16(x, x_dtype, ldx, emb, lde, D);
     const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
-    if (bf) hipLaunchKernelGGL(sqdist_loss_fwd_kernel<true>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, loss_i, dist_i, vec_ok);
-    else hipLaunchKernelGGL(sqdist_loss_fwd_kernel<false>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, loss_i, dist_i, vec_ok);
+    dispatch_bools(x_dtype == SE_DTYPE_BF16, [&](auto XB) {
+        hipLaunchKernelGGL(sqdist_loss_fwd_kernel<XB()>, dim3(blocks), dim3(256), 0, s, x, ldx, labels, emb, lde, B, D, C, loss_i, dist_i, vec_ok);
+    });
     SE_LAUNCH_CHECK();
     if (loss_mean) {
         launch_mean(loss_i, B, loss_mean, s);
@@ -552,7 +439,7 @@ constexpr int NN_ACC_MIN_TILES = 4;     // up to 4 class tiles: one wave walks t
 extern "C" int64_t se_nn_accuracy_workspace_bytes(int64_t B, int64_t C)
 {
     if (B <= 0 || C <= 0) return 0;
-    return tile32::tiles_per_block(B, C, NN_ACC_MIN_TILES) * 32 >= C ? 0 : B * 16;      // per sample: two counters + one ordered word
+    return tile32::tiles_per_block(B, C, NN_ACC_MIN_TILES) * 32 >= C ? 0 : metric::workspace_bytes(B, 0);
 }
 
 extern "C" int se_nn_accuracy(const float *y_pred, int64_t ldp, const int64_t *labels, const float *emb,
@@ -571,14 +458,13 @@ extern "C" int se_nn_accuracy(const float *y_pred, int64_t ldp, const int64_t *l
     hipStream_t s = (hipStream_t)stream;
     const int tpb = tile32::tiles_per_block(B, C, NN_ACC_MIN_TILES);
     const int64_t slices = ((C + 31) / 32 + tpb - 1) / tpb;
-    unsigned long long *part_best = (unsigned long long *)workspace;
-    uint32_t *part_cnt = need > 0 ? (uint32_t *)((char *)workspace + B * 8) : nullptr;
+    const metric::Workspace ws = metric::workspace(workspace, B, need > 0, false);
     if (need > 0) SE_HIP_CHECK(hipMemsetAsync(workspace, 0, (size_t)need, s));
     hipLaunchKernelGGL(nn_accuracy_kernel, dim3((unsigned)((B + 31) / 32), (unsigned)slices), dim3(64), 0, s,
-                       y_pred, ldp, labels, emb, lde, B, D, C, dot_prod_sim, k, acc, scores, lds, best, tpb, part_cnt, part_best);
+                       y_pred, ldp, labels, emb, lde, B, D, C, dot_prod_sim, k, acc, scores, lds, best, tpb, ws.part_cnt, ws.part_best);
     SE_LAUNCH_CHECK();
     if (slices > 1) {
-        hipLaunchKernelGGL(nn_accuracy_finish_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, part_cnt, part_best, B, k, acc, best);
+        hipLaunchKernelGGL(nn_accuracy_finish_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, ws.part_cnt, ws.part_best, B, k, acc, best);
         SE_LAUNCH_CHECK();
     }
     return SE_OK;
@@ -590,10 +476,11 @@ extern "C" int se_l2norm_fwd(const void *x, int x_dtype, int64_t ldx, int64_t B,
     if (B < 0 || D <= 0) return fail(SE_ERR_INVALID, "se_l2norm_fwd: bad shape");
     if (B == 0) return SE_OK;
     if (!x || !xhat || ldx < D || ldxhat < D) return fail(SE_ERR_INVALID, "se_l2norm_fwd: bad argument");
+    if (!is_float_dtype(x_dtype)) return fail(SE_ERR_INVALID, "se_l2norm_fwd: bad dtype %d", x_dtype);
     const unsigned blocks = row_blocks(B, LOSS_ROWS_PER_BLOCK, 256 * 32);
-    if (x_dtype == SE_DTYPE_BF16) hipLaunchKernelGGL(l2norm_fwd_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, B, D, xhat, ldxhat, inv_norm, sumsq);
-    else if (x_dtype == SE_DTYPE_F32) hipLaunchKernelGGL(l2norm_fwd_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, B, D, xhat, ldxhat, inv_norm, sumsq);
-    else return fail(SE_ERR_INVALID, "se_l2norm_fwd: bad dtype %d", x_dtype);
+    dispatch_bools(x_dtype == SE_DTYPE_BF16, [&](auto XB) {
+        hipLaunchKernelGGL(l2norm_fwd_kernel<XB()>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, ldx, B, D, xhat, ldxhat, inv_norm, sumsq);
+    });
     SE_LAUNCH_CHECK();
     return SE_OK;
 }

@@ -1,7 +1,9 @@
 // tile32.h -- the fp32 32 x 32 output tile on v_mfma_f32_32x32x2_f32 of the DeViSE kernels (devise.hip): one wave per tile, operands
 // staged through LDS in K-chunks (64 k unless a kernel asks for more) with even and odd k de-interleaved, so that lanes 0-31 (k = 2t)
 // and 32-63 (k = 2t + 1) each feed four MFMA steps from one 16-byte LDS read.  nn_accuracy_kernel (loss_kernels.hip) works on the same
-// tile and shares acc_row and tiles_per_block; its staging and chunk loop are its own (see the comment there).
+// tile and shares acc_row and tiles_per_block; its staging and chunk loop are its own (see the comment there).  The embedding heads
+// (embed_head.hip) stage their class chunks with stage(); the chunks their four waves share are staged by all 256 threads with the
+// head's own loops in this layout.  What these kernels do with a finished tile of class scores is metric:: of loss_head.h.
 #pragma once
 #include "se_common.h"
 

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from test_labelembed_host import GROUP_CLASSES, scan_group_labels
+
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,6 +114,26 @@ def test_centroid_grad_all_rows_in_one_class():
     want = oracle_centroid_grad(x, labels, cent, w, C)
     assert np.array_equal(got.view(np.int32), want.view(np.int32))
     assert (got[:-1].view(np.int32) == 0).all() and np.abs(got[-1]).max() > 0
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
+def test_centroid_grad_group_boundaries(dtype):
+    """Labels that fix how many rows of a class every ballot of 64 holds (1 ... 9: one, two and three groups of four with every
+    remainder, and a partial last ballot), once with per-row weights and once with grad_scale."""
+    B, D, C = 300, 5, GROUP_CLASSES
+    rng = np.random.default_rng(41)
+    labels = scan_group_labels(B, rng)
+    x = rng.standard_normal((B, D)).astype(np.float32)
+    if dtype == BF16:
+        x = torch.from_numpy(x).bfloat16().float().numpy()
+    cent = (rng.standard_normal((C, D)) * 0.5).astype(np.float32)
+    w = rng.uniform(0.01, 2.0, size=B).astype(np.float32)
+    scale = np.float32(0.1 / B)
+    for weights in (w, None):
+        got = centroid_grad(x, dtype, labels, cent, weights, scale, C, pad=3)
+        want = oracle_centroid_grad(x, labels, cent, weights if weights is not None else np.full(B, scale, np.float32), C)
+        assert (want != 0).all()
+        assert np.array_equal(got.view(np.int32), want.view(np.int32)), weights is None
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from oracle import loss_oracle as lo
-from test_labelembed_host import COL1, CONTIG, NO_MASK_CASE, PADDED, TABLE_CASES, case_inputs, pitch, table_grad_rule
+from test_labelembed_host import (COL1, CONTIG, GROUP_CLASSES, NO_MASK_CASE, PADDED, TABLE_CASES, case_inputs, pitch, scan_group_labels,
+                                  table_grad_rule)
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -110,6 +111,32 @@ def test_bit_contracts(case):
     rc = run_both(case, o1, o2, table, np.clip(y, 0, C - 1), g)["table"]
     for k in tab:
         assert np.array_equal(rc[k], tab[k]), k
+
+
+@pytest.mark.parametrize("every_third_out", [False, True], ids=["all-rows-count", "every-third-row-wt0"])
+def test_table_grad_group_boundaries(every_third_out):
+    """Labels that fix how many rows of a class every ballot of 64 holds (1 ... 9: one, two and three groups of four with every
+    remainder, and a partial last ballot).  Every row's true class wins out2 (mask = 1, all rows count); in the second run every
+    third row's true class loses it instead, so that rows with wt == 0 sit inside the groups and are skipped."""
+    B, C = 300, GROUP_CLASSES
+    rng = np.random.default_rng(43)
+    y = scan_group_labels(B, rng)
+    o1, o2 = (rng.standard_normal((B, C)).astype(np.float32) * 2 for _ in range(2))
+    table = (np.eye(C) + 0.5 * rng.standard_normal((C, C))).astype(np.float32)
+    g = rng.standard_normal(B).astype(np.float32)
+    counts = np.ones(B, dtype=bool)
+    if every_third_out:
+        counts[::3] = False
+    rows = np.arange(B)
+    o2[rows[counts], y[counts]] = o2.max(axis=1)[counts] + 7.0
+    o2[rows[~counts], y[~counts]] -= 30.0
+    r = run_both((B, C, PADDED), o1, o2, table, y, g)
+    ref, tab = r["ref"], r["table"]
+    mask = ref["aux"].view(np.float32)[:B * AUX].reshape(B, AUX)[:, 4]
+    assert np.array_equal(mask != 0, counts)
+    want = table_grad_rule(ref["dtar"].view(np.float32), y, C)
+    assert (want[:9] != 0).any(axis=1).all()
+    assert np.array_equal(tab["dtab"], want.view(np.int32))
 
 
 def test_no_row_with_mask_one():

@@ -191,9 +191,9 @@ def test_table_grad_rule_is_ordered_float32_addition():
 LE_GRID_CAP = 4096              # SE_LABELEMBED_GRID_CAP: workgroups of the per-sample kernels ...
 ROWS_PER_BLOCK = 4              # ... of LE_ROWS_PER_BLOCK samples each; larger batches stride
 BALLOT = 64                     # labels one ballot of the table-gradient kernel scans
-LABELS_IN_FLIGHT = 4 * BALLOT   # LT_CHUNKS chunks of labels are loaded together: longer batches go round the outer loop again
-ROWS_TOGETHER = 4               # LT_ROWS matched rows are loaded together: more matches in one ballot go round the walk again
-COLS_PER_WAVE = 4 * 64          # LT_COLS columns per lane: wider tables take more than one column block (gridDim.y)
+LABELS_IN_FLIGHT = 4 * BALLOT   # class_scan::CHUNKS chunks of labels are loaded together: longer batches go round the outer loop again
+ROWS_TOGETHER = 4               # class_scan::ROWS matched rows are loaded together: more matches in one ballot go round the walk again
+COLS_PER_WAVE = 4 * 64          # class_scan::COLS columns per lane: wider tables take more than one column block (gridDim.y)
 # The grid of the table-gradient kernel is not capped: one wave per (table row, column block), so no row loop exists to reach.
 
 CONTIG, PADDED, COL1 = "contig", "padded", "col1"     # tests/test_gpu_loss_matrix.py's input layouts
@@ -209,6 +209,39 @@ TABLE_CASES = [
     (LE_GRID_CAP * ROWS_PER_BLOCK + 9, 5, PADDED),
 ]
 NO_MASK_CASE = TABLE_CASES[2]       # run once more with no row of mask = 1: the batch scale is B / 1e-8 and d_table all +0
+
+
+GROUP_CLASSES = 12              # classes of scan_group_labels: 0 - 8 with fixed counts per ballot, 9 - 11 take the other rows
+
+
+def scan_group_labels(B, rng):
+    """Labels that fix where the per-class scan (csrc/class_scan.h; centroid and table gradients) cuts its groups of ROWS_TOGETHER rows:
+    in every full ballot of 64 rows class k = 0 ... 8 holds exactly k + 1 rows at random positions (group remainders 1, 2, 3, 0 over one,
+    two and three groups), in a partial last ballot classes 0 ... 7 do; the other rows fall in classes 9 - 11."""
+    y = np.empty(B, dtype=np.int64)
+    for c0 in range(0, B, BALLOT):
+        n = min(BALLOT, B - c0)
+        counted = np.arange(9 if n == BALLOT else 8)
+        fixed = np.repeat(counted, counted + 1)
+        assert fixed.size <= n
+        y[c0:c0 + n] = rng.permutation(np.concatenate([fixed, rng.integers(9, GROUP_CLASSES, size=n - fixed.size)]))
+    return y
+
+
+def test_scan_group_labels_fix_every_group_remainder():
+    B = 300                                                                     # four full ballots and one of 44 rows
+    y = scan_group_labels(B, np.random.default_rng(3))
+    assert y.min() == 0 and y.max() < GROUP_CLASSES
+    for c0 in range(0, B, BALLOT):
+        chunk = y[c0:c0 + BALLOT]
+        counted = 9 if chunk.size == BALLOT else 8
+        assert [int((chunk == k).sum()) for k in range(counted)] == list(range(1, counted + 1))
+        assert (chunk >= counted).sum() == chunk.size - counted * (counted + 1) // 2 and (chunk[chunk >= counted] >= 9).all()
+    per_ballot = np.arange(1, 10)
+    assert {int(n % ROWS_TOGETHER) for n in per_ballot} == {0, 1, 2, 3} and {int(-(-n // ROWS_TOGETHER)) for n in per_ballot} == {1, 2, 3}
+    # the ordered float32 rule takes the pattern and gives every counted class a gradient
+    d_tar = np.random.default_rng(4).standard_normal((B, GROUP_CLASSES)).astype(np.float32)
+    assert (table_grad_rule(d_tar, y, GROUP_CLASSES)[:9] != 0).all()
 
 
 def pitch(layout, d):
