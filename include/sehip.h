@@ -189,6 +189,62 @@ int se_embed_head_fwd(int mode, const void *x, int x_dtype, int64_t ldx, const i
                       se_stream_t stream);
 
 /*
+ * Joint head of `--cls_weight`: the embedding loss on the model's first output, the cross-entropy of the classifier branch and the
+ * metrics of both outputs in ONE forward launch; both gradients in one backward launch.
+ * Replaces: utils.inv_correlation(embedding[y], p) (utils.py:44-46) as the loss of `--loss inv_corr | unnorm_corr | softmax_corr`
+ *           beside a classifier branch (learn_image_embeddings.py:160-180), utils.nn_accuracy(embedding, True, k) for every k
+ *           (utils.py:57-100) or, for one-hot-like targets, 'accuracy' and utils.top_k_acc (utils.py:49-54) on that output, Keras 2.2's
+ *           'categorical_crossentropy' with 'accuracy' / utils.top_k_acc on the `prob` output, and what TF autodiff derives from both.
+ *   p [B, D] f32 (ldp): the first output as it stands in the graph -- the l2norm layer's output for inv_corr, the softmax output for
+ *           softmax_corr, the raw embedding for unnorm_corr.  It is NOT normalised again (the classifier branch reads the same tensor,
+ *           which is why se_embed_head_fwd mode 0 cannot serve here).
+ *   labels [B] int64, clamped to [0, C - 1].  C: the rows of emb AND the columns of logits.
+ *   emb [C, D] f32 (lde), or NULL: the identity table of `--embedding onehot`, which needs D == C and SE_HEAD_METRIC_ARGMAX.
+ * Embedding role:
+ *   emb_loss_i [B] = 1 - dot(emb[y_i], p_i); the dot is the row chain of se_cosine_loss_fwd (its x . emb[y]), with that entry
+ *           point's rule for the 16-byte path, so the summation order is fixed.  emb == NULL: the single operation 1.0f - p[i, y_i].
+ *   SE_HEAD_METRIC_NEAREST: n_better, n_within [B] int32, p_best [B] int32 and scores [B, C] f32 (lds) are what
+ *           se_nn_accuracy(dot_prod_sim = 1) computes from p, bit for bit; (n_within >= 1) && (n_better < k) is its 0/1 value for
+ *           every k (see se_embed_head_fwd).  p_above is not written.
+ *   SE_HEAD_METRIC_ARGMAX (needs D == C): one scan of the row of p itself.  p_best [B] int32 = its arg-max class with np.argmax's
+ *           rules (lowest index on ties, the first NaN wins); p_above [B] int32 = the number of entries strictly greater than
+ *           p[i, y_i].  p_best == y is Keras' accuracy, p_above < k is tf.nn.in_top_k.  Non-finite rows follow se_softmax_xent_fwd's
+ *           best / above: a row with a NaN or +inf, or of nothing but -inf, has p_above = C.  n_better, n_within and scores are
+ *           not written.
+ * Classifier role (logits != NULL; [B, C] f32 / bf16, ldz): cls_loss_i [B], aux (se_softmax_xent_aux_floats(B) floats), z_best and
+ *   z_above [B] int32 carry the bits of se_softmax_xent_fwd(smoothing = 0) on the same inputs -- it is the same row code.
+ *   logits == NULL runs the embedding role alone (unnorm_corr / softmax_corr without --cls_weight).
+ * Both roles run in one grid up to C = 8192 (the register paths of the cross-entropy); longer rows of logits take a second launch.
+ * The bits do not depend on that, on the launch geometry or on concurrent work.
+ *   bwd: dp [B, D] f32 (lddp): dp[i, d] = fl(-w_i * emb[y_i, d]); emb == NULL: -w_i at column y_i, +0 elsewhere.
+ *        w_i = grad_emb_loss_i[i] (NULL: grad_emb_scale for every row).  dz [B, C] f32 / bf16 (lddz) carries the bits of
+ *        se_softmax_xent_bwd(smoothing = 0) with grad_cls_loss_i / grad_cls_scale and the forward's aux.  Every element of dp and dz
+ *        is written.  logits == NULL skips dz; dp == NULL skips the embedding role.
+ *   workspace: se_joint_head_workspace_bytes(metric, B, D, C) bytes, 8-byte aligned (0 for the arg-max metric and while one
+ *        workgroup walks all class tiles of its 32 samples); the call zeroes what it needs of it on `stream`.
+ *   Asynchronous on `stream`, no allocation, no host synchronisation, integer atomics only: capturable in a HIP graph.
+ *   B == 0 returns SE_OK and touches nothing.  SE_ERR_INVALID: a bad metric or dtype; a leading dimension below the width;
+ *   emb == NULL with SE_HEAD_METRIC_NEAREST or D != C; SE_HEAD_METRIC_ARGMAX with D != C; a null required pointer (p, labels,
+ *   emb_loss_i; n_better and n_within under SE_HEAD_METRIC_NEAREST; p_above under SE_HEAD_METRIC_ARGMAX; cls_loss_i and aux -- bwd:
+ *   aux and dz -- whenever logits is given); a missing, short or misaligned workspace.  p_best, scores, z_best, z_above may be NULL.
+ */
+#define SE_HEAD_METRIC_NEAREST 0   /* nearest class embedding by dot product: n_better / n_within (utils.nn_accuracy, dot_prod_sim) */
+#define SE_HEAD_METRIC_ARGMAX  1   /* arg-max of p itself against the label: p_best / p_above ('accuracy', utils.top_k_acc)      */
+int64_t se_joint_head_workspace_bytes(int metric, int64_t B, int64_t D, int64_t C);
+int se_joint_head_fwd(const float *p, int64_t ldp, const int64_t *labels, const float *emb, int64_t lde,
+                      int64_t B, int64_t D, int64_t C, int metric,
+                      float *emb_loss_i, int32_t *n_better, int32_t *n_within, int32_t *p_best, int32_t *p_above,
+                      float *scores, int64_t lds,
+                      const void *logits, int z_dtype, int64_t ldz, float *cls_loss_i, float *aux,
+                      int32_t *z_best, int32_t *z_above,
+                      void *workspace, int64_t workspace_bytes, se_stream_t stream);
+int se_joint_head_bwd(const int64_t *labels, const float *emb, int64_t lde, int64_t B, int64_t D, int64_t C,
+                      const float *grad_emb_loss_i, float grad_emb_scale, float *dp, int64_t lddp,
+                      const void *logits, int z_dtype, int64_t ldz, const float *aux,
+                      const float *grad_cls_loss_i, float grad_cls_scale, void *dz, int dz_dtype, int64_t lddz,
+                      se_stream_t stream);
+
+/*
  * Label-embedding baseline loss (Sun et al.), forward and backward.
  * Replaces: labelembed_loss(out1, out2, tar, targets, tau, alpha, beta) and cross_entropy
  *           (learn_labelembedding.py:17-37); the backward is what TF autodiff derives from it

@@ -194,11 +194,13 @@ class Trainer(object):
     metrics: dict output_name -> list of metric fns with ``.name``.
     A batch from the sequences is ``(X, y)`` or ``(X, [y_1, y_2, ...])``.
     optimizer: 'sgd' (Keras SGD with ``momentum`` / ``nesterov``) or 'adagrad' (Keras Adagrad with ``epsilon``: ``flat.flat_v`` is the
-             accumulator of squared gradients, ``momentum`` and ``nesterov`` are ignored); both with ``lr / (1 + decay * iterations)``."""
+             accumulator of squared gradients, ``momentum`` and ``nesterov`` are ignored); both with ``lr / (1 + decay * iterations)``.
+    joint_head: a ``utils.JointEmbeddingHead`` whose loss callables and metrics are among ``losses`` / ``metrics``: every step calls
+             its ``begin(ys, outs)`` once before they run, so that one launch serves them all.  None: nothing changes."""
 
     def __init__(self, model, losses, metrics=None, lr=0.1, momentum=0.9, nesterov=False, clipnorm=None, decay=0.0,
                  l2_of=None, autocast_dtype=torch.bfloat16, bucket_bytes=25 << 20, trainable=None, memory_format=None,
-                 optimizer='sgd', epsilon=1e-7):
+                 optimizer='sgd', epsilon=1e-7, joint_head=None):
         if optimizer not in ('sgd', 'adagrad'):
             raise ValueError("optimizer must be 'sgd' or 'adagrad', got %r" % (optimizer,))
         self.optimizer, self.epsilon = optimizer, float(epsilon)
@@ -208,6 +210,7 @@ class Trainer(object):
             model.to(memory_format=memory_format)
         self.losses = losses
         self.metrics = metrics or {}
+        self.joint_head = joint_head             # utils.JointEmbeddingHead: one launch serves the losses and metrics of all outputs
         self.lr, self.momentum, self.nesterov, self.clipnorm, self.decay = lr, momentum, nesterov, clipnorm, decay
         self.autocast_dtype = autocast_dtype
         self.iterations = 0
@@ -240,6 +243,8 @@ class Trainer(object):
     def _loss_and_metrics(self, outs, y, logs):
         ys = y if isinstance(y, (tuple, list)) else (y,)
         total = None
+        if self.joint_head is not None:
+            self.joint_head.begin(ys, outs)
         for (name, (fn, weight)), out, yt in zip(self.losses.items(), outs, ys):
             li = fn(yt, out)
             # a fused loss head exposes the normalised embedding it computed; metrics are defined on it

@@ -16,6 +16,7 @@ look-ahead (at most 4) of a dataset that streams its images (``-stream`` names) 
 (batches are composed on the device); ``--log_dir`` writes a JSON-lines log instead of TensorBoard events.
 """
 import argparse
+import os
 import pickle
 
 import numpy as np
@@ -135,6 +136,22 @@ def head_by_default(loss, onehot_metrics, num_top_k):
     return True
 
 
+def joint_head_by_default(loss, onehot, cls_weight):
+    """Whether utils.JointEmbeddingHead (embedding loss, classifier cross-entropy and the metrics of both outputs in one launch)
+    replaces the torch composition.  It serves `--cls_weight > 0` with `--loss inv_corr | unnorm_corr | softmax_corr`, class table or
+    `onehot`, and `--cls_weight 0` with unnorm_corr / softmax_corr; `mse` with a classifier branch and inv_corr without one keep
+    what they have.  Unlike head_by_default this one changes logged values (Keras' probability clip in the classifier loss,
+    tf.nn.in_top_k's ties for top-k of logits and one-hot outputs, the kernel's summation order in the embedding loss), so it
+    stays behind the host-side switch SE_JOINT_HEAD=1 until a change that owns those differences flips the default."""
+    if os.environ.get('SE_JOINT_HEAD') != '1':
+        return False
+    if loss not in ('inv_corr', 'unnorm_corr', 'softmax_corr'):
+        return False
+    if cls_weight > 0:
+        return True
+    return loss in ('unnorm_corr', 'softmax_corr')
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description='Learns to map images onto class embeddings (MI355X build).',
                                      formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -193,7 +210,16 @@ def main(argv=None):
 
     # ---- loss / metrics (learn_image_embeddings.py:160-180)
     onehot_like = (args.loss == 'softmax_corr') or (args.embedding == 'onehot')
-    if args.loss == 'inv_corr' and args.cls_weight > 0:
+    joint = None
+    if joint_head_by_default(args.loss, args.embedding == 'onehot', args.cls_weight) and \
+            (not onehot_like or emb_dev.shape[1] == data_generator.num_classes):     # arg-max metrics read the label's column
+        # one launch per step: embedding loss, Keras' clipped cross-entropy and every metric of both outputs
+        post = (lambda o: torch.softmax(o, -1)) if (args.loss == 'softmax_corr' and args.cls_weight <= 0) else None
+        joint = utils.JointEmbeddingHead(None if args.embedding == 'onehot' else emb_dev, 'argmax' if onehot_like else 'nearest', post=post,
+                                          shared_labels=True)      # transform_inputs feeds [y, y]
+        loss = joint.inv_correlation
+        metrics = [joint.accuracy()] + [joint.accuracy(k) for k in args.top_k_acc]
+    elif args.loss == 'inv_corr' and args.cls_weight > 0:
         # the classifier branch needs the normalised embedding as a tensor of the graph (ClsModel applies the l2norm kernel);
         # the cosine loss is then the plain inv_correlation on it, like the reference (utils.py:44-46)
         loss = lambda y, o: utils.inv_correlation(emb_dev[y], o)
@@ -223,8 +249,10 @@ def main(argv=None):
     losses = {embedding_layer_name: (loss, 1.0)}
     all_metrics = {embedding_layer_name: metrics}
     if args.cls_weight > 0:
-        losses['prob'] = (categorical_crossentropy, args.cls_weight)
-        all_metrics['prob'] = [accuracy] + [utils.top_k_acc(k) for k in args.top_k_acc]
+        losses['prob'] = (joint.categorical_crossentropy if joint else categorical_crossentropy, args.cls_weight)
+        all_metrics['prob'] = ([joint.cls_accuracy()] + [joint.cls_accuracy(k) for k in args.top_k_acc]) if joint else \
+            ([accuracy] + [utils.top_k_acc(k) for k in args.top_k_acc])
+    trainer_kw = {'joint_head': joint} if joint else {}
 
     # Keras kernel regularisers folded into the update: backbone 2e-4, classifier 5e-4
     l2_of = {id(p): embed_model.regularizer for p in embed_model.regularized_parameters()} if getattr(embed_model, 'regularizer', 0) else {}
@@ -239,10 +267,10 @@ def main(argv=None):
     # ---- optional warm-up of the new layers only (learn_image_embeddings.py:183-207)
     if args.finetune and args.finetune_init > 0:
         train_cli.warm_up(args, model, losses, all_metrics, l2_of, train_seq, val_seq,
-                          lambda n: ('embedding' in n) or ('prob' in n), 'Pre-training new layers')
+                          lambda n: ('embedding' in n) or ('prob' in n), 'Pre-training new layers', **trainer_kw)
 
     # ---- main training (learn_image_embeddings.py:209-243)
-    trainer = train_cli.fit(args, model, losses, all_metrics, l2_of, data_generator, train_seq, val_seq, world)
+    trainer = train_cli.fit(args, model, losses, all_metrics, l2_of, data_generator, train_seq, val_seq, world, **trainer_kw)
 
     # ---- final evaluation (learn_image_embeddings.py:246-255)
     final = trainer.evaluate(val_seq())

@@ -15,7 +15,7 @@ from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, MET
 
 __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
-    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "embed_head_forward", "embedding_head", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
+    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "embed_head_forward", "embedding_head", "joint_head", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
     "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
     "adagrad_step_", "ADAGRAD_MAX_BLOCKS", "shortcut_add", "LAYOUT_NCHW", "LAYOUT_NHWC",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
@@ -477,6 +477,125 @@ def embedding_head(x, labels, embedding, mode="cosine", want_normalized=True, wa
     want_xhat = bool(want_normalized) and mode == "cosine"
     loss_i, xhat, n_better, n_within, best, scores = _EmbedHead.apply(x, labels, embedding, mode, want_xhat, bool(want_scores), bool(want_best))
     return EmbeddingHead(loss_i, xhat if want_xhat else None, n_better, n_within, best if want_best else None, scores if want_scores else None)
+
+
+JOINT_HEAD_METRICS = {"nearest": DEFINES["SE_HEAD_METRIC_NEAREST"], "argmax": DEFINES["SE_HEAD_METRIC_ARGMAX"]}
+JointHead = collections.namedtuple("JointHead", "emb_loss_i cls_loss_i n_better n_within p_best p_above scores z_best z_above")
+
+
+def _pitch(t):
+    """Row pitch of a 2-d tensor with contiguous rows (a single row has no meaningful stride)."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+class _JointHead(torch.autograd.Function):
+    """Embedding loss on ``p``, cross-entropy on ``logits`` and the metrics of both in one se_joint_head_fwd; the gradients with
+    respect to ``p`` and ``logits`` in one se_joint_head_bwd.  Every integer output is a non-differentiable by-product."""
+
+    @staticmethod
+    def forward(ctx, p, logits, labels, embedding, metric, want_scores):
+        require_gpu(p, labels, embedding, logits)
+        code = JOINT_HEAD_METRICS[metric]
+        _f32_rows(p, "p")
+        B, D = p.shape
+        if labels.dtype != torch.int64 or labels.numel() != B or not labels.is_contiguous():
+            raise SehipError("labels must be a contiguous int64 [B] tensor")
+        if embedding is not None:
+            _f32_rows(embedding, "embedding")
+            if embedding.shape[1] != D:
+                raise SehipError("embedding must be float32 [C, %d]" % D)
+            _check_loss_inputs(labels, embedding, "joint_head")
+            C = embedding.shape[0]
+        else:
+            C = D
+            if os.environ.get("SEHIP_CHECK_LABELS") and B and (int(labels.min()) < 0 or int(labels.max()) >= C):
+                raise IndexError("joint_head: labels span [%d, %d] but there are %d classes" % (int(labels.min()), int(labels.max()), C))
+        if logits is not None:
+            _rows(logits, "logits")
+            if logits.shape[0] != B or logits.shape[1] != C:
+                raise SehipError("logits must be [%d, %d], got %s" % (B, C, tuple(logits.shape)))
+        dev = p.device
+
+        def f32(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+
+        def i32(*shape):
+            return torch.empty(shape, dtype=torch.int32, device=dev)
+
+        nearest = metric == "nearest"
+        emb_loss_i = f32(B)
+        n_better, n_within = (i32(B), i32(B)) if nearest else (None, None)
+        p_best = i32(B)
+        p_above = None if nearest else i32(B)
+        scores = f32(B, C) if (want_scores and nearest) else None
+        cls_loss_i = aux = z_best = z_above = None
+        if logits is not None:
+            cls_loss_i, aux = f32(B), f32(call("se_softmax_xent_aux_floats", B))
+            z_best, z_above = i32(B), i32(B)
+        need = call("se_joint_head_workspace_bytes", code, B, D, C)
+        ws = torch.empty((need // 8,), dtype=torch.int64, device=dev) if need else None     # (fresh: the call may be captured in a HIP graph)
+        call("se_joint_head_fwd", p, _pitch(p), labels, embedding, _pitch(embedding) if embedding is not None else 0, B, D, C, code,
+             emb_loss_i, n_better, n_within, p_best, p_above, scores, C,
+             logits, _dtype_code(logits) if logits is not None else DTYPE_F32, _pitch(logits) if logits is not None else 0, cls_loss_i, aux,
+             z_best, z_above, ws, need)
+        ctx.save_for_backward(labels, embedding, logits, aux)
+        ctx.dims = (B, D, C)
+        empty_f, empty_i = emb_loss_i.new_empty(0), p_best.new_empty(0)
+        extras = tuple(empty_i if t is None else t for t in (n_better, n_within, p_best, p_above)) + \
+            (empty_f if scores is None else scores,) + tuple(empty_i if t is None else t for t in (z_best, z_above))
+        ctx.mark_non_differentiable(*extras)
+        if cls_loss_i is None:
+            cls_loss_i = emb_loss_i.new_empty(0)
+            ctx.mark_non_differentiable(cls_loss_i)
+        return (emb_loss_i, cls_loss_i) + extras
+
+    @staticmethod
+    def backward(ctx, grad_emb, grad_cls, *_unused):
+        labels, embedding, logits, aux = ctx.saved_tensors
+        B, D, C = ctx.dims
+        dp = dz = None
+        if ctx.needs_input_grad[0]:
+            dp = torch.empty((B, D), dtype=torch.float32, device=labels.device)
+        z = logits if (logits is not None and ctx.needs_input_grad[1]) else None
+        if z is not None:
+            dz = torch.empty((B, C), dtype=z.dtype, device=z.device)
+        ge = grad_emb.to(torch.float32).contiguous() if dp is not None else None
+        gc = grad_cls.to(torch.float32).contiguous() if dz is not None else None
+        call("se_joint_head_bwd", labels, embedding, _pitch(embedding) if embedding is not None else 0, B, D, C, ge, 0.0, dp, D,
+             z, _dtype_code(z) if z is not None else DTYPE_F32, _pitch(z) if z is not None else 0, aux, gc, 0.0, dz,
+             _dtype_code(dz) if dz is not None else DTYPE_F32, C)
+        return dp, dz, None, None, None, None
+
+
+def joint_head(p, labels, embedding, logits=None, metric="nearest", want_scores=False):
+    """The head of ``--cls_weight``: the embedding loss ``1 - <embedding[y], p>`` on the model's first output ``p`` [B, D] float32 --
+    used as it comes, the l2norm / softmax layer of the model has already run --, Keras 2.2's clipped cross-entropy on ``logits``
+    [B, C] (float32 / bfloat16; None: the embedding part alone) and the metrics of both outputs, in ONE HIP launch forward and one
+    backward (se_joint_head_fwd / se_joint_head_bwd).  ``embedding`` float32 [C, D], or None for the identity table of one-hot
+    targets (then D == C and ``metric`` must be "argmax").
+
+    Returns ``JointHead(emb_loss_i, cls_loss_i, n_better, n_within, p_best, p_above, scores, z_best, z_above)``.  ``emb_loss_i`` and
+    ``cls_loss_i`` [B] are differentiable with respect to ``p`` and ``logits``; the rest are int32 [B] by-products (``scores`` [B, C]
+    float32 with ``want_scores``), None where they do not apply:
+      metric "nearest": ``nn_accuracy(p, labels, embedding, dot_prod_sim=True, k)`` is ``(n_within >= 1) & (n_better < k)`` for every
+                        k, ``p_best`` the nearest class, ``scores`` the similarity matrix -- the bits of se_nn_accuracy;
+      metric "argmax":  ``p_best`` = arg-max of the row of p (np.argmax rules), ``p_above`` = entries strictly above the label's:
+                        ``p_best == labels`` is Keras' accuracy, ``p_above < k`` is tf.nn.in_top_k;
+      ``z_best`` / ``z_above``: the same two for the logits, ``cls_loss_i`` and they the bits of ``softmax_cross_entropy``.
+    Labels are clamped to [0, C - 1]; ``SEHIP_CHECK_LABELS=1`` checks them on the host."""
+    if metric not in JOINT_HEAD_METRICS:
+        raise SehipError("metric must be 'nearest' or 'argmax', got %r" % (metric,))
+    if embedding is None and metric != "argmax":
+        raise SehipError("joint_head: the identity table (embedding None) goes with metric 'argmax'")
+    p = p if p.stride(-1) == 1 else p.contiguous()
+    if logits is not None and logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    out = _JointHead.apply(p, logits, labels, embedding, metric, bool(want_scores))
+    emb_loss_i, cls_loss_i, n_better, n_within, p_best, p_above, scores, z_best, z_above = out
+    nearest, cls = metric == "nearest", logits is not None
+    return JointHead(emb_loss_i, cls_loss_i if cls else None, n_better if nearest else None, n_within if nearest else None, p_best,
+                     None if nearest else p_above, scores if (nearest and want_scores) else None, z_best if cls else None,
+                     z_above if cls else None)
 
 
 class _LabelEmbedLoss(torch.autograd.Function):

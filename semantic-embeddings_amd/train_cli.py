@@ -152,10 +152,10 @@ def adagrad_trainer(args, model, losses, metrics, l2_of, lr, max_decay=0.0, num_
                    memory_format=mode[1], optimizer='adagrad', **kw)
 
 
-def warm_up(args, model, losses, metrics, l2_of, train_seq, val_seq, trainable, message):
+def warm_up(args, model, losses, metrics, l2_of, train_seq, val_seq, trainable, message, **trainer_kw):
     """``--finetune_init`` epochs on the parameters ``trainable(name)`` picks; afterwards every parameter of the model trains."""
     print(message)
-    pre = _trainer(args, model, losses, metrics, l2_of, trainable=trainable)
+    pre = _trainer(args, model, losses, metrics, l2_of, trainable=trainable, **trainer_kw)
     pre.fit(train_seq(), val_seq(), epochs=args.finetune_init, verbose=not args.no_progress)
     pre.close()            # drop its gradient hooks before the second trainer registers its own
     for p in model.parameters():
@@ -175,9 +175,9 @@ class JsonLogger(utils.Callback):
                 f.write(json.dumps(dict(logs, epoch=epoch + 1)) + '\n')
 
 
-def fit(args, model, losses, metrics, l2_of, data_generator, train_seq, val_seq, world):
+def fit(args, model, losses, metrics, l2_of, data_generator, train_seq, val_seq, world, **trainer_kw):
     """The main training run under ``--lr_schedule``; returns its trainer.  ``--snapshot`` / ``--initial_epoch`` apply to the
-    scripts whose parser has them."""
+    scripts whose parser has them; ``trainer_kw`` goes to the ``Trainer`` as it is."""
     sched_args = {k: v for k, v in vars(args).items() if v is not None}
     callbacks, num_epochs = utils.get_lr_schedule(args.lr_schedule, data_generator.num_train, args.batch_size, schedule_args=sched_args)
     epochs = args.epochs if args.epochs else num_epochs
@@ -187,7 +187,7 @@ def fit(args, model, losses, metrics, l2_of, data_generator, train_seq, val_seq,
         ck = {'save_best_only': True, 'monitor': args.snapshot_best} if args.snapshot_best else {}
         callbacks.append(utils.ModelCheckpoint(args.snapshot, **ck) if world <= 1 else utils.TemplateModelCheckpoint(model, args.snapshot, **ck))
     decay = max_decay_rate(args.max_decay, data_generator.num_train, args.batch_size, epochs)
-    trainer = _trainer(args, model, losses, metrics, l2_of, decay=decay)
+    trainer = _trainer(args, model, losses, metrics, l2_of, decay=decay, **trainer_kw)
     trainer.fit(train_seq(), val_seq(), epochs=epochs, initial_epoch=getattr(args, 'initial_epoch', 0), callbacks=callbacks,
                 verbose=not args.no_progress)
     return trainer

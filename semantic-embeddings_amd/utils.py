@@ -248,6 +248,171 @@ class SquaredDistanceHead(_HeadCounts, SquaredDistanceLoss):
         return SquaredDistanceLoss.__call__(self, y_true, y_pred)
 
 
+def _softmax_crossentropy(y_true, logits):
+    """Cross-entropy of softmax(logits) against integer labels or target distributions, per sample (torch's, unclipped)."""
+    if _is_labels(y_true):
+        return torch.nn.functional.cross_entropy(logits.float(), y_true, reduction='none')
+    return -(y_true.float() * torch.log_softmax(logits.float(), dim=-1)).sum(dim=-1)
+
+
+def _argmax_accuracy(y_true, y_pred):
+    target = y_true if _is_labels(y_true) else y_true.argmax(dim=-1)
+    return (y_pred.argmax(dim=-1) == target).float()
+
+
+class JointEmbeddingHead(object):
+    """Loss and metrics of BOTH outputs of a model with a classifier branch (`--cls_weight`: the embedding output and ``prob``), or of
+    the embedding output alone, from one ``sehip.joint_head`` launch per batch and one backward launch.
+
+    ``embedding``: the class table [C, D] (float32 device tensor), or None for the identity table of ``--embedding onehot``.
+    ``metric``: 'nearest' (``max_sim_acc``: the nearest class embedding by dot product) or 'argmax' (``acc``: arg-max of the output
+    itself, for one-hot-like targets; needs D == C).  ``post``: what the loss applies to the first output before the dot product
+    (the softmax of ``--loss softmax_corr`` without a classifier branch; None: nothing).  ``shared_labels``: the caller's promise
+    that both outputs are always trained against the same labels (``transform_inputs`` feeds ``[y, y]``), for loops that hand over
+    two copies of the label array (the trainer's HIP-graph step keeps one static copy per target); without it the second target must
+    BE the first tensor, anything else falls back.
+
+    ``begin(ys, outs)`` makes the forward call for the batch; afterwards the loss callables ``inv_correlation`` and
+    ``categorical_crossentropy`` and the metrics of ``accuracy(k)`` (first output) and ``cls_accuracy(k)`` (``prob``) return its
+    results when they are called on those very tensors -- the identity + version check of ``_HeadCounts``.  On any other tensors, on
+    CPU tensors or with gathered embeddings as ``y_true`` everything is today's composition: never wrong, only slower.
+    What differs on the fast path: the classifier loss has Keras 2.2's probability clip, top-k on logits / one-hot outputs follows
+    tf.nn.in_top_k (ties in favour of the target), and the embedding loss is summed in the kernel's fixed order."""
+
+    def __init__(self, embedding, metric='nearest', post=None, shared_labels=False):
+        if metric not in ('nearest', 'argmax'):
+            raise ValueError("metric must be 'nearest' or 'argmax', got %r" % (metric,))
+        if embedding is None and metric != 'argmax':
+            raise ValueError("the identity table (embedding None) goes with metric 'argmax'")
+        self.embedding, self.metric, self.post, self.shared_labels = embedding, metric, post, bool(shared_labels)
+        self._emb_side = self._cls_side = None
+        self.inv_correlation = self._emb_loss
+        self.categorical_crossentropy = self._cls_loss
+
+    # ---- the one forward call
+
+    _key = staticmethod(_HeadCounts._key)
+
+    def _table(self, like):
+        if self.embedding is not None:
+            return self.embedding
+        return torch.eye(like.shape[-1], dtype=torch.float32, device=like.device)
+
+    def _fast(self, ys, outs):
+        if len(outs) not in (1, 2) or len(ys) != len(outs):
+            return False
+        y, p = ys[0], outs[0]
+        if not (torch.is_tensor(y) and torch.is_tensor(p) and _is_labels(y) and y.dtype == torch.int64 and y.is_contiguous()):
+            return False
+        if not (p.is_cuda and y.is_cuda and p.dim() == 2 and p.is_floating_point() and p.shape[0] == y.shape[0]):
+            return False
+        C = p.shape[1] if self.embedding is None else self.embedding.shape[0]
+        if self.embedding is not None and (not self.embedding.is_cuda or self.embedding.shape[1] != p.shape[1]):
+            return False
+        if self.metric == 'argmax' and p.shape[1] != C:
+            return False
+        if len(outs) == 2:
+            z = outs[1]
+            if not (torch.is_tensor(z) and z.is_cuda and z.dim() == 2 and tuple(z.shape) == (p.shape[0], C)
+                    and z.dtype in (torch.float32, torch.bfloat16)):
+                return False
+            y2 = ys[1]                                                                  # one label array serves both outputs
+            if not torch.is_tensor(y2):
+                return False
+            if self._key(y2) != self._key(y) and not (self.shared_labels and _is_labels(y2) and y2.dtype == y.dtype and
+                                                      y2.shape == y.shape and y2.device == y.device):
+                return False
+        return True
+
+    def begin(self, ys, outs):
+        """One ``sehip.joint_head`` for the batch: ``ys`` the targets per output, ``outs`` the model's one or two outputs."""
+        self._emb_side = self._cls_side = None
+        ys = tuple(ys) if isinstance(ys, (tuple, list)) else (ys,)
+        outs = tuple(outs) if isinstance(outs, (tuple, list)) else (outs,)
+        if not self._fast(ys, outs):
+            return False
+        p = outs[0].float()
+        if self.post is not None:
+            p = self.post(p)
+        z = outs[1] if len(outs) == 2 else None
+        out = sehip.joint_head(p, ys[0], self.embedding, logits=z, metric=self.metric)
+        # the tensors themselves are kept as well: their storage cannot be recycled for another batch while the results stand
+        self._emb_side = (ys[0], outs[0], self._key(ys[0]), self._key(outs[0]), out)
+        if z is not None:
+            self._cls_side = (ys[1], z, self._key(ys[1]), self._key(z), out)
+        return True
+
+    def _stored(self, side, y_true, y_pred):
+        if side is None or not (torch.is_tensor(y_true) and torch.is_tensor(y_pred)):
+            return None
+        if self._key(y_true) != side[2] or self._key(y_pred) != side[3]:
+            return None
+        return side[4]
+
+    # ---- losses
+
+    def _emb_loss(self, y_true, y_pred):
+        out = self._stored(self._emb_side, y_true, y_pred)
+        if out is not None:
+            return out.emb_loss_i
+        p = y_pred.float()
+        if self.post is not None:
+            p = self.post(p)
+        target = self._table(p).to(p.device)[y_true] if _is_labels(y_true) else y_true
+        return inv_correlation(target, p)
+
+    def _cls_loss(self, y_true, logits):
+        out = self._stored(self._cls_side, y_true, logits)
+        if out is not None:
+            return out.cls_loss_i
+        return _softmax_crossentropy(y_true, logits)
+
+    # ---- metrics
+
+    def _topk_fallback(self, k):
+        return _argmax_accuracy if k is None else top_k_acc(k)
+
+    def accuracy(self, k=None):
+        """The metric of the first output under today's name: ``max_sim_acc`` / ``max_sim_acc<k>`` (metric 'nearest';
+        ``utils.nn_accuracy(embedding, dot_prod_sim=True, k)``) or ``acc`` (k None: arg-max == label) / ``acc<k>``
+        (``utils.top_k_acc(k)``) for metric 'argmax'."""
+        if self.metric == 'nearest':
+            kk = 1 if k is None else max(int(k), 1)
+            fallback = nn_accuracy(self.embedding, dot_prod_sim=True, k=kk)
+            name = fallback.name
+
+            def fast(out, y_true):
+                return ((out.n_within >= 1) & (out.n_better < kk)).float()
+        else:
+            fallback = self._topk_fallback(k)
+            name = 'acc' if k is None else 'acc{}'.format(k)
+
+            def fast(out, y_true):
+                return (out.p_best == y_true).float() if k is None else (out.p_above < int(k)).float()
+
+        def metric(y_true, y_pred):
+            out = self._stored(self._emb_side, y_true, y_pred)
+            return fallback(y_true, y_pred) if out is None else fast(out, y_true)
+
+        metric.name = name
+        metric.__name__ = name
+        return metric
+
+    def cls_accuracy(self, k=None):
+        """``acc`` (k None) / ``acc<k>`` of the ``prob`` output: arg-max == label / tf.nn.in_top_k of the logits."""
+        fallback = self._topk_fallback(k)
+
+        def metric(y_true, logits):
+            out = self._stored(self._cls_side, y_true, logits)
+            if out is None:
+                return fallback(y_true, logits)
+            return (out.z_best == y_true).float() if k is None else (out.z_above < int(k)).float()
+
+        metric.name = 'acc' if k is None else 'acc{}'.format(k)
+        metric.__name__ = metric.name
+        return metric
+
+
 def devise_ranking_loss(embedding, margin=0.1):
     """DeViSE ranking loss (utils.py:103-122): fused HIP kernel (MFMA contraction with the hinge, its row sums and the
     active mask in the epilogue; the mask feeds the backward contraction).  ``y_true``: gathered embeddings [B, D] (the

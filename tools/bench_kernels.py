@@ -31,6 +31,8 @@
                                                   temporary directory, the ILSVRC preset at batch 128 with 16 decode threads: images/s of
                                                   streamed composition with look-ahead 0, 2 and 4, its split into decode, packing, upload
                                                   and tables + se_image_batch, and the resident composition of the same images)
+    python tools/bench_kernels.py joint          (the joint head of --cls_weight, forward + backward: today's torch composition, the
+                                                  embedding role and se_softmax_xent_* as separate launches, and the one joint launch)
     python tools/bench_kernels.py qg [--small] [--ranking-path]
                                                  (one query-vs-gallery AP leg, recall_precision_device(..., gallery=...): 50,000 queries x
                                                   1,281,167 gallery rows x D = 1000, 1000 classes of ~1281 rows; --small: 2,000 x 60,000 x
@@ -70,7 +72,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -108,6 +110,8 @@ def main():
         return bench_stream()
     if args.what == "head":
         return bench_head()
+    if args.what == "joint":
+        return bench_joint()
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -817,6 +821,96 @@ def bench_head(reps=40, batch=20):
                 print("head %-6s %4d x %4d x %4d %-4s: " % (mname, B, D, C, dname) +
                       "; ".join("%s %.1f (%.1f-%.1f)" % (nm, v[0], v[1], v[2]) for nm, v in zip(names, t)) +
                       "; head vs 1 / 2 / 3 metrics: x%.2f x%.2f x%.2f; bits equal %s" % (t[-3][0] / ref, t[-2][0] / ref, t[-1][0] / ref, same))
+
+
+def bench_joint(reps=40, batch=10):
+    """Joint head of `--cls_weight` (learn_image_embeddings.py with SE_JOINT_HEAD=1), forward + backward of loss and metrics for one
+    batch, three sequences timed alternately in one process (per shape `reps` windows of `batch` back-to-back steps, HIP events
+    around a window; median / 10th / 90th percentile of the per-step time):
+      composition  today's default: utils.inv_correlation(emb[y], p) + nn.functional.cross_entropy through autograd, and per metric
+                   one utils.nn_accuracy (class table) or arg-max / top-k (one-hot) on the first output and arg-max / top-k on the
+                   logits; with 1 and with 3 metrics per output (no --top_k_acc, two k)
+      separate     se_joint_head_fwd without logits + se_softmax_xent_fwd, se_joint_head_bwd without logits + se_softmax_xent_bwd:
+                   four launches on preallocated buffers
+      joint        one se_joint_head_fwd + one se_joint_head_bwd on the same buffers
+    The two kernel sequences deliver the counts every k is read from, so the number of metrics does not change them."""
+    import utils
+    from sehip._lib import call
+
+    def windows(fns):
+        for f in fns:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(reps):
+            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(batch):
+                    f()
+                b.record()
+                torch.cuda.synchronize()
+                ts[k].append(a.elapsed_time(b) / batch * 1e3)
+        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
+
+    print("joint head, forward + backward: torch composition (1 / 3 metrics per output) vs separate launches vs one joint launch; us per "
+          "step, median (10th-90th percentile) of %d windows of %d steps, candidates alternating" % (reps, batch))
+    for B, D, C, onehot in ((128, 100, 100, False), (96, 200, 200, False), (128, 555, 555, False), (128, 1000, 1000, False),
+                            (128, 8142, 8142, True)):
+        rng = np.random.default_rng(B + D + C)
+        p = torch.from_numpy(rng.standard_normal((B, D)).astype(np.float32)).cuda()
+        p = torch.softmax(p, -1) if onehot else torch.nn.functional.normalize(p, dim=-1)
+        z = torch.from_numpy(rng.standard_normal((B, C)).astype(np.float32) * 3).cuda()
+        y = torch.from_numpy(rng.integers(0, C, B)).cuda()
+        emb = None
+        if not onehot:
+            emb = torch.from_numpy(rng.standard_normal((C, D)).astype(np.float32)).cuda()
+            sehip.normalize_rows_(emb)
+        table = torch.eye(C, device="cuda") if onehot else emb
+        metric = 1 if onehot else 0
+        f = lambda *s: torch.empty(s, dtype=torch.float32, device="cuda")
+        i = lambda *s: torch.empty(s, dtype=torch.int32, device="cuda")
+        out = {n: dict(el=f(B), nb=i(B), nw=i(B), pb=i(B), pa=i(B), cl=f(B), aux=f(3 * B), zb=i(B), za=i(B), dp=f(B, D), dz=f(B, C)) for n in ("sep", "joint")}
+        need = call("se_joint_head_workspace_bytes", metric, B, D, C)
+        ws = torch.empty(max(need // 8, 1), dtype=torch.int64, device="cuda")
+        lde = D if emb is not None else 0
+        wc = 0.1 / B
+
+        def kernels(o, joint):
+            zz = z if joint else None
+            call("se_joint_head_fwd", p, D, y, emb, lde, B, D, C, metric, o["el"], o["nb"], o["nw"], o["pb"], o["pa"], None, C,
+                 zz, 0, C, o["cl"] if joint else None, o["aux"] if joint else None, o["zb"], o["za"], ws, need)
+            if not joint:
+                call("se_softmax_xent_fwd", z, 0, C, y, B, C, 0.0, o["cl"], o["aux"], o["zb"], o["za"], None)
+            call("se_joint_head_bwd", y, emb, lde, B, D, C, None, 1.0 / B, o["dp"], D, zz, 0, C, o["aux"] if joint else None, None, wc,
+                 o["dz"] if joint else None, 0, C)
+            if not joint:
+                call("se_softmax_xent_bwd", z, 0, C, y, o["aux"], None, wc, B, C, 0.0, o["dz"], 0, C)
+
+        first = [utils.nn_accuracy(emb, dot_prod_sim=True, k=k) for k in (1, 5, 10)] if not onehot else \
+            [lambda yt, o: (o.argmax(-1) == yt).float(), utils.top_k_acc(5), utils.top_k_acc(10)]
+        second = [lambda yt, o: (o.argmax(-1) == yt).float(), utils.top_k_acc(5), utils.top_k_acc(10)]
+
+        def composition(n):
+            pp, zz = p.detach().requires_grad_(True), z.detach().requires_grad_(True)
+            total = utils.inv_correlation(table[y], pp).mean() + 0.1 * torch.nn.functional.cross_entropy(zz, y, reduction="none").mean()
+            with torch.no_grad():
+                for m in first[:n]:
+                    m(y, pp.detach()).sum()
+                for m in second[:n]:
+                    m(y, zz.detach()).sum()
+            total.backward()
+            return pp.grad, zz.grad
+
+        t = windows([lambda: composition(1), lambda: composition(3), lambda: kernels(out["sep"], False), lambda: kernels(out["joint"], True)])
+        same = all(torch.equal(out["sep"][k].view(torch.int32), out["joint"][k].view(torch.int32))
+                   for k in ("el", "cl", "aux", "zb", "za", "dp", "dz", "pb") + (("pa",) if onehot else ("nb", "nw")))
+        names = ["composition, 1 metric", "composition, 3 metrics", "separate launches", "joint launch"]
+        print("joint %4d x %4d x %4d %-7s: " % (B, D, C, "one-hot" if onehot else "table") +
+              "; ".join("%s %.1f (%.1f-%.1f)" % (nm, v[0], v[1], v[2]) for nm, v in zip(names, t)) +
+              "; separate / joint: x%.2f; composition (1 / 3 metrics) / joint: x%.2f x%.2f; separate and joint bits equal %s" %
+              (t[2][0] / t[3][0], t[0][0] / t[3][0], t[1][0] / t[3][0], same))
 
 
 def bench_image(B=128, reps=20, stored=256):

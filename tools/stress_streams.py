@@ -63,6 +63,18 @@ ag_p, ag_a, ag_g = dev(f32(3000005)), dev(np.abs(f32(3000005))), dev(f32(3000005
 ag_l2 = dev(np.full(3000005, 4e-4, dtype=np.float32))
 
 
+zb = dev(f32(4096, C) * 3)                                         # logits: a wave per row
+zb_wide = dev(f32(512, 1000) * 3)
+
+
+def joint_step(p, table, z, metric):
+    """one se_joint_head_fwd and one se_joint_head_bwd through autograd"""
+    p, z = p.detach().requires_grad_(True), z.detach().requires_grad_(True)
+    out = sehip.joint_head(p, yb[:p.shape[0]], table, logits=z, metric=metric)
+    dp, dz = torch.autograd.grad(out.emb_loss_i.sum() + 0.1 * out.cls_loss_i.sum(), (p, z))
+    return tuple(t.detach() for t in out if t is not None) + (dp, dz)
+
+
 def as_tuple(r):
     return tuple(r) if isinstance(r, (tuple, list)) else (r,)
 
@@ -88,6 +100,9 @@ OPS = {
     "nn_accuracy": lambda: sehip.nn_accuracy(xb, yb, emb, dot_prod_sim=True, k=5),
     "embed_head cosine": lambda: sehip.embed_head_forward(xb, yb, emb, mode="cosine", want_best=True),
     "embed_head sqdist, class slices": lambda: sehip.embed_head_forward(xb[:512], yb[:512], emb_wide, mode="sqdist", want_dist=True, want_best=True),
+    "joint_head nearest fwd+bwd": lambda: joint_step(xb, emb, zb, "nearest"),
+    "joint_head nearest, class slices": lambda: joint_step(xb[:512], emb_wide, zb_wide, "nearest"),
+    "joint_head argmax, one-hot": lambda: joint_step(zb, None, zb, "argmax"),
     "devise_ranking_loss": lambda: sehip.devise_ranking_loss(xb, yb, emb),
     "image_batch": lambda: sehip.image_batch(img_arena, img_t["src_off"], img_t["src_hw"], img_t["xmap"], img_t["xk"], img_t["ymap"], img_t["yk"],
                                              img_t["erase"], img_t["seed"], img_stats[0], img_stats[1]),
