@@ -29,6 +29,7 @@
 #ifndef SEHIP_H
 #define SEHIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -401,6 +402,57 @@ int se_softmax_xent_bwd(const void *logits, int z_dtype, int64_t ldz, const int6
 #define SE_ADAGRAD_MAX_BLOCKS 2048
 int se_adagrad_step(float *p, float *accum, const float *g, const float *l2, int64_t n, float lr, const float *lr_dev,
                     float grad_scale, float epsilon, se_stream_t stream);
+
+/*
+ * Keras 2.2 SGD on a flat float32 parameter buffer with a deterministic global-norm clip: the norm and clip factor of the
+ * regularised gradient (se_grad_clip_factor: one launch over the buffers and a one-wave finalising launch), then the whole update in
+ * one launch (se_sgd_step) -- gradient scale, L2 regulariser, clip factor, learning rate, momentum and Nesterov folded in.
+ * Replaces: Keras 2.2 optimizers.SGD.get_updates with clipnorm [third party, not in the reference tree] as every trainer of
+ *           learn_image_embeddings.py / learn_classifier.py / learn_center_loss.py / learn_labelembedding.py compiles it
+ *           (keras.optimizers.SGD(lr=..., momentum=0.9, nesterov=..., clipnorm=args.clipgrad)), and the whole-buffer passes that
+ *           otherwise scale the gradient, add the regulariser's, take the norm, clip, and apply velocity and weights one by one.
+ *   Common to both: g [n] in, ONLY READ (after the calls it still holds the raw gradient, neither scaled, regularised nor clipped);
+ *   l2 [n] or NULL: the coefficient 2 lambda of every element; per element, every operation a separately rounded float32 operation
+ *   (no FMA contraction; correctly rounded division):
+ *       g1 = grad_scale == 1 ? g : g * grad_scale
+ *       g2 = l2 ? g1 + l2 * p : g1
+ *   Any pointer alignment and any n: 16-byte accesses when every buffer of the call is 16-byte aligned (the n % 4 last elements
+ *   are taken one by one), 4-byte accesses otherwise; int64 indices; grids capped at SE_SGD_MAX_BLOCKS workgroups of 256 threads
+ *   that stride over the buffers.  Asynchronous on `stream`, no allocation, no atomics, no host synchronisation: capturable in a
+ *   HIP graph, and the same inputs give the same bits.
+ *
+ * se_grad_clip_factor: stats[0] = norm = (float)sqrt(S), S = sum of (double)g2 * (double)g2 in float64 (a float32 square is exact
+ *   in float64); stats[1] = factor = min(clipnorm / (norm + 1e-12f), 1.0f) with a float32 sum and a float32 quotient, NaN for a
+ *   NaN norm (and 0 for an infinite one): the value of torch.clamp(clipnorm / (norm + 1e-12), max=1.0).
+ *   p [n] may be NULL when l2 is.  workspace: se_grad_clip_workspace_bytes() bytes of device memory, 8-byte aligned; its contents
+ *   before the call do not matter and nothing is kept in it between calls.  stats: 2 floats of device memory.
+ *   The order of the additions is fixed by n and the alignment class (16-byte or not) alone: thread t of workgroup b adds its
+ *   elements in ascending order (four per 16-byte unit; the n % 4 tail elements go to threads 0 .. 2 of workgroup 0, behind their units), the 64 lanes
+ *   of a wave are summed by one xor butterfly (offsets 32, 16, ... 1), the four waves in order, and each workgroup writes its float64
+ *   partial to workspace[b]; the finalising wave adds partials lane, lane + 64, ... in ascending order and its lanes by the same
+ *   butterfly.  No floating-point atomics.
+ *   n = 0 returns SE_OK without a launch and leaves stats alone; n < 0, a clipnorm that is not finite and > 0, a NULL g /
+ *   workspace / stats with n > 0, a workspace that is not 8-byte aligned, or l2 without p is SE_ERR_INVALID.
+ *
+ * se_sgd_step: p [n] in / out, v [n] in / out (the velocity, zeros before the first step).  Per element, each operation rounded:
+ *       g3   = clip_dev ? g2 * clip_dev[0] : g2               clip_dev = &stats[1] of se_grad_clip_factor
+ *       step = lr * g3
+ *       v'   = momentum * v - step                            Keras: v = self.momentum * m - lr * g
+ *       p'   = nesterov ? (p + momentum * v') - step          Keras: p + self.momentum * v - lr * g
+ *                       : p + v'
+ *   lr_dev NULL: the learning rate is the argument lr; otherwise it is read from lr_dev[0] on the device when the kernel runs (lr
+ *   is then ignored), as clip_dev[0] is, so a captured launch follows a schedule without being captured again.
+ *   Words that are +0 in p, v, g and l2 stay +0 in p and v (for a finite factor and learning rate); a NaN or Inf in g, or a NaN
+ *   factor, spreads as the formula says: it is not an error.
+ *   n = 0 returns SE_OK without a launch (every pointer may then be NULL); n < 0, a momentum < 0 or NaN, or a NULL p / v / g with
+ *   n > 0 is SE_ERR_INVALID.
+ */
+#define SE_SGD_MAX_BLOCKS 2048
+size_t se_grad_clip_workspace_bytes(void);
+int se_grad_clip_factor(const float *g, const float *p, const float *l2, int64_t n, float grad_scale, float clipnorm,
+                        void *workspace, float *stats, se_stream_t stream);
+int se_sgd_step(float *p, float *v, const float *g, const float *l2, int64_t n, float lr, const float *lr_dev,
+                float grad_scale, const float *clip_dev, float momentum, int nesterov, se_stream_t stream);
 
 /*
  * The pyramidal residual shortcut in one launch, and the gradient of its pooled operand:

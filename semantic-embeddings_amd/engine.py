@@ -195,14 +195,19 @@ class Trainer(object):
     A batch from the sequences is ``(X, y)`` or ``(X, [y_1, y_2, ...])``.
     optimizer: 'sgd' (Keras SGD with ``momentum`` / ``nesterov``) or 'adagrad' (Keras Adagrad with ``epsilon``: ``flat.flat_v`` is the
              accumulator of squared gradients, ``momentum`` and ``nesterov`` are ignored); both with ``lr / (1 + decay * iterations)``.
+    fused_sgd: True (opt-in; 'sgd' on a GPU only, ``ValueError`` otherwise): the update is ``sehip.grad_clip_factor`` +
+             ``sehip.sgd_step_`` -- two launches and a one-wave one instead of the whole-buffer torch lines; ``flat_g`` is only read
+             and ``grad_stats`` holds the device [norm, clip factor] of the last update (None without ``clipnorm``).
     joint_head: a ``utils.JointEmbeddingHead`` whose loss callables and metrics are among ``losses`` / ``metrics``: every step calls
              its ``begin(ys, outs)`` once before they run, so that one launch serves them all.  None: nothing changes."""
 
     def __init__(self, model, losses, metrics=None, lr=0.1, momentum=0.9, nesterov=False, clipnorm=None, decay=0.0,
                  l2_of=None, autocast_dtype=torch.bfloat16, bucket_bytes=25 << 20, trainable=None, memory_format=None,
-                 optimizer='sgd', epsilon=1e-7, joint_head=None):
+                 optimizer='sgd', epsilon=1e-7, joint_head=None, fused_sgd=False):
         if optimizer not in ('sgd', 'adagrad'):
             raise ValueError("optimizer must be 'sgd' or 'adagrad', got %r" % (optimizer,))
+        if fused_sgd and optimizer != 'sgd':
+            raise ValueError("fused_sgd=True is the fused form of optimizer='sgd', not of %r" % (optimizer,))
         self.optimizer, self.epsilon = optimizer, float(epsilon)
         self.model = model
         self.memory_format = memory_format       # None: leave model and batches as they come (channels_last by construction)
@@ -221,6 +226,17 @@ class Trainer(object):
                 p.requires_grad_(trainable(name))
         self.flat = FlatState(model, l2_of)
         self.reducer = BucketedAllReduce(self.flat, bucket_bytes)
+        # fused_sgd: apply_update is sehip.grad_clip_factor (with clipnorm) + sehip.sgd_step_ instead of the whole-buffer torch lines
+        self.fused_sgd = bool(fused_sgd)
+        self.grad_stats = None               # fused_sgd with clipnorm: device [norm, clip factor] of the last update; never synchronised here
+        if self.fused_sgd:
+            if not self.flat.flat_p.is_cuda:
+                raise ValueError('fused_sgd=True needs the parameters on a GPU (they are on %s): the kernels have no CPU form'
+                                 % (self.flat.flat_p.device,))
+            if self.clipnorm:
+                dev = self.flat.flat_p.device
+                self._clip_ws = torch.empty(int(sehip.lib().se_grad_clip_workspace_bytes()), dtype=torch.uint8, device=dev)
+                self.grad_stats = torch.zeros(2, dtype=torch.float32, device=dev)
         self.stop_training = False
         self._graph = None
         self._graph_tried = False
@@ -450,6 +466,8 @@ class Trainer(object):
         ``optimizer='adagrad'``: one ``sehip.adagrad_step_`` launch instead (``_apply_adagrad``)."""
         if self.optimizer == 'adagrad':
             return self._apply_adagrad(grad_scale, lr_tensor, count)
+        if self.fused_sgd:
+            return self._apply_fused_sgd(grad_scale, lr_tensor, count)
         flat = self.flat
         g = flat.flat_g
         if grad_scale != 1.0:
@@ -474,6 +492,26 @@ class Trainer(object):
                 flat.flat_p.add_(v, alpha=self.momentum).add_(g, alpha=-lr)
             else:
                 flat.flat_p.add_(v)
+        if count:
+            self.iterations += 1
+
+    def _apply_fused_sgd(self, grad_scale, lr_tensor, count):
+        """The same Keras-SGD update as ``sehip.grad_clip_factor`` (only with ``clipnorm``: norm and clip factor of the scaled,
+        regularised gradient into ``grad_stats``) followed by ONE ``sehip.sgd_step_`` launch that reads the factor on the device.
+        ``flat_g`` stays as backward or the all-reduce wrote it, and eager and captured calls use one arithmetic."""
+        flat = self.flat
+        g, l2 = flat.flat_g, flat.flat_l2 if flat.has_l2 else None
+        clip = None
+        if self.clipnorm:
+            sehip.grad_clip_factor(g, flat.flat_p, l2, grad_scale=grad_scale, clipnorm=self.clipnorm, workspace=self._clip_ws,
+                                   out=self.grad_stats)
+            clip = self.grad_stats[1:]
+        if lr_tensor is not None:
+            lr = lr_tensor
+        else:
+            lr = self.lr / (1.0 + self.decay * self.iterations) if self.decay > 0 else self.lr
+        sehip.sgd_step_(flat.flat_p, flat.flat_v, g, l2, lr=lr, grad_scale=grad_scale, clip=clip, momentum=self.momentum,
+                        nesterov=self.nesterov)
         if count:
             self.iterations += 1
 

@@ -30,7 +30,7 @@ Param = collections.namedtuple("Param", "ctype pointee name")     # pointee: ele
 Prototype = collections.namedtuple("Prototype", "restype params stream")   # stream: a trailing se_stream_t follows params
 
 _SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "se_stream_t": ctypes.c_void_p}
-_RESTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
+_RESTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
 # torch dtypes a tensor may have for a pointer to each element type (int16 / int32 carry the bit patterns of unsigned data)
 _POINTEES = {"float": (torch.float32,), "double": (torch.float64,), "int32_t": (torch.int32,), "int64_t": (torch.int64,),
              "uint16_t": (torch.int16, torch.uint16), "uint32_t": (torch.int32, torch.uint32), "char *": (),

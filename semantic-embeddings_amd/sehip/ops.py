@@ -17,7 +17,7 @@ __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
     "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "embed_head_forward", "embedding_head", "joint_head", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
     "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
-    "adagrad_step_", "ADAGRAD_MAX_BLOCKS", "shortcut_add", "LAYOUT_NCHW", "LAYOUT_NHWC",
+    "adagrad_step_", "ADAGRAD_MAX_BLOCKS", "grad_clip_factor", "sgd_step_", "SGD_MAX_BLOCKS", "shortcut_add", "LAYOUT_NCHW", "LAYOUT_NHWC",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
@@ -795,6 +795,71 @@ def adagrad_step_(p, accum, g, l2=None, lr=0.01, grad_scale=1.0, epsilon=1e-7):
             raise SehipError("a learning-rate tensor must hold one float32 value on %s" % (p.device,))
         lr, lr_dev = 0.0, lr
     call("se_adagrad_step", p, accum, g, l2, n, float(lr), lr_dev, float(grad_scale), float(epsilon))
+    return p
+
+
+SGD_MAX_BLOCKS = DEFINES["SE_SGD_MAX_BLOCKS"]     # grid cap of se_grad_clip_factor / se_sgd_step: 256 threads per workgroup, 4 elements per thread
+
+
+def _flat_f32(n, device, *named):
+    """Every tensor of ``named`` ((tensor or None, name) pairs) is a contiguous float32 tensor of ``n`` elements on ``device``."""
+    for t, what in named:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or t.device != device):
+            raise SehipError("%s must be a contiguous float32 tensor of %d elements on %s" % (what, n, device))
+
+
+def _lr_arg(lr, device):
+    """``(lr, lr_dev)`` of an entry point that reads its learning rate from the argument or from a device scalar."""
+    if not torch.is_tensor(lr):
+        return float(lr), None
+    require_gpu(lr)
+    if lr.dtype != torch.float32 or lr.numel() != 1 or lr.device != device:
+        raise SehipError("a learning-rate tensor must hold one float32 value on %s" % (device,))
+    return 0.0, lr
+
+
+def grad_clip_factor(g, p=None, l2=None, grad_scale=1.0, clipnorm=None, workspace=None, out=None):
+    """``stats`` = [norm, factor] (a 2-element float32 device tensor) of the regularised gradient ``g2 = g * grad_scale + l2 * p``
+    (``se_grad_clip_factor``: two launches): the Euclidean norm, its squares summed in float64 in an order that ``g.numel()`` and the
+    pointers' alignment fix, and ``factor = min(clipnorm / (norm + 1e-12), 1)``, NaN for a NaN norm -- what
+    ``torch.clamp(clipnorm / (norm + 1e-12), max=1.0)`` gives.  ``g``, ``p`` and ``l2`` (None: no regulariser; ``p`` is then not
+    read) are contiguous float32 device tensors of one size and only read.  ``workspace`` (any device tensor of at least
+    ``se_grad_clip_workspace_bytes()`` bytes) and ``out`` are used when given, so that a captured call allocates nothing.  Of an
+    empty ``g`` the norm is 0 and the factor 1 when ``out`` is not given; a given ``out`` is left alone."""
+    require_gpu(g, p, l2, workspace, out)
+    if clipnorm is None:
+        raise SehipError("grad_clip_factor needs clipnorm")
+    n = g.numel()
+    _flat_f32(n, g.device, (g, "g"), (p, "p"), (l2, "l2"))
+    if l2 is not None and p is None:
+        raise SehipError("l2 needs p")
+    need = int(call("se_grad_clip_workspace_bytes"))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=g.device)
+    elif workspace.numel() * workspace.element_size() < need or not workspace.is_contiguous() or workspace.device != g.device:
+        raise SehipError("the workspace must be a contiguous tensor of at least %d bytes on %s" % (need, g.device))
+    if out is None:
+        out = torch.tensor([0.0, 1.0], dtype=torch.float32, device=g.device)
+    elif out.dtype != torch.float32 or out.numel() != 2 or not out.is_contiguous() or out.device != g.device:
+        raise SehipError("out must be a contiguous float32 tensor of 2 elements on %s" % (g.device,))
+    call("se_grad_clip_factor", g, p if l2 is not None else None, l2, n, float(grad_scale), float(clipnorm), workspace, out)
+    return out
+
+
+def sgd_step_(p, v, g, l2=None, lr=0.01, grad_scale=1.0, clip=None, momentum=0.9, nesterov=False):
+    """In place, one launch (``se_sgd_step``): Keras 2.2's SGD update ``v = momentum * v - lr * g3; p += v`` (Nesterov:
+    ``p += momentum * v - lr * g3``) with ``g3 = (g * grad_scale + l2 * p) * clip[0]`` (keras.optimizers.SGD with ``clipnorm``; every
+    operation a separately rounded float32 operation, include/sehip.h).  ``p``, ``v``, ``g`` and ``l2`` (None: no regulariser) are
+    contiguous float32 device tensors of one size; ``g`` is only read.  ``lr``: a float, or a 0-dim float32 device tensor that is read
+    on the device when the kernel runs (a captured launch then follows the schedule).  ``clip``: None, or a float32 device tensor
+    whose first element is read on the device as the clip factor (``grad_clip_factor(...)[1:]``).  Returns ``p``."""
+    require_gpu(p, v, g, l2, clip)
+    n = p.numel()
+    _flat_f32(n, p.device, (p, "p"), (v, "v"), (g, "g"), (l2, "l2"))
+    lr, lr_dev = _lr_arg(lr, p.device)
+    if clip is not None and (clip.dtype != torch.float32 or clip.numel() < 1 or clip.device != p.device):
+        raise SehipError("a clip-factor tensor must hold a float32 value on %s" % (p.device,))
+    call("se_sgd_step", p, v, g, l2, n, lr, lr_dev, float(grad_scale), clip, float(momentum), int(bool(nesterov)))
     return p
 
 

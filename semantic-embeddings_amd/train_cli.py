@@ -132,8 +132,9 @@ def load_pretrained(model, path, dev):
 
 def _trainer(args, model, losses, metrics, l2_of, **kw):
     mode = backbone_mode(args.architecture)       # (autocast dtype, memory format) of the PyTorch-ROCm backbone
+    # SE_FUSED_SGD=1: the fused clip + update kernels (engine.Trainer(fused_sgd=True)); the default stays the torch composition
     return Trainer(model, losses, metrics, lr=args.sgd_lr, momentum=0.9, nesterov=args.nesterov, clipnorm=args.clipgrad,
-                   l2_of=l2_of, autocast_dtype=mode[0], memory_format=mode[1], **kw)
+                   l2_of=l2_of, autocast_dtype=mode[0], memory_format=mode[1], fused_sgd=os.environ.get('SE_FUSED_SGD') == '1', **kw)
 
 
 def max_decay_rate(max_decay, num_train, batch_size, epochs):

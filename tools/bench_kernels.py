@@ -17,6 +17,10 @@
     python tools/bench_kernels.py adagrad        (se_adagrad_step over the flat buffers of ResNet-110-fc and ResNet-50, with and without the
                                                   regulariser, next to the torch composition of the same update, and the ResNet-110-fc
                                                   DeViSE training step next to the cosine-loss one)
+    python tools/bench_kernels.py sgd            (the fused Keras-SGD pair sehip.grad_clip_factor + sehip.sgd_step_ next to the torch composition
+                                                  of Trainer.apply_update at 1.75 M, 25.6 M and 68 M floats per buffer, {clip + regulariser,
+                                                  clip only, neither} x {plain, Nesterov}, and the ResNet-110-fc cosine-loss step with and
+                                                  without Trainer(fused_sgd=True))
     python tools/bench_kernels.py labelembed     (label-embedding loss forward + backward on the learned table next to the composition it
                                                   replaces -- Embedding gather, loss on the gathered rows, torch's embedding backward -- as
                                                   bare kernels and through autograd, and the ResNet-110-fc label-embedding training step
@@ -72,7 +76,7 @@ def timeit(fn, reps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -98,6 +102,8 @@ def main():
         return bench_image()
     if args.what == "adagrad":
         return bench_adagrad()
+    if args.what == "sgd":
+        return bench_sgd()
     if args.what == "labelembed":
         return bench_labelembed()
     if args.what == "tiny":
@@ -1254,6 +1260,123 @@ def bench_adagrad(reps=40, batch=20, steps=200):
         step = float(np.median(ms[name]))
         print("ResNet-110-fc %s, batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d steps; %s), "
               "%.0f images/s" % (what, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
+
+
+def bench_sgd(reps=30, batch=10, steps=200):
+    """The Keras-SGD update of the four SGD trainers (engine.Trainer.apply_update): the fused pair sehip.grad_clip_factor +
+    sehip.sgd_step_ next to the torch composition of the same update, whose lines are copied here as the trainer runs them in a
+    captured step (learning rate in a device scalar, one process: no gradient scale).  Flat buffers of 1.75 M (ResNet-110-fc), 25.6 M
+    (ResNet-50) and 68 M floats (the [8142, 8142] label-embedding table and its backbone); {clip + regulariser, clip only, neither} x
+    {plain, Nesterov}; the candidates timed alternately in one process: `reps` windows of `batch` back-to-back calls each (HIP events
+    around a window) after 3 warm-up calls, median / 10th / 90th percentile of the per-call time.  Bytes of the fused pair: 1 stream (3
+    with the regulariser) for the norm, 3 (4) in and 2 out for the update, over its time, against the 6.29 TB/s a float4 copy
+    reaches on MI355X; the 7 MB buffers stay in the on-chip caches between calls, so theirs is not an HBM rate.  Then one
+    ResNet-110-fc training step (batch 128, fp32, HIP-graph replay, cosine loss, clipnorm 10) with Trainer(fused_sgd=True) next to the
+    default trainer, the two timed alternately."""
+    sys.path.insert(0, os.path.join(ROOT, "semantic-embeddings_amd"))
+    import utils
+    from datasets import SyntheticGenerator
+    from engine import Trainer
+    HBM = 6.29e12
+    lr, mom, clipnorm = 0.001, 0.9, 10.0
+
+    def windows(fns):
+        for f in fns:
+            for _ in range(3):
+                f()
+        torch.cuda.synchronize()
+        ts = [[] for _ in fns]
+        for _ in range(reps):
+            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(batch):
+                    f()
+                b.record()
+                torch.cuda.synchronize()
+                ts[k].append(a.elapsed_time(b) / batch * 1e3)
+        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
+
+    for n in (1750016, 25600000, 68000000):
+        gen = torch.Generator(device="cuda").manual_seed(0)
+        p = torch.randn(n, device="cuda", generator=gen) * 0.05
+        g = torch.randn(n, device="cuda", generator=gen) * 1e-2
+        l2 = torch.full((n,), 1e-3, device="cuda")
+        v, gc = torch.zeros_like(p), g.clone()                # gc: the composition overwrites its gradient
+        lr_t = torch.full((), lr, device="cuda")
+        ws = torch.empty(sehip.SGD_MAX_BLOCKS * 8, dtype=torch.uint8, device="cuda")
+        stats = torch.zeros(2, device="cuda")
+
+        def fused(clip, reg, nesterov):
+            def f():
+                if clip:
+                    sehip.grad_clip_factor(g, p, l2 if reg else None, clipnorm=clipnorm, workspace=ws, out=stats)
+                sehip.sgd_step_(p, v, g, l2 if reg else None, lr=lr_t, clip=stats[1:] if clip else None, momentum=mom, nesterov=nesterov)
+            return f
+
+        def composition(clip, reg, nesterov):
+            def f():                                          # engine.Trainer.apply_update with lr_tensor, grad_scale == 1
+                if reg:
+                    gc.addcmul_(l2, p)
+                if clip:
+                    norm = torch.linalg.vector_norm(gc)
+                    gc.mul_(torch.clamp(clipnorm / (norm + 1e-12), max=1.0))
+                step = gc * lr_t
+                v.mul_(mom).sub_(step)
+                if nesterov:
+                    p.add_(v, alpha=mom).sub_(step)
+                else:
+                    p.add_(v)
+            return f
+
+        configs = [(c, r, nes) for c, r in ((True, True), (True, False), (False, False)) for nes in (False, True)]
+        res = windows([fn(*cfg) for cfg in configs for fn in (fused, composition)])
+        assert bool(torch.isfinite(p).all()) and bool(torch.isfinite(v).all())
+        for i, (clip, reg, nes) in enumerate(configs):
+            k, t = res[2 * i], res[2 * i + 1]
+            streams = ((3 if reg else 1) if clip else 0) + (4 if reg else 3) + 2
+            gbs = streams * 4.0 * n / (k[0] * 1e-6)
+            verdict = "the ranges overlap" if k[2] >= t[1] else "apart"
+            print("sgd %d floats per buffer (%.1f MB), %s, %s: fused %.1f us (%.1f-%.1f), torch composition %.1f us (%.1f-%.1f): x%.2f, %s; "
+                  "the fused pair moves %.0f MB = %.0f GB/s = %.1f%% of the HBM copy rate"
+                  % (n, 4.0 * n / 1e6, "clip + regulariser" if reg else ("clip only" if clip else "no clip, no regulariser"),
+                     "Nesterov" if nes else "plain", k[0], k[1], k[2], t[0], t[1], t[2], t[0] / k[0], verdict, streams * 4.0 * n / 1e6,
+                     gbs / 1e9, 100.0 * gbs / HBM), flush=True)
+        del p, g, l2, v, gc
+
+    E = np.load(os.path.join(ROOT, "tests", "golden", "embeddings.npz"))["cifar100_unitsphere"]
+    Ed = torch.from_numpy(E.astype(np.float32)).cuda()
+    trainers = {}
+    for name in ("composition", "fused"):
+        torch.manual_seed(0)
+        model = utils.build_network(100, "resnet-110-fc", input_channels=3).cuda()
+        l2_of = {id(p): model.regularizer for p in model.regularized_parameters()}
+        tr = Trainer(model, {"l2norm": (utils.CosineEmbeddingLoss(Ed), 1.0)}, {"l2norm": [utils.nn_accuracy(Ed, dot_prod_sim=True)]},
+                     lr=0.1, momentum=0.9, clipnorm=10.0, l2_of=l2_of, autocast_dtype=None, memory_format=torch.contiguous_format,
+                     fused_sgd=name == "fused")
+        seq = SyntheticGenerator(100, 32, 3, 128 * 8, 128).train_sequence(128, shuffle=False)
+        batches = [seq[i] for i in range(8)]
+        assert tr.enable_graphs(*batches[0]), name
+        for i in range(10):
+            tr.train_step(*batches[i % 8], {})
+        trainers[name] = (tr, batches)
+    ms = {name: [] for name in trainers}
+    for _ in range(5):                       # alternate the two trainers: the same machine state for both
+        for name, (tr, batches) in trainers.items():
+            logs = {}
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for i in range(steps):
+                tr.train_step(*batches[i % 8], logs)
+            b.record()
+            torch.cuda.synchronize()
+            assert np.isfinite(float(logs["loss"]))
+            ms[name].append(a.elapsed_time(b) / steps)
+    for name, what in (("composition", "default trainer (torch composition)"), ("fused", "Trainer(fused_sgd=True), as SE_FUSED_SGD=1 builds it")):
+        step = float(np.median(ms[name]))
+        print("ResNet-110-fc cosine-loss step, %s, batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 5 x %d steps; %s), "
+              "%.0f images/s" % (what, step, steps, ", ".join("%.3f" % v for v in sorted(ms[name])), 128 / step * 1e3))
 
 
 def bench_shortcut(reps=30, batch=10, B=128):

@@ -61,6 +61,14 @@ img_stats = (dev(np.float32([125.3, 129.7, 118.5])), dev(np.float32([57.0, 56.7,
 # one Adagrad step over 3,000,005 parameters (two trips of the grid-stride loop and a tail), regulariser and scale folded in
 ag_p, ag_a, ag_g = dev(f32(3000005)), dev(np.abs(f32(3000005))), dev(f32(3000005))
 ag_l2 = dev(np.full(3000005, 4e-4, dtype=np.float32))
+# the fused SGD pair over the same buffers: norm + clip factor (a workgroup reduction and a finalising wave), then the update
+sgd_ws = torch.empty(sehip.SGD_MAX_BLOCKS * 8, dtype=torch.uint8, device="cuda")
+
+
+def sgd_pair(p, v):
+    stats = sehip.grad_clip_factor(ag_g, p, ag_l2, grad_scale=0.5, clipnorm=10.0, workspace=sgd_ws)
+    sehip.sgd_step_(p, v, ag_g, ag_l2, lr=0.01, grad_scale=0.5, clip=stats[1:], momentum=0.9, nesterov=True)
+    return p, v, stats
 
 
 zb = dev(f32(4096, C) * 3)                                         # logits: a wave per row
@@ -107,6 +115,8 @@ OPS = {
     "image_batch": lambda: sehip.image_batch(img_arena, img_t["src_off"], img_t["src_hw"], img_t["xmap"], img_t["xk"], img_t["ymap"], img_t["yk"],
                                              img_t["erase"], img_t["seed"], img_stats[0], img_stats[1]),
     "adagrad_step_": lambda: (lambda p, acc: (sehip.adagrad_step_(p, acc, ag_g, ag_l2, lr=0.01, grad_scale=0.5), acc))(ag_p.clone(), ag_a.clone()),
+    "grad_clip_factor": lambda: sehip.grad_clip_factor(ag_g, ag_p, ag_l2, grad_scale=0.5, clipnorm=10.0, workspace=sgd_ws),
+    "grad_clip_factor + sgd_step_": lambda: sgd_pair(ag_p.clone(), ag_a.clone()),
 }
 SIDE = {
     "distance tiles": lambda: sehip.pairwise_dist(g20[:6000], g20[:6000]),
