@@ -11,24 +11,16 @@
 // g is only read.  A streaming kernel: 3 (4 with l2) streams in, 2 out, nothing shared between elements, so no LDS, no barrier, no
 // atomics and the same bits whatever the launch geometry.  16-byte accesses when all pointers are 16-byte aligned (the n % 4 tail
 // elements are taken one by one), 4-byte accesses otherwise; int64 indices; a grid-stride loop under a capped grid.
-#include "se_common.h"
+#include "flat_update.h"
 
 #pragma clang fp contract(off)
 
 namespace se {
 
-constexpr int AG_THREADS = 256;
-constexpr int AG_VEC = 4;
-
 template <bool L2>
 __device__ __forceinline__ void ag_update(float &p, float &a, float g, float l2, float lr, float grad_scale, float epsilon)
 {
-    const float g1 = grad_scale == 1.0f ? g : g * grad_scale;
-    float g2 = g1;
-    if constexpr (L2) {
-        const float r = l2 * p;
-        g2 = g1 + r;
-    }
+    const float g2 = reg_grad<L2>(g, p, l2, grad_scale);
     const float sq = g2 * g2;
     const float an = a + sq;
     const float den = sqrtf(an) + epsilon;
@@ -39,43 +31,22 @@ __device__ __forceinline__ void ag_update(float &p, float &a, float g, float l2,
 }
 
 template <bool VEC, bool L2>
-__global__ __launch_bounds__(AG_THREADS) void adagrad_step_kernel(float *__restrict__ p, float *__restrict__ accum,
-                                                                  const float *__restrict__ g, const float *__restrict__ l2, int64_t n,
-                                                                  float lr, const float *__restrict__ lr_dev, float grad_scale,
-                                                                  float epsilon)
+__global__ __launch_bounds__(FLAT_THREADS) void adagrad_step_kernel(float *__restrict__ p, float *__restrict__ accum,
+                                                                    const float *__restrict__ g, const float *__restrict__ l2, int64_t n,
+                                                                    float lr, const float *__restrict__ lr_dev, float grad_scale,
+                                                                    float epsilon)
 {
     if (lr_dev) lr = lr_dev[0];
-    const int64_t tid = (int64_t)blockIdx.x * AG_THREADS + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * AG_THREADS;
-    if constexpr (VEC) {
-        const int64_t units = n / AG_VEC;
-        for (int64_t u = tid; u < units; u += stride) {
-            float4 pv = ((const float4 *)p)[u], av = ((const float4 *)accum)[u];
-            const float4 gv = ((const float4 *)g)[u];
-            float4 lv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (L2) lv = ((const float4 *)l2)[u];
-            ag_update<L2>(pv.x, av.x, gv.x, lv.x, lr, grad_scale, epsilon);
-            ag_update<L2>(pv.y, av.y, gv.y, lv.y, lr, grad_scale, epsilon);
-            ag_update<L2>(pv.z, av.z, gv.z, lv.z, lr, grad_scale, epsilon);
-            ag_update<L2>(pv.w, av.w, gv.w, lv.w, lr, grad_scale, epsilon);
-            ((float4 *)accum)[u] = av;
-            ((float4 *)p)[u] = pv;
-        }
-        const int64_t i = units * AG_VEC + tid;             // the n % 4 tail: threads 0 .. 2 of the first workgroup
-        if (i < n) {
-            float pi = p[i], ai = accum[i];
-            ag_update<L2>(pi, ai, g[i], L2 ? l2[i] : 0.f, lr, grad_scale, epsilon);
-            accum[i] = ai;
-            p[i] = pi;
-        }
-    } else {
-        for (int64_t i = tid; i < n; i += stride) {
-            float pi = p[i], ai = accum[i];
-            ag_update<L2>(pi, ai, g[i], L2 ? l2[i] : 0.f, lr, grad_scale, epsilon);
-            accum[i] = ai;
-            p[i] = pi;
-        }
-    }
+    flat_stream<VEC>(n, [&](auto width, int64_t i) {
+        constexpr int W = decltype(width)::value;
+        FlatVal<W> pv = flat_load<W>(p + i), av = flat_load<W>(accum + i), lv{};
+        const FlatVal<W> gv = flat_load<W>(g + i);
+        if constexpr (L2) lv = flat_load<W>(l2 + i);
+#pragma unroll
+        for (int k = 0; k < W; k++) ag_update<L2>(pv.e[k], av.e[k], gv.e[k], lv.e[k], lr, grad_scale, epsilon);
+        flat_store(accum + i, av);
+        flat_store(p + i, pv);
+    });
 }
 
 }  // namespace se
@@ -89,19 +60,12 @@ extern "C" int se_adagrad_step(float *p, float *accum, const float *g, const flo
     if (!(epsilon >= 0.f)) return fail(SE_ERR_INVALID, "se_adagrad_step: epsilon %g must be >= 0", (double)epsilon);
     if (n == 0) return SE_OK;
     if (!p || !accum || !g) return fail(SE_ERR_INVALID, "se_adagrad_step: null pointer");
-    const bool vec = n >= AG_VEC && aligned16(p) && aligned16(accum) && aligned16(g) && (!l2 || aligned16(l2));
-    const int64_t per_block = (int64_t)AG_THREADS * (vec ? AG_VEC : 1);
-    int64_t blocks = (n + per_block - 1) / per_block;
-    if (blocks > SE_ADAGRAD_MAX_BLOCKS) blocks = SE_ADAGRAD_MAX_BLOCKS;
-    const dim3 grid((unsigned)blocks), block(AG_THREADS);
+    const bool vec = flat_vec_ok(n, p, accum, g, l2);
+    const dim3 grid(flat_blocks(n, vec, SE_ADAGRAD_MAX_BLOCKS)), block(FLAT_THREADS);
     hipStream_t s = (hipStream_t)stream;
-    if (vec) {
-        if (l2) hipLaunchKernelGGL((adagrad_step_kernel<true, true>), grid, block, 0, s, p, accum, g, l2, n, lr, lr_dev, grad_scale, epsilon);
-        else hipLaunchKernelGGL((adagrad_step_kernel<true, false>), grid, block, 0, s, p, accum, g, l2, n, lr, lr_dev, grad_scale, epsilon);
-    } else {
-        if (l2) hipLaunchKernelGGL((adagrad_step_kernel<false, true>), grid, block, 0, s, p, accum, g, l2, n, lr, lr_dev, grad_scale, epsilon);
-        else hipLaunchKernelGGL((adagrad_step_kernel<false, false>), grid, block, 0, s, p, accum, g, l2, n, lr, lr_dev, grad_scale, epsilon);
-    }
+    dispatch_bools(vec, l2 != nullptr, [&](auto V, auto L) {
+        hipLaunchKernelGGL((adagrad_step_kernel<V(), L()>), grid, block, 0, s, p, accum, g, l2, n, lr, lr_dev, grad_scale, epsilon);
+    });
     SE_LAUNCH_CHECK();
     return SE_OK;
 }

@@ -19,72 +19,46 @@
 // wave, the four waves in order, one float64 partial per workgroup, and one wave that adds the partials the same way -- no atomics.
 // 16-byte accesses when all pointers are 16-byte aligned (the n % 4 tail elements are taken one by one), 4-byte accesses otherwise;
 // int64 indices; a grid-stride loop under a capped grid.
-#include "se_common.h"
+#include "flat_update.h"
 
 #pragma clang fp contract(off)
 
 namespace se {
 
-constexpr int SGD_THREADS = 256;
-constexpr int SGD_VEC = 4;
-
-// the regularised gradient of one element: the first two lines of ag_update (adagrad.hip)
-template <bool L2>
-__device__ __forceinline__ float sgd_grad(float g, float p, float l2, float grad_scale)
-{
-    const float g1 = grad_scale == 1.0f ? g : g * grad_scale;
-    float g2 = g1;
-    if constexpr (L2) {
-        const float r = l2 * p;
-        g2 = g1 + r;
-    }
-    return g2;
-}
-
 template <bool L2>
 __device__ __forceinline__ void sq_add(double &s, float g, float p, float l2, float grad_scale)
 {
-    const double g2 = (double)sgd_grad<L2>(g, p, l2, grad_scale);
+    const double g2 = (double)reg_grad<L2>(g, p, l2, grad_scale);
     const double sq = g2 * g2;
     s = s + sq;
 }
 
 // workspace[blockIdx.x] = this workgroup's float64 sum of squares
 template <bool VEC, bool L2>
-__global__ __launch_bounds__(SGD_THREADS) void grad_sqsum_kernel(const float *__restrict__ g, const float *__restrict__ p,
-                                                                 const float *__restrict__ l2, int64_t n, float grad_scale,
-                                                                 double *__restrict__ partials)
+__global__ __launch_bounds__(FLAT_THREADS) void grad_sqsum_kernel(const float *__restrict__ g, const float *__restrict__ p,
+                                                                  const float *__restrict__ l2, int64_t n, float grad_scale,
+                                                                  double *__restrict__ partials)
 {
-    __shared__ double wave_part[SGD_THREADS / WAVE];
-    const int64_t tid = (int64_t)blockIdx.x * SGD_THREADS + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * SGD_THREADS;
+    __shared__ double wave_part[FLAT_THREADS / WAVE];
     double s = 0.0;
-    if constexpr (VEC) {
-        const int64_t units = n / SGD_VEC;
-        for (int64_t u = tid; u < units; u += stride) {
-            const float4 gv = ((const float4 *)g)[u];
-            float4 pv = make_float4(0.f, 0.f, 0.f, 0.f), lv = pv;
-            if constexpr (L2) {
-                pv = ((const float4 *)p)[u];
-                lv = ((const float4 *)l2)[u];
-            }
-            sq_add<L2>(s, gv.x, pv.x, lv.x, grad_scale);
-            sq_add<L2>(s, gv.y, pv.y, lv.y, grad_scale);
-            sq_add<L2>(s, gv.z, pv.z, lv.z, grad_scale);
-            sq_add<L2>(s, gv.w, pv.w, lv.w, grad_scale);
+    flat_stream<VEC>(n, [&](auto width, int64_t i) {
+        constexpr int W = decltype(width)::value;
+        const FlatVal<W> gv = flat_load<W>(g + i);
+        FlatVal<W> pv{}, lv{};
+        if constexpr (L2) {
+            pv = flat_load<W>(p + i);
+            lv = flat_load<W>(l2 + i);
         }
-        const int64_t i = units * SGD_VEC + tid;            // the n % 4 tail: threads 0 .. 2 of the first workgroup
-        if (i < n) sq_add<L2>(s, g[i], L2 ? p[i] : 0.f, L2 ? l2[i] : 0.f, grad_scale);
-    } else {
-        for (int64_t i = tid; i < n; i += stride) sq_add<L2>(s, g[i], L2 ? p[i] : 0.f, L2 ? l2[i] : 0.f, grad_scale);
-    }
+#pragma unroll
+        for (int k = 0; k < W; k++) sq_add<L2>(s, gv.e[k], pv.e[k], lv.e[k], grad_scale);
+    });
     s = wave_sum(s);
     if (lane_id() == 0) wave_part[threadIdx.x / WAVE] = s;
     wg_barrier();
     if (threadIdx.x == 0) {
         double t = wave_part[0];
 #pragma unroll
-        for (int w = 1; w < SGD_THREADS / WAVE; w++) t = t + wave_part[w];
+        for (int w = 1; w < FLAT_THREADS / WAVE; w++) t = t + wave_part[w];
         partials[blockIdx.x] = t;
     }
 }
@@ -119,7 +93,7 @@ __global__ __launch_bounds__(WAVE) void grad_clip_final_kernel(const double *__r
 template <bool L2, bool CLIP, bool NESTEROV>
 __device__ __forceinline__ void sgd_update(float &p, float &v, float g, float l2, float lr, float grad_scale, float factor, float momentum)
 {
-    const float g2 = sgd_grad<L2>(g, p, l2, grad_scale);
+    const float g2 = reg_grad<L2>(g, p, l2, grad_scale);
     float g3 = g2;
     if constexpr (CLIP) g3 = g2 * factor;
     const float step = lr * g3;
@@ -136,53 +110,24 @@ __device__ __forceinline__ void sgd_update(float &p, float &v, float g, float l2
 }
 
 template <bool VEC, bool L2, bool CLIP, bool NESTEROV>
-__global__ __launch_bounds__(SGD_THREADS) void sgd_step_kernel(float *__restrict__ p, float *__restrict__ v, const float *__restrict__ g,
-                                                               const float *__restrict__ l2, int64_t n, float lr,
-                                                               const float *__restrict__ lr_dev, float grad_scale,
-                                                               const float *__restrict__ clip_dev, float momentum)
+__global__ __launch_bounds__(FLAT_THREADS) void sgd_step_kernel(float *__restrict__ p, float *__restrict__ v, const float *__restrict__ g,
+                                                                const float *__restrict__ l2, int64_t n, float lr,
+                                                                const float *__restrict__ lr_dev, float grad_scale,
+                                                                const float *__restrict__ clip_dev, float momentum)
 {
     if (lr_dev) lr = lr_dev[0];
     float factor = 1.0f;
     if constexpr (CLIP) factor = clip_dev[0];
-    const int64_t tid = (int64_t)blockIdx.x * SGD_THREADS + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * SGD_THREADS;
-    if constexpr (VEC) {
-        const int64_t units = n / SGD_VEC;
-        for (int64_t u = tid; u < units; u += stride) {
-            float4 pv = ((const float4 *)p)[u], vv = ((const float4 *)v)[u];
-            const float4 gv = ((const float4 *)g)[u];
-            float4 lv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (L2) lv = ((const float4 *)l2)[u];
-            sgd_update<L2, CLIP, NESTEROV>(pv.x, vv.x, gv.x, lv.x, lr, grad_scale, factor, momentum);
-            sgd_update<L2, CLIP, NESTEROV>(pv.y, vv.y, gv.y, lv.y, lr, grad_scale, factor, momentum);
-            sgd_update<L2, CLIP, NESTEROV>(pv.z, vv.z, gv.z, lv.z, lr, grad_scale, factor, momentum);
-            sgd_update<L2, CLIP, NESTEROV>(pv.w, vv.w, gv.w, lv.w, lr, grad_scale, factor, momentum);
-            ((float4 *)v)[u] = vv;
-            ((float4 *)p)[u] = pv;
-        }
-        const int64_t i = units * SGD_VEC + tid;            // the n % 4 tail: threads 0 .. 2 of the first workgroup
-        if (i < n) {
-            float pi = p[i], vi = v[i];
-            sgd_update<L2, CLIP, NESTEROV>(pi, vi, g[i], L2 ? l2[i] : 0.f, lr, grad_scale, factor, momentum);
-            v[i] = vi;
-            p[i] = pi;
-        }
-    } else {
-        for (int64_t i = tid; i < n; i += stride) {
-            float pi = p[i], vi = v[i];
-            sgd_update<L2, CLIP, NESTEROV>(pi, vi, g[i], L2 ? l2[i] : 0.f, lr, grad_scale, factor, momentum);
-            v[i] = vi;
-            p[i] = pi;
-        }
-    }
-}
-
-// workgroups of a streaming launch over n elements: ceil(n / (256 * elements per thread)), capped
-inline unsigned sgd_blocks(int64_t n, bool vec)
-{
-    const int64_t per_block = (int64_t)SGD_THREADS * (vec ? SGD_VEC : 1);
-    const int64_t blocks = (n + per_block - 1) / per_block;
-    return (unsigned)(blocks > SE_SGD_MAX_BLOCKS ? SE_SGD_MAX_BLOCKS : blocks);
+    flat_stream<VEC>(n, [&](auto width, int64_t i) {
+        constexpr int W = decltype(width)::value;
+        FlatVal<W> pv = flat_load<W>(p + i), vv = flat_load<W>(v + i), lv{};
+        const FlatVal<W> gv = flat_load<W>(g + i);
+        if constexpr (L2) lv = flat_load<W>(l2 + i);
+#pragma unroll
+        for (int k = 0; k < W; k++) sgd_update<L2, CLIP, NESTEROV>(pv.e[k], vv.e[k], gv.e[k], lv.e[k], lr, grad_scale, factor, momentum);
+        flat_store(v + i, vv);
+        flat_store(p + i, pv);
+    });
 }
 
 }  // namespace se
@@ -201,9 +146,9 @@ extern "C" int se_grad_clip_factor(const float *g, const float *p, const float *
     if (!g || !workspace || !stats) return fail(SE_ERR_INVALID, "se_grad_clip_factor: null pointer");
     if (l2 && !p) return fail(SE_ERR_INVALID, "se_grad_clip_factor: l2 needs p");
     if (((uintptr_t)workspace) & 7) return fail(SE_ERR_INVALID, "se_grad_clip_factor: the workspace must be 8-byte aligned");
-    const bool vec = n >= SGD_VEC && aligned16(g) && (!l2 || (aligned16(l2) && aligned16(p)));
-    const unsigned blocks = sgd_blocks(n, vec);
-    const dim3 grid(blocks), block(SGD_THREADS);
+    const bool vec = flat_vec_ok(n, g, l2 ? p : nullptr, l2);   // p is a buffer of the call only with l2
+    const unsigned blocks = flat_blocks(n, vec, SE_SGD_MAX_BLOCKS);
+    const dim3 grid(blocks), block(FLAT_THREADS);
     hipStream_t s = (hipStream_t)stream;
     double *partials = (double *)workspace;
     dispatch_bools(vec, l2 != nullptr, [&](auto V, auto L) {
@@ -222,8 +167,8 @@ extern "C" int se_sgd_step(float *p, float *v, const float *g, const float *l2, 
     if (!(momentum >= 0.f)) return fail(SE_ERR_INVALID, "se_sgd_step: momentum %g must be >= 0", (double)momentum);
     if (n == 0) return SE_OK;
     if (!p || !v || !g) return fail(SE_ERR_INVALID, "se_sgd_step: null pointer");
-    const bool vec = n >= SGD_VEC && aligned16(p) && aligned16(v) && aligned16(g) && (!l2 || aligned16(l2));
-    const dim3 grid(sgd_blocks(n, vec)), block(SGD_THREADS);
+    const bool vec = flat_vec_ok(n, p, v, g, l2);
+    const dim3 grid(flat_blocks(n, vec, SE_SGD_MAX_BLOCKS)), block(FLAT_THREADS);
     hipStream_t s = (hipStream_t)stream;
     dispatch_bools(vec, [&](auto V) {                       // 16 instantiations: VEC x L2 x CLIP x NESTEROV
         dispatch_bools(l2 != nullptr, clip_dev != nullptr, nesterov != 0, [&](auto L, auto C, auto N) {

@@ -444,8 +444,7 @@ class Trainer(object):
         self._sX.copy_(X, non_blocking=True)
         for dst, src in zip(self._sy, ys):
             dst.copy_(src, non_blocking=True)
-        lr = self.lr / (1.0 + self.decay * self.iterations) if self.decay > 0 else self.lr
-        self._lr_t.fill_(float(lr))
+        self._lr_t.fill_(float(self._update_lr()))
         ga, gb = self._graph
         ga.replay()
         self._allreduce_flat(self._graph_allreduce)
@@ -460,14 +459,14 @@ class Trainer(object):
                                      'rerun with SE_TRAIN_GRAPHS=0 to tell)' % self._graph_steps)
         return self._g_loss
 
-    def apply_update(self, grad_scale=1.0, lr_tensor=None, count=True):
-        """Keras-SGD update on the flat buffers (regulariser -> clip -> decayed lr -> momentum).  With ``lr_tensor``
-        (a device scalar) the learning rate is read on the device, so the launches can be captured in a HIP graph.
-        ``optimizer='adagrad'``: one ``sehip.adagrad_step_`` launch instead (``_apply_adagrad``)."""
-        if self.optimizer == 'adagrad':
-            return self._apply_adagrad(grad_scale, lr_tensor, count)
-        if self.fused_sgd:
-            return self._apply_fused_sgd(grad_scale, lr_tensor, count)
+    def _update_lr(self, lr_tensor=None):
+        """The learning rate of this update: the device scalar when given, else Keras's ``lr / (1 + decay * iterations)``."""
+        if lr_tensor is not None:
+            return lr_tensor
+        return self.lr / (1.0 + self.decay * self.iterations) if self.decay > 0 else self.lr
+
+    def _regularise_and_clip(self, grad_scale):
+        """The whole-buffer passes over ``flat_g``, in place: ``g *= scale; g += l2 * p; g *= clamp(clipnorm / (|g| + 1e-12), max=1)``."""
         flat = self.flat
         g = flat.flat_g
         if grad_scale != 1.0:
@@ -477,25 +476,41 @@ class Trainer(object):
         if self.clipnorm:
             norm = torch.linalg.vector_norm(g)
             g.mul_(torch.clamp(self.clipnorm / (norm + 1e-12), max=1.0))   # stays on the device
-        v = flat.flat_v
-        if lr_tensor is not None:
-            step = g * lr_tensor                      # lr lives on the device (graph replay)
+
+    def apply_update(self, grad_scale=1.0, lr_tensor=None, count=True):
+        """Keras-SGD update on the flat buffers (regulariser -> clip -> decayed lr -> momentum).  With ``lr_tensor``
+        (a device scalar) the learning rate is read on the device, so the launches can be captured in a HIP graph.
+        ``optimizer='adagrad'``: one ``sehip.adagrad_step_`` launch instead (``_apply_adagrad``)."""
+        lr = self._update_lr(lr_tensor)
+        if self.optimizer == 'adagrad':
+            self._apply_adagrad(grad_scale, lr)
+        elif self.fused_sgd:
+            self._apply_fused_sgd(grad_scale, lr)
+        else:
+            self._apply_sgd(grad_scale, lr)
+        if count:
+            self.iterations += 1
+
+    def _apply_sgd(self, grad_scale, lr):
+        """The default path: whole-buffer torch launches.  The two spellings round differently and both are pinned."""
+        flat = self.flat
+        self._regularise_and_clip(grad_scale)
+        g, v = flat.flat_g, flat.flat_v
+        if torch.is_tensor(lr):
+            step = g * lr                             # lr lives on the device (graph replay)
             v.mul_(self.momentum).sub_(step)
             if self.nesterov:
                 flat.flat_p.add_(v, alpha=self.momentum).sub_(step)
             else:
                 flat.flat_p.add_(v)
         else:
-            lr = self.lr / (1.0 + self.decay * self.iterations) if self.decay > 0 else self.lr
             v.mul_(self.momentum).add_(g, alpha=-lr)
             if self.nesterov:
                 flat.flat_p.add_(v, alpha=self.momentum).add_(g, alpha=-lr)
             else:
                 flat.flat_p.add_(v)
-        if count:
-            self.iterations += 1
 
-    def _apply_fused_sgd(self, grad_scale, lr_tensor, count):
+    def _apply_fused_sgd(self, grad_scale, lr):
         """The same Keras-SGD update as ``sehip.grad_clip_factor`` (only with ``clipnorm``: norm and clip factor of the scaled,
         regularised gradient into ``grad_stats``) followed by ONE ``sehip.sgd_step_`` launch that reads the factor on the device.
         ``flat_g`` stays as backward or the all-reduce wrote it, and eager and captured calls use one arithmetic."""
@@ -506,36 +521,19 @@ class Trainer(object):
             sehip.grad_clip_factor(g, flat.flat_p, l2, grad_scale=grad_scale, clipnorm=self.clipnorm, workspace=self._clip_ws,
                                    out=self.grad_stats)
             clip = self.grad_stats[1:]
-        if lr_tensor is not None:
-            lr = lr_tensor
-        else:
-            lr = self.lr / (1.0 + self.decay * self.iterations) if self.decay > 0 else self.lr
         sehip.sgd_step_(flat.flat_p, flat.flat_v, g, l2, lr=lr, grad_scale=grad_scale, clip=clip, momentum=self.momentum,
                         nesterov=self.nesterov)
-        if count:
-            self.iterations += 1
 
-    def _apply_adagrad(self, grad_scale, lr_tensor, count):
+    def _apply_adagrad(self, grad_scale, lr):
         """Keras-Adagrad update (``a += g^2; w -= lr g / (sqrt(a) + epsilon)``, a = ``flat.flat_v``) as ONE launch of the fused kernel,
         which scales the gradient and adds the regulariser's on the way and leaves ``flat_g`` as backward wrote it.  Only ``clipnorm``
         needs the regularised gradient in memory first: the whole-buffer lines of the SGD path then run in front of the kernel."""
         flat = self.flat
-        g, l2 = flat.flat_g, flat.flat_l2 if flat.has_l2 else None
+        l2 = flat.flat_l2 if flat.has_l2 else None
         if self.clipnorm:
-            if grad_scale != 1.0:
-                g.mul_(grad_scale)
-            if flat.has_l2:
-                g.addcmul_(flat.flat_l2, flat.flat_p)
-            norm = torch.linalg.vector_norm(g)
-            g.mul_(torch.clamp(self.clipnorm / (norm + 1e-12), max=1.0))
+            self._regularise_and_clip(grad_scale)
             grad_scale, l2 = 1.0, None
-        if lr_tensor is not None:
-            lr = lr_tensor
-        else:
-            lr = self.lr / (1.0 + self.decay * self.iterations) if self.decay > 0 else self.lr
-        sehip.adagrad_step_(flat.flat_p, flat.flat_v, g, l2, lr=lr, grad_scale=grad_scale, epsilon=self.epsilon)
-        if count:
-            self.iterations += 1
+        sehip.adagrad_step_(flat.flat_p, flat.flat_v, flat.flat_g, l2, lr=lr, grad_scale=grad_scale, epsilon=self.epsilon)
 
     # ---------------------------------------------------------------- loops
 

@@ -774,33 +774,6 @@ def devise_ranking_loss(y_pred, target, embedding, margin=0.1):
     return _DeviseLoss.apply(y_pred, target, embedding, float(margin))
 
 
-ADAGRAD_MAX_BLOCKS = DEFINES["SE_ADAGRAD_MAX_BLOCKS"]     # grid cap of se_adagrad_step: 256 threads per workgroup, 4 elements per thread
-
-
-def adagrad_step_(p, accum, g, l2=None, lr=0.01, grad_scale=1.0, epsilon=1e-7):
-    """In place, one launch (``se_adagrad_step``): Keras 2.2's Adagrad update ``accum += g2 * g2; p -= lr * g2 / (sqrt(accum) + epsilon)``
-    with ``g2 = g * grad_scale + l2 * p`` (keras.optimizers.Adagrad as learn_devise.py:87,114 uses it; every operation a separately
-    rounded float32 operation, include/sehip.h).  ``p``, ``accum``, ``g`` and ``l2`` (None: no regulariser) are contiguous float32
-    device tensors of one size; ``g`` is only read.  ``lr``: a float, or a 0-dim float32 device tensor that is read on the device
-    when the kernel runs (a captured launch then follows the schedule).  Returns ``p``."""
-    require_gpu(p, accum, g, l2)
-    n = p.numel()
-    for t, what in ((p, "p"), (accum, "accum"), (g, "g"), (l2, "l2")):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or t.device != p.device):
-            raise SehipError("%s must be a contiguous float32 tensor of %d elements on %s" % (what, n, p.device))
-    lr_dev = None
-    if torch.is_tensor(lr):
-        require_gpu(lr)
-        if lr.dtype != torch.float32 or lr.numel() != 1 or lr.device != p.device:
-            raise SehipError("a learning-rate tensor must hold one float32 value on %s" % (p.device,))
-        lr, lr_dev = 0.0, lr
-    call("se_adagrad_step", p, accum, g, l2, n, float(lr), lr_dev, float(grad_scale), float(epsilon))
-    return p
-
-
-SGD_MAX_BLOCKS = DEFINES["SE_SGD_MAX_BLOCKS"]     # grid cap of se_grad_clip_factor / se_sgd_step: 256 threads per workgroup, 4 elements per thread
-
-
 def _flat_f32(n, device, *named):
     """Every tensor of ``named`` ((tensor or None, name) pairs) is a contiguous float32 tensor of ``n`` elements on ``device``."""
     for t, what in named:
@@ -816,6 +789,26 @@ def _lr_arg(lr, device):
     if lr.dtype != torch.float32 or lr.numel() != 1 or lr.device != device:
         raise SehipError("a learning-rate tensor must hold one float32 value on %s" % (device,))
     return 0.0, lr
+
+
+ADAGRAD_MAX_BLOCKS = DEFINES["SE_ADAGRAD_MAX_BLOCKS"]     # grid cap of se_adagrad_step: 256 threads per workgroup, 4 elements per thread
+
+
+def adagrad_step_(p, accum, g, l2=None, lr=0.01, grad_scale=1.0, epsilon=1e-7):
+    """In place, one launch (``se_adagrad_step``): Keras 2.2's Adagrad update ``accum += g2 * g2; p -= lr * g2 / (sqrt(accum) + epsilon)``
+    with ``g2 = g * grad_scale + l2 * p`` (keras.optimizers.Adagrad as learn_devise.py:87,114 uses it; every operation a separately
+    rounded float32 operation, include/sehip.h).  ``p``, ``accum``, ``g`` and ``l2`` (None: no regulariser) are contiguous float32
+    device tensors of one size; ``g`` is only read.  ``lr``: a float, or a 0-dim float32 device tensor that is read on the device
+    when the kernel runs (a captured launch then follows the schedule).  Returns ``p``."""
+    require_gpu(p, accum, g, l2)
+    n = p.numel()
+    _flat_f32(n, p.device, (p, "p"), (accum, "accum"), (g, "g"), (l2, "l2"))
+    lr, lr_dev = _lr_arg(lr, p.device)
+    call("se_adagrad_step", p, accum, g, l2, n, lr, lr_dev, float(grad_scale), float(epsilon))
+    return p
+
+
+SGD_MAX_BLOCKS = DEFINES["SE_SGD_MAX_BLOCKS"]     # grid cap of se_grad_clip_factor / se_sgd_step: 256 threads per workgroup, 4 elements per thread
 
 
 def grad_clip_factor(g, p=None, l2=None, grad_scale=1.0, clipnorm=None, workspace=None, out=None):

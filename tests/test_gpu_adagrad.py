@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from _flat_buffers import SIZES, _big_n, _bits, _dev
 from test_adagrad_host import F, adagrad_inputs, adagrad_oracle
 
 pytestmark = pytest.mark.gpu
@@ -14,32 +15,11 @@ pytestmark = pytest.mark.gpu
 LR, EPS = 0.01, 1e-7
 
 
-def _bits(t):
-    return (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).view(np.int32)
-
-
-def _dev(a, offset):
-    """``a`` on the device, 256-byte aligned (offset 0) or ``offset`` elements past such an address."""
-    buf = torch.zeros(len(a) + offset, dtype=torch.float32, device="cuda")
-    assert buf.data_ptr() % 256 == 0
-    view = buf[offset:]
-    view.copy_(torch.from_numpy(a))
-    return view
-
-
-def _big_n():
-    import sehip
-    return sehip.ADAGRAD_MAX_BLOCKS * 256 * 4 + 5          # one more trip of the grid-stride loop than the capped grid covers, and a tail
-
-
-SIZES = [1, 3, 4, 5, 63, 64, 65, 1023, 4103, "big"]
-
-
 @pytest.mark.parametrize("offset", [0, 1], ids=["aligned", "offset1"])
 @pytest.mark.parametrize("n", SIZES)
 def test_three_steps_are_bit_exact(n, offset):
     import sehip
-    n = _big_n() if n == "big" else n
+    n = _big_n(sehip.ADAGRAD_MAX_BLOCKS) if n == "big" else n
     p0, a0, g0, l20 = adagrad_inputs(n, 100 + n % 97)
     grads = [g0] + [adagrad_inputs(n, 200 + s + n % 97)[2] for s in (1, 2)]
     for with_l2, scale, lr_on_device in itertools.product((False, True), (1.0, 0.5), (False, True)):

@@ -8,32 +8,12 @@ import numpy as np
 import pytest
 import torch
 
+from _flat_buffers import SIZES, _big_n, _bits, _dev
 from test_sgd_host import F, U, clip_factor, clip_oracle, exact_sum_inputs, sgd_inputs, sgd_oracle
 
 pytestmark = pytest.mark.gpu
 
 LR, MOM = 0.01, 0.9
-
-
-def _bits(t):
-    return (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)).view(np.int32)
-
-
-def _dev(a, offset):
-    """``a`` on the device, 256-byte aligned (offset 0) or ``offset`` elements past such an address."""
-    buf = torch.zeros(len(a) + offset, dtype=torch.float32, device="cuda")
-    assert buf.data_ptr() % 256 == 0
-    view = buf[offset:]
-    view.copy_(torch.from_numpy(a))
-    return view
-
-
-def _big_n():
-    import sehip
-    return sehip.SGD_MAX_BLOCKS * 256 * 4 + 5              # one more trip of the grid-stride loop than the capped grid covers, and a tail
-
-
-SIZES = [1, 3, 4, 5, 63, 64, 65, 1023, 4103, "big"]
 
 
 def test_the_feature_is_exported():
@@ -47,7 +27,7 @@ def test_the_feature_is_exported():
 def test_three_steps_are_bit_exact(n, offset):
     """p and v equal sgd_oracle fed the factor read back from stats; g is only read; the factor is the formula of the norm."""
     import sehip
-    n = _big_n() if n == "big" else n
+    n = _big_n(sehip.SGD_MAX_BLOCKS) if n == "big" else n
     p0, v0, g0, l20 = sgd_inputs(n, 100 + n % 97)
     grads = [g0] + [sgd_inputs(n, 200 + s + n % 97)[2] for s in (1, 2)]
     clipnorm = 0.5 * float(np.sqrt(n))                     # |g| is log-uniform up to 100: the clip is active
@@ -90,7 +70,7 @@ def test_norm_is_bit_exact_where_the_squares_sum_exactly(n, offset):
     """Inputs whose squares sum exactly in float64 in any order (test_sgd_host.exact_sum_inputs; the property is checked here on the
     host): the norm equals the oracle's bit for bit, whatever order the kernel adds in.  Two calls give the same bits."""
     import sehip
-    n = _big_n() if n == "big" else n
+    n = _big_n(sehip.SGD_MAX_BLOCKS) if n == "big" else n
     g, p, l2 = exact_sum_inputs(n, 300 + n % 89)
     g2 = g.astype(np.float64) + l2.astype(np.float64) * p.astype(np.float64)
     assert np.array_equal((g + l2 * p).astype(np.float64), g2)                       # the float32 g2 is exact

@@ -73,6 +73,27 @@ def timeit(fn, reps):
     return float(np.median(ts)), float(np.min(ts))
 
 
+def windows(fns, reps, batch):
+    """The method of the alternating benchmarks: 3 warm-up calls of every candidate, then ``reps`` rounds in which the candidates take
+    turns (the same machine state for every candidate), each timed by HIP events around a window of ``batch`` back-to-back calls.
+    Per candidate: (median, 10th percentile, 90th percentile) of the per-call time in microseconds."""
+    for f in fns:
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for k, f in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(batch):
+                f()
+            b.record()
+            torch.cuda.synchronize()
+            ts[k].append(a.elapsed_time(b) / batch * 1e3)
+    return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
@@ -540,23 +561,6 @@ def bench_xent(reps=60, batch=20, steps=200):
     from sehip._lib import call
     HBM = 6.29e12
 
-    def windows(fns):
-        for f in fns:
-            for _ in range(3):
-                f()
-        torch.cuda.synchronize()
-        ts = [[] for _ in fns]
-        for _ in range(reps):
-            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(batch):
-                    f()
-                b.record()
-                torch.cuda.synchronize()
-                ts[k].append(a.elapsed_time(b) / batch * 1e3)
-        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
-
     for dtype, dcode, esz in ((torch.float32, 0, 4), (torch.bfloat16, 1, 2)):
         for B, C in ((128, 100), (128, 1000), (1024, 1000), (256, 8142)):
             for s in (0.0, 0.1):
@@ -582,7 +586,7 @@ def bench_xent(reps=60, batch=20, steps=200):
                     F.cross_entropy(zt.float(), y, label_smoothing=s).backward()
                     zt.argmax(dim=-1)
                     zt.topk(5, dim=-1)
-                k, o, t = windows((kernels, op, composition))
+                k, o, t = windows((kernels, op, composition), reps, batch)
                 gbs = 3.0 * B * C * esz / (k[0] * 1e-6)
                 print("xent B=%d C=%d %s s=%.1f: kernels %.1f us (%.1f-%.1f), autograd op %.1f us (%.1f-%.1f), torch composition %.1f us "
                       "(%.1f-%.1f): x%.2f / x%.2f; kernels move %.0f GB/s = %.1f%% of the HBM copy rate"
@@ -642,23 +646,6 @@ def bench_labelembed(reps=60, batch=20, steps=200):
     import torch.nn.functional as F
     from sehip._lib import call
 
-    def windows(fns):
-        for f in fns:
-            for _ in range(3):
-                f()
-        torch.cuda.synchronize()
-        ts = [[] for _ in fns]
-        for _ in range(reps):
-            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(batch):
-                    f()
-                b.record()
-                torch.cuda.synchronize()
-                ts[k].append(a.elapsed_time(b) / batch * 1e3)
-        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
-
     for B, C in ((128, 100), (128, 1000), (256, 8142)):
         rng = np.random.default_rng(B + C)
         o1, o2 = (torch.from_numpy((rng.standard_normal((B, C)) * 2).astype(np.float32)).cuda() for _ in range(2))
@@ -691,7 +678,7 @@ def bench_labelembed(reps=60, batch=20, steps=200):
         def composed_op():
             c1.grad = c2.grad = tc.grad = None
             sehip.labelembed_loss(c1, c2, F.embedding(y, tc), y).mean().backward()
-        k, ck, o, co = windows((kernels, composed_kernels, op, composed_op))
+        k, ck, o, co = windows((kernels, composed_kernels, op, composed_op), reps, batch)
         parts = [timeit(f, reps)[0] * 1e3 for f in (
             lambda: call("se_labelembed_table_loss_fwd", o1, C, o2, C, table, C, y, B, C, 2.0, 0.9, 0.5, loss_i, aux),
             lambda: call("se_labelembed_table_loss_bwd", o1, C, o2, C, table, C, y, g, 0.0, B, C, 2.0, 0.9, 0.5, aux, d1, C, d2, C, None, 0),
@@ -762,23 +749,6 @@ def bench_head(reps=40, batch=20):
     contraction does not read it back).  The sequence's xhat always goes through memory: the metric reads it."""
     from sehip._lib import call
 
-    def windows(fns):
-        for f in fns:
-            for _ in range(3):
-                f()
-        torch.cuda.synchronize()
-        ts = [[] for _ in fns]
-        for _ in range(reps):
-            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(batch):
-                    f()
-                b.record()
-                torch.cuda.synchronize()
-                ts[k].append(a.elapsed_time(b) / batch * 1e3)
-        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
-
     print("embedding heads: one se_embed_head_fwd vs loss launch + n se_nn_accuracy launches; us per call, median (10th-90th percentile) of "
           "%d windows of %d calls, candidates alternating" % (reps, batch))
     for mode, mname in ((0, "cosine"), (1, "sqdist")):
@@ -816,7 +786,7 @@ def bench_head(reps=40, batch=20):
                 fns = [lambda: head(True), lambda: head(False)] + [lambda n=n: sequence(n) for n in (1, 2, 3)]
                 if mode == 1:
                     fns = fns[:1] + fns[2:]
-                t = windows(fns)
+                t = windows(fns, reps, batch)
                 same = torch.equal(loss_i.view(torch.int32), loss_s.view(torch.int32))
                 for j, k in enumerate((1, 5, 10)):
                     same = same and torch.equal(((nw >= 1) & (nb < k)).float(), accs[j])
@@ -842,23 +812,6 @@ def bench_joint(reps=40, batch=10):
     The two kernel sequences deliver the counts every k is read from, so the number of metrics does not change them."""
     import utils
     from sehip._lib import call
-
-    def windows(fns):
-        for f in fns:
-            for _ in range(3):
-                f()
-        torch.cuda.synchronize()
-        ts = [[] for _ in fns]
-        for _ in range(reps):
-            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(batch):
-                    f()
-                b.record()
-                torch.cuda.synchronize()
-                ts[k].append(a.elapsed_time(b) / batch * 1e3)
-        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
 
     print("joint head, forward + backward: torch composition (1 / 3 metrics per output) vs separate launches vs one joint launch; us per "
           "step, median (10th-90th percentile) of %d windows of %d steps, candidates alternating" % (reps, batch))
@@ -909,7 +862,7 @@ def bench_joint(reps=40, batch=10):
             total.backward()
             return pp.grad, zz.grad
 
-        t = windows([lambda: composition(1), lambda: composition(3), lambda: kernels(out["sep"], False), lambda: kernels(out["joint"], True)])
+        t = windows([lambda: composition(1), lambda: composition(3), lambda: kernels(out["sep"], False), lambda: kernels(out["joint"], True)], reps, batch)
         same = all(torch.equal(out["sep"][k].view(torch.int32), out["joint"][k].view(torch.int32))
                    for k in ("el", "cl", "aux", "zb", "za", "dp", "dz", "pb") + (("pa",) if onehot else ("nb", "nw")))
         names = ["composition, 1 metric", "composition, 3 metrics", "separate launches", "joint launch"]
@@ -1112,23 +1065,6 @@ def bench_tiny(reps=40, batch=20, stored=10000):
     from datasets import CIFAR10_AUGMENTATION, InMemoryDatasetGenerator
     from datasets.common import affine_matrices
 
-    def windows(fns):
-        for f in fns:
-            for _ in range(3):
-                f()
-        torch.cuda.synchronize()
-        ts = [[] for _ in fns]
-        for _ in range(reps):
-            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(batch):
-                    f()
-                b.record()
-                torch.cuda.synchronize()
-                ts[k].append(a.elapsed_time(b) / batch * 1e3)
-        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
-
     rng = np.random.default_rng(0)
     X = rng.integers(0, 256, (stored, 32, 32, 3)).astype(np.float32)
     labels = [0] * stored
@@ -1149,7 +1085,7 @@ def bench_tiny(reps=40, batch=20, stored=10000):
         whole = lambda: affine.compose_batch(idx, train=True, augment=True, rng=draws)
         torch_whole = lambda: plain.compose_batch(idx, train=True, augment=True)
         torch_dev = lambda: plain.apply_transform(gathered, *drawn).contiguous(memory_format=torch.channels_last)
-        k, w, tw, td = windows((kernel, whole, torch_whole, torch_dev))
+        k, w, tw, td = windows((kernel, whole, torch_whole, torch_dev), reps, batch)
         assert bool(torch.isfinite(out).all())
         nbytes = 4.0 * B * 32 * 32 * 3
         print("tiny batch %d x 32 x 32 x 3 ('cifar-10' preset): se_tiny_batch %.1f us (%.1f-%.1f), %.2f MB out = %.0f GB/s; whole compose_batch "
@@ -1177,23 +1113,6 @@ def bench_adagrad(reps=40, batch=20, steps=200):
     HBM = 6.29e12
     lr, eps = 0.001, 1e-7
 
-    def windows(fns):
-        for f in fns:
-            for _ in range(3):
-                f()
-        torch.cuda.synchronize()
-        ts = [[] for _ in fns]
-        for _ in range(reps):
-            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(batch):
-                    f()
-                b.record()
-                torch.cuda.synchronize()
-                ts[k].append(a.elapsed_time(b) / batch * 1e3)
-        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
-
     for arch, outputs in (("resnet-110-fc", 100), ("resnet-50", 1000)):
         torch.manual_seed(0)
         model = utils.build_network(outputs, arch, input_channels=3).cuda()
@@ -1213,7 +1132,7 @@ def bench_adagrad(reps=40, batch=20, steps=200):
                 a.addcmul_(g, g)
                 p.sub_((g * lr_t).div_(a.sqrt().add_(eps)))
             return f
-        k1, k0, t1, t0 = windows((kernel(l2), kernel(None), composition(l2), composition(None)))
+        k1, k0, t1, t0 = windows((kernel(l2), kernel(None), composition(l2), composition(None)), reps, batch)
         assert bool(torch.isfinite(p).all())
         for what, k, t, streams in (("with the regulariser", k1, t1, 6), ("without", k0, t0, 5)):
             gbs = streams * 4.0 * n / (k[0] * 1e-6)
@@ -1280,23 +1199,6 @@ def bench_sgd(reps=30, batch=10, steps=200):
     HBM = 6.29e12
     lr, mom, clipnorm = 0.001, 0.9, 10.0
 
-    def windows(fns):
-        for f in fns:
-            for _ in range(3):
-                f()
-        torch.cuda.synchronize()
-        ts = [[] for _ in fns]
-        for _ in range(reps):
-            for k, f in enumerate(fns):                       # alternate: the same machine state for every candidate
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(batch):
-                    f()
-                b.record()
-                torch.cuda.synchronize()
-                ts[k].append(a.elapsed_time(b) / batch * 1e3)
-        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
-
     for n in (1750016, 25600000, 68000000):
         gen = torch.Generator(device="cuda").manual_seed(0)
         p = torch.randn(n, device="cuda", generator=gen) * 0.05
@@ -1330,7 +1232,7 @@ def bench_sgd(reps=30, batch=10, steps=200):
             return f
 
         configs = [(c, r, nes) for c, r in ((True, True), (True, False), (False, False)) for nes in (False, True)]
-        res = windows([fn(*cfg) for cfg in configs for fn in (fused, composition)])
+        res = windows([fn(*cfg) for cfg in configs for fn in (fused, composition)], reps, batch)
         assert bool(torch.isfinite(p).all()) and bool(torch.isfinite(v).all())
         for i, (clip, reg, nes) in enumerate(configs):
             k, t = res[2 * i], res[2 * i + 1]
@@ -1398,23 +1300,6 @@ def bench_shortcut(reps=30, batch=10, B=128):
         hw_out = 32 >> stage
         shapes.append((k, 4 * widths[k - 1], 4 * widths[k], hw_out * stride, stride))
 
-    def windows(fns):
-        for f in fns:
-            for _ in range(3):
-                f()
-        torch.cuda.synchronize()
-        ts = [[] for _ in fns]
-        for _ in range(reps):
-            for j, f in enumerate(fns):                       # alternate: the same machine state for both candidates
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                for _ in range(batch):
-                    f()
-                b.record()
-                torch.cuda.synchronize()
-                ts[j].append(a.elapsed_time(b) / batch * 1e3)
-        return [(float(np.median(t)), float(np.percentile(t, 10)), float(np.percentile(t, 90))) for t in ts]
-
     for dtype, fmt, label in ((torch.float32, torch.contiguous_format, "fp32 NCHW"), (torch.bfloat16, torch.channels_last, "bf16 NHWC")):
         for k, cin, c, hx, stride in shapes:
             h = hx // stride
@@ -1431,7 +1316,7 @@ def bench_shortcut(reps=30, batch=10, B=128):
                 return torch.autograd.grad(s + F.pad(sc, (0, 0, 0, 0, 0, c - cin)), (s, x), g)
             (fs, fx), (ts_, tx) = fused(), composition()
             assert torch.equal(fs, ts_) and float((fx.float() - tx.float()).abs().max()) <= 2.0 ** -7 * float(tx.float().abs().max())
-            kf, kt = windows((fused, composition))
+            kf, kt = windows((fused, composition), reps, batch)
             eb = 4 if dtype == torch.float32 else 2
             nbytes = eb * (2 * s.numel() + 2 * x.numel() + B * cin * h * h)
             print("shortcut %s, block %d: s %d x %d x %d x %d, x %d channels at %d x %d, stride %d: fused %.1f us (%.1f-%.1f), torch "
