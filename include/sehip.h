@@ -671,8 +671,8 @@ int se_hierarchical_precision_r16(const uint16_t *rank, int64_t ldr, int64_t q, 
  *   rcp       [num_classes, 2, se_hprec_curve_len(list_len), 2] f64 out, per class: the divisors of the ranks BEHIND the
  *             query, (1 / (best_wup[i] - 1), 1 / (best_lcs[i] - 1)) -- dropping the query from its ranking shifts the
  *             curve and subtracts its self-similarity (class_hierarchy.py:280-290) -- then those of the ranks AHEAD of
- *             it, (1 / best_wup[i], 1 / best_lcs[i]).  Both chunk-transposed (4096-position chunks, position 16 t + e of
- *             a chunk at slot 256 e + t) so that the 256 threads of the metric kernel, each owning 16 consecutive ranks,
+ *             it, (1 / best_wup[i], 1 / best_lcs[i]).  Both chunk-transposed (2048-position chunks, position 8 t + e of
+ *             a chunk at slot 256 e + t) so that the 256 threads of the metric kernel, each owning 8 consecutive ranks,
  *             read contiguous 16-byte pairs.
  */
 int64_t se_hprec_curve_len(int64_t list_len);

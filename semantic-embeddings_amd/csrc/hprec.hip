@@ -7,8 +7,8 @@
 // the descending-sorted similarities of the whole gallery, cumulated) are computed once on the host and passed in;
 // the 0.6 h the reference spends here at N = 50k is the gather + prefix sums over Q x N ranks, which is this kernel.
 //
-// Persistent 256-thread workgroups (two per CU) take one query at a time and walk its ranking in 4096-rank chunks (thread t owns
-// 16 consecutive ranks): rank -> class (a byte / 16-bit copy of the gallery's classes in LDS, filled once per workgroup) ->
+// Persistent 256-thread workgroups (two per CU) take one query at a time and walk its ranking in 2048-rank chunks (thread t owns
+// 8 consecutive ranks): rank -> class (a byte / 16-bit copy of the gallery's classes in LDS, filled once per workgroup) ->
 // similarity pair (LDS), float64 running sums by a DPP wave scan + ONE barrier per chunk (wave totals double-buffered in LDS,
 // the carry replicated in every thread), per-thread accumulation of the trapezoid / AP terms (reduced once per query).  Chunks
 // come in three forms: interior ones (every rank live, behind the query, inside the AHP window, no cut-off: 2 adds + 2 FMAs per
