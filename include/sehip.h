@@ -573,6 +573,48 @@ int se_rank_rows_check(const float *pdist, int64_t ldp, int64_t q, int64_t n, co
                        se_stream_t stream);
 
 /*
+ * Float64 retrieval (opt-in: float64 feature files, whose distances the reference computes and ranks in float64).
+ *
+ * se_pairwise_dist_f64: all-pairs distance matrix of float64 operands, out[i, j] = dist(a[i], b[j]), i < q, j < n.
+ * Replaces: `pdist = -np.dot(features, features.T)`               evaluate_retrieval.py:59   for float64 features
+ *           `pdist = ne.evaluate('A + B - 2 * C', ...)`           evaluate_retrieval.py:61-62
+ * Canonical float64 arithmetic, held bit for bit (NaN payloads aside):
+ *   C[i, j]   = the sequential float64 FMA chain acc = fma(a[i, k], b[j, k], acc), k = 0 .. d - 1 ascending, from acc = +0.0
+ *               (v_fma_f64; ONE chain: there are no K blocks -- the float64 BLAS of the host follows no rule that could be pinned,
+ *               DESIGN.md section 3.1);
+ *   cosine    out = -C;
+ *   Euclidean out = (sqa[i] + sqb[j]) - 2 * C: one addition and one subtraction, each rounded on its own (no contraction; 2 * C is
+ *               exact) -- numexpr's left-to-right evaluation of 'A + B - 2 * C'.
+ *   a [q, d], b [n, d] float64 (lda, ldb); sqa [q], sqb [n] float64 row square norms, required for SE_METRIC_EUCLID only (the
+ *   caller computes them -- and normalises rows for the cosine metric -- with the reference's own NumPy lines on the host);
+ *   metric: SE_METRIC_COSINE or SE_METRIC_EUCLID; out [q, n] float64 (ldo);
+ *   img [q, n] float32 (ldi) or NULL: img = (float)out, rounded to nearest even.  The cast is monotone non-decreasing, so the
+ *   canonical ranking of img (se_rank_rows) orders every pair of columns with different images as out does.
+ *   q == 0 or n == 0 returns SE_OK without a launch; d == 0 gives the distances of empty dot products.  Asynchronous on `stream`,
+ *   no workspace, no atomics.
+ *
+ * se_rank_refine_f64: turns rank = se_rank_rows(img) into the canonical ranking of out64 itself -- (float64 distance, index)
+ * ascending, NaN last, -0.0 == +0.0, equal values index-ascending: `np.argsort(pdist, axis = -1)` of float64 distances
+ * (evaluate_retrieval.py:67) with ties in canonical order.  Per row, every maximal run of adjacent ranks whose images are equal
+ * (==: +-0 are one run, the NaNs are one run) is sorted in place by (float64 canonical key, index); ranks outside such runs are
+ * not touched.  Runs of any length up to n: up to 8 ranks in one thread's registers, up to 1,024 from LDS, longer ones by a
+ * second launch from the workspace (chunks of 1,024 sorted from LDS, then ranked against each other by binary search).  The result does not rest on the lane-order property that
+ * se_rank_rows_init probes.
+ *   out64 [q, n] float64 (ld64), img [q, n] float32 (ldi): as written by se_pairwise_dist_f64 (any matrix pair with
+ *   img = (float)out64 will do); rank [q, n] in / out: int32 when idx64 == 0, int64 when idx64 == 1 (ldr in elements);
+ *   idx64 == 2 (uint16) is SE_ERR_UNSUPPORTED.  Indices outside [0, n) are read as 0 (no gather leaves its row).
+ *   workspace: se_rank_refine_f64_workspace_bytes(q, n) bytes of device memory, 16-byte aligned; its contents before the call do
+ *   not matter.  Asynchronous on `stream`, no allocation, no atomics, no host synchronisation: capturable in a HIP graph.
+ */
+int se_pairwise_dist_f64(const double *a, int64_t lda, const double *b, int64_t ldb, const double *sqa,
+                         const double *sqb, int64_t q, int64_t n, int64_t d, int metric, double *out,
+                         int64_t ldo, float *img, int64_t ldi, se_stream_t stream);
+int64_t se_rank_refine_f64_workspace_bytes(int64_t q, int64_t n);
+int se_rank_refine_f64(const double *out64, int64_t ld64, const float *img, int64_t ldi, int64_t q, int64_t n,
+                       void *rank, int idx64, int64_t ldr, void *workspace, int64_t workspace_bytes,
+                       se_stream_t stream);
+
+/*
  * The k nearest columns of every row of a distance matrix, canonical order, with a global
  * column offset (sharded galleries: shard r passes col_offset = first gallery row of the shard).
  *   out_d [q, k] f32, out_i [q, k] int32 (global indices).  k <= n, k <= SE_TOPK_MAX.

@@ -314,7 +314,8 @@ class ClassHierarchy(object):
     def hierarchical_precision_device(self, features, labels, ks=[1, 10, 50, 100], compute_ahp=False, compute_ap=False,
                                       normalize=False, ids=None, tile_rows=None, distributed=False, group=None, kblocks=None,
                                       gather_per_query=True, kernels=None, per_query=True, head_via_topk=True,
-                                      gallery=None, gallery_labels=None, gallery_ids=None, tile_cols=None, rank_gallery=False):
+                                      gallery=None, gallery_labels=None, gallery_ids=None, tile_cols=None, rank_gallery=False,
+                                      precision=None):
         """``hierarchical_precision(pairwise_retrieval(features, normalize), labels, ...)`` (ignore_qids = True, every
         image is query and gallery item) without leaving the GPU: the rankings stay device tensors
         (``evaluate_retrieval.ranking_tiles``) and the per-query gather + prefix sums run in
@@ -358,10 +359,15 @@ class ClassHierarchy(object):
         overrides the size, not the check).  Several ranks: the QUERIES are sharded, the gallery is replicated (a whole ranking needs
         the whole gallery), rows gathered or sums reduced as above.  No queries at all: the means are NaN, the dictionaries empty.
         ``kernels`` (tests): ``{'normalize_rows_', 'row_sqnorm', 'pairwise_dist', 'rank_rows', 'hierarchical_precision', 'device'}``, the
-        names the counting path looks up."""
+        names the counting path looks up.
+
+        ``precision='float64'`` (opt-in; CLI: ``--float64``): float64 ``features`` are ranked in float64, as the reference ranks them --
+        ``ranking_tiles(..., precision='float64')`` -- and every metric is read from those full rankings (the fused top-L path is a
+        float32 path and is not taken).  The metric kernels read ranks only and are the same.  All-pairs in one process only: a
+        ``gallery``, ``kblocks`` or several ranks raise ``ValueError``, as float32 features do."""
         import torch
         import torch.distributed as dist
-        from evaluate_retrieval import RANKING_KERNELS, _resolve_kblocks, resolve_kernels
+        from evaluate_retrieval import RANKING_KERNELS, _resolve_kblocks, is_float64, resolve_kernels, to_device_f64
         from recall_precision import gallery_problem, recall_precision_device, to_device_f32
         from sharded_retrieval import shard_bounds, sharded_topk
         if rank_gallery and gallery is None:
@@ -370,6 +376,10 @@ class ClassHierarchy(object):
             raise ValueError('un-clipped AHP needs the whole ranking of the gallery, which a separate gallery does not get by default: '
                              'pass compute_ahp=K (--clip_ahp K on the command line), or opt into that ranking with rank_gallery=True '
                              '(--rank_gallery)')
+        f64 = is_float64(precision)
+        if f64 and (gallery is not None or kblocks is not None):
+            raise ValueError("precision='float64' ranks all pairs of one float64 feature matrix with ONE FMA chain per distance: a "
+                             "separate gallery (rank_gallery included) stays float32, kblocks does not apply")
         # ---- the problem, the device and this rank's queries ----
         given = dict(kernels or {})
         native_metrics = 'hierarchical_precision' not in given
@@ -387,10 +397,12 @@ class ClassHierarchy(object):
             return {m: float('nan') for m in names}, ({m: {} for m in names} if per_query else None)
         world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
         rank = dist.get_rank(group) if world > 1 else 0
+        if f64 and world > 1:
+            raise ValueError("precision='float64' runs in one process: the sharded multi-GPU evaluation stays float32")
         q0, q1 = shard_bounds(nq, world)[rank] if world > 1 else (0, nq)
         # top-L lists are enough when no metric reads past the head of a ranking; a separate gallery is ranked in full on request only
         head_only = (not compute_ap) and (not compute_ahp or ahp_clip is not None)
-        use_top_lists = (not rank_gallery) if gallery is not None else (head_only and (world > 1 or head_via_topk))
+        use_top_lists = (not rank_gallery) if gallery is not None else (head_only and (world > 1 or head_via_topk) and not f64)
         if rank_gallery:    # before anything is launched
             tile_rows = _ranked_gallery_tile_rows(dev, q1 - q0, ng, C, 4 * int(p.qf.shape[1]) * (nq + ng), ncol, tile_rows,
                                                   native_metrics, 'rank_rows' not in given)
@@ -421,7 +433,7 @@ class ClassHierarchy(object):
             return {'curves': sehip.hprec_reciprocal_curves(*best)}
 
         # ---- operands: ONE device copy of the features when every image is query and gallery item ----
-        fq = to_device_f32(p.qf, dev)
+        fq = to_device_f64(p.qf, dev) if f64 else to_device_f32(p.qf, dev)
         fg = fq if p.gf is p.qf else to_device_f32(p.gf, dev)
         gcls_d = torch.from_numpy(p.gcls).to(dev)
         if gallery is None:
@@ -454,7 +466,9 @@ class ClassHierarchy(object):
         def ranked_tiles():
             """Full rankings of this rank's queries, tile by tile; each tile is consumed before the next one overwrites it."""
             extra = reciprocal_curves()     # once per gallery, shared by every tile
-            if gallery is not None:
+            if f64:
+                tiles_kw = {'precision': 'float64'}
+            elif gallery is not None:
                 tiles_kw = {'gallery': fg, 'kernels': {k: given[k] for k in RANKING_KERNELS if k in given}}
             # (16-bit ranks between the two kernels -- ranking_tiles(idx16=True), se_hierarchical_precision_r16 -- give the same results
             # from half the bytes, but measured at 50k x 50k the ranking gains 0.24 ms and the metric kernel, which is not bound by its

@@ -22,7 +22,11 @@ reference: evaluate_retrieval.py:22-73 (pairwise_retrieval), :76-151 (reporting 
 * ``--rank_gallery`` (extension, with ``--gallery_feat``): every query's row IS ranked against the whole gallery, tile of queries
   by tile, and every metric is read from that one ranking -- the whole-list ``AHP (WUP)`` / ``AHP (LCS_HEIGHT)`` columns the
   reference prints by default included, so ``--clip_ahp`` is no longer required (8 bytes per query and gallery item pass through
-  device memory: meant for galleries of CIFAR / CUB / NABirds / Cars size).
+  device memory: meant for galleries of CIFAR / CUB / NABirds / Cars size);
+* ``--float64`` (extension; ``pairwise_retrieval(..., precision='float64')``): float64 feature files are evaluated in float64 like the
+  reference does -- float64 distances from one sequential FMA chain (``se_pairwise_dist_f64``), ranked exactly (``se_rank_rows`` on
+  their float32 image, then ``se_rank_refine_f64``) -- instead of being cast to float32 behind a warning.  All-pairs, one process
+  only: ``--gallery_feat`` / ``--rank_gallery`` and the sharded multi-GPU evaluation stay float32 and refuse the flag.
 """
 import argparse
 import os.path
@@ -142,6 +146,43 @@ def _native_pairwise_dist(a, b, cosine, sqa, sqb, kblocks, out=None):
     return sehip.pairwise_dist(a, b, metric=sehip.METRIC_COSINE if cosine else sehip.METRIC_EUCLID, sqa=sqa, sqb=sqb, kblocks=kblocks, out=out)
 
 
+F64_RANKING_KERNELS = ('pairwise_dist_f64', 'rank_rows_f64')
+
+
+def _native_pairwise_dist_f64(a, b, cosine, sqa, sqb, out=None, img=True):
+    import sehip
+    return sehip.pairwise_dist_f64(a, b, metric=sehip.METRIC_COSINE if cosine else sehip.METRIC_EUCLID, sqa=sqa, sqb=sqb, out=out, img=img)
+
+
+def is_float64(precision):
+    """``precision`` of the retrieval entry points: None (the float32 kernels) or 'float64' (float64 distances, ranked exactly)."""
+    if precision not in (None, 'float64'):
+        raise ValueError("precision must be None or 'float64', not {!r}".format(precision))
+    return precision == 'float64'
+
+
+def host_normalize_f64(features):
+    """The reference's own line (evaluate_retrieval.py:58) on a float64 matrix: float64-identical to it by construction."""
+    return features / np.linalg.norm(features, axis=-1, keepdims=True)
+
+
+def host_sqnorm_f64(features):
+    """``np.sum(features ** 2, axis = -1)`` (evaluate_retrieval.py:61) on a float64 matrix."""
+    return np.sum(features ** 2, axis=-1)
+
+
+def to_device_f64(x, dev):
+    """The float64 feature matrix ``x`` (array or tensor) as a device tensor of its own; anything but float64 raises: upcasting
+    would compute something the reference never does."""
+    import torch
+    if (x.dtype != torch.float64) if torch.is_tensor(x) else (not isinstance(x, np.ndarray) or x.dtype != np.float64):
+        raise ValueError("precision='float64' takes float64 features, got {}: float32 features are what the float32 kernels "
+                         "(precision=None) rank bit for bit like the reference".format(getattr(x, 'dtype', type(x).__name__)))
+    if torch.is_tensor(x):
+        return x.detach().to(device=dev).contiguous().clone()
+    return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+
 def resolve_kernels(kernels, names):
     """``kernels`` (None, or the CPU stand-ins of the tests) as a new dict in which every one of ``names`` it lacks is the native
     one: the ``sehip`` function of that name, ``pairwise_dist(a, b, cosine, sqa, sqb, kblocks, out)`` the one adapter of
@@ -151,7 +192,7 @@ def resolve_kernels(kernels, names):
     if 'device' in names:
         import torch
         kernels['device'] = torch.device(kernels.get('device') or torch.device('cuda', torch.cuda.current_device()))
-    own = {'pairwise_dist': _native_pairwise_dist, 'ranking_tiles': ranking_tiles}
+    own = {'pairwise_dist': _native_pairwise_dist, 'pairwise_dist_f64': _native_pairwise_dist_f64, 'ranking_tiles': ranking_tiles}
     for k in names:
         if k not in kernels and k in own:
             kernels[k] = own[k]
@@ -162,7 +203,7 @@ def resolve_kernels(kernels, names):
 
 
 def ranking_tiles(features, normalize=False, tile_rows=None, idx64=False, queries=None, kblocks=None, whole_if_fits=True,
-                  prenormalized=False, idx16=False, gallery=None, kernels=None):
+                  prenormalized=False, idx16=False, gallery=None, kernels=None, precision=None):
     """Generator over ``(first_row, rank_tile)`` with ``rank_tile`` an int32 (int64 if ``idx64``)
     DEVICE tensor ``[rows, N]``: the canonical ranking of queries ``first_row .. first_row+rows``.
     **A tile is valid until the next one is drawn**: the tiles of one iteration share one distance and one rank buffer.  Without a
@@ -188,7 +229,26 @@ def ranking_tiles(features, normalize=False, tile_rows=None, idx64=False, querie
     touched again once the iteration has ended.  ``tile_rows`` defaults to ``DEFAULT_TILE_BYTES`` worth of rows
     (``hierarchical_precision_device(..., rank_gallery=True)`` sizes it from the free device memory instead); ``idx64`` / ``idx16`` /
     ``whole_if_fits`` do not apply.  ``kernels`` (tests): CPU stand-ins ``{'normalize_rows_', 'row_sqnorm', 'pairwise_dist',
-    'rank_rows'}``."""
+    'rank_rows'}``.
+
+    ``precision='float64'`` (opt-in): ``features`` is a float64 device tensor and every tile is the canonical ranking of FLOAT64
+    distances -- ``se_pairwise_dist_f64`` (one sequential float64 FMA chain; ``kblocks`` does not apply and must be None), ``se_rank_rows``
+    on the float32 image, ``se_rank_refine_f64`` on the runs of equal images.  Rows are normalised / their square norms taken on the
+    host with the reference's NumPy lines (N x D: nothing next to N x N).  A tile row holds 8 + 4 bytes per pair next to its ranks,
+    which the tile size accounts for.  All-pairs only (``gallery`` raises), int32 or int64 ranks (``idx16`` raises).
+    ``kernels`` (tests): ``{'pairwise_dist_f64', 'rank_rows_f64'}``."""
+    if is_float64(precision):
+        if gallery is not None or idx16:
+            raise ValueError("precision='float64' ranks all pairs of one feature matrix into int32 / int64 ranks: a separate gallery "
+                             "and 16-bit ranks stay float32")
+        if kblocks is not None and len(kblocks):
+            raise ValueError("precision='float64' computes ONE float64 FMA chain per distance: kblocks does not apply")
+        return _ranking_tiles_f64(features, normalize, tile_rows, idx64, queries, whole_if_fits, prenormalized, kernels)
+    return _ranking_tiles_f32(features, normalize, tile_rows, idx64, queries, kblocks, whole_if_fits, prenormalized, idx16, gallery, kernels)
+
+
+def _ranking_tiles_f32(features, normalize, tile_rows, idx64, queries, kblocks, whole_if_fits, prenormalized, idx16, gallery, kernels):
+    """The generator of ``ranking_tiles`` for the float32 kernels."""
     all_pairs = gallery is None
     if not all_pairs and (idx64 or idx16):
         raise ValueError('ranking_tiles(..., gallery=...) writes int32 ranks')
@@ -241,7 +301,44 @@ def ranking_tiles(features, normalize=False, tile_rows=None, idx64=False, querie
         yield r0, (kernels['rank_rows'](dist) if rk is None else kernels['rank_rows'](dist, out=rk[:rows]))
 
 
-def pairwise_retrieval(features, normalize=False, return_generator=True, kblocks=None):
+def _ranking_tiles_f64(features, normalize, tile_rows, idx64, queries, whole_if_fits, prenormalized, kernels):
+    """The generator of ``ranking_tiles(..., precision='float64')``."""
+    import torch
+    if not torch.is_tensor(features) or features.dtype != torch.float64:
+        raise ValueError("precision='float64' takes a float64 tensor [N, D]")
+    kernels = resolve_kernels(kernels, F64_RANKING_KERNELS)
+    n, d = features.shape
+    sq = None
+    if normalize and not prenormalized:
+        features.copy_(torch.from_numpy(host_normalize_f64(features.cpu().numpy())))
+    elif not normalize:
+        sq = torch.from_numpy(host_sqnorm_f64(features.cpu().numpy())).to(features.device)
+    q0, q1 = (0, n) if queries is None else queries
+    pair_bytes = 8 + 4 + (8 if idx64 else 4)       # float64 distance, float32 image, rank
+    if tile_rows is None:
+        tile_rows = max(128, min(n, (DEFAULT_TILE_BYTES // (pair_bytes * max(n, 1))) // 128 * 128))
+        if whole_if_fits and features.is_cuda:
+            import sehip
+            ws = max(sehip.rank_rows_workspace_bytes(q1 - q0, n), sehip._lib.call('se_rank_refine_f64_workspace_bytes', q1 - q0, n))
+            extra_ws = max(0, ws - sehip.workspace_bytes(features.device))
+            held = sum(int(b.numel()) for b in _tile_cache.get(sehip.ops._device_index(features.device), {}).values())
+            if pair_bytes * n * (q1 - q0) + extra_ws <= (torch.cuda.mem_get_info(features.device)[0] + held) // 3:
+                tile_rows = max(tile_rows, q1 - q0)
+    tile_rows = max(1, int(tile_rows))
+    pd = im = rk = None          # (CPU stand-ins of the tests allocate their own results)
+    if features.is_cuda and q1 > q0:
+        rows_max = min(tile_rows, q1 - q0)
+        pd = _cached_rows('pd64', rows_max, n, torch.float64, features.device)
+        im = _cached_rows('pd', rows_max, n, torch.float32, features.device)
+        rk = _cached_rows('rk', rows_max, n, torch.int64 if idx64 else torch.int32, features.device)
+    for r0 in range(q0, q1, tile_rows):
+        rows = min(tile_rows, q1 - r0)
+        dist, image = kernels['pairwise_dist_f64'](features[r0:r0 + rows], features, normalize, None if sq is None else sq[r0:r0 + rows], sq,
+                                                   None if pd is None else pd[:rows], True if im is None else im[:rows])
+        yield r0, (kernels['rank_rows_f64'](dist, image, idx64=idx64) if rk is None else kernels['rank_rows_f64'](dist, image, out=rk[:rows]))
+
+
+def pairwise_retrieval(features, normalize=False, return_generator=True, kblocks=None, precision=None):
     """ Uses each image as query and retrieves its nearest neighbors.
 
     # Arguments (identical to the reference, evaluate_retrieval.py:22-41):
@@ -250,6 +347,9 @@ def pairwise_retrieval(features, normalize=False, return_generator=True, kblocks
     - normalize: Whether to L2-normalize the features.
     - return_generator: If True, a generator will be returned instead of a dictionary.
     - kblocks (extension): None | 'openblas' | list -- K-block list of the host BLAS to reproduce for D > 448.
+    - precision (extension): None -- the float32 kernels (float64 features are cast, with a warning); 'float64' -- float64 features
+      only (float32 ones raise ``ValueError``): float64 distances from one sequential FMA chain, ranked exactly (DESIGN.md section
+      3.1), the reference's computation for such features.  ``kblocks`` does not apply.
 
     # Returns:
         generator (or dict) of ``(image ID, list of all image IDs ordered by increasing distance)``.
@@ -258,6 +358,8 @@ def pairwise_retrieval(features, normalize=False, return_generator=True, kblocks
     import sehip  # raises SehipError if the HIP library is missing -- no CPU fallback
 
     features, ind2id, owned = _as_feature_matrix(features)
+    if is_float64(precision):
+        return _pairwise_retrieval_f64(features, ind2id, normalize, return_generator, kblocks)
     if isinstance(features, np.ndarray) and features.dtype == np.float64:
         # the reference computes in the caller's dtype (evaluate_retrieval.py:57-67): float64 features give float64 distances and
         # their ranking.  The kernels are float32 (the dtype of every feature dump the reference writes,
@@ -276,17 +378,39 @@ def pairwise_retrieval(features, normalize=False, return_generator=True, kblocks
         if not owned and isinstance(features, np.ndarray) and features.dtype == np.float32:
             np.copyto(features, dev.cpu().numpy())
 
-    def gen():
-        for r0, tile in ranking_tiles(dev, normalize, kblocks=kblocks or (), prenormalized=True):
-            ranks = tile.cpu().numpy()
-            for i in range(ranks.shape[0]):
-                ret = ranks[i]
-                if ind2id is not None:
-                    yield ind2id[r0 + i], ind2id[ret].tolist()
-                else:
-                    yield r0 + i, ret.tolist()
+    g = _ranked_ids(ranking_tiles(dev, normalize, kblocks=kblocks or (), prenormalized=True), ind2id)
+    return g if return_generator else dict(g)
 
-    g = gen()
+
+def _ranked_ids(tiles, ind2id):
+    """``(image ID, list of all image IDs ordered by increasing distance)`` for every row of every ranking tile."""
+    for r0, tile in tiles:
+        ranks = tile.cpu().numpy()
+        for i in range(ranks.shape[0]):
+            ret = ranks[i]
+            if ind2id is not None:
+                yield ind2id[r0 + i], ind2id[ret].tolist()
+            else:
+                yield r0 + i, ret.tolist()
+
+
+def _pairwise_retrieval_f64(features, ind2id, normalize, return_generator, kblocks):
+    """``pairwise_retrieval(..., precision='float64')``: the checks and the host normalisation come before the GPU is asked for."""
+    import torch
+    import sehip
+    if not isinstance(features, np.ndarray) or features.dtype != np.float64:
+        raise ValueError("precision='float64' takes float64 features, got {}: float32 features are what the float32 kernels "
+                         "(precision=None) rank bit for bit like the reference".format(getattr(features, 'dtype', type(features).__name__)))
+    if kblocks is not None:
+        raise ValueError("precision='float64' computes ONE float64 FMA chain per distance: kblocks does not apply")
+    if features.ndim != 2:
+        raise ValueError('Feature matrix must be 2-dimensional. Actual shape: {}'.format(features.shape))
+    if normalize:
+        # the reference's line, on the caller's array like the reference (`features /= ...`, evaluate_retrieval.py:58)
+        features /= np.linalg.norm(features, axis=-1, keepdims=True)
+    sehip._lib.require_gpu()
+    dev = torch.from_numpy(np.ascontiguousarray(features)).cuda()
+    g = _ranked_ids(ranking_tiles(dev, normalize, prenormalized=True, precision='float64'), ind2id)
     return g if return_generator else dict(g)
 
 
@@ -376,6 +500,7 @@ def build_parser():
     g.add_argument('--skip_ap', action='store_true', default=False,
                    help='Do not compute AP; with --clip_ahp only the head of each ranking is needed (sharded-gallery top-k under several ranks).')
     g.add_argument('--kblocks', type=str, default=None, help="'openblas': restart the fp32 dot-product chain per OpenBLAS K block (D > 448).")
+    add_float64_flag(g)
     add_gallery_flags(g)
     # (absent from the namespace unless given -- a run without it parses to exactly what it did before the flag existed)
     g.add_argument('--rank_gallery', action='store_true', default=argparse.SUPPRESS,
@@ -394,12 +519,38 @@ def add_gallery_flags(group):
                        help='Dataset split the ids of --gallery_feat belong to.')
 
 
+def add_float64_flag(group):
+    """--float64 of evaluate_retrieval.py and plot_recall_precision.py (absent from the namespace unless given, like --rank_gallery)."""
+    group.add_argument('--float64', action='store_true', default=argparse.SUPPRESS,
+                       help='Evaluate float64 --feat files in float64 like the reference: float64 distances, ranked exactly, and no '
+                            'cast-to-float32 warning (float32 files are not affected).  All-pairs on one GPU only: --gallery_feat, '
+                            '--rank_gallery, --kblocks and the sharded multi-GPU evaluation stay float32 and refuse this flag.')
+
+
+def check_float64_flag(parser, args):
+    """The flag combinations --float64 refuses (both CLIs)."""
+    if getattr(args, 'float64', False):
+        if args.gallery_feat or getattr(args, 'rank_gallery', False):
+            parser.error('--float64 evaluates all pairs of a --feat file: --gallery_feat / --rank_gallery stay float32')
+        if args.kblocks:
+            parser.error('--float64 computes ONE float64 FMA chain per distance: --kblocks does not apply')
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            parser.error('--float64 runs in one process on one GPU: the sharded multi-GPU evaluation stays float32')
+
+
+def float64_precision(args, features):
+    """``precision`` for one --feat file: 'float64' for a float64 matrix under --float64, else None."""
+    wanted = getattr(args, 'float64', False) and isinstance(features, np.ndarray) and features.dtype == np.float64
+    return 'float64' if wanted else None
+
+
 def parse_args(argv=None):
     """``build_parser().parse_args(argv)`` plus the checks that span several flags."""
     parser = build_parser()
     args = parser.parse_args(argv)
     if getattr(args, 'rank_gallery', False) and not args.gallery_feat:
         parser.error('--rank_gallery needs --gallery_feat (without a gallery every ranking is a full one already)')
+    check_float64_flag(parser, args)
     return args
 
 
@@ -483,6 +634,8 @@ def main(argv=None):
         gallery_kw = gallery_arguments(args, i, data_generator, embed_labels)
         if gallery_kw and getattr(args, 'rank_gallery', False):
             gallery_kw['rank_gallery'] = True
+        if float64_precision(args, features):       # (the keyword is only passed when the flag asks for it)
+            gallery_kw['precision'] = 'float64'
         perf[feat_name] = hierarchy.hierarchical_precision_device(
             features, labels_test, ks, compute_ahp=args.clip_ahp if args.clip_ahp else True, compute_ap=not args.skip_ap,
             normalize=normalize, ids=None if ind2id is None else ind2id.tolist(), distributed=world > 1,

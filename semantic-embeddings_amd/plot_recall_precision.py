@@ -11,12 +11,14 @@ reference: plot_recall_precision.py:19-86.  Differences a user can observe:
   ``--csv FILE`` writes ``feature,level,mean_precision`` rows, ``--kblocks openblas`` reaches the ranking (D > 448);
   ``--gallery_feat FILE`` / ``--gallery_split`` (a group of their own): the matching ``--feat`` file holds queries against that
   gallery, whose relevant items are located by counting instead of by ranking the gallery;
+  ``--float64``: float64 ``--feat`` files are ranked in float64 like the reference does (all-pairs only; see evaluate_retrieval.py);
 * matplotlib is only imported when a figure is drawn; with ``--csv`` and without matplotlib the figure is skipped.
 """
 import argparse
 from collections import OrderedDict
 
-from evaluate_retrieval import _as_feature_matrix, add_gallery_flags, feat_entry, gallery_arguments, load_labels, str2bool
+from evaluate_retrieval import (_as_feature_matrix, add_float64_flag, add_gallery_flags, check_float64_flag, feat_entry, float64_precision,
+                                gallery_arguments, load_labels, str2bool)
 
 
 def build_parser():
@@ -38,6 +40,7 @@ def build_parser():
     g.add_argument('--save', type=str, default=None, help='Write the figure to this file (format from the extension) instead of showing it.')
     g.add_argument('--csv', type=str, default=None, help='Write "feature,level,mean_precision" rows to this file.')
     g.add_argument('--kblocks', type=str, default=None, help="'openblas': restart the fp32 dot-product chain per OpenBLAS K block (D > 448).")
+    add_float64_flag(p.add_argument_group('Extensions of this build: float64 feature files (not in the reference)'))
     add_gallery_flags(p.add_argument_group('Extensions of this build: queries against a separate gallery (not in the reference)'))
     return p
 
@@ -76,7 +79,9 @@ def main(argv=None):
     """Returns ``{feature name: (levels, mean_precision, mAP)}``."""
     from recall_precision import recall_precision_device
 
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_float64_flag(parser, args)
     if args.bins is not None and args.bins <= 0:
         raise SystemExit('--bins must be positive')
     data_generator, embed_labels, labels_test = load_labels(args)
@@ -85,9 +90,10 @@ def main(argv=None):
     for i, feat_dump in enumerate(args.feat):
         feat_name, normalize = feat_entry(args, i)
         features, ind2id, _ = _as_feature_matrix(feat_dump)
+        extra = {'precision': 'float64'} if float64_precision(args, features) else {}
         levels, means, mAP, _ = recall_precision_device(features, labels_test, normalize=normalize, bins=args.bins,
                                                         ids=None if ind2id is None else ind2id.tolist(), kblocks=args.kblocks,
-                                                        **gallery_arguments(args, i, data_generator, embed_labels))
+                                                        **gallery_arguments(args, i, data_generator, embed_labels), **extra)
         curves[feat_name] = (levels, means, mAP)
         print('{}: mAP {:.4f}, {} levels'.format(feat_name, mAP, len(levels)))
     if args.csv:

@@ -30,7 +30,7 @@ import warnings
 
 import numpy as np
 
-from evaluate_retrieval import RANKING_KERNELS, _as_feature_matrix, _cached_rows, _resolve_kblocks, resolve_kernels
+from evaluate_retrieval import RANKING_KERNELS, _as_feature_matrix, _cached_rows, _resolve_kblocks, is_float64, resolve_kernels, to_device_f64
 
 
 def class_indices(*label_lists):
@@ -130,7 +130,8 @@ def _accumulators(nq, groups, total, bins, dev):
 
 
 def recall_precision_device(features, labels, normalize=False, bins=None, ids=None, kblocks=None, tile_rows=None, kernels=None,
-                            gallery=None, gallery_labels=None, gallery_ids=None, tile_cols=None, distributed=False, group=None):
+                            gallery=None, gallery_labels=None, gallery_ids=None, tile_cols=None, distributed=False, group=None,
+                            precision=None):
     """``plot_recall_precision.py``'s per-feature-file computation (lines 52-79) without leaving the GPU: the rankings stay device
     tensors (``evaluate_retrieval.ranking_tiles``; every image is query and gallery item), ``se_relevant_positions`` finds the
     positions of each query's relevant items, ``se_recall_precision_reduce`` turns them into per-query AP and per-class sums
@@ -148,7 +149,14 @@ def recall_precision_device(features, labels, normalize=False, bins=None, ids=No
     matrix without ``gallery_ids`` shares no id with the queries.  No ranking of the gallery is made: the positions of the relevant
     items are counted (``query_gallery_positions``), so the gallery may be far longer than a row ``se_rank_rows`` sorts in registers.
     ``tile_cols`` (tests): gallery columns per distance slab.  ``distributed``: every rank counts over its shard of the gallery
-    (``sharded_retrieval.shard_bounds``) and ONE integer all-reduce per query tile adds the counts; all ranks return the same values."""
+    (``sharded_retrieval.shard_bounds``) and ONE integer all-reduce per query tile adds the counts; all ranks return the same values.
+
+    ``precision='float64'`` (opt-in): float64 ``features`` are ranked in float64 (``ranking_tiles(..., precision='float64')``); all-pairs
+    only -- with a ``gallery`` or with ``kblocks`` it raises ``ValueError``."""
+    f64 = is_float64(precision)
+    if f64 and (gallery is not None or kblocks is not None):
+        raise ValueError("precision='float64' ranks all pairs of one float64 feature matrix with ONE FMA chain per distance: a separate "
+                         "gallery stays float32, kblocks does not apply")
     if gallery is not None:
         return _recall_precision_gallery(features, labels, normalize, bins, ids, kblocks, tile_rows, tile_cols, kernels, gallery,
                                          gallery_labels, gallery_ids, distributed, group)
@@ -161,14 +169,15 @@ def recall_precision_device(features, labels, normalize=False, bins=None, ids=No
     counts = np.bincount(cls_h, minlength=C)
     r_cls = counts - 1                                    # relevant items of a query of class c: the rest of its class
     class_off = np.concatenate([[0], np.cumsum(r_cls)]).astype(np.int64)
-    feats = to_device_f32(p.qf, dev)
+    feats = to_device_f64(p.qf, dev) if f64 else to_device_f32(p.qf, dev)
+    tiles_kw = {'precision': 'float64'} if f64 else {}
 
     cls_d = torch.from_numpy(cls_h).to(dev)
     qidx_d = torch.arange(n, dtype=torch.int32, device=dev)
     class_off_d = torch.from_numpy(class_off).to(dev)
     ap, prec_sum, first_miss, bin_sum, bin_count = _accumulators(n, C, int(class_off[-1]), bins, dev)
     # each tile is consumed before the next one is drawn (ranking_tiles reuses its buffers)
-    for r0, tile in kernels['ranking_tiles'](feats, normalize, tile_rows=tile_rows, kblocks=kblocks):
+    for r0, tile in kernels['ranking_tiles'](feats, normalize, tile_rows=tile_rows, kblocks=kblocks, **tiles_kw):
         rows = int(tile.shape[0])
         qc = cls_h[r0:r0 + rows]
         hit_off = np.concatenate([[0], np.cumsum(r_cls[qc])]).astype(np.int64)

@@ -19,7 +19,8 @@ __all__ = [
     "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
     "adagrad_step_", "ADAGRAD_MAX_BLOCKS", "grad_clip_factor", "sgd_step_", "SGD_MAX_BLOCKS", "shortcut_add", "LAYOUT_NCHW", "LAYOUT_NHWC",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
-    "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "topk_rows",
+    "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "pairwise_dist_f64",
+    "rank_refine_f64_", "rank_rows_f64", "topk_rows",
     "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
     "recall_precision_reduce", "count_preceding", "count_to_positions", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
     "svm_axpby", "class_pair_tables", "cholesky_lower_", "eigh", "eigh_schedule", "EIGH_NOT_CONVERGED", "EIGH_NONFINITE", "image_batch", "resample_tables", "tiny_batch", "TINY_BATCH_MAX_BLOCKS", "FILL_MODES",
@@ -971,9 +972,10 @@ def pairwise_dist(a, b=None, metric=METRIC_COSINE, sqa=None, sqb=None, kblocks=N
 _ws_cache = {}
 
 
-def _workspace(nbytes, device):
-    """Grow-only per-device scratch buffer (the C ABI never allocates)."""
-    key = _device_index(device)
+def _workspace(nbytes, device, kind=None):
+    """Grow-only per-device scratch buffer (the C ABI never allocates).  ``kind``: a buffer of its own under that name, for an entry
+    point that keeps state in its workspace between its launches while another may run on a second stream."""
+    key = _device_index(device) if kind is None else (kind, _device_index(device))
     ws = _ws_cache.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = None
@@ -1010,7 +1012,8 @@ def release_workspace(device=None):
     if device is None:
         _ws_cache.clear()
     else:
-        _ws_cache.pop(_device_index(device), None)
+        for key in [k for k in _ws_cache if k == _device_index(device) or (isinstance(k, tuple) and k[1] == _device_index(device))]:
+            _ws_cache.pop(key)
 
 
 def phase_timing(on=True):
@@ -1054,6 +1057,69 @@ def rank_rows(pdist, idx64=False, out=None, idx16=False):
     ws = _workspace(call("se_rank_rows_workspace_bytes", q, n), pdist.device)
     call("se_rank_rows", pdist, pdist.stride(0), q, n, out, _rank_width_code(out), out.stride(0), ws, ws.numel())
     return out
+
+
+def _f64_rows(t, what):
+    if t.dtype != torch.float64:
+        raise SehipError("%s must be float64" % what)
+    return _rows(t, what)
+
+
+def pairwise_dist_f64(a, b=None, metric=METRIC_COSINE, sqa=None, sqb=None, out=None, img=True):
+    """Float64 all-pairs distances ``[q, n]`` of float64 operands (``se_pairwise_dist_f64``: ONE sequential float64 FMA chain per
+    element) and their float32 image.  ``sqa`` / ``sqb``: float64 row square norms, required for the
+    Euclidean metric -- the caller computes them with the reference's NumPy line (evaluate_retrieval.py:61).  ``img``: True
+    (allocate), a float32 ``[q, n]`` tensor, or None / False (no image).  Returns ``(out, img)``."""
+    require_gpu(a, b, sqa, sqb, out, img if isinstance(img, torch.Tensor) else None)
+    b = a if b is None else b
+    _f64_rows(a, "a"); _f64_rows(b, "b")
+    q, d = a.shape
+    n = b.shape[0]
+    if b.shape[1] != d:
+        raise SehipError("a and b must have the same number of columns")
+    if metric == METRIC_EUCLID:
+        if sqa is None or (sqb is None and b is not a):
+            raise SehipError("the float64 Euclidean metric needs sqa and sqb (np.sum(x ** 2, axis=-1) of the host)")
+        sqb = sqa if sqb is None else sqb
+        for t, rows in ((sqa, q), (sqb, n)):
+            if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != rows:
+                raise SehipError("sqa / sqb must be contiguous float64 vectors of one entry per row")
+    if out is None:
+        out = empty_rows(q, n, torch.float64, a.device)
+    _f64_rows(out, "out")
+    if img is True:
+        img = empty_rows(q, n, torch.float32, a.device)
+    elif img is False:
+        img = None
+    if img is not None:
+        _f32_rows(img, "img")
+    if tuple(out.shape) != (q, n) or (img is not None and tuple(img.shape) != (q, n)):
+        raise SehipError("out / img must be [%d, %d] matrices" % (q, n))
+    call("se_pairwise_dist_f64", a, a.stride(0), b, b.stride(0), sqa, sqb, q, n, d, int(metric), out, out.stride(0), img,
+         0 if img is None else img.stride(0))
+    return out, img
+
+
+def rank_refine_f64_(pdist64, img, rank):
+    """``se_rank_refine_f64``: ``rank = rank_rows(img)`` (int32 or int64) becomes, in place, the canonical ranking of the float64
+    distances ``pdist64`` -- every run of adjacent ranks with equal float32 images is sorted by (float64 distance, index)."""
+    require_gpu(pdist64, img, rank)
+    _f64_rows(pdist64, "pdist64"); _f32_rows(img, "img")
+    if rank.dtype not in (torch.int32, torch.int64) or rank.dim() != 2 or rank.stride(1) != 1:
+        raise SehipError("rank must be an int32 or int64 matrix with contiguous rows")
+    if img.shape != pdist64.shape or rank.shape != pdist64.shape:
+        raise SehipError("pdist64, img and rank must have the same shape")
+    q, n = pdist64.shape
+    # (a buffer of its own: the row flags the first launch leaves for the second must not meet a ranking on another stream)
+    ws = _workspace(call("se_rank_refine_f64_workspace_bytes", q, n), pdist64.device, kind="refine_f64")
+    call("se_rank_refine_f64", pdist64, pdist64.stride(0), img, img.stride(0), q, n, rank, _rank_width_code(rank), rank.stride(0), ws,
+         ws.numel())
+    return rank
+
+
+def rank_rows_f64(pdist64, img, idx64=False, out=None):
+    """Canonical ``np.argsort`` of float64 distances: ``rank_rows`` of their float32 image, then ``rank_refine_f64_``."""
+    return rank_refine_f64_(pdist64, img, rank_rows(img, idx64=idx64, out=out))
 
 
 def rank_rows_check(pdist, rank):

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Kernel-level microbenchmarks (HIP-event timing on the launch stream) used while tuning.
     python tools/bench_kernels.py pdist|rank|loss|topk [--n 50000 --d 100 --reps 5]
+    python tools/bench_kernels.py pdist64 [--n 50000 --d 100]   (the opt-in float64 retrieval step, leg by leg: float64 distances, their float32
+                                                  image, se_rank_rows on it, se_rank_refine_f64; the float32 step next to them)
     python tools/bench_kernels.py recprec        (10k x 10k and 50k x 50k, 100 classes; --n is not used)
     python tools/bench_kernels.py svm            (margin + reduction kernels and whole LinearSVC fits: 50,000 x 100 x 100 and
                                                   1,281,167 x 1000 x 1000; --n / --d are not used; --svm-sizes small skips the large one)
@@ -97,7 +99,7 @@ def windows(fns, reps, batch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -139,6 +141,8 @@ def main():
         return bench_head()
     if args.what == "joint":
         return bench_joint()
+    if args.what == "pdist64":
+        return bench_pdist64(args.n, args.d, max(args.reps, 10))
     n, d = args.n, args.d
     q = args.q or n
     x = torch.from_numpy(np.random.default_rng(0).standard_normal((n, d)).astype(np.float32)).cuda()
@@ -364,6 +368,67 @@ def main():
         x2, y2, E2 = torch.randn(B2, 100, device="cuda"), torch.randint(0, 100, (B2,), device="cuda"), E[:100, :100].contiguous()
         med, mn = timeit(lambda: sehip.cosine_loss_forward(x2, y2, E2), 20)
         print("loss fwd B=128 D=100: median %.1f us" % (med * 1e3))
+
+
+FP64_VECTOR_PEAK_TFLOPS = 78.6     # AMD's published FP64 vector rate of the MI355X (MI355X_MICROARCH.md lists no FP64 row)
+HBM_MEASURED_TBS = 6.29            # MI355X_MICROARCH.md: float4 copy
+
+
+def bench_pdist64(n, d, reps):
+    """The float64 retrieval step (precision='float64') on one tile of an n x n x d all-pairs problem, tiled as
+    evaluate_retrieval.ranking_tiles tiles it (whole when 16 B per pair fit a third of the free device memory, else
+    DEFAULT_TILE_BYTES worth of rows), every leg on its own: se_pairwise_dist_f64 without and with the float32 image, se_rank_rows
+    on the image, se_rank_refine_f64; the float32 step (se_pairwise_dist + se_rank_rows) of the same tile next to them.  One
+    process; 3 warm-up calls per leg, then `reps` rounds in which the legs take turns, HIP events around each call: median
+    (10th-90th percentile) in ms.  The tile's time is scaled to the whole problem by the number of tiles.
+    Bounds of the distance leg: 2 q n d operations over AMD's published FP64 vector rate, and 12 q n bytes written over the measured
+    copy bandwidth; the larger is the least time the hardware could take."""
+    import evaluate_retrieval as er
+    rng = np.random.default_rng(0)
+    x64 = torch.from_numpy(rng.standard_normal((n, d))).cuda()
+    x64.copy_(torch.from_numpy(er.host_normalize_f64(x64.cpu().numpy())))
+    x32 = x64.float()
+    sehip.normalize_rows_(x32)
+    pair_bytes = 16
+    rows = max(128, min(n, (er.DEFAULT_TILE_BYTES // (pair_bytes * n)) // 128 * 128))
+    if pair_bytes * n * n <= torch.cuda.mem_get_info()[0] // 3:
+        rows = n
+    tiles = -(-n // rows)
+    pd64, img = sehip.empty_rows(rows, n, torch.float64, "cuda"), sehip.empty_rows(rows, n, torch.float32, "cuda")
+    rk, pd32 = sehip.empty_rows(rows, n, torch.int32, "cuda"), sehip.empty_rows(rows, n, torch.float32, "cuda")
+    sehip.pairwise_dist_f64(x64[:rows], x64, out=pd64, img=img)
+    sehip.rank_rows(img, out=rk)
+    first = rk.clone()
+    torch.cuda.synchronize()
+    runs = int((torch.gather(img[:256], 1, first[:256, 1:].long()) == torch.gather(img[:256], 1, first[:256, :-1].long())).sum())
+
+    def refine():                        # (every call repairs the same image ranking: the copy is timed on its own and subtracted)
+        rk.copy_(first)
+        sehip.rank_refine_f64_(pd64, img, rk)
+    legs = [("se_pairwise_dist_f64, no image", lambda: sehip.pairwise_dist_f64(x64[:rows], x64, out=pd64, img=None)),
+            ("se_pairwise_dist_f64 + image", lambda: sehip.pairwise_dist_f64(x64[:rows], x64, out=pd64, img=img)),
+            ("se_rank_rows on the image", lambda: sehip.rank_rows(img, out=rk)),
+            ("rank copy + se_rank_refine_f64", refine),
+            ("rank copy alone", lambda: rk.copy_(first)),
+            ("float32: se_pairwise_dist", lambda: sehip.pairwise_dist(x32[:rows], x32, out=pd32)),
+            ("float32: se_rank_rows", lambda: sehip.rank_rows(pd32, out=rk))]
+    res = windows([f for _, f in legs], reps, 1)
+    print("pdist64 n=%d d=%d: tile of %d rows (%d tile%s; whole-problem times = tile x %d), %d rounds, ms per call: median (10th-90th percentile)"
+          % (n, d, rows, tiles, "" if tiles == 1 else "s", tiles, reps))
+    for (name, _), (med, lo, hi) in zip(legs, res):
+        print("  %-34s %9.3f (%9.3f - %9.3f)   whole problem %9.2f" % (name, med / 1e3, lo / 1e3, hi / 1e3, med / 1e3 * tiles))
+    t = {name: med / 1e3 for (name, _), (med, _, _) in zip(legs, res)}
+    dist = t["se_pairwise_dist_f64 + image"]
+    t_flop, t_mem = 2.0 * rows * n * d / (FP64_VECTOR_PEAK_TFLOPS * 1e9), 12.0 * rows * n / (HBM_MEASURED_TBS * 1e9)
+    print("  distance + image: %.1f TFLOP/s = %.2f of the %.1f TFLOP/s FP64 vector rate; %.2f TB/s written; least time %.3f ms (%s bound) = %.2f of the leg"
+          % (2.0 * rows * n * d / dist / 1e9, t_flop / dist, FP64_VECTOR_PEAK_TFLOPS, 12.0 * rows * n / dist / 1e9, max(t_flop, t_mem),
+             "operation" if t_flop > t_mem else "memory", max(t_flop, t_mem) / dist))
+    repair = t["rank copy + se_rank_refine_f64"] - t["rank copy alone"]
+    print("  repair alone: %.3f ms = %.2f x the se_rank_rows leg; %.1f pairs of adjacent ranks per row share an image (first 256 rows)"
+          % (repair, repair / t["se_rank_rows on the image"], runs / min(256, rows)))
+    f64 = dist + t["se_rank_rows on the image"] + repair
+    f32 = t["float32: se_pairwise_dist"] + t["float32: se_rank_rows"]
+    print("  float64 step %.3f ms, float32 step %.3f ms: %.1f x" % (f64, f32, f64 / f32))
 
 
 def bench_eigh(s, label):

@@ -38,6 +38,9 @@ counts = np.bincount(cls.cpu().numpy(), minlength=C)
 best = np.stack([np.cumsum(np.repeat(tab[c][np.argsort(-tab[c], kind="stable")], counts[np.argsort(-tab[c], kind="stable")])) for c in range(C)])
 tab_d, best_d = dev(tab), dev(best)
 rk_mid = sehip.rank_rows(pd_mid)
+g64 = g20[:4096].double()                                           # float64 retrieval: distances + image, ranking + run repair
+pd64, img64 = sehip.pairwise_dist_f64(g64[:1024], g64)
+pd64[:, 100:1300] = 1.0 + pd64[:, 100:1300] * 2.0 ** -30; img64 = pd64.float()   # 1,200 columns of image 1.0f: a run beyond the LDS sort
 ks = torch.arange(1, 251, dtype=torch.int32, device="cuda")
 qidx = torch.arange(1024, dtype=torch.int32, device="cuda")
 curves = sehip.hprec_reciprocal_curves(best_d, best_d)
@@ -95,6 +98,8 @@ OPS = {
     "rank_rows 3,001 columns": lambda: sehip.rank_rows(pd_short),
     "rank_rows 20,000 columns": lambda: sehip.rank_rows(pd_mid),
     "rank_rows 60,000 columns (runs + merge)": lambda: sehip.rank_rows(pd_long),
+    "pairwise_dist_f64 cosine": lambda: sehip.pairwise_dist_f64(g64[:2048], g64),
+    "rank_rows_f64 (image ranking + run repair)": lambda: sehip.rank_rows_f64(pd64, img64),
     "topk_rows k=251": lambda: sehip.topk_rows(pd_mid, 251),
     "topk_rows k=1000": lambda: sehip.topk_rows(pd_mid, 1000),
     "topk_merge packed 8 parts": lambda: sehip.topk_merge(parts),
