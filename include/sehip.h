@@ -672,6 +672,38 @@ int se_retrieve_topk(const float *queries, int64_t ldq, const float *gallery, in
                      se_stream_t stream);
 
 /*
+ * k-nearest-neighbour classification: the vote over every query's neighbour list (a consumer of se_retrieve_topk / se_topk_merge).
+ * Replaces: sklearn.neighbors.KNeighborsClassifier(n_neighbors = k, weights = 'uniform', algorithm = 'brute') -- the counts behind
+ *           predict_proba and the smallest-label-among-ties rule of predict -- on neighbour lists that are already there (the
+ *           reference has no k-NN line), for several k and the `top` best classes at once.
+ *   idx       [q, list_len] int32 global gallery indices, best first (ldi elements between rows); 1 <= list_len <= SE_TOPK_MAX
+ *   cls       [gallery] int32 class index of every gallery item
+ *   qidx      [q] int32 gallery index of the query itself, or NULL
+ *   ks        [nk] int32 cut-offs, HOST pointer (read before the launch): strictly ascending, each in [1, list_len];
+ *             nk <= SE_KNN_KS_MAX (more is SE_ERR_UNSUPPORTED)
+ *   top       classes to report per (query, cut-off): 1 .. SE_KNN_TOP_MAX and <= num_classes
+ *   out_cls, out_votes   [q, nk, top] int32
+ * Who votes: the list is walked in order.  An entry outside [0, gallery) -- the 2^31 - 1 pads of short shards, -1 -- is skipped (no
+ * gather leaves cls), and so is an entry equal to qidx[i] (leave-one-out).  Every other entry is one of the query's NEIGHBOURS and
+ * votes for class cls[entry] with weight 1; a class value outside [0, num_classes) casts no vote but still counts as a neighbour.
+ * For cut-off ks[j] the first ks[j] neighbours vote -- all of them when the list holds fewer (a list of exactly ks[j] entries that
+ * contains the query, or pads).
+ * Ranking: out_cls[i, j, :] = the `top` best classes under (votes descending, class index ascending), out_votes their vote counts;
+ * classes without a vote fill the tail in ascending class index with 0 votes.  The tie rule is that of se_rank_rows on negated
+ * scores and of scikit-learn's uniform-weight predict.
+ *   Everything is an integer: the same inputs give the same bits on every launch geometry.  num_classes is not limited (the
+ *   per-query vote table has 2 * list_len slots, whatever the number of classes).  q == 0 or nk == 0 returns SE_OK without a launch.
+ *   SE_ERR_INVALID: a NULL idx / cls / ks / out_cls / out_votes, ldi < list_len, list_len outside [1, SE_TOPK_MAX], top out of range,
+ *   cut-offs that do not ascend or leave [1, list_len], num_classes < 1, a negative size.
+ *   Asynchronous on `stream`; no workspace, no allocation, no host synchronisation, no float atomics: capturable in a HIP graph.
+ */
+#define SE_KNN_TOP_MAX 16
+#define SE_KNN_KS_MAX 32
+int se_knn_vote(const int32_t *idx, int64_t ldi, int64_t q, int64_t list_len, const int32_t *cls, int64_t gallery,
+                int num_classes, const int32_t *qidx, const int32_t *ks, int nk, int top, int32_t *out_cls,
+                int32_t *out_votes, se_stream_t stream);
+
+/*
  * Hierarchical retrieval metrics of every query from its ranking (the consumer of se_rank_rows / se_retrieve_topk).
  * Replaces: the per-query loop of ClassHierarchy.hierarchical_precision (class_hierarchy.py:211-316):
  *           P@k (WUP / LCS_HEIGHT), AHP or AHP@K (np.trapz of cum / best, :303-309), AP (:310-314), with the

@@ -19,6 +19,10 @@ Mirrors the pieces of the reference's ``evaluate_classification_accuracy.py`` th
 * ``main`` / ``__main__``: the reference's command line and result table (``print_performance``), with features extracted on the
   device from a ``--model_dump`` of learn_image_embeddings.py (``torch.save`` of the module).
 
+* ``knn_classification`` / ``--knn K [K ...]`` (an extension of this build; the reference has none): k-nearest-neighbour
+  classification of the test images against the training images -- ``se_retrieve_topk`` for the neighbour lists, ``se_knn_vote``
+  (knn_vote.hip) for the vote; ties go to the smaller class index, as in scikit-learn's ``KNeighborsClassifier``.
+
 Class rankings of the new modes come from ``se_rank_rows`` on the negated scores: descending score, ties in ascending class
 index (the reference's ``argsort(-1)[:, ::-1]`` breaks ties in an unspecified order).
 """
@@ -226,6 +230,83 @@ def nn_classification_model(data, centroids, model, layer=None, custom_objects={
     return nn_classification(feat, centroids)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# k-nearest-neighbour classification (an extension of this build: the reference has no k-NN mode)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+def knn_classification(X_train, y_train, X_test=None, ks=(1,), normalize=False, num_classes=None, top=5, kblocks=None, kernels=None,
+                       return_votes=False):
+    """k-NN classification of the rows of ``X_test`` against the training set: ``{k: class ranking [N, top] (NumPy int32)}``, best
+    class first -- most votes among the k nearest training rows, ties in ascending class index (scikit-learn's
+    ``KNeighborsClassifier(weights='uniform')`` rule), classes without a vote behind them in ascending index.  ``evaluate`` takes
+    every ranking as it is.
+
+    Features: float32 ``[N, D]`` arrays or device tensors.  With ``normalize`` the rows are L2-normalised (``se_normalize_rows``) and
+    the metric is cosine, otherwise squared Euclidean on the raw features -- the two metrics of evaluate_retrieval.py, with its
+    canonical (distance, index) order among equal distances.  The neighbour lists are ONE fused distance + top-k call
+    (``sehip.retrieve_topk`` with ``k = max(ks)``; ``kblocks``: as in ``pairwise_retrieval``, for the reference's BLAS arithmetic
+    at D > 448) and the vote is ``sehip.knn_vote`` over them: the N x N_train distances are never written.
+    ``X_test=None``: leave-one-out on the training set -- lists of ``max(ks) + 1`` entries from which every row's own index is dropped.
+    ``num_classes`` defaults to ``max(y_train) + 1``; ``top`` is capped at it.  ``max(ks)`` (+ 1) above the number of training rows
+    or above ``sehip.TOPK_MAX`` raises ``ValueError`` before anything is launched.
+    ``return_votes``: also ``{k: vote counts [N, top]}`` of the ranked classes.
+    ``kernels`` (tests): CPU stand-ins ``{'retrieve_topk', 'knn_vote', 'normalize_rows_', 'device'}``."""
+    import torch
+    import sehip
+    from evaluate_retrieval import _resolve_kblocks, resolve_kernels
+    from recall_precision import to_device_f32
+    ks = [int(k) for k in ([ks] if isinstance(ks, (int, np.integer)) else ks)]
+    if not ks or min(ks) < 1:
+        raise ValueError('ks must hold at least one k >= 1, got {}'.format(ks))
+    loo = X_test is None
+    n_train, d = int(X_train.shape[0]), int(X_train.shape[1])
+    y = np.asarray(y_train)
+    if y.shape != (n_train,) or not np.issubdtype(y.dtype, np.integer):
+        raise ValueError('y_train must hold one integer class index per training row')
+    list_len = max(ks) + (1 if loo else 0)
+    if list_len > n_train:
+        raise ValueError('k = {} needs {} training rows{}, there are {}'.format(max(ks), list_len, ' (leave-one-out)' if loo else '', n_train))
+    if list_len > sehip.TOPK_MAX:
+        raise ValueError('k = {}{} exceeds the longest neighbour list of the fused top-k, {}'.format(
+            max(ks), ' (+ 1 for leave-one-out)' if loo else '', sehip.TOPK_MAX))
+    if not loo and int(X_test.shape[1]) != d:
+        raise ValueError('test rows have {} feature dimensions, training rows {}'.format(X_test.shape[1], d))
+    C = int(num_classes) if num_classes is not None else int(y.max()) + 1
+    top = min(int(top), C)
+    if top < 1 or top > sehip.KNN_TOP_MAX:
+        raise ValueError('top must lie in [1, {}], got {}'.format(sehip.KNN_TOP_MAX, top))
+    kblocks = _resolve_kblocks(kblocks, d)
+    kernels = resolve_kernels(kernels, ('retrieve_topk', 'knn_vote', 'normalize_rows_', 'device'))
+    dev = kernels['device']
+    gallery = to_device_f32(X_train, dev)
+    queries = gallery if loo else to_device_f32(X_test, dev)
+    if normalize:
+        kernels['normalize_rows_'](gallery)
+        if queries is not gallery:
+            kernels['normalize_rows_'](queries)
+    _, lists = kernels['retrieve_topk'](queries, gallery, list_len, metric=sehip.METRIC_COSINE if normalize else sehip.METRIC_EUCLID,
+                                        kblocks=kblocks)
+    cuts = sorted(set(ks))
+    qidx = torch.arange(n_train, dtype=torch.int32, device=dev) if loo else None
+    out_cls, out_votes = kernels['knn_vote'](lists, torch.from_numpy(y.astype(np.int32)).to(dev), C, cuts, top=top, qidx=qidx)
+    out_cls, out_votes = out_cls.cpu().numpy(), out_votes.cpu().numpy()
+    ranks = OrderedDict((k, out_cls[:, cuts.index(k)]) for k in ks)
+    if return_votes:
+        return ranks, OrderedDict((k, out_votes[:, cuts.index(k)]) for k in ks)
+    return ranks
+
+
+def knn_classification_model(data, model, layer=None, normalize=False, ks=(1,), custom_objects={}, batch_size=1):
+    """``--knn`` mode: train and test features of ``model`` like ``train_and_predict`` extracts them (one un-augmented pass over the
+    training set) -> ``knn_classification``: ``{k: class ranking of every test image}``."""
+    sys.stderr.write('Extracting features...\n')
+    X_train = extract_features(data, model, layer, 'train')
+    X_test = extract_features(data, model, layer, 'test', batch_size)
+    n = (data.num_train // 10) * 10
+    sys.stderr.write('Searching for nearest training images...\n')
+    return knn_classification(X_train, np.asarray(data.labels_train)[:n], X_test, ks, normalize, num_classes=len(data.classes))
+
+
 def print_performance(perf, metrics=METRICS):
     """The reference's result table (evaluate_classification_accuracy.py:111-126)."""
     print()
@@ -269,6 +350,8 @@ def build_parser():
     g.add_argument('--norm', type=str2bool, action='append', help='Whether to L2-normalize the corresponding features or not (defaults to False).')
     g.add_argument('--prob_features', type=str2bool, action='append', help='Whether to use the extracted features as class probabilities instead of training an SVM.')
     g.add_argument('--centroids', type=str, action='append', help='Optionally, a pickle dump containing a dictionary with an item "embedding" referring to a numpy array of class centroids for performing nearest-neighbor classification.')
+    g = parser.add_argument_group('Extensions of this build (not in the reference)')
+    g.add_argument('--knn', type=int, nargs='+', default=None, metavar='K', help='Classify the test images of every --model that is neither --prob_features nor --centroids by a vote among their K nearest training images instead of an SVM; one table row per K. --norm selects the cosine metric, otherwise squared Euclidean distances are used.')
     return parser
 
 
@@ -281,14 +364,15 @@ def _layer_arg(v):
 
 def main(argv=None, modes=None):
     """The reference's command line (evaluate_classification_accuracy.py:138-188); returns the table's OrderedDict.
-    ``modes`` (tests): a dict overriding 'svm' / 'centroids' / 'prob' with callables of the same signatures."""
+    ``modes`` (tests): a dict overriding 'svm' / 'centroids' / 'prob' / 'knn' with callables of the same signatures.
+    ``--knn K [K ...]`` (an extension): models that would get an SVM are classified by k-NN, one row ``"<name> [k-NN, k=K]"`` per K."""
     from class_hierarchy import ClassHierarchy
     from evaluate_retrieval import load_labels
     args = build_parser().parse_args(argv)
     data_generator = load_labels(args)[0]
     id_type = str if args.str_ids else int
     hierarchy = ClassHierarchy.from_file(args.hierarchy, is_a_relations=args.is_a, id_type=id_type) if args.hierarchy else None
-    run = {'svm': train_and_predict, 'centroids': nn_classification_model, 'prob': extract_predictions}
+    run = {'svm': train_and_predict, 'centroids': nn_classification_model, 'prob': extract_predictions, 'knn': knn_classification_model}
     run.update(modes or {})
     perf = OrderedDict()
     for i, model in enumerate(args.model):
@@ -302,6 +386,10 @@ def main(argv=None, modes=None):
             pred = run['prob'](data_generator, model, layer, {}, args.batch_size)
         elif centroids:
             pred = run['centroids'](data_generator, centroids, model, layer, {}, args.batch_size)
+        elif args.knn:
+            for k, pred in run['knn'](data_generator, model, layer, normalize, args.knn, {}, args.batch_size).items():
+                perf['{} [k-NN, k={}]'.format(model_name, k)] = evaluate(pred, data_generator, hierarchy)
+            continue
         else:
             pred = run['svm'](data_generator, model, layer, normalize, args.augmentation_epochs, args.C, {}, args.batch_size)
         perf[model_name] = evaluate(pred, data_generator, hierarchy)

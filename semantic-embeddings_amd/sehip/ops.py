@@ -21,7 +21,7 @@ __all__ = [
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "pairwise_dist_f64",
     "rank_refine_f64_", "rank_rows_f64", "topk_rows",
-    "topk_merge", "retrieve_topk", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
+    "topk_merge", "retrieve_topk", "knn_vote", "KNN_TOP_MAX", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
     "recall_precision_reduce", "count_preceding", "count_to_positions", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
     "svm_axpby", "class_pair_tables", "cholesky_lower_", "eigh", "eigh_schedule", "EIGH_NOT_CONVERGED", "EIGH_NONFINITE", "image_batch", "resample_tables", "tiny_batch", "TINY_BATCH_MAX_BLOCKS", "FILL_MODES",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
@@ -1193,6 +1193,36 @@ def retrieve_topk(queries, gallery, k, metric=METRIC_COSINE, col_offset=0, sqq=N
     call("se_retrieve_topk", queries, queries.stride(0), gallery, gallery.stride(0), sqq, sqg, q, n, d, int(metric), kb, nkb,
          int(col_offset), int(k), od, oi, ws, ws.numel())
     return od, oi
+
+
+KNN_TOP_MAX = DEFINES["SE_KNN_TOP_MAX"]     # classes se_knn_vote reports per (query, cut-off)
+
+
+def knn_vote(idx, cls, num_classes, ks, top=5, qidx=None):
+    """k-NN class votes over neighbour lists (``se_knn_vote``): for every query and every cut-off of ``ks``, the ``top`` classes with
+    the most votes among its first k neighbours -- votes descending, ties in ascending class index, classes without a vote behind
+    them in ascending index -- and their vote counts.
+
+    idx [Q, L] int32 neighbour lists, best first, as ``retrieve_topk`` / ``topk_merge`` write them (contiguous rows; any row
+    pitch); cls [N] int32; ``ks``: strictly ascending host integers in [1, L]; qidx [Q] int32 | None: the gallery index of each
+    query, dropped from its list (leave-one-out).  Entries outside [0, N) are skipped.  Returns ``(out_cls, out_votes)``, int32
+    ``[Q, len(ks), top]``."""
+    require_gpu(idx, cls, qidx)
+    if idx.dtype != torch.int32 or idx.dim() != 2 or idx.stride(1) != 1:
+        raise SehipError("idx must be a 2-d int32 tensor with contiguous rows")
+    _i32(cls, "cls")
+    if qidx is not None:
+        _i32(qidx, "qidx")
+        if qidx.numel() != idx.shape[0]:
+            raise SehipError("qidx must hold one gallery index per query")
+    ks = [int(k) for k in ks]
+    Q, L = idx.shape
+    out_cls = torch.empty((Q, len(ks), int(top)), dtype=torch.int32, device=idx.device)
+    out_votes = torch.empty_like(out_cls)
+    ldi = idx.stride(0) if Q > 1 else max(idx.stride(0), L)
+    call("se_knn_vote", idx, ldi, Q, L, cls, cls.numel(), int(num_classes), qidx, (ctypes.c_int32 * len(ks))(*ks), len(ks), int(top),
+         out_cls, out_votes)
+    return out_cls, out_votes
 
 
 class HprecCurves:

@@ -3,6 +3,9 @@
     python tools/bench_kernels.py pdist|rank|loss|topk [--n 50000 --d 100 --reps 5]
     python tools/bench_kernels.py pdist64 [--n 50000 --d 100]   (the opt-in float64 retrieval step, leg by leg: float64 distances, their float32
                                                   image, se_rank_rows on it, se_rank_refine_f64; the float32 step next to them)
+    python tools/bench_kernels.py knn            (se_knn_vote next to the torch composition gather -> scatter_add -> topk, and the whole
+                                                  knn_classification: 10,000 x 50,000 x 100 with k = 20, 100 classes; 50,000 x 50,000 x 100 with
+                                                  k = 200, 1000 classes; --n / --d are not used)
     python tools/bench_kernels.py recprec        (10k x 10k and 50k x 50k, 100 classes; --n is not used)
     python tools/bench_kernels.py svm            (margin + reduction kernels and whole LinearSVC fits: 50,000 x 100 x 100 and
                                                   1,281,167 x 1000 x 1000; --n / --d are not used; --svm-sizes small skips the large one)
@@ -99,7 +102,7 @@ def windows(fns, reps, batch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -141,6 +144,8 @@ def main():
         return bench_head()
     if args.what == "joint":
         return bench_joint()
+    if args.what == "knn":
+        return bench_knn()
     if args.what == "pdist64":
         return bench_pdist64(args.n, args.d, max(args.reps, 10))
     n, d = args.n, args.d
@@ -1158,6 +1163,51 @@ def bench_tiny(reps=40, batch=20, stored=10000):
               "(%.1f-%.1f) = x%.2f of the kernel, whole compose_batch %.1f us (%.1f-%.1f) = x%.2f of the affine compose_batch"
               % (B, k[0], k[1], k[2], nbytes / 1e6, nbytes / (k[0] * 1e-6) / 1e9, w[0], w[1], w[2], td[0], td[1], td[2], td[0] / k[0],
                  tw[0], tw[1], tw[2], tw[0] / w[0]), flush=True)
+
+
+def bench_knn(reps=30, batch=10):
+    """k-NN classification (evaluate_classification_accuracy.knn_classification): se_knn_vote alone on the neighbour lists of
+    se_retrieve_topk next to the torch composition it replaces -- cls[idx] -> scatter_add into a [q, C] int32 histogram -> topk(5) --
+    the two timed alternately in one process: `reps` windows of `batch` back-to-back calls each (HIP events around a window) after 3
+    warm-up calls, median / 10th / 90th percentile of the per-call time.  Then the whole knn_classification on features already on the
+    device (lists + vote + the copy of the [q, 5] rankings to the host; host clock around a call that ends in that copy, median of 5
+    after one warm-up call).  Shapes: 10,000 test x 50,000 training rows x D = 100 with k = 20 and 100 classes; 50,000 x 50,000 x 100
+    with k = 200 and 1000 classes; seeded Gaussian features, squared Euclidean distances.  Bytes of the vote: the lists in, the two
+    [q, 5] results out (the class table stays in cache)."""
+    import time
+    import evaluate_classification_accuracy as eca
+    rng = np.random.default_rng(0)
+    for q, n, d, k, C in ((10000, 50000, 100, 20, 100), (50000, 50000, 100, 200, 1000)):
+        train = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).cuda()
+        test = torch.from_numpy(rng.standard_normal((q, d)).astype(np.float32)).cuda()
+        y = rng.integers(0, C, size=n)
+        cls = torch.from_numpy(y.astype(np.int32)).cuda()
+        _, lists = sehip.retrieve_topk(test, train, k, metric=sehip.METRIC_EUCLID)
+        cls64, lists64 = cls.long(), lists.long()      # (the composition's index conversions are not timed)
+        ones = torch.ones((q, k), dtype=torch.int32, device="cuda")
+
+        def kernel():
+            return sehip.knn_vote(lists, cls, C, [k], top=5)
+
+        def composition():
+            hist = torch.zeros((q, C), dtype=torch.int32, device="cuda").scatter_add_(1, cls64[lists64], ones)
+            return torch.topk(hist, 5, dim=1)
+        votes_k, votes_t = kernel()[1][:, 0], composition()[0]
+        assert torch.equal(votes_k, votes_t.int()), "the two legs disagree on the vote counts"
+        kt, tt = windows((kernel, composition), reps, batch)
+        moved = 4.0 * q * k + 2 * 4.0 * q * 5
+        print("knn vote q=%d k=%d C=%d: se_knn_vote %.1f us (%.1f-%.1f), torch composition %.1f us (%.1f-%.1f): x%.2f; the kernel moves %.1f MB "
+              "= %.0f GB/s" % (q, k, C, kt[0], kt[1], kt[2], tt[0], tt[1], tt[2], tt[0] / kt[0], moved / 1e6, moved / (kt[0] * 1e-6) / 1e9), flush=True)
+        eca.knn_classification(train, y, test, ks=[k], num_classes=C)
+        ts = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eca.knn_classification(train, y, test, ks=[k], num_classes=C)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        print("knn_classification %d x %d x %d, k=%d, C=%d, features on the device: median %.2f ms (min %.2f, max %.2f) per call, rankings on the host"
+              % (q, n, d, k, C, float(np.median(ts)), min(ts), max(ts)), flush=True)
+        del train, test, lists, lists64, ones
 
 
 def bench_adagrad(reps=40, batch=20, steps=200):

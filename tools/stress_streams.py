@@ -109,6 +109,7 @@ OPS = {
     "retrieve_topk slab (3,001 rows)": lambda: sehip.retrieve_topk(g3[:512], g3, 64),
     "hierarchical_precision": lambda: sehip.hierarchical_precision(rk_mid, cls, cls[:1024].contiguous(), qidx, tab_d, tab_d, best_d, best_d, ks,
                                                                      ahp_len=0, want_ap=True, curves=curves),
+    "knn_vote (LDS vote tables)": lambda: sehip.knn_vote(rk_mid[:, :201], cls, C, [1, 5, 20, 200], top=5, qidx=qidx),
     "cosine_loss fwd+bwd": lambda: (sehip.cosine_loss_forward(xb, yb, emb)[0], sehip.cosine_loss_backward(xb, yb, emb)),
     "nn_accuracy": lambda: sehip.nn_accuracy(xb, yb, emb, dot_prod_sim=True, k=5),
     "embed_head cosine": lambda: sehip.embed_head_forward(xb, yb, emb, mode="cosine", want_best=True),
