@@ -704,6 +704,42 @@ int se_knn_vote(const int32_t *idx, int64_t ldi, int64_t q, int64_t list_len, co
                 int32_t *out_votes, se_stream_t stream);
 
 /*
+ * Completion of given ranked lists to rankings of the whole gallery: what turns rankings that come from somewhere else (another
+ * system, an approximate index, re-ranked or truncated lists) into the [q, gallery] index matrices that se_hierarchical_precision
+ * and se_relevant_positions read.
+ * Replaces: `ret = ret + [id for id in all_ids if id not in sret]`, class_hierarchy.py:262-264 ("IDs missing in retrieval results
+ *           will be appended to the end"), the per-query Python set and list comprehension over all_ids, for a tile of queries.
+ *   lists     [q, list_len] int32 gallery indices, best first (ldl elements between rows); may be NULL when list_len == 0
+ *   len       [q] int32 number of valid entries of each row, in [0, list_len] (clamped to it); NULL = every row has list_len
+ *   order     [gallery] int32: the all_ids order as gallery indices, a permutation of 0 .. gallery - 1; NULL = the identity
+ *   rank      [q, gallery] int32 out (ldr elements between rows; elements gallery .. ldr - 1 of a row are not written)
+ *   status    [q] int32 out: 0 for a clean row; bit 0: some valid entry lies outside [0, gallery); bit 1: some index occurs more
+ *             than once
+ * A clean row gets rank[i, :len_i] = lists[i, :len_i], followed by the elements of `order` that are not in the list, in `order`'s
+ * order: exactly `gallery` entries, a permutation.  A row with status != 0 gets `order` itself (the identity when order is NULL):
+ * a valid permutation, so that no consumer gathers outside its tables, but one that means nothing -- the caller looks at status
+ * before it scores.  A bad row is replaced as a whole, not "keeping the first occurrence", so that the result depends neither on
+ * the launch geometry nor on the order in which lanes meet a duplicate.
+ * No gather leaves its row: an entry is range-checked before it is used as a bit position, nothing is read beyond len_i entries of
+ * a row and nothing is written beyond `gallery` entries of a row (an element of `order` outside [0, gallery) -- a broken contract --
+ * is never written).
+ *   Galleries of up to SE_COMPLETE_LDS_ITEMS items keep the per-row membership bitmap in LDS (gallery / 8 bytes per workgroup)
+ *   and need no workspace; larger ones keep it in se_complete_rankings_workspace_bytes(q, gallery) bytes of 4-byte aligned device
+ *   scratch (one bitmap per workgroup of a capped grid), set with integer global atomics.  list_len and gallery are at most
+ *   SE_COMPLETE_MAX_ITEMS.
+ *   q == 0 or gallery == 0 returns SE_OK without a launch.  SE_ERR_INVALID: a NULL lists (with list_len > 0) / rank / status,
+ *   ldl < list_len, ldr < gallery, a negative size or one above SE_COMPLETE_MAX_ITEMS, a workspace that is too small.
+ *   Integers only: the same inputs give the same bits on every launch geometry, and nothing rests on the lane-order property that
+ *   se_rank_rows_init probes.  Asynchronous on `stream`; no allocation, no host synchronisation: capturable in a HIP graph.
+ */
+#define SE_COMPLETE_LDS_ITEMS 262144   /* galleries up to this size keep the per-row membership bitmap in LDS */
+#define SE_COMPLETE_MAX_ITEMS 1073741824
+int64_t se_complete_rankings_workspace_bytes(int64_t q, int64_t gallery);
+int se_complete_rankings(const int32_t *lists, int64_t ldl, const int32_t *len, int64_t q, int64_t list_len,
+                         const int32_t *order, int64_t gallery, int32_t *rank, int64_t ldr, int32_t *status,
+                         void *workspace, int64_t workspace_bytes, se_stream_t stream);
+
+/*
  * Hierarchical retrieval metrics of every query from its ranking (the consumer of se_rank_rows / se_retrieve_topk).
  * Replaces: the per-query loop of ClassHierarchy.hierarchical_precision (class_hierarchy.py:211-316):
  *           P@k (WUP / LCS_HEIGHT), AHP or AHP@K (np.trapz of cum / best, :303-309), AP (:310-314), with the

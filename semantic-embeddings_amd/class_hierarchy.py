@@ -492,6 +492,110 @@ class ClassHierarchy(object):
             res_d[:, columns['AP']] = torch.from_numpy(aps[q0:q1]).to(dev)
         return _metric_rows_to_results(res_d, columns, nq, p.q_ids, q0, q1, world, group, gather_per_query, per_query)
 
+    def hierarchical_precision_ranked(self, retrieved, labels, ks=[1, 10, 50, 100], compute_ahp=False, compute_ap=False,
+                                      ignore_qids=True, all_ids=None, per_query=True, tile_rows=None, kernels=None):
+        """``hierarchical_precision(retrieved, labels, ks, compute_ahp, compute_ap, ignore_qids, all_ids)`` (class_hierarchy.py:211-316)
+        for GIVEN rankings -- from another system, an approximate index, re-ranked or truncated lists -- scored on the device instead
+        of in the reference's per-query Python loop.
+
+        ``retrieved``: the reference's dict ``query id -> ranked id list`` or generator of such pairs, or, where Python lists are
+        impossible, the array form ``(query_ids [Q], ranking [Q, L][, lengths [Q]])`` with ``ranking`` a 2-d integer array or (device)
+        tensor of ids (``recall_precision.ranked_problem``).  ``labels`` maps id -> class label.  The gallery is ``all_ids`` when that
+        is given: ids missing from a list are appended in its order (class_hierarchy.py:262-264), on the device
+        (``se_complete_rankings``).  Without ``all_ids`` the gallery is the id set of the first list and every list must be a
+        permutation of it.  Returns ``(means, per_query)`` as the reference does; ``per_query=False`` returns ``(means, None)``.
+
+        Best-possible curves: the reference takes a class's curve from the first query of that class -- the sorted similarities of
+        that query's (completed) list.  Every completed list holds the whole gallery, so that curve is the one
+        ``hierarchical_precision_device`` builds from the gallery's class counts (``_best_curves``), whichever query comes first:
+        the class tables (device tables included), ``_best_curves``, ``hprec_reciprocal_curves``, the scoring call and
+        ``_metric_rows_to_results`` are reused as they are.  That equivalence is what fails for partial lists WITHOUT ``all_ids``,
+        where the reference's curve depends on which ids the first query of a class happens to list: those are refused.
+
+        Tiles of query rows: index lists up, ``complete_rankings``, ``hierarchical_precision``; a tile is consumed before the next is
+        made, and its size comes from the free device memory (``recall_precision.ranked_tile_rows``; ``tile_rows`` overrides the
+        size, not the check).
+        Head-only shortcut: when no metric reads past the head of a ranking (no AP; AHP clipped or off) and every list holds at
+        least ``min(N, max(ks, clip) + 1)`` entries, nothing is completed -- the heads are scored with that list length, exactly as
+        the top-L path of ``hierarchical_precision_device`` scores its lists, so top-250 lists against 1.28 M gallery items never
+        become a Q x N matrix.  (Duplicates inside a head are then not looked for.)
+
+        ``ValueError``: an id that is not in the gallery (named, with its query); a list that names an id twice (its query named);
+        partial lists without ``all_ids`` (use the host ``hierarchical_precision``); ``max(ks)`` or the AHP clip beyond what a
+        ranking holds (the gallery, less the query's own item when queries are gallery items and ``ignore_qids``); an empty
+        gallery.  No queries: NaN means and empty dictionaries, as ``hierarchical_precision_device`` returns.  One process, one GPU.
+        ``kernels`` (tests): CPU stand-ins ``{'complete_rankings', 'hierarchical_precision', 'device'}``."""
+        import torch
+        from evaluate_retrieval import resolve_kernels
+        from recall_precision import _raise_on_bad_rows, ranked_problem, ranked_tile_rows
+        given = dict(kernels or {})
+        native_metrics = 'hierarchical_precision' not in given
+        kernels = resolve_kernels(given, ('complete_rankings', 'hierarchical_precision', 'device'))
+        ks = [ks] if isinstance(ks, int) else list(ks)
+        ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
+        ahp_len = -1 if not compute_ahp else (0 if ahp_clip is None else ahp_clip)
+        ncol = 2 * len(ks) + 3
+        columns = _metric_columns(ks, compute_ahp, compute_ap)
+        p = ranked_problem(retrieved, labels, ignore_qids, all_ids)
+        nq, ng, C, dev = len(p.q_ids), len(p.g_ids), len(p.class_list), kernels['device']
+        if nq == 0:         # nothing to average
+            return {m: float('nan') for m in columns}, ({m: {} for m in columns} if per_query else None)
+        if ng == 0:
+            raise ValueError('the gallery is empty')
+        kmax = max(ks + [ahp_clip or 0])
+        scored = ng - 1 if (p.qidx is not None and (p.qidx >= 0).any()) else ng      # entries of the shortest scored ranking
+        if kmax > scored or min(ks) < 1 or (ahp_clip is not None and ahp_clip < 1):
+            raise ValueError('cut-offs {} and AHP clip {} must lie in [1, {}]: a ranking of the {} gallery items{} holds no more'
+                             .format(ks, ahp_clip, scored, ng, ', the query\'s own item dropped,' if scored < ng else ''))
+        # top-L heads are enough when no metric reads past the head of a ranking and every list has one
+        L = min(ng, kmax + 1)
+        head_only = (not compute_ap) and (not compute_ahp or ahp_clip is not None) and int(p.lengths.min()) >= L
+
+        # ---- class tables and best-possible curves, as hierarchical_precision_device builds them ----
+        if (not given) and dev.type == 'cuda':
+            wup_t, lcs_t = self.similarity_tables_device(p.class_list, device=dev)
+        else:
+            wup_t, lcs_t = self.similarity_tables(p.class_list)
+        counts = np.bincount(p.gcls, minlength=C)
+        if not head_only:       # before anything is launched
+            curve_len = 0
+            if native_metrics:
+                import sehip
+                curve_len = int(sehip._lib.call('se_hprec_curve_len', ng))
+            tile_rows = ranked_tile_rows(dev, nq, ng, p.list_len, 2 * 8 * C * ng + 32 * C * curve_len, 8 * ncol, tile_rows,
+                                         'hierarchical precision')
+        else:
+            tile_rows = max(1, min(nq, int(tile_rows or max(128, (1 << 28) // max(p.list_len, 1)))))
+        best = [_best_curves(t, counts, ng, dev) for t in (wup_t, lcs_t)]
+        if head_only:
+            best = [b[:, :L + 1].contiguous() for b in best]
+        tables = [_on_device(t, dev) for t in (wup_t, lcs_t)] + best
+        extra = {}
+        if native_metrics:      # the best curves pre-divided for se_hierarchical_precision: once per gallery, shared by every tile
+            import sehip
+            extra = {'curves': sehip.hprec_reciprocal_curves(*best)}
+        gcls_d, qcls_d = torch.from_numpy(p.gcls).to(dev), torch.from_numpy(p.qcls).to(dev)
+        qidx_d = None if p.qidx is None else torch.from_numpy(p.qidx).to(dev)
+        ks_d = torch.tensor(ks, dtype=torch.int32, device=dev)
+
+        def score(ranks, r0, want_ap):       # metric rows of queries r0 .. r0 + len(ranks)
+            r1 = r0 + ranks.shape[0]
+            return kernels['hierarchical_precision'](ranks, gcls_d, qcls_d[r0:r1].contiguous(), None if qidx_d is None else qidx_d[r0:r1].contiguous(),
+                                                     *tables, ks_d, ahp_len=ahp_len, want_ap=want_ap, **extra)
+
+        outs = []
+        for r0 in range(0, nq, tile_rows):      # each tile is consumed before the next one is made
+            r1 = min(nq, r0 + tile_rows)
+            lists_d, len_d = p.index_tile(r0, r1, dev)
+            if head_only:
+                outs.append(score(lists_d[:, :L].contiguous(), r0, False))
+            else:
+                rank, status = kernels['complete_rankings'](lists_d, ng, lengths=len_d)
+                _raise_on_bad_rows(status, p, r0)
+                outs.append(score(rank, r0, compute_ap))
+        res_d = outs[0] if len(outs) == 1 else torch.cat(outs)
+        return _metric_rows_to_results(res_d, columns, nq, p.q_ids, 0, nq, 1, None, True, per_query)
+
 
 def _metric_columns(ks, compute_ahp, compute_ap):
     """Metric name -> column of se_hierarchical_precision's ``[Q, 2 len(ks) + 3]`` output, in the order of the result dictionaries:

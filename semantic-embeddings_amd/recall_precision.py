@@ -267,6 +267,250 @@ def gallery_problem(features, labels, ids=None, gallery=None, gallery_labels=Non
     return EvalProblem(qf, gf, q_ids, qcls, gcls, class_list, qidx)
 
 
+RankedProblem = collections.namedtuple('RankedProblem', 'q_ids g_ids qcls gcls class_list qidx list_len lengths index_tile')
+
+
+def _integer_ids(ids):
+    """``ids`` as a 1-d int64 array when they are integers that fit one, else None."""
+    try:
+        a = np.asarray(ids) if len(ids) else np.zeros(0, dtype=np.int64)
+    except (ValueError, TypeError):     # ids of several shapes
+        return None
+    if a.ndim != 1 or a.dtype.kind not in 'iu' or (a.dtype == np.uint64 and len(a) and int(a.max()) >= 2 ** 63):
+        return None
+    return a.astype(np.int64)
+
+
+class _GalleryIndex(object):
+    """ids -> gallery indices (-1: not a gallery id).  Integer ids are looked up vectorised -- a search in the sorted gallery ids plus
+    an equality check, on whichever device the ids are -- other hashables through a dict."""
+
+    def __init__(self, g_ids):
+        self.ids = g_ids
+        arr = _integer_ids(g_ids)
+        self.sorted = self.sorter = self.row_of = None
+        self.on = {}
+        if arr is not None:
+            self.sorter = np.argsort(arr, kind='stable')
+            self.sorted = arr[self.sorter]
+            unique = not (self.sorted[1:] == self.sorted[:-1]).any()
+        else:
+            self.row_of = {g: j for j, g in enumerate(g_ids)}
+            unique = len(self.row_of) == len(g_ids)
+        if not unique:
+            raise ValueError('the gallery ids are not distinct: a ranking cannot be a permutation of them')
+
+    def _dict(self):
+        if self.row_of is None:
+            self.row_of = {g: j for j, g in enumerate(self.ids)}
+        return self.row_of
+
+    def of_tensor(self, ids):
+        """int64 tensor of the gallery indices of an integer tensor of ids, on its device."""
+        import torch
+        if self.sorted is None or not len(self.ids):
+            return torch.full(ids.shape, -1, dtype=torch.int64, device=ids.device)
+        if ids.device not in self.on:
+            self.on[ids.device] = (torch.from_numpy(self.sorted).to(ids.device), torch.from_numpy(self.sorter).to(ids.device))
+        srt, sorter = self.on[ids.device]
+        ids = ids.to(torch.int64)
+        pos = torch.searchsorted(srt, ids.contiguous()).clamp_(max=len(self.ids) - 1)
+        return torch.where(srt[pos] == ids, sorter[pos], torch.full_like(pos, -1))
+
+    def of_sequence(self, ids):
+        """int64 array of the gallery indices of a sequence of ids."""
+        import torch
+        arr = _integer_ids(ids) if self.sorted is not None else None
+        if arr is not None:
+            return self.of_tensor(torch.from_numpy(arr)).numpy()
+        get = self._dict().get
+        out = np.empty(len(ids), dtype=np.int64)
+        for j, i in enumerate(ids):
+            try:
+                out[j] = get(i, -1)
+            except TypeError:       # unhashable: no id
+                out[j] = -1
+        return out
+
+
+def ranked_problem(retrieved, labels, ignore_qids=True, all_ids=None):
+    """Host bookkeeping of an evaluation of GIVEN rankings (ClassHierarchy.hierarchical_precision_ranked, recall_precision_ranked):
+    ``RankedProblem(q_ids, g_ids, qcls, gcls, class_list, qidx, list_len, lengths, index_tile)``.
+
+    ``retrieved``: the reference's forms -- a dict ``query id -> ranked id list`` or a generator of such pairs -- or the array form
+    ``(query_ids [Q], ranking [Q, L])`` / ``(query_ids, ranking, lengths [Q])`` with ``ranking`` a 2-d integer array or (device) tensor
+    of ids, row i holding ``lengths[i]`` (default L) ids.  The gallery is ``all_ids`` when that is given (gallery index = position in
+    it, so ids missing from a list are appended in ``all_ids`` order by completing in index order); otherwise it is the id set of the
+    first list, and every list must be a permutation of it -- partial lists without ``all_ids`` raise ``ValueError``.
+    ``qidx[i]``: gallery index of query i's id, -1 when it is no gallery id; None with ``ignore_qids=False`` (the kernels' NULL:
+    keep everything).  Classes: ``class_indices`` over queries and gallery.  ``lengths``: int32 [Q] on the host.
+    ``index_tile(r0, r1, dev)`` -> ``(lists, lengths)``: the lists of queries r0 .. r1 as int32 gallery indices ``[r1 - r0, list_len]``
+    on ``dev`` (entries behind a row's length are -1) and their lengths (None when every row is full); an id that is not in the
+    gallery raises ``ValueError`` naming the id and the query."""
+    import torch
+    rows = ranking = None
+    if isinstance(retrieved, tuple) and len(retrieved) in (2, 3):
+        q_ids, ranking = retrieved[0], retrieved[1]
+        q_ids = q_ids.tolist() if hasattr(q_ids, 'tolist') else list(q_ids)
+        if not torch.is_tensor(ranking):
+            ranking = np.asarray(ranking)
+        if ranking.ndim != 2 or (ranking.dtype.kind not in 'iu' if isinstance(ranking, np.ndarray) else
+                                 (ranking.dtype.is_floating_point or ranking.dtype == torch.bool)):
+            raise ValueError('the array form takes a 2-d integer ranking [queries, list length]')
+        if int(ranking.shape[0]) != len(q_ids):
+            raise ValueError('{} query ids for {} ranking rows'.format(len(q_ids), int(ranking.shape[0])))
+        L = int(ranking.shape[1])
+        if len(retrieved) == 3 and retrieved[2] is not None:
+            lengths = retrieved[2]
+            lengths = (lengths.cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)).astype(np.int64).reshape(-1)
+            if len(lengths) != len(q_ids) or (len(lengths) and (lengths.min() < 0 or lengths.max() > L)):
+                raise ValueError('lengths must hold one value in [0, {}] per query'.format(L))
+        else:
+            lengths = np.full(len(q_ids), L, dtype=np.int64)
+        if isinstance(ranking, np.ndarray):
+            ranking = torch.from_numpy(np.ascontiguousarray(ranking if ranking.dtype != np.uint64 else ranking.astype(np.int64)))
+    else:
+        items = list(retrieved.items() if hasattr(retrieved, 'items') else retrieved)
+        q_ids = [qid for qid, _ in items]
+        rows = [ret if isinstance(ret, (list, tuple, np.ndarray)) else list(ret) for _, ret in items]
+        lengths = np.array([len(r) for r in rows], dtype=np.int64)
+        L = int(lengths.max()) if len(rows) else 0
+    nq = len(q_ids)
+
+    def first_list():
+        if rows is not None:
+            return list(rows[0].tolist() if isinstance(rows[0], np.ndarray) else rows[0])
+        return ranking[0, :int(lengths[0])].cpu().tolist()
+
+    if all_ids is not None and len(all_ids):        # (an empty all_ids is none, as in the reference)
+        g_ids = all_ids.tolist() if hasattr(all_ids, 'tolist') else list(all_ids)
+    else:
+        g_ids = first_list() if nq else []
+        if nq and (lengths != len(g_ids)).any():
+            i = int(np.flatnonzero(lengths != len(g_ids))[0])
+            raise ValueError('the list of query {!r} holds {} ids, the first list {}: without all_ids every list must rank the whole '
+                             'gallery.  Pass all_ids (missing ids are then appended in its order), or use the host '
+                             'hierarchical_precision, which keeps the reference\'s rule for partial lists without all_ids'
+                             .format(q_ids[i], int(lengths[i]), len(g_ids)))
+    index = _GalleryIndex(g_ids)
+    ng = len(g_ids)
+    class_list, (qcls, gcls) = class_indices([labels[i] for i in q_ids], [labels[i] for i in g_ids])
+    qidx = index.of_sequence(q_ids).astype(np.int32) if ignore_qids else None
+    full = bool((lengths == L).all())
+
+    def index_tile(r0, r1, dev):
+        n = r1 - r0
+        len_t = torch.from_numpy(lengths[r0:r1])
+        if ranking is not None:
+            idx = index.of_tensor(ranking[r0:r1].to(dev) if dev.type == 'cuda' else ranking[r0:r1])
+        else:
+            flat = [i for r in rows[r0:r1] for i in (r.tolist() if isinstance(r, np.ndarray) else r)]
+            flat_idx = torch.from_numpy(index.of_sequence(flat))
+            if full:
+                idx = flat_idx.view(n, L)
+            else:
+                idx = torch.full((n, L), -1, dtype=torch.int64)
+                idx[torch.arange(L)[None, :] < len_t[:, None]] = flat_idx
+        idx = idx.to(dev)
+        len_d = None if full else len_t.to(dev)
+        bad = idx < 0 if full else (idx < 0) & (torch.arange(L, device=dev)[None, :] < len_d[:, None])
+        if bool(bad.any()):
+            r, c = (int(v) for v in bad.nonzero()[0])
+            unknown = ranking[r0 + r, c].item() if ranking is not None else rows[r0 + r][c]
+            raise ValueError('id {!r} at position {} of the ranking of query {!r} is not in the gallery of {} ids'
+                             .format(unknown, c, q_ids[r0 + r], ng))
+        if not full:
+            idx = idx.masked_fill(torch.arange(L, device=dev)[None, :] >= len_d[:, None], -1)
+        return idx.to(torch.int32), (None if full else len_d.to(torch.int32))
+
+    return RankedProblem(q_ids, g_ids, qcls, gcls, class_list, qidx, L, lengths.astype(np.int32), index_tile)
+
+
+def ranked_tile_rows(dev, nq, ng, list_len, fixed, row_extra, tile_rows, what):
+    """Query rows per tile of an evaluation of given rankings, from what it holds on the device, known before anything is launched:
+    ``fixed`` bytes whatever the tile, and per tile row the completed ranking (int32, rows of 16-byte pitch), the index list with
+    the temporaries of its id look-up (28 bytes per entry) and ``row_extra`` bytes of results.  Sized from the free device memory the
+    way ``class_hierarchy._ranked_gallery_tile_rows`` sizes its tiles; ``tile_rows`` overrides the size, not the check: a problem that
+    cannot fit raises ``ValueError`` with the estimate."""
+    from class_hierarchy import _free_device_bytes
+    row_bytes = 4 * ((ng + 3) // 4 * 4) + 28 * list_len + row_extra
+    free = _free_device_bytes(dev)
+    budget = None if free is None else free - free // 10
+    rows = max(1, nq)
+    if tile_rows is not None:
+        rows = max(1, min(rows, int(tile_rows)))
+    elif budget is not None:
+        rows = max(1, min(rows, (budget - fixed) // row_bytes))
+        if 128 < rows < nq:
+            rows = rows // 128 * 128
+    estimate = fixed + rows * row_bytes
+    if budget is not None and estimate > budget:
+        raise ValueError('{} of {} given rankings over a gallery of {} items needs an estimated {:,} bytes of device memory ({:,} whatever '
+                         'the tile, {:,} for a tile of {} query row{}), {:,} are free: fewer classes, shorter lists or a smaller gallery'
+                         .format(what, nq, ng, estimate, fixed, estimate - fixed, rows, '' if rows == 1 else 's', free))
+    return rows
+
+
+def _raise_on_bad_rows(status, p, r0):
+    """``status`` of ``complete_rankings`` for the tile that starts at query r0: a flagged row raises, naming its query."""
+    bad = status.nonzero()
+    if int(bad.numel()):
+        r = int(bad[0])
+        raise ValueError('the ranking of query {!r} names a gallery id more than once{}: it cannot be scored'
+                         .format(p.q_ids[r0 + r], '' if not int(status[r]) & 1 else ' or an id outside the gallery'))
+
+
+def recall_precision_ranked(retrieved, labels, bins=None, ignore_qids=True, all_ids=None, tile_rows=None, kernels=None):
+    """The recall-precision curve and mAP of plot_recall_precision.py:52-79 for GIVEN rankings -- from another system, an approximate
+    index, re-ranked or truncated lists -- instead of features: ``retrieved``, ``labels``, ``ignore_qids`` and ``all_ids`` as
+    ``ranked_problem`` takes them (the reference's dict / generator, or the array form).  Every list is completed to a ranking of the
+    whole gallery on the device (``se_complete_rankings``: ids missing from a list follow in ``all_ids`` order; every relevant position
+    is needed, so there is no head-only shortcut), tile by tile, then ``se_relevant_positions`` and ``se_recall_precision_reduce`` run
+    as in ``recall_precision_device(..., gallery=...)``, with its (class, is-a-gallery-item) reduce groups.  One process, one GPU.
+    ``kernels`` (tests): CPU stand-ins ``{'complete_rankings', 'relevant_positions', 'recall_precision_reduce', 'device'}``.
+    Returns ``(levels, mean_precision, mAP, per_query_ap)``.  Raises ``ValueError`` for an empty gallery, an id that is not in the
+    gallery, a list that names an id twice and partial lists without ``all_ids``."""
+    import torch
+    kernels = resolve_kernels(kernels, ('complete_rankings', 'relevant_positions', 'recall_precision_reduce', 'device'))
+    bins = _number_of_bins(bins)
+    p = ranked_problem(retrieved, labels, ignore_qids, all_ids)
+    nq, ng, C, dev = len(p.q_ids), len(p.g_ids), len(p.class_list), kernels['device']
+    if nq and ng == 0:
+        raise ValueError('the gallery is empty')
+    # reduce groups as in _recall_precision_gallery: class 2 c + (the query is a gallery item of its class that leaves its ranking)
+    gcounts = np.bincount(p.gcls, minlength=C)
+    present = (p.qidx >= 0) & (p.gcls[np.maximum(p.qidx, 0)] == p.qcls) if (p.qidx is not None and ng) else np.zeros(nq, dtype=bool)
+    rc = 2 * p.qcls.astype(np.int64) + present
+    r_rc = np.repeat(gcounts, 2).astype(np.int64)
+    r_rc[1::2] -= 1
+    r_rc = np.maximum(r_rc, 0)
+    nq_rc = np.bincount(rc, minlength=2 * C)
+    class_off = np.concatenate([[0], np.cumsum(r_rc)]).astype(np.int64)
+    max_r = int(r_rc.max()) if C else 0
+    tile_rows = ranked_tile_rows(dev, nq, ng, p.list_len, 8 * int(class_off[-1]), 4 * max_r + 64, tile_rows, 'the recall-precision curve')
+
+    gcls_d, qcls_d = torch.from_numpy(p.gcls).to(dev), torch.from_numpy(p.qcls).to(dev)
+    qidx_d = None if p.qidx is None else torch.from_numpy(p.qidx).to(dev)
+    class_off_d = torch.from_numpy(class_off).to(dev)
+    ap, prec_sum, first_miss, bin_sum, bin_count = _accumulators(nq, max(2 * C, 1), int(class_off[-1]), bins, dev)
+    for r0 in range(0, nq, tile_rows):      # each tile is consumed before the next one is made
+        r1 = min(nq, r0 + tile_rows)
+        lists_d, len_d = p.index_tile(r0, r1, dev)
+        rank, status = kernels['complete_rankings'](lists_d, ng, lengths=len_d)
+        _raise_on_bad_rows(status, p, r0)
+        rc_t = rc[r0:r1]
+        hit_off = np.concatenate([[0], np.cumsum(r_rc[rc_t])]).astype(np.int64)
+        order = np.argsort(rc_t, kind='stable').astype(np.int32)
+        class_start = np.concatenate([[0], np.cumsum(np.bincount(rc_t, minlength=2 * C))]).astype(np.int32)
+        hit_off_d = torch.from_numpy(hit_off).to(dev)
+        hit_pos = kernels['relevant_positions'](rank, gcls_d, qcls_d[r0:r1].contiguous(), None if qidx_d is None else qidx_d[r0:r1].contiguous(),
+                                                hit_off_d, num_classes=C, total=int(hit_off[-1]))
+        kernels['recall_precision_reduce'](hit_pos, hit_off_d, torch.from_numpy(order).to(dev), torch.from_numpy(class_start).to(dev),
+                                           class_off_d, bins, ap[r0:r1], prec_sum, first_miss, bin_sum, bin_count)
+    _warn_singletons(int(nq_rc[r_rc == 0].sum()))
+    return _merge_levels(ap.cpu().numpy(), r_rc, nq_rc, class_off, bins, prec_sum, first_miss, bin_sum, bin_count)
+
+
 def _recall_precision_gallery(features, labels, normalize, bins, ids, kblocks, tile_rows, tile_cols, kernels, gallery, gallery_labels,
                               gallery_ids, distributed, group):
     """``recall_precision_device`` with a separate gallery.  Per query tile (queries sorted by class):

@@ -21,7 +21,7 @@ __all__ = [
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "pairwise_dist_f64",
     "rank_refine_f64_", "rank_rows_f64", "topk_rows",
-    "topk_merge", "retrieve_topk", "knn_vote", "KNN_TOP_MAX", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
+    "topk_merge", "retrieve_topk", "knn_vote", "KNN_TOP_MAX", "complete_rankings", "COMPLETE_LDS_ITEMS", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
     "recall_precision_reduce", "count_preceding", "count_to_positions", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
     "svm_axpby", "class_pair_tables", "cholesky_lower_", "eigh", "eigh_schedule", "EIGH_NOT_CONVERGED", "EIGH_NONFINITE", "image_batch", "resample_tables", "tiny_batch", "TINY_BATCH_MAX_BLOCKS", "FILL_MODES",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
@@ -1223,6 +1223,49 @@ def knn_vote(idx, cls, num_classes, ks, top=5, qidx=None):
     call("se_knn_vote", idx, ldi, Q, L, cls, cls.numel(), int(num_classes), qidx, (ctypes.c_int32 * len(ks))(*ks), len(ks), int(top),
          out_cls, out_votes)
     return out_cls, out_votes
+
+
+COMPLETE_LDS_ITEMS = DEFINES["SE_COMPLETE_LDS_ITEMS"]     # galleries up to this size need no workspace in complete_rankings
+
+
+def complete_rankings(lists, gallery, lengths=None, order=None, out=None):
+    """Given ranked lists completed to rankings of the whole gallery (``se_complete_rankings``; class_hierarchy.py:262-264:
+    ``ret + [id for id in all_ids if id not in sret]``).
+
+    lists [Q, L] int32 gallery indices, best first (contiguous rows; any row pitch); ``gallery``: the number of gallery items;
+    lengths [Q] int32 | None: the valid entries of each row, in [0, L] (None: all L); order [gallery] int32 | None: the
+    ``all_ids`` order as gallery indices, a permutation of 0 .. gallery - 1 (None: the identity); out: int32 [Q, >= gallery]
+    with contiguous rows to write into (columns ``gallery ..`` stay as they are).
+    Returns ``(rank, status)``: rank [Q, gallery] int32 (a view of ``out`` when that is given), status [Q] int32 -- 0 for a clean
+    row, bit 0: an entry outside [0, gallery), bit 1: an index more than once.  A row with a non-zero status holds ``order``
+    itself, which means nothing: look at ``status`` before scoring."""
+    require_gpu(lists, lengths, order, out)
+    if lists.dtype != torch.int32 or lists.dim() != 2 or (lists.shape[1] > 0 and lists.stride(1) != 1):
+        raise SehipError("lists must be a 2-d int32 tensor with contiguous rows")
+    Q, L = lists.shape
+    gallery = int(gallery)
+    if gallery < 0:
+        raise SehipError("gallery must be a non-negative number of items")
+    if lengths is not None:
+        _i32(lengths, "lengths")
+        if lengths.numel() != Q:
+            raise SehipError("lengths must hold one entry per row of lists")
+    if order is not None:
+        _i32(order, "order")
+        if order.numel() != gallery:
+            raise SehipError("order must hold the %d gallery indices, it holds %d" % (gallery, order.numel()))
+    if out is None:
+        out = empty_rows(Q, gallery, torch.int32, lists.device)
+    elif out.dtype != torch.int32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != Q or out.shape[1] < gallery:
+        raise SehipError("out must be an int32 [%d, >= %d] tensor with contiguous rows" % (Q, gallery))
+    status = (torch.empty if gallery > 0 else torch.zeros)((Q,), dtype=torch.int32, device=lists.device)     # (no gallery: no launch)
+    ldl = lists.stride(0) if Q > 1 and L > 0 else max(lists.stride(0), L)
+    ldr = out.stride(0) if Q > 1 else max(out.stride(0), gallery)
+    nbytes = call("se_complete_rankings_workspace_bytes", Q, gallery)
+    ws = _workspace(nbytes, lists.device, "complete_rankings") if nbytes else None
+    call("se_complete_rankings", lists if L > 0 else None, ldl, lengths, Q, L, order, gallery, out, ldr, status, ws,
+         ws.numel() if ws is not None else 0)
+    return out[:, :gallery], status
 
 
 class HprecCurves:

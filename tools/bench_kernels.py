@@ -6,6 +6,9 @@
     python tools/bench_kernels.py knn            (se_knn_vote next to the torch composition gather -> scatter_add -> topk, and the whole
                                                   knn_classification: 10,000 x 50,000 x 100 with k = 20, 100 classes; 50,000 x 50,000 x 100 with
                                                   k = 200, 1000 classes; --n / --d are not used)
+    python tools/bench_kernels.py ranked         (se_complete_rankings at 10,000 x 10,000 and 50,000 x 50,000, list lengths 0 / 250 / N, both
+                                                  order forms, next to a copy of the same bytes and a torch composition; the whole
+                                                  hierarchical_precision_ranked next to the host function; --n / --d are not used)
     python tools/bench_kernels.py recprec        (10k x 10k and 50k x 50k, 100 classes; --n is not used)
     python tools/bench_kernels.py svm            (margin + reduction kernels and whole LinearSVC fits: 50,000 x 100 x 100 and
                                                   1,281,167 x 1000 x 1000; --n / --d are not used; --svm-sizes small skips the large one)
@@ -102,7 +105,7 @@ def windows(fns, reps, batch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn", "ranked"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -146,6 +149,8 @@ def main():
         return bench_joint()
     if args.what == "knn":
         return bench_knn()
+    if args.what == "ranked":
+        return bench_ranked()
     if args.what == "pdist64":
         return bench_pdist64(args.n, args.d, max(args.reps, 10))
     n, d = args.n, args.d
@@ -1208,6 +1213,95 @@ def bench_knn(reps=30, batch=10):
         print("knn_classification %d x %d x %d, k=%d, C=%d, features on the device: median %.2f ms (min %.2f, max %.2f) per call, rankings on the host"
               % (q, n, d, k, C, float(np.median(ts)), min(ts), max(ts)), flush=True)
         del train, test, lists, lists64, ones
+
+
+def bench_ranked(reps=10, batch=3, host_rows=500):
+    """Evaluation of given rankings.  se_complete_rankings at 10,000 x 10,000 and 50,000 x 50,000 with lists of 0, 250 and N entries
+    and both `order` forms (NULL; a random permutation), next to a device-to-device copy of the same 4 q N bytes and next to a torch
+    composition of the same completion -- key = position in the list for listed items, list length + position in `order` for the
+    others, then argsort(key) -- the three timed alternately: `reps` windows of `batch` back-to-back calls (HIP events around a
+    window) after 3 warm-up calls, median / 10th / 90th percentile of the per-call time.  At 50,000 x 50,000 the composition runs on
+    a tile of 10,000 rows and its time is multiplied by 5.  Lists: row i is the permutation j -> ((10 i + 3) j + 7 i) mod N (10 i + 3
+    is coprime to N = 2^a 5^b), cut to the list length.  Then the whole hierarchical_precision_ranked (P@1..250, whole-list AHP, AP;
+    100 classes) at 10,000 x 10,000 on a dictionary of top-250 lists with all_ids, host clock around the call (median of 3 after a
+    warm-up call), next to the host hierarchical_precision on the first `host_rows` queries of the same dictionary (one call, scaled to
+    all queries)."""
+    import time
+    import tempfile
+    rng = np.random.default_rng(0)
+    for q, n in ((10000, 10000), (50000, 50000)):
+        rows = torch.arange(q, dtype=torch.int64, device="cuda")[:, None]
+        full = torch.empty((q, n), dtype=torch.int32, device="cuda")
+        for r0 in range(0, q, 5000):
+            full[r0:r0 + 5000] = (((10 * rows[r0:r0 + 5000] + 3) * torch.arange(n, dtype=torch.int64, device="cuda")[None, :] + 7 * rows[r0:r0 + 5000]) % n).int()
+        order = torch.from_numpy(rng.permutation(n).astype(np.int32)).cuda()
+        inv = torch.empty(n, dtype=torch.int64, device="cuda")
+        inv[order.long()] = torch.arange(n, dtype=torch.int64, device="cuda")
+        out, dst = sehip.empty_rows(q, n, torch.int32, "cuda"), torch.empty((q, n), dtype=torch.int32, device="cuda")
+        tq = min(q, 10000)          # rows of the torch composition
+        for L in (0, 250, n):
+            lists = full[:, :L]
+            lists64 = lists[:tq].long()
+            pos = torch.arange(L, dtype=torch.int64, device="cuda")[None, :].expand(tq, L)
+            for name, od, key0 in (("NULL", None, torch.arange(n, dtype=torch.int64, device="cuda")), ("permutation", order, inv)):
+                def kernel():
+                    return sehip.complete_rankings(lists, n, order=od, out=out)
+
+                def copy():
+                    return dst.copy_(out)
+
+                def composition():
+                    key = (L + key0)[None, :].repeat(tq, 1)
+                    if L:
+                        key.scatter_(1, lists64, pos)
+                    return torch.argsort(key, dim=1).int()
+                rank, status = kernel()
+                assert not bool(status.any()) and torch.equal(rank[:tq], composition()), "the two legs disagree"
+                kt, ct, tt = windows((kernel, copy, composition), reps, batch)
+                scale = q / tq
+                print("complete_rankings %d x %d, list length %d, order %s: se_complete_rankings %.0f us (%.0f-%.0f) = %.2f TB/s written; "
+                      "copy of the same %.1f GB %.0f us (%.0f-%.0f): kernel / copy x%.2f; torch composition%s %.0f us (%.0f-%.0f): x%.1f the kernel"
+                      % (q, n, L, name, kt[0], kt[1], kt[2], 4.0 * q * n / (kt[0] * 1e-6) / 1e12, 4.0 * q * n / 1e9, ct[0], ct[1], ct[2], kt[0] / ct[0],
+                         "" if tq == q else " (%d rows, x%d)" % (tq, scale), tt[0] * scale, tt[1] * scale, tt[2] * scale, tt[0] * scale / kt[0]), flush=True)
+            del lists64, pos
+        del full, out, dst
+        torch.cuda.empty_cache()
+
+    # ---- the whole evaluation at 10,000 x 10,000 ----
+    from class_hierarchy import ClassHierarchy
+    n = q = 10000
+    edges = np.load(os.path.join(ROOT, "tests", "golden", "hierarchy_cifar.npz"))["edges"]
+    with tempfile.NamedTemporaryFile("w", suffix=".txt", delete=False) as f:
+        for p, c in edges.tolist():
+            f.write("%d %d\n" % (p, c))
+    hier = ClassHierarchy.from_file(f.name, id_type=int)
+    os.unlink(f.name)
+    labels = rng.integers(0, 100, size=n).tolist()
+    i = np.arange(q, dtype=np.int64)[:, None]
+    top = (((10 * i + 3) * np.arange(250, dtype=np.int64)[None, :] + i) % n)        # (j = 0 is the query itself)
+    retrieved = {k: top[k].tolist() for k in range(q)}
+    all_ids = list(range(n))
+    ks = list(range(1, 251))
+
+    def device():
+        return hier.hierarchical_precision_ranked(retrieved, labels, ks, compute_ahp=True, compute_ap=True, all_ids=all_ids, per_query=False)[0]
+    got = device()
+    ts = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        device()
+        ts.append(time.perf_counter() - t0)
+    head = {k: retrieved[k] for k in range(host_rows)}
+    t0 = time.perf_counter()
+    _, host_q = hier.hierarchical_precision(head, labels, ks, compute_ahp=True, compute_ap=True, all_ids=all_ids)
+    th = (time.perf_counter() - t0) * q / host_rows
+    _, dev_q = hier.hierarchical_precision_ranked(head, labels, ks, compute_ahp=True, compute_ap=True, all_ids=all_ids)
+    err = max(abs(dev_q[m][k] - host_q[m][k]) for m in host_q for k in head)
+    print("hierarchical_precision_ranked %d x %d (top-250 lists as a dict, all_ids, P@1..250 + AHP + AP, 100 classes): median %.3f s (min %.3f, "
+          "max %.3f) per call; host hierarchical_precision on the same dictionary: %.1f s (%d queries timed, scaled): x%.0f; largest per-query "
+          "difference on those queries %.1e; mean AP %.4f" % (q, n, float(np.median(ts)), min(ts), max(ts), th, host_rows, th / float(np.median(ts)), err,
+                                                              got["AP"]), flush=True)
 
 
 def bench_adagrad(reps=40, batch=20, steps=200):

@@ -44,6 +44,8 @@ pd64[:, 100:1300] = 1.0 + pd64[:, 100:1300] * 2.0 ** -30; img64 = pd64.float()  
 ks = torch.arange(1, 251, dtype=torch.int32, device="cuda")
 qidx = torch.arange(1024, dtype=torch.int32, device="cuda")
 curves = sehip.hprec_reciprocal_curves(best_d, best_d)
+cr_len = dev(rng.integers(0, 251, size=1024).astype(np.int32))       # se_complete_rankings: ragged top-250 lists, a shuffled all_ids order
+cr_order = dev(rng.permutation(20000).astype(np.int32))
 emb = dev(f32(C, 100)); sehip.normalize_rows_(emb)
 xb = dev(f32(4096, 100)); yb = dev(rng.integers(0, C, size=4096).astype(np.int64))
 emb_wide = dev(f32(1000, 100)); sehip.normalize_rows_(emb_wide)      # 32 class tiles: the embedding head cuts them into slices
@@ -110,6 +112,8 @@ OPS = {
     "hierarchical_precision": lambda: sehip.hierarchical_precision(rk_mid, cls, cls[:1024].contiguous(), qidx, tab_d, tab_d, best_d, best_d, ks,
                                                                      ahp_len=0, want_ap=True, curves=curves),
     "knn_vote (LDS vote tables)": lambda: sehip.knn_vote(rk_mid[:, :201], cls, C, [1, 5, 20, 200], top=5, qidx=qidx),
+    "complete_rankings (LDS bitmap, ragged)": lambda: sehip.complete_rankings(rk_mid[:, :250], 20000, lengths=cr_len, order=cr_order),
+    "complete_rankings (whole lists)": lambda: sehip.complete_rankings(rk_mid, 20000),
     "cosine_loss fwd+bwd": lambda: (sehip.cosine_loss_forward(xb, yb, emb)[0], sehip.cosine_loss_backward(xb, yb, emb)),
     "nn_accuracy": lambda: sehip.nn_accuracy(xb, yb, emb, dot_prod_sim=True, k=5),
     "embed_head cosine": lambda: sehip.embed_head_forward(xb, yb, emb, mode="cosine", want_best=True),
