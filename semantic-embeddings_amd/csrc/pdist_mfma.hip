@@ -211,14 +211,6 @@ __device__ __forceinline__ void pd_stream_rows(const float *stage, float *gbase,
     }
 }
 
-template <int METRIC>
-__device__ __forceinline__ float pd_finish(float v, float sa, float sb)
-{
-    if (METRIC == SE_METRIC_COSINE) return -v;
-    if (METRIC == SE_METRIC_EUCLID) return (sa + sb) - 2.0f * v;
-    return v;
-}
-
 // flags
 constexpr int PDF_VEC_A = 1, PDF_VEC_B = 2, PDF_VEC_O = 4, PDF_NO_STORE = 8, PDF_NO_MFMA = 16, PDF_STAGGER = 32, PDF_PLAIN_ST = 64, PDF_NO_GSTORE = 128;
 
@@ -405,7 +397,7 @@ __global__ __launch_bounds__(PD_THREADS, (PD_WAVES / 4) * PD_WGS_PER_CU) void pd
                 const bool full_rows = rows_here == PD_BM;
                 const int lr0 = wm * PD_WROWS + 4 * hi;
 #define PD_FVAL(MI_, J, R)                                                                                                   \
-    pd_finish<METRIC>(MULTI_KB ? tot[(MI_) * 2 + (J)][R] : acc[(MI_) * 2 + (J)][R],                                            \
+    dist_finish<METRIC>(MULTI_KB ? tot[(MI_) * 2 + (J)][R] : acc[(MI_) * 2 + (J)][R],                                            \
                       METRIC == SE_METRIC_EUCLID ? fsa[((R) & 3) + 4 * ((R) >> 2)] : 0.f, sbq)
                 if (EPI == EPI_GROUPMIN) {
 #pragma unroll
@@ -512,7 +504,7 @@ __global__ __launch_bounds__(PD_THREADS, (PD_WAVES / 4) * PD_WGS_PER_CU) void pd
         _Pragma("unroll") for (int cc = 0; cc < 4; cc++) {                                                                   \
             const int gc_ = gl0 + 8 * (G) + cc;                                                                              \
             const float sb_ = METRIC == SE_METRIC_EUCLID ? sqb[cur_n0 + (gc_ < cols_here ? gc_ : cols_here - 1)] : 0.f;      \
-            E[cc] = pd_finish<METRIC>(rv_[cc], saq2[J], sb_);                                                                \
+            E[cc] = dist_finish<METRIC>(rv_[cc], saq2[J], sb_);                                                                \
         }                                                                                                                    \
     }
                     if (mirror) {
@@ -600,7 +592,7 @@ __global__ __launch_bounds__(PD_THREADS, (PD_WAVES / 4) * PD_WGS_PER_CU) void pd
                 // (Euclidean: the stage takes the raw dot products, pd_stream_rows finishes them with the norms staged in sN)
 #define PD_VAL(MI_, J, R)                                                                                                    \
     (METRIC == SE_METRIC_EUCLID ? (MULTI_KB ? tot[(MI_) * 2 + (J)][R] : acc[(MI_) * 2 + (J)][R])                               \
-                                : pd_finish<METRIC>(MULTI_KB ? tot[(MI_) * 2 + (J)][R] : acc[(MI_) * 2 + (J)][R], 0.f, 0.f))
+                                : dist_finish<METRIC>(MULTI_KB ? tot[(MI_) * 2 + (J)][R] : acc[(MI_) * 2 + (J)][R], 0.f, 0.f))
 #pragma unroll
                 for (int h = 0; h < PD_BM / PD_SR; h++) {
                     wg_barrier();   // operands of the last chunk / the previous stage contents are no longer needed

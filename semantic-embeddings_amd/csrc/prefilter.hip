@@ -225,13 +225,7 @@ int pf_spill_counts(unsigned *rowcnt, const unsigned *spill_cnt, int64_t queries
 }
 
 // ---- tile loop --------------------------------------------------------------------------------------------------------------------
-template <int METRIC>
-__device__ __forceinline__ float pf_finish(float v, float sa, float sb)
-{
-    if (METRIC == SE_METRIC_COSINE) return -v;
-    if (METRIC == SE_METRIC_EUCLID) return (sa + sb) - 2.0f * v;
-    return v;
-}
+#define PF_T(i) SE_PHASE_T(fa.prof, i)      // tuning build: cycles per phase of the two tile kernels
 
 // global -> registers: chunk [k0, k0 + 128) of rows [row0, row0 + NL * 32) of an fp16 matrix with pitch `ld` elements (multiple of 128 columns,
 // 16-byte aligned rows; NL pieces per thread = NL * 32 rows).  Rows beyond nrows are clamped (read twice, ignored by the epilogues): no masking anywhere in the loop.
@@ -364,9 +358,6 @@ __global__ __launch_bounds__(PF_THREADS, PF_WGS_PER_CU) void pf_tile_kernel(
     }
 #ifdef SE_TUNING
     uint64_t t_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t_last = fa.prof ? __builtin_amdgcn_s_memtime() : 0;
-#define PF_T(i) if (fa.prof) { const uint64_t now = __builtin_amdgcn_s_memtime(); t_acc[i] += now - t_last; t_last = now; }
-#else
-#define PF_T(i)
 #endif
     int c = 0;
     pf_stage<PF_NLOAD_A>(sA, ra);
@@ -430,7 +421,7 @@ __global__ __launch_bounds__(PF_THREADS, PF_WGS_PER_CU) void pf_tile_kernel(
             const bool full_rows = rows_here == PF_BM;
             const int lr0 = wm * 64 + 4 * hi;
 #define PF_SA(MI_, R) (METRIC == SE_METRIC_EUCLID ? tSqRow[lr0 + (MI_) * 32 + ((R) & 3) + 8 * ((R) >> 2)] : 0.f)
-#define PF_VAL(MI_, J, R) pf_finish<METRIC>(acc[MI_][J][R] * unscale, PF_SA(MI_, R), sbq)
+#define PF_VAL(MI_, J, R) dist_finish<METRIC>(acc[MI_][J][R] * unscale, PF_SA(MI_, R), sbq)
             if (EPI == PF_STORE) {
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
@@ -544,7 +535,7 @@ __global__ __launch_bounds__(PF_THREADS, PF_WGS_PER_CU) void pf_tile_kernel(
                     const float sbq = METRIC == SE_METRIC_EUCLID ? tSqCol[lc] : 0.f;
                     auto emit = [&](int i, float a) {
                         const int lr = lr0 + (i >> 4) * 32 + (i & 3) + 8 * ((i >> 2) & 3);
-                        const float v = pf_finish<METRIC>(a * unscale, METRIC == SE_METRIC_EUCLID ? tSqRow[lr] : 0.f, sbq);
+                        const float v = dist_finish<METRIC>(a * unscale, METRIC == SE_METRIC_EUCLID ? tSqRow[lr] : 0.f, sbq);
                         if (__builtin_expect(slot < (unsigned)fa.cap, 1)) lst[slot] = make_uint2(__float_as_uint(v), (uint32_t)(cur_m0 + lr));
                         else pf_spill_append(fa, cur_n0 + lc, nsub, make_uint2(__float_as_uint(v), (uint32_t)(cur_m0 + lr)));
                         slot++;
@@ -606,7 +597,6 @@ __global__ __launch_bounds__(PF_THREADS, PF_WGS_PER_CU) void pf_tile_kernel(
     if (fa.prof && threadIdx.x == 0)
         for (int i = 0; i < 12; i++) atomicAdd(&fa.prof[i], (unsigned long long)t_acc[i]);
 #endif
-#undef PF_T
 #undef PF_JOB_SIDE
 #undef PF_TILE_SIDE
 }
@@ -714,9 +704,6 @@ __global__ __launch_bounds__(PB_THREADS, 1) void pf_big_kernel(
     }
 #ifdef SE_TUNING
     uint64_t t_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t_last = fa.prof ? __builtin_amdgcn_s_memtime() : 0;
-#define PF_T(i) if (fa.prof) { const uint64_t now = __builtin_amdgcn_s_memtime(); t_acc[i] += now - t_last; t_last = now; }
-#else
-#define PF_T(i)
 #endif
     int buf = 0;
     PB_JOB_SIDE(cur.tn)
@@ -887,7 +874,7 @@ __global__ __launch_bounds__(PB_THREADS, 1) void pf_big_kernel(
                         m &= ~(0x80000000u >> i);
                         const int lr = lr0 + (2 * h + (i >> 4)) * 32 + (i & 3) + 8 * ((i >> 2) & 3);
                         const float a = mine[i];
-                        const float v = pf_finish<METRIC>(a * unscale, METRIC == SE_METRIC_EUCLID ? tSqRow[lr] : 0.f, sbq);
+                        const float v = dist_finish<METRIC>(a * unscale, METRIC == SE_METRIC_EUCLID ? tSqRow[lr] : 0.f, sbq);
                         if (__builtin_expect(slot < (unsigned)fa.cap, 1)) lst[slot] = make_uint2(__float_as_uint(v), (uint32_t)(cur_m0 + lr));
                         else pf_spill_append(fa, cur_n0 + lc, nsub, make_uint2(__float_as_uint(v), (uint32_t)(cur_m0 + lr)));
                         slot++;
@@ -915,7 +902,6 @@ __global__ __launch_bounds__(PB_THREADS, 1) void pf_big_kernel(
     if (fa.prof && threadIdx.x == 0)
         for (int i = 0; i < 12; i++) atomicAdd(&fa.prof[i], (unsigned long long)t_acc[i]);
 #endif
-#undef PF_T
 #undef PB_JOB_SIDE
 #undef PB_TILE_SIDE
 }

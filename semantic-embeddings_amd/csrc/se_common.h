@@ -58,6 +58,14 @@ inline const char *tuning_env(const char *) { return nullptr; }
 constexpr bool kTuning = false;
 #endif
 
+// Phase timer of the kernels that profile themselves in the tuning build: the cycles since the previous mark go to t_acc[i] when `on`
+// (the kernel declares `uint64_t t_acc[], t_last` under the same #ifdef)
+#ifdef SE_TUNING
+#define SE_PHASE_T(on, i) if (on) { const uint64_t now = __builtin_amdgcn_s_memtime(); t_acc[i] += now - t_last; t_last = now; }
+#else
+#define SE_PHASE_T(on, i)
+#endif
+
 // Work-group barrier of every kernel in this library: drain this wave's LDS queue, THEN barrier.
 // __syncthreads() alone is not enough on gfx950 with this compiler: for a barrier at a loop header the waitcnt pass can leave
 // the back edge without an s_waitcnt lgkmcnt(0) between the previous stage's ds_write and the s_barrier (seen in the ISA of the
@@ -239,6 +247,14 @@ struct KBlocks {
     int n;
     int len[SE_MAX_KB];
 };
+// metric epilogue of a canonical dot product: v = a.b, sa = |a|^2, sb = |b|^2 (Euclidean only)
+template <int METRIC>
+__device__ __forceinline__ float dist_finish(float v, float sa, float sb)
+{
+    if (METRIC == SE_METRIC_COSINE) return -v;
+    if (METRIC == SE_METRIC_EUCLID) return (sa + sb) - 2.0f * v;
+    return v;
+}
 // host: validate a caller's K-block list into `kbs`; *multi = more than one block.  SE_OK or an error code (text set).
 int make_kblocks(const char *who, const int32_t *kblocks, int nkb, int64_t d, KBlocks &kbs, bool &multi);
 

@@ -29,6 +29,34 @@ __device__ __forceinline__ float key_to_float(uint32_t key)
     return __uint_as_float(u);
 }
 
+// The 64-bit composite every list here is sorted on: canonical key above the index, so that ties go to the lower index.
+__device__ __forceinline__ uint64_t pack_key(uint32_t key, uint32_t idx) { return ((uint64_t)key << 32) | idx; }
+
+// The first k entries of a sorted composite list -> distances out_d[base .. base + k) and indices out_i[base .. base + k) (+ col_offset),
+// by threads tid, tid + stride, ...  (The kernel's own output pointers and an element offset, not pointers to the row: with row
+// pointers topk_lists_kernel came out at 142 VGPRs instead of 93 and se_retrieve_topk at 50,000 x 50,000, k = 600 took 7.5 ms instead of 6.65.)
+__device__ __forceinline__ void emit_topk(const uint64_t *cand, int k, float *__restrict__ out_d, int32_t *__restrict__ out_i, int64_t base,
+                                          int64_t col_offset, int tid, int stride)
+{
+    for (int r = tid; r < k; r += stride) {
+        const uint64_t c = cand[r];
+        out_d[base + r] = key_to_float((uint32_t)(c >> 32));
+        out_i[base + r] = (int32_t)(col_offset + (int64_t)(uint32_t)c);
+    }
+}
+
+// f(std::integral_constant<int, PER>{}) for the first PER of {1, 2, 4, 8, 16} with total <= PER * unit (16 beyond that): the values per
+// thread or lane of the register sorts below, picked on the device (list lengths) and on the host (k of the wave merge)
+template <class F>
+__host__ __device__ __forceinline__ void with_width(unsigned total, unsigned unit, F f)
+{
+    if (total <= unit) f(std::integral_constant<int, 1>{});
+    else if (total <= 2 * unit) f(std::integral_constant<int, 2>{});
+    else if (total <= 4 * unit) f(std::integral_constant<int, 4>{});
+    else if (total <= 8 * unit) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
+}
+
 // In-LDS bitonic sort of P (power of two) uint64 values, ascending, by the whole workgroup.
 __device__ __forceinline__ void bitonic_sort_u64(uint64_t *v, int P, int nthreads)
 {
@@ -129,11 +157,11 @@ __device__ __forceinline__ void topk_select_row(const float *__restrict__ drow, 
             const uint64_t tie_ballot = __ballot(is_tie);
             if (is_lt) {
                 const uint32_t slot = atomicAdd(&ctl[2], 1u);
-                cand[slot] = ((uint64_t)key << 32) | (uint32_t)i;
+                cand[slot] = pack_key(key, (uint32_t)i);
             }
             if (is_tie) {
                 const uint32_t ord = tie_base + (uint32_t)__popcll(tie_ballot & lt_mask);
-                if (ord < need_ties) cand[n_lt + ord] = ((uint64_t)key << 32) | (uint32_t)i;
+                if (ord < need_ties) cand[n_lt + ord] = pack_key(key, (uint32_t)i);
             }
             tie_base += (uint32_t)__popcll(tie_ballot);
         }
@@ -141,11 +169,7 @@ __device__ __forceinline__ void topk_select_row(const float *__restrict__ drow, 
 
         // ---------- sort the k survivors on (key, index) and emit ----------
         bitonic_sort_u64(cand, P, TK_THREADS);
-        for (int r = tid; r < k; r += TK_THREADS) {
-            const uint64_t c = cand[r];
-            od[r] = key_to_float((uint32_t)(c >> 32));
-            oi[r] = (int32_t)(col_offset + (int64_t)(uint32_t)c);
-        }
+        emit_topk(cand, k, od, oi, 0, col_offset, tid, TK_THREADS);
     }
 }
 
@@ -161,73 +185,117 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float *__re
 }
 
 // ------------------------------------------------------------------------------------------------
-// Register-blocked bitonic sort of P = TK_THREADS * PER values held PER per thread (value e = tid * PER + r):
+// Register-blocked bitonic sort of P = THREADS * PER values held PER per thread (value e = tid * PER + r):
 // partners closer than PER live in the same thread, closer than 64 * PER in the same wave (shuffle, no barrier);
 // only the log2(P / (64 PER))-deep far strides go through LDS.  A 2048-value sort needs 6 barrier stages
 // instead of the 66 of the all-LDS version above.
-template <typename T>
-__device__ __forceinline__ T shfl_xor_any(T v, int mask)
+//   THREADS = TK_THREADS: the whole workgroup sorts, tid = threadIdx.x, lds = P values.
+//   THREADS = 64        : ONE wave sorts its own values, tid = lane -- no far strides, hence no LDS and no barrier (lds unused).
+// (tid comes from the kernel: recomputing threadIdx.x & 63 next to the network cost pf_refine_kernel 30 VGPRs.)
+
+// v (32 or 64 bits) of lane `a` (XOR = false) or of lane (own ^ a) (XOR = true)
+template <bool XOR, typename T>
+__device__ __forceinline__ T shfl_any(T v, int a)
 {
-    if constexpr (sizeof(T) == 8) {
-        const uint32_t lo = (uint32_t)v, hi = (uint32_t)((uint64_t)v >> 32);
-        return (T)(((uint64_t)(uint32_t)__shfl_xor((int)hi, mask, 64) << 32) | (uint32_t)__shfl_xor((int)lo, mask, 64));
-    } else {
-        return (T)__shfl_xor((int)v, mask, 64);
-    }
+    auto word = [&](uint32_t w) { return (uint32_t)(XOR ? __shfl_xor((int)w, a, 64) : __shfl((int)w, a, 64)); };
+    if constexpr (sizeof(T) == 8) return (T)(((uint64_t)word((uint32_t)((uint64_t)v >> 32)) << 32) | word((uint32_t)v));
+    else return (T)word((uint32_t)v);
 }
 
-template <typename T, int PER>
-__device__ __forceinline__ void blocked_bitonic_sort(T (&v)[PER], T *lds)
+// what separates the stages of a THREADS-wide step from each other: a workgroup barrier, or LDS program order within one wave
+template <int THREADS>
+__device__ __forceinline__ void sort_sync()
 {
-    constexpr int P = TK_THREADS * PER;
-    const int tid = threadIdx.x;
-#define TK_CE_REMOTE(O, R)                                                     \
-    {                                                                          \
-        const int e = tid * PER + (R);                                         \
-        const bool take_min = (((e & k) == 0) == ((e & j) == 0));              \
-        v[R] = take_min ? ((O) < v[R] ? (O) : v[R]) : ((O) > v[R] ? (O) : v[R]); \
-    }
+    if constexpr (THREADS == WAVE) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    else wg_barrier();
+}
+
+// keep the smaller (take_min) or the larger of v and its partner's value o
+template <typename T>
+__device__ __forceinline__ T keep_of(T v, T o, bool take_min) { return take_min ? (o < v ? o : v) : (o > v ? o : v); }
+
+// One phase of the network: sorted runs of length k / 2, alternately ascending and descending, -> runs of length k.  SHFL_UNROLL: the
+// unroll count of the shuffle stages (1: k is a run-time value).  The register stages are guarded by jj <= j in the workgroup form and
+// by jj < k in the wave form -- the same strides; the other spelling cost topk_sample_kernel 2 % (se_topk_rows, 50,000 x 50,000) and
+// topk_merge_wave_kernel<16> 2 KB of code and 10 VGPRs.
+template <typename T, int PER, int THREADS, int SHFL_UNROLL>
+__device__ __forceinline__ void bitonic_phase(T (&v)[PER], T *lds, const int tid, const int k)
+{
+    static_assert(THREADS == WAVE || THREADS == TK_THREADS, "one wave or the whole top-k workgroup");
+    int j = k >> 1;
+    if constexpr (THREADS > WAVE) {
 #pragma unroll 1
-    for (int k = 2; k <= P; k <<= 1) {
-        int j = k >> 1;
-#pragma unroll 1
-        for (; j >= 64 * PER; j >>= 1) {               // partner in another wave: through LDS
+        for (; j >= 64 * PER; j >>= 1) {                   // partner in another wave: through LDS
             wg_barrier();
 #pragma unroll
             for (int r = 0; r < PER; r++) lds[tid * PER + r] = v[r];
             wg_barrier();
 #pragma unroll
             for (int r = 0; r < PER; r++) {
-                const T o = lds[(tid * PER + r) ^ j];
-                TK_CE_REMOTE(o, r)
+                const int e = tid * PER + r;
+                v[r] = keep_of(v[r], lds[e ^ j], ((e & k) == 0) == ((e & j) == 0));
             }
         }
-#pragma unroll 1
-        for (; j >= PER; j >>= 1) {                    // partner thread in the same wave: shuffle, no barrier
-            const int lm = j / PER;
+    }
+#pragma unroll SHFL_UNROLL
+    for (; j >= PER; j >>= 1) {                            // partner thread in the same wave: shuffle, no barrier
+        const int lm = j / PER;
+#pragma unroll
+        for (int r = 0; r < PER; r++) {
+            const int e = tid * PER + r;
+            v[r] = keep_of(v[r], shfl_any<true>(v[r], lm), ((e & k) == 0) == ((e & j) == 0));
+        }
+    }
+#pragma unroll
+    for (int jj = PER >> 1; jj > 0; jj >>= 1) {            // partner register of the same thread (static indices)
+        if (THREADS == WAVE ? jj < k : jj <= j) {
 #pragma unroll
             for (int r = 0; r < PER; r++) {
-                const T o = shfl_xor_any(v[r], lm);
-                TK_CE_REMOTE(o, r)
-            }
-        }
-#pragma unroll
-        for (int jj = PER >> 1; jj > 0; jj >>= 1) {    // partner register of the same thread (static indices)
-            if (jj <= j) {
-#pragma unroll
-                for (int r = 0; r < PER; r++) {
-                    if ((r & jj) == 0) {
-                        const bool up = (((tid * PER + r) & k) == 0);
-                        const T a = v[r], b = v[r | jj];
-                        const bool sw = (a > b) == up;
-                        v[r] = sw ? b : a;
-                        v[r | jj] = sw ? a : b;
-                    }
+                if ((r & jj) == 0) {
+                    const bool up = (((tid * PER + r) & k) == 0);
+                    const T a = v[r], b = v[r | jj];
+                    const bool sw = (a > b) == up;
+                    v[r] = sw ? b : a;
+                    v[r | jj] = sw ? a : b;
                 }
             }
         }
     }
-#undef TK_CE_REMOTE
+}
+
+template <typename T, int PER, int THREADS>
+__device__ __forceinline__ void bitonic_sort_blocked(T (&v)[PER], T *lds, const int tid)
+{
+#pragma unroll 1
+    for (int k = 2; k <= THREADS * PER; k <<= 1) bitonic_phase<T, PER, THREADS, 1>(v, lds, tid, k);
+}
+
+// The last phase on its own: a BITONIC sequence of THREADS * PER values (blocked layout) -> ascending order, log2(THREADS * PER)
+// stages with the direction fixed and every stage unrolled.
+template <typename T, int PER, int THREADS>
+__device__ __forceinline__ void bitonic_merge_blocked(T (&v)[PER], T *lds, const int tid) { bitonic_phase<T, PER, THREADS, 6>(v, lds, tid, THREADS * PER); }
+
+// Candidates -> sorted composite list in LDS: the THREADS threads load entries 0 .. total - 1 through load(e), pad with ~0 to the next
+// width of with_width, sort in registers, and write entries 0 .. keep - 1 to out (which may be the buffer load() reads, and lds).
+// THREADS = TK_THREADS: lds = room for the far strides (THREADS * PER values); THREADS = 64: one wave on its own, lds unused.
+template <int THREADS, class Load>
+__device__ __forceinline__ void sort_candidates(unsigned total, int keep, Load load, uint64_t *lds, uint64_t *out, const int tid)
+{
+    with_width(total, THREADS, [&](auto per) {
+        constexpr int PER = decltype(per)::value;
+        uint64_t cv[PER];
+#pragma unroll
+        for (int r = 0; r < PER; r++) {
+            const int e = tid * PER + r;
+            cv[r] = e < (int)total ? load(e) : ~0ull;
+        }
+        bitonic_sort_blocked<uint64_t, PER, THREADS>(cv, lds, tid);
+        sort_sync<THREADS>();
+#pragma unroll
+        for (int r = 0; r < PER; r++)
+            if (tid * PER + r < keep) out[tid * PER + r] = cv[r];
+        sort_sync<THREADS>();
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -261,7 +329,7 @@ __global__ __launch_bounds__(TK_THREADS, 4) void topk_sample_kernel(const float 
 #pragma unroll
             for (int r = 0; r < TK_SAMPLES / TK_THREADS; r++)
                 sv[r] = canon_key(drow[(int64_t)(tid * (TK_SAMPLES / TK_THREADS) + r) * N / TK_SAMPLES]);
-            blocked_bitonic_sort<uint32_t, TK_SAMPLES / TK_THREADS>(sv, smp);
+            bitonic_sort_blocked<uint32_t, TK_SAMPLES / TK_THREADS, TK_THREADS>(sv, smp, tid);
             wg_barrier();
 #pragma unroll
             for (int r = 0; r < TK_SAMPLES / TK_THREADS; r++) smp[tid * (TK_SAMPLES / TK_THREADS) + r] = sv[r];
@@ -284,7 +352,7 @@ __global__ __launch_bounds__(TK_THREADS, 4) void topk_sample_kernel(const float 
                 const int i = i0 + e * TK_THREADS + tid;
                 if (i < N && key[e] <= pivot) {
                     const uint32_t slot = atomicAdd(&ctl[0], 1u);
-                    if (slot < TK_CAP) cand[slot] = ((uint64_t)key[e] << 32) | (uint32_t)i;
+                    if (slot < TK_CAP) cand[slot] = pack_key(key[e], (uint32_t)i);
                 }
             }
         }
@@ -295,29 +363,8 @@ __global__ __launch_bounds__(TK_THREADS, 4) void topk_sample_kernel(const float 
             continue;
         }
         // sort the candidates on (key, index): registers + shuffles, padded with ~0 to TK_THREADS * PER
-#define TK_SORT_CAND(PER)                                                                     \
-    {                                                                                         \
-        uint64_t cv[PER];                                                                     \
-        _Pragma("unroll") for (int r = 0; r < PER; r++) {                                     \
-            const int e = tid * PER + r;                                                      \
-            cv[r] = (e < (int)total) ? cand[e] : ~0ull;                                       \
-        }                                                                                     \
-        blocked_bitonic_sort<uint64_t, PER>(cv, cand);                                        \
-        wg_barrier();                                                                      \
-        _Pragma("unroll") for (int r = 0; r < PER; r++) cand[tid * PER + r] = cv[r];          \
-        wg_barrier();                                                                      \
-    }
-        if (total <= TK_THREADS) TK_SORT_CAND(1)
-        else if (total <= 2 * TK_THREADS) TK_SORT_CAND(2)
-        else if (total <= 4 * TK_THREADS) TK_SORT_CAND(4)
-        else if (total <= 8 * TK_THREADS) TK_SORT_CAND(8)
-        else TK_SORT_CAND(16)
-#undef TK_SORT_CAND
-        for (int r = tid; r < k; r += TK_THREADS) {
-            const uint64_t c = cand[r];
-            out_d[row * k + r] = key_to_float((uint32_t)(c >> 32));
-            out_i[row * k + r] = (int32_t)(col_offset + (int64_t)(uint32_t)c);
-        }
+        sort_candidates<TK_THREADS>(total, TK_CAP, [&](int e) { return cand[e]; }, cand, cand, tid);
+        emit_topk(cand, k, out_d, out_i, row * k, col_offset, tid, TK_THREADS);
     }
 }
 
@@ -334,16 +381,12 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *__restrict
             if (t < m) {
                 const int p = t / k, r = t - p * k;
                 const int64_t src = (int64_t)p * part_stride + row * k + r;
-                v = ((uint64_t)canon_key(d[src]) << 32) | (uint32_t)idx[src];
+                v = pack_key(canon_key(d[src]), (uint32_t)idx[src]);
             }
             mg_lds[t] = v;
         }
         bitonic_sort_u64(mg_lds, P, 256);
-        for (int r = threadIdx.x; r < k; r += 256) {
-            const uint64_t c = mg_lds[r];
-            out_d[row * k + r] = key_to_float((uint32_t)(c >> 32));
-            out_i[row * k + r] = (int32_t)(uint32_t)c;
-        }
+        emit_topk(mg_lds, k, out_d, out_i, row * k, 0, threadIdx.x, 256);
     }
 }
 
@@ -507,76 +550,6 @@ static FusedPlan fused_plan(int64_t n, int64_t ldg, int k)
     return p;
 }
 
-// Bitonic sort of 64 * PER values held PER per lane by ONE wave (value e = lane * PER + r): partner registers of the same lane,
-// then lanes via shuffles -- no LDS, no barrier.
-template <typename T, int PER>
-__device__ __forceinline__ void wave_bitonic_sort(T (&v)[PER], int lane)
-{
-    constexpr int P = 64 * PER;
-#pragma unroll 1
-    for (int k = 2; k <= P; k <<= 1) {
-#pragma unroll 1
-        for (int jj = k >> 1; jj >= PER; jj >>= 1) {          // partner in another lane
-            const int lm = jj / PER;
-#pragma unroll
-            for (int r = 0; r < PER; r++) {
-                const T o = shfl_xor_any(v[r], lm);
-                const int e = lane * PER + r;
-                const bool take_min = (((e & k) == 0) == ((e & jj) == 0));
-                v[r] = take_min ? (o < v[r] ? o : v[r]) : (o > v[r] ? o : v[r]);
-            }
-        }
-#pragma unroll
-        for (int jj = PER >> 1; jj > 0; jj >>= 1) {            // partner register of the same lane (static indices)
-            if (jj < k) {
-#pragma unroll
-                for (int r = 0; r < PER; r++) {
-                    if ((r & jj) == 0) {
-                        const bool up = (((lane * PER + r) & k) == 0);
-                        const T a = v[r], b = v[r | jj];
-                        const bool sw = (a > b) == up;
-                        v[r] = sw ? b : a;
-                        v[r | jj] = sw ? a : b;
-                    }
-                }
-            }
-        }
-    }
-}
-
-// The last phase of that sort on its own: a BITONIC sequence of 64 * PER values (blocked layout) -> ascending order.  log2(64 * PER) stages.
-template <typename T, int PER>
-__device__ __forceinline__ void wave_bitonic_merge(T (&v)[PER], int lane)
-{
-#pragma unroll
-    for (int jj = 32 * PER; jj >= PER; jj >>= 1) {            // partner in another lane
-        const int lm = jj / PER;
-        const bool take_min = (lane & lm) == 0;
-#pragma unroll
-        for (int r = 0; r < PER; r++) {
-            const T o = shfl_xor_any(v[r], lm);
-            v[r] = take_min ? (o < v[r] ? o : v[r]) : (o > v[r] ? o : v[r]);
-        }
-    }
-#pragma unroll
-    for (int jj = PER >> 1; jj > 0; jj >>= 1) {                // partner register of the same lane (static indices)
-#pragma unroll
-        for (int r = 0; r < PER; r++) {
-            if ((r & jj) == 0) {
-                const T a = v[r], b = v[r | jj];
-                const bool sw = a > b;
-                v[r] = sw ? b : a;
-                v[r | jj] = sw ? a : b;
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src)
-{
-    return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)v, src, 64);
-}
-
 // se_topk_merge for k <= 1024: ONE WAVE per query keeps the best 64 * PER >= k entries in registers and folds the parts in one at a
 // time -- min(best[e], part[P - 1 - e]) of two ascending lists is a bitonic sequence holding the P smallest of their union, and
 // log2(P) compare-exchange stages put it in order again.  No LDS, no barrier.  (The first version sorted all parts * k entries of a
@@ -595,14 +568,14 @@ __global__ __launch_bounds__(256) void topk_merge_wave_kernel(const float *__res
 #pragma unroll
             for (int r = 0; r < PER; r++) {
                 const int e = lane * PER + r;
-                w[r] = e < k ? (((uint64_t)canon_key(d[base + e]) << 32) | (uint32_t)idx[base + e]) : ~0ull;
+                w[r] = e < k ? pack_key(canon_key(d[base + e]), (uint32_t)idx[base + e]) : ~0ull;
             }
             bool ok = true;
 #pragma unroll
             for (int r = 0; r + 1 < PER; r++) ok = ok && w[r] <= w[r + 1];
-            const uint64_t nxt = shfl_u64(w[0], lane < 63 ? lane + 1 : 63);
+            const uint64_t nxt = shfl_any<false>(w[0], lane < 63 ? lane + 1 : 63);
             ok = ok && (lane == 63 || w[PER - 1] <= nxt);
-            if (__ballot(!ok) != 0ull) wave_bitonic_sort<uint64_t, PER>(w, lane);      // (wave-uniform; not expected)
+            if (__ballot(!ok) != 0ull) bitonic_sort_blocked<uint64_t, PER, WAVE>(w, nullptr, lane);      // (wave-uniform; not expected)
             if (p == 0) {
 #pragma unroll
                 for (int r = 0; r < PER; r++) v[r] = w[r];
@@ -610,10 +583,10 @@ __global__ __launch_bounds__(256) void topk_merge_wave_kernel(const float *__res
             }
 #pragma unroll
             for (int r = 0; r < PER; r++) {
-                const uint64_t o = shfl_u64(w[PER - 1 - r], 63 - lane);                 // the part, descending
+                const uint64_t o = shfl_any<false>(w[PER - 1 - r], 63 - lane);          // the part, descending
                 v[r] = o < v[r] ? o : v[r];
             }
-            wave_bitonic_merge<uint64_t, PER>(v, lane);
+            bitonic_merge_blocked<uint64_t, PER, WAVE>(v, nullptr, lane);
         }
 #pragma unroll
         for (int r = 0; r < PER; r++) {
@@ -626,24 +599,30 @@ __global__ __launch_bounds__(256) void topk_merge_wave_kernel(const float *__res
     }
 }
 
-// tau[q] = j-th smallest of the G group minima of query q: one wave per query, 4 keys per lane, bitonic sort in registers.
+// The j-th smallest (1-based) of the G <= 256 group minima gm_row[0 .. G) of one query, by one wave: 4 keys per lane, bitonic sort in
+// registers.  NaN when there are fewer than j numbers among them.  The result is valid in lane (j - 1) / 4, which the callers let write.
+__device__ __forceinline__ float wave_jth_group_min(const float *__restrict__ gm_row, int G, int j, int lane)
+{
+    uint32_t v[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int e = lane * 4 + r;
+        v[r] = e < G ? canon_key(gm_row[e]) : 0xFFFFFFFFu;
+    }
+    bitonic_sort_blocked<uint32_t, 4, WAVE>(v, nullptr, lane);
+    const int want = j - 1;
+    const uint32_t key = (want & 3) == 0 ? v[0] : ((want & 3) == 1 ? v[1] : ((want & 3) == 2 ? v[2] : v[3]));
+    return key == 0xFFFFFFFFu ? __builtin_nanf("") : key_to_float(key);
+}
+
+// tau[q] = j-th smallest of the G group minima of query q: one wave per query.
 __global__ __launch_bounds__(256) void topk_tau_kernel(const float *__restrict__ gm, int64_t gm_ld, int64_t Q, int G, int j, float *__restrict__ tau)
 {
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= Q) return;
-    uint32_t v[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int e = lane * 4 + r;
-        v[r] = e < G ? canon_key(gm[q * gm_ld + e]) : 0xFFFFFFFFu;
-    }
-    wave_bitonic_sort<uint32_t, 4>(v, lane);
-    const int want = j - 1;
-    if (lane == (want >> 2)) {
-        const uint32_t key = (want & 3) == 0 ? v[0] : ((want & 3) == 1 ? v[1] : ((want & 3) == 2 ? v[2] : v[3]));
-        tau[q] = key == 0xFFFFFFFFu ? __builtin_nanf("") : key_to_float(key);   // NaN: nothing passes, the query goes to the fallback
-    }
+    const float t = wave_jth_group_min(gm + q * gm_ld, G, j, lane);
+    if (lane == ((j - 1) >> 2)) tau[q] = t;       // NaN: nothing passes, the query goes to the fallback
 }
 
 // candidate lists of the fp32 fused passes -> canonical top-k, one workgroup per query: the whole list sorted on the (key, index)
@@ -663,30 +642,8 @@ __global__ __launch_bounds__(TK_THREADS) void topk_lists_kernel(const uint2 *__r
         }
         const uint2 *lst = lists + row * cap;
         wg_barrier();     // the previous row's output reads of cand are done
-#define TK_SORT_LIST(PER)                                                                     \
-    {                                                                                         \
-        uint64_t cv[PER];                                                                     \
-        _Pragma("unroll") for (int r = 0; r < PER; r++) {                                     \
-            const int e = tid * PER + r;                                                      \
-            cv[r] = ~0ull;                                                                    \
-            if (e < (int)total) { const uint2 c = lst[e]; cv[r] = ((uint64_t)canon_key(__uint_as_float(c.x)) << 32) | c.y; } \
-        }                                                                                     \
-        blocked_bitonic_sort<uint64_t, PER>(cv, cand);                                        \
-        wg_barrier();                                                                      \
-        _Pragma("unroll") for (int r = 0; r < PER; r++) if (tid * PER + r < k) cand[tid * PER + r] = cv[r]; \
-        wg_barrier();                                                                      \
-    }
-        if (total <= TK_THREADS) TK_SORT_LIST(1)
-        else if (total <= 2 * TK_THREADS) TK_SORT_LIST(2)
-        else if (total <= 4 * TK_THREADS) TK_SORT_LIST(4)
-        else if (total <= 8 * TK_THREADS) TK_SORT_LIST(8)
-        else TK_SORT_LIST(16)
-#undef TK_SORT_LIST
-        for (int r = tid; r < k; r += TK_THREADS) {
-            const uint64_t c = cand[r];
-            out_d[row * k + r] = key_to_float((uint32_t)(c >> 32));
-            out_i[row * k + r] = (int32_t)(col_offset + (int64_t)(uint32_t)c);
-        }
+        sort_candidates<TK_THREADS>(total, k, [&](int e) { const uint2 c = lst[e]; return pack_key(canon_key(__uint_as_float(c.x)), c.y); }, cand, cand, tid);
+        emit_topk(cand, k, out_d, out_i, row * k, col_offset, tid, TK_THREADS);
     }
 }
 
@@ -732,17 +689,8 @@ __global__ __launch_bounds__(256) void pf_thr_kernel(const float *__restrict__ g
     const int lane = threadIdx.x & 63;
     const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= Q) return;
-    uint32_t v[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const int e = lane * 4 + r;
-        v[r] = e < G ? canon_key(gm[q * gm_ld + e]) : 0xFFFFFFFFu;
-    }
-    wave_bitonic_sort<uint32_t, 4>(v, lane);
-    const int want = j - 1;
-    if (lane == (want >> 2)) {
-        const uint32_t key = (want & 3) == 0 ? v[0] : ((want & 3) == 1 ? v[1] : ((want & 3) == 2 ? v[2] : v[3]));
-        const float tau = key == 0xFFFFFFFFu ? __builtin_nanf("") : key_to_float(key);
+    const float tau = wave_jth_group_min(gm + q * gm_ld, G, j, lane);
+    if (lane == ((j - 1) >> 2)) {
         const float hq = qn[q], rq = qr[q], HG = __uint_as_float(gctl[0]), RG = __uint_as_float(gctl[1]);
         const float e_round = hq * RG + rq * HG + rq * RG;
         const float e_acc = (float)(kp / 16) * 9.5368e-7f * 1.01f * (hq * HG);
@@ -758,8 +706,17 @@ __global__ __launch_bounds__(256) void pf_thr_kernel(const float *__restrict__ g
     }
 }
 
+// four steps of the canonical chain: gallery columns x.x .. x.w against q[0 .. 3], in this order
+__device__ __forceinline__ float fma4(float acc, float4 x, const float *__restrict__ q)
+{
+    acc = __builtin_fmaf(x.x, q[0], acc);
+    acc = __builtin_fmaf(x.y, q[1], acc);
+    acc = __builtin_fmaf(x.z, q[2], acc);
+    return __builtin_fmaf(x.w, q[3], acc);
+}
+
 // exact canonical dot product of gallery row `g` with the (wave-uniform) query row: fmaf chain over k ascending, restarted per K-block,
-// block sums added in order -- what the fp32 MFMA tiles and topk_fallback_kernel compute, bit for bit
+// block sums added in order -- what the fp32 MFMA tiles compute, bit for bit
 template <bool VEC>
 __device__ __forceinline__ float rf_chain(const float *__restrict__ g, const float *__restrict__ qv, const KBlocks &kbs)
 {
@@ -776,20 +733,9 @@ __device__ __forceinline__ float rf_chain(const float *__restrict__ g, const flo
 #pragma unroll
                 for (int i = 0; i < 8; i++) x[i] = *(const float4 *)(g + kk + 4 * i);
 #pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    acc = __builtin_fmaf(x[i].x, qv[kk + 4 * i], acc);
-                    acc = __builtin_fmaf(x[i].y, qv[kk + 4 * i + 1], acc);
-                    acc = __builtin_fmaf(x[i].z, qv[kk + 4 * i + 2], acc);
-                    acc = __builtin_fmaf(x[i].w, qv[kk + 4 * i + 3], acc);
-                }
+                for (int i = 0; i < 8; i++) acc = fma4(acc, x[i], qv + kk + 4 * i);
             }
-            for (; kk + 4 <= end; kk += 4) {
-                const float4 x = *(const float4 *)(g + kk);
-                acc = __builtin_fmaf(x.x, qv[kk], acc);
-                acc = __builtin_fmaf(x.y, qv[kk + 1], acc);
-                acc = __builtin_fmaf(x.z, qv[kk + 2], acc);
-                acc = __builtin_fmaf(x.w, qv[kk + 3], acc);
-            }
+            for (; kk + 4 <= end; kk += 4) acc = fma4(acc, *(const float4 *)(g + kk), qv + kk);
         }
         for (; kk < end; kk++) acc = __builtin_fmaf(g[kk], qv[kk], acc);
         tot = kb == 0 ? acc : tot + acc;
@@ -825,21 +771,9 @@ __device__ __forceinline__ float rf_chain_staged(const float *const (&src)[RF_NI
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             if (kk + RF_KC <= end4) {
 #pragma unroll
-                for (int j = 0; j < RF_KC; j += 4) {
-                    const float4 v4 = *reinterpret_cast<const float4 *>(rd + j);
-                    acc = __builtin_fmaf(v4.x, qv[kk + j], acc);
-                    acc = __builtin_fmaf(v4.y, qv[kk + j + 1], acc);
-                    acc = __builtin_fmaf(v4.z, qv[kk + j + 2], acc);
-                    acc = __builtin_fmaf(v4.w, qv[kk + j + 3], acc);
-                }
+                for (int j = 0; j < RF_KC; j += 4) acc = fma4(acc, *reinterpret_cast<const float4 *>(rd + j), qv + kk + j);
             } else {
-                for (int j = 0; kk + j < end4; j += 4) {
-                    const float4 v4 = *reinterpret_cast<const float4 *>(rd + j);
-                    acc = __builtin_fmaf(v4.x, qv[kk + j], acc);
-                    acc = __builtin_fmaf(v4.y, qv[kk + j + 1], acc);
-                    acc = __builtin_fmaf(v4.z, qv[kk + j + 2], acc);
-                    acc = __builtin_fmaf(v4.w, qv[kk + j + 3], acc);
-                }
+                for (int j = 0; kk + j < end4; j += 4) acc = fma4(acc, *reinterpret_cast<const float4 *>(rd + j), qv + kk + j);
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         };
@@ -902,27 +836,11 @@ __global__ __launch_bounds__(TK_THREADS) void topk_fallback_kernel(const float *
                     src[i] = gallery + (int64_t)(cr < N ? cr : N - 1) * ldg + 4 * (lane % RF_LPC);
                 }
                 const float tot = rf_chain_staged(src, gallery + (int64_t)cc * ldg, qv, kbs, rowbuf, lane);
-                float v;
-                if (METRIC == SE_METRIC_COSINE) v = -tot;
-                else v = (sqg[cc] + sq_q) - 2.0f * tot;
-                if (lane < RF_CPR && c < N) drow[c] = v;
+                if (lane < RF_CPR && c < N) drow[c] = dist_finish<METRIC>(tot, METRIC == SE_METRIC_EUCLID ? sqg[cc] : 0.f, sq_q);
             }
         } else
-        for (int c = threadIdx.x; c < N; c += TK_THREADS) {
-            const float *g = gallery + (int64_t)c * ldg;
-            float tot = 0.f;
-            int beg = 0;
-            for (int kb = 0; kb < kbs.n; kb++) {
-                float acc = 0.f;
-                for (int kk = beg; kk < beg + kbs.len[kb]; kk++) acc = __builtin_fmaf(g[kk], qv[kk], acc);
-                tot = kb == 0 ? acc : tot + acc;
-                beg += kbs.len[kb];
-            }
-            float v;
-            if (METRIC == SE_METRIC_COSINE) v = -tot;
-            else v = (sqg[c] + sq_q) - 2.0f * tot;
-            drow[c] = v;
-        }
+        for (int c = threadIdx.x; c < N; c += TK_THREADS)
+            drow[c] = dist_finish<METRIC>(rf_chain<false>(gallery + (int64_t)c * ldg, qv, kbs), METRIC == SE_METRIC_EUCLID ? sqg[c] : 0.f, sq_q);
         wg_barrier();     // (global writes of this workgroup are visible to it after the barrier)
         topk_select_row(drow, N, col_offset, k, P, out_d + row * k, out_i + row * k, tk_lds64);
         wg_barrier();
@@ -933,10 +851,32 @@ __global__ __launch_bounds__(TK_THREADS) void topk_fallback_kernel(const float *
 
 #ifdef SE_TUNING
 __device__ unsigned long long rf_prof[8];      // tuning build, SE_TOPK_VERBOSE: cycles per phase of pf_refine_kernel, summed over every wave
-#define RF_T(i) if (stats) { const uint64_t now = __builtin_amdgcn_s_memtime(); t_acc[i] += now - t_last; t_last = now; }
-#else
-#define RF_T(i)
 #endif
+#define RF_T(i) SE_PHASE_T(stats, i)
+
+// The digit (0 .. 255) whose bin of the wave's 256-bin histogram holds the `remaining`-th smallest key (1-based), and that key's rank
+// within the bin (-> remaining); both wave-uniform.  Lane l scans bins 4 l .. 4 l + 3 out of registers.
+// (topk_select_row keeps its own scan: 2048 bins, wave 0 of eight -- the lane that owns the bin publishes digit and rank through the
+// LDS words every wave reads behind the barrier that follows anyway; this form's two shuffles would be an LDS round trip more per pass.)
+__device__ __forceinline__ uint32_t wave_radix_digit(const uint32_t *hist, uint32_t &remaining, int lane)
+{
+    uint32_t c[4], local = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { c[i] = hist[lane * 4 + i]; local += c[i]; }
+    const uint32_t incl = wave_incl_scan(local);
+    uint32_t run = incl - local, digit = 0, rem = 0;
+    const bool mine = remaining > run && remaining <= incl;             // exactly one lane
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const bool hit = mine && remaining > run && remaining <= run + c[i];
+        digit = hit ? (uint32_t)(lane * 4 + i) : digit;
+        rem = hit ? remaining - run : rem;
+        run += c[i];
+    }
+    const int src = __ffsll((long long)__ballot(mine)) - 1;
+    remaining = (uint32_t)__shfl((int)rem, src, 64);
+    return (uint32_t)__shfl((int)digit, src, 64);
+}
 
 template <int METRIC, bool VEC, bool LONGROWS>
 __global__ __launch_bounds__(RF_WAVES * 64, 3) void pf_refine_kernel(const uint2 *__restrict__ lists, const uint2 *__restrict__ spill_lists, int nsub, const unsigned *__restrict__ rowcnt, int64_t cap, int parts, int64_t Q,
@@ -1011,6 +951,25 @@ __global__ __launch_bounds__(RF_WAVES * 64, 3) void pf_refine_kernel(const uint2
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         }
         RF_T(1)
+        // one walk over the query's candidates, staged or not: f(entry, valid) for 64 entries per step, one per lane, every lane in every
+        // step (wave-uniform: f may ballot); !valid past the end of the list / of a sub-list (the entry is then some other one of it)
+        auto for_each_entry = [&](auto f) {
+            if (staged) {
+                for (unsigned e0 = 0; e0 < total; e0 += 64) {
+                    const unsigned e = e0 + lane;
+                    f(stg[e < total ? e : 0], e < total);
+                }
+            } else {
+                for (int p = 0; p < parts; p++) {
+                    const uint2 *lp = sub_list(p);
+                    const unsigned cp = cnts[p];
+                    for (unsigned e0 = 0; e0 < cp; e0 += 64) {
+                        const unsigned e = e0 + lane;
+                        f(lp[e < cp ? e : 0], e < cp);
+                    }
+                }
+            }
+        };
         uint32_t m = 0;
         float B = 0.f;
         const float e_q = eps[urow], thr_q = thr[urow];
@@ -1022,39 +981,12 @@ __global__ __launch_bounds__(RF_WAVES * 64, 3) void pf_refine_kernel(const uint2
 #pragma unroll
                 for (int i = 0; i < 4; i++) hist[lane * 4 + i] = 0;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                if (staged) {
-                    for (unsigned e = lane; e < total; e += 64) {
-                        const uint32_t key = canon_key(__uint_as_float(stg[e].x));
-                        if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-                    }
-                } else {
-                    for (int p = 0; p < parts; p++) {
-                        const uint2 *lp = sub_list(p);
-                        const unsigned cp = cnts[p];
-                        for (unsigned e = lane; e < cp; e += 64) {
-                            const uint32_t key = canon_key(__uint_as_float(lp[e].x));
-                            if ((key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-                        }
-                    }
-                }
+                for_each_entry([&](uint2 c, bool valid) {
+                    const uint32_t key = canon_key(__uint_as_float(c.x));
+                    if (valid && (key & pmask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+                });
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                uint32_t c[4], local = 0;
-#pragma unroll
-                for (int i = 0; i < 4; i++) { c[i] = hist[lane * 4 + i]; local += c[i]; }
-                const uint32_t incl = wave_incl_scan(local);
-                uint32_t run = incl - local, digit = 0, rem = 0;
-                const bool mine = remaining > run && remaining <= incl;             // exactly one lane
-#pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    const bool hit = mine && remaining > run && remaining <= run + c[i];
-                    digit = hit ? (uint32_t)(lane * 4 + i) : digit;
-                    rem = hit ? remaining - run : rem;
-                    run += c[i];
-                }
-                const int src = __ffsll((long long)__ballot(mine)) - 1;
-                digit = (uint32_t)__shfl((int)digit, src, 64);
-                remaining = (uint32_t)__shfl((int)rem, src, 64);
-                prefix |= digit << shift;
+                prefix |= wave_radix_digit(hist, remaining, lane) << shift;
                 pmask |= 255u << shift;
             }
             const uint32_t kth = prefix;
@@ -1065,34 +997,16 @@ __global__ __launch_bounds__(RF_WAVES * 64, 3) void pf_refine_kernel(const uint2
                 B = b1 < thr_q ? b1 : thr_q;
                 const uint32_t bkey = canon_key(B);
                 // ---- R: entries with d~ <= B, plus every NaN d~ ----
-                if (staged) {
-                    // (sel doubled as the prefix array: every lane is past its last read of it -- the loop below writes it)
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    for (unsigned e0 = 0; e0 < total; e0 += 64) {
-                        const unsigned e = e0 + lane;
-                        const uint2 c = stg[e < total ? e : 0];
-                        const uint32_t key = canon_key(__uint_as_float(c.x));
-                        const bool take = e < total && (key <= bkey || key == 0xFFFFFFFFu);
-                        const uint64_t bm = __ballot(take);
-                        const uint32_t pos = m + wave_prefix_count(bm);
-                        if (take && pos < (uint32_t)RF_MAX) sel[pos] = c.y;
-                        m += (uint32_t)__popcll(bm);
-                    }
-                } else
-                for (int p = 0; p < parts; p++) {
-                    const uint2 *lp = sub_list(p);
-                    const unsigned cp = cnts[p];
-                    for (unsigned e0 = 0; e0 < cp; e0 += 64) {
-                        const unsigned e = e0 + lane;
-                        const uint2 c = lp[e < cp ? e : 0];
-                        const uint32_t key = canon_key(__uint_as_float(c.x));
-                        const bool take = e < cp && (key <= bkey || key == 0xFFFFFFFFu);
-                        const uint64_t bm = __ballot(take);
-                        const uint32_t pos = m + wave_prefix_count(bm);
-                        if (take && pos < (uint32_t)RF_MAX) sel[pos] = c.y;
-                        m += (uint32_t)__popcll(bm);
-                    }
-                }
+                // (staged: sel doubled as the prefix array -- every lane is past its last read of it, the walk below writes it)
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                for_each_entry([&](uint2 c, bool valid) {
+                    const uint32_t key = canon_key(__uint_as_float(c.x));
+                    const bool take = valid && (key <= bkey || key == 0xFFFFFFFFu);
+                    const uint64_t bm = __ballot(take);
+                    const uint32_t pos = m + wave_prefix_count(bm);
+                    if (take && pos < (uint32_t)RF_MAX) sel[pos] = c.y;
+                    m += (uint32_t)__popcll(bm);
+                });
                 ok = m <= (uint32_t)RF_MAX;
             }
         }
@@ -1125,56 +1039,27 @@ __global__ __launch_bounds__(RF_WAVES * 64, 3) void pf_refine_kernel(const uint2
                         src[i] = gallery + (int64_t)sel[ec < m ? ec : m - 1] * ldg + 4 * (lane % RF_LPC);
                     }
                     const float tot = rf_chain_staged(src, gallery + (int64_t)gi * ldg, qv, kbs, rowbuf, lane);
-                    float v;
-                    if (METRIC == SE_METRIC_COSINE) v = -tot;
-                    else v = (sqg[gi] + sq_q) - 2.0f * tot;
-                    if (chain_lane) comp[e] = ((uint64_t)canon_key(v) << 32) | gi;
+                    const float v = dist_finish<METRIC>(tot, METRIC == SE_METRIC_EUCLID ? sqg[gi] : 0.f, sq_q);
+                    if (chain_lane) comp[e] = pack_key(canon_key(v), gi);
                 }
             } else
             for (uint32_t e0 = 0; e0 < m; e0 += 64) {
                 const uint32_t e = e0 + lane;
                 const uint32_t gi = sel[e < m ? e : m - 1];
                 const float tot = rf_chain<VEC>(gallery + (int64_t)gi * ldg, qv, kbs);
-                float v;
-                if (METRIC == SE_METRIC_COSINE) v = -tot;
-                else v = (sqg[gi] + sq_q) - 2.0f * tot;
-                if (e < m) comp[e] = ((uint64_t)canon_key(v) << 32) | gi;
+                const float v = dist_finish<METRIC>(tot, METRIC == SE_METRIC_EUCLID ? sqg[gi] : 0.f, sq_q);
+                if (e < m) comp[e] = pack_key(canon_key(v), gi);
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             RF_T(4)
             // ---- sort R on (key, index); accept iff the k-th exact distance is <= B - eps ----
-            uint32_t kkey = 0;
-#define RF_SORT_OUT(P2)                                                                        \
-    {                                                                                          \
-        uint64_t sv[P2];                                                                       \
-        _Pragma("unroll") for (int r = 0; r < P2; r++) {                                       \
-            const int e = lane * P2 + r;                                                       \
-            sv[r] = e < (int)m ? comp[e] : ~0ull;                                              \
-        }                                                                                      \
-        wave_bitonic_sort<uint64_t, P2>(sv, lane);                                             \
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                 \
-        _Pragma("unroll") for (int r = 0; r < P2; r++) {                                       \
-            const int e = lane * P2 + r;                                                       \
-            if (e < k) comp[e] = sv[r];                                                        \
-        }                                                                                      \
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                 \
-    }
-            if (m <= 64) RF_SORT_OUT(1)
-            else if (m <= 128) RF_SORT_OUT(2)
-            else if (m <= 256) RF_SORT_OUT(4)
-            else if (m <= 512) RF_SORT_OUT(8)
-            else RF_SORT_OUT(16)
-#undef RF_SORT_OUT
-            kkey = (uint32_t)(comp[k - 1] >> 32);
+            sort_candidates<WAVE>(m, k, [&](int e) { return comp[e]; }, nullptr, comp, lane);
+            const uint32_t kkey = (uint32_t)(comp[k - 1] >> 32);
             RF_T(5)
             const float dk = kkey == 0xFFFFFFFFu ? __builtin_nanf("") : key_to_float(kkey);
             ok = dk <= B - 1.01f * e_q;                     // false for NaN
             if (ok) {
-                for (int r = lane; r < k; r += 64) {
-                    const uint64_t c = comp[r];
-                    out_d[urow * k + r] = key_to_float((uint32_t)(c >> 32));
-                    out_i[urow * k + r] = (int32_t)(col_offset + (int64_t)(uint32_t)c);
-                }
+                emit_topk(comp, k, out_d, out_i, urow * k, col_offset, lane, 64);
                 if (stats && lane == 0) { atomicAdd(&stats[0], m); atomicAdd(&stats[1], total); }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1308,13 +1193,10 @@ static int topk_merge_launch(const char *who, const float *d, const int32_t *idx
     if (!d || !idx || !out_d || !out_i) return fail(SE_ERR_INVALID, "%s: null pointer", who);
     if (k <= 1024) {      // one wave per query, the running best list in registers (64 * PER >= k entries)
         const int64_t wgrid = (q + 3) / 4 < 8192 ? (q + 3) / 4 : 8192;
-#define SE_MERGE_WAVE(PER) hipLaunchKernelGGL(topk_merge_wave_kernel<PER>, dim3((unsigned)wgrid), dim3(256), 0, (hipStream_t)stream, d, idx, part_stride, parts, q, k, out_d, out_i)
-        if (k <= 64) SE_MERGE_WAVE(1);
-        else if (k <= 128) SE_MERGE_WAVE(2);
-        else if (k <= 256) SE_MERGE_WAVE(4);
-        else if (k <= 512) SE_MERGE_WAVE(8);
-        else SE_MERGE_WAVE(16);
-#undef SE_MERGE_WAVE
+        with_width((unsigned)k, WAVE, [&](auto per) {
+            hipLaunchKernelGGL(topk_merge_wave_kernel<decltype(per)::value>, dim3((unsigned)wgrid), dim3(256), 0, (hipStream_t)stream, d, idx, part_stride,
+                               parts, q, k, out_d, out_i);
+        });
         SE_LAUNCH_CHECK();
         return SE_OK;
     }
@@ -1347,6 +1229,18 @@ extern "C" int64_t se_retrieve_topk_workspace_bytes(int64_t q, int64_t n, int64_
     return retrieve_topk_plan(q, n, d, ldg, k).need;
 }
 
+// queries [q0, q0 + rows) of a fused loop over tiles of qt queries: their rows, squared norms (or null) and slice of the outputs
+struct QueryTile {
+    int64_t rows;
+    const float *qs, *sq;
+    float *out_d;
+    int32_t *out_i;
+};
+static QueryTile query_tile(int64_t q0, int64_t qt, int64_t q, const float *queries, int64_t ldq, const float *sqq, int k, float *out_d, int32_t *out_i)
+{
+    return {q - q0 < qt ? q - q0 : qt, queries + q0 * ldq, sqq ? sqq + q0 : nullptr, out_d + q0 * k, out_i + q0 * k};
+}
+
 // the bf16 pre-filter path of one query tile (see the block comment above pf_thr_kernel)
 static int retrieve_topk_prefilter(const float *queries, int64_t ldq, const float *gallery, int64_t ldg, const float *sqq, const float *sqg,
                                    int64_t q, int64_t n, int64_t d, int metric, const KBlocks &kbs, int64_t col_offset, int k, float *out_d,
@@ -1367,9 +1261,9 @@ static int retrieve_topk_prefilter(const float *queries, int64_t ldq, const floa
     if (const int rc = pf_convert(gallery, ldg, n, d, gimg, gnrm, gres, ctl, s)) return rc;
     phase_mark("convert", s);
     for (int64_t q0 = 0; q0 < q; q0 += L.qt) {
-        const int64_t rows = (q - q0 < L.qt) ? (q - q0) : L.qt;
-        const float *qs = queries + q0 * ldq;
-        const float *sq = sqq ? sqq + q0 : nullptr;
+        const QueryTile t = query_tile(q0, L.qt, q, queries, ldq, sqq, k, out_d, out_i);
+        const int64_t rows = t.rows;
+        const float *qs = t.qs, *sq = t.sq;
         // all-pairs call: every item is query and gallery item -- one image serves both sides
         const bool sym = (qs == gallery) && (ldq == ldg) && (rows == n) && (metric != SE_METRIC_EUCLID || sq == sqg);
         const uint16_t *qi = gimg;
@@ -1401,12 +1295,13 @@ static int retrieve_topk_prefilter(const float *queries, int64_t ldq, const floa
         const bool count = verbose || phase_timing_on();               // [2..3] of nflag: entries recomputed exactly / candidates, summed over the queries
 
         const int64_t rgrid = (rows + RF_WAVES - 1) / RF_WAVES < 8192 ? (rows + RF_WAVES - 1) / RF_WAVES : 8192;
-#define SE_RF_LAUNCH(M, V, LR) hipLaunchKernelGGL((pf_refine_kernel<M, V, LR>), dim3((unsigned)rgrid), dim3(RF_WAVES * 64), 0, s, lists, spill_lists, L.nsub, rowcnt, L.cap, L.parts, rows, thr, eps, qs, ldq, \
-                                                  gallery, ldg, sq, sqg, kbs, col_offset, k, out_d + q0 * k, out_i + q0 * k, nflag, count ? nflag + 2 : nullptr)
         const bool longrows = vec && d >= RF_STAGE_D;                  // the build with the LDS-staged row gather
-        if (metric == SE_METRIC_COSINE) { if (longrows) SE_RF_LAUNCH(SE_METRIC_COSINE, true, true); else if (vec) SE_RF_LAUNCH(SE_METRIC_COSINE, true, false); else SE_RF_LAUNCH(SE_METRIC_COSINE, false, false); }
-        else { if (longrows) SE_RF_LAUNCH(SE_METRIC_EUCLID, true, true); else if (vec) SE_RF_LAUNCH(SE_METRIC_EUCLID, true, false); else SE_RF_LAUNCH(SE_METRIC_EUCLID, false, false); }
-#undef SE_RF_LAUNCH
+        dispatch_bools(metric == SE_METRIC_COSINE, vec, longrows, [&](auto cosine, auto v, auto lr) {
+            if constexpr (v() || !lr())                                // (long rows are vector rows)
+                hipLaunchKernelGGL((pf_refine_kernel<cosine() ? SE_METRIC_COSINE : SE_METRIC_EUCLID, v(), lr()>), dim3((unsigned)rgrid), dim3(RF_WAVES * 64), 0, s,
+                                   lists, spill_lists, L.nsub, rowcnt, L.cap, L.parts, rows, thr, eps, qs, ldq, gallery, ldg, sq, sqg, kbs, col_offset, k,
+                                   t.out_d, t.out_i, nflag, count ? nflag + 2 : nullptr);
+        });
         SE_LAUNCH_CHECK();
         phase_mark("refine", s);
         if (verbose) {   // -DSE_TUNING build only: synchronises and reports how the lists came out
@@ -1435,7 +1330,7 @@ static int retrieve_topk_prefilter(const float *queries, int64_t ldq, const floa
                     (long long)n, (long long)d, kp, k, p.S, p.G, p.j, L.parts, (long long)L.cap, (long long)rows, (int)sym, h[1],
                     okq > 0 ? (double)h[3] / okq : 0.0, okq > 0 ? (double)h[2] / okq : 0.0, (double)gmaxn, (double)gmaxr, hc[2]);
         }
-        rc = launch_topk_fallback(metric, qs, ldq, gallery, ldg, sq, sqg, rows, n, d, kbs, col_offset, k, scratch, out_d + q0 * k, out_i + q0 * k, nflag, s);
+        rc = launch_topk_fallback(metric, qs, ldq, gallery, ldg, sq, sqg, rows, n, d, kbs, col_offset, k, scratch, t.out_d, t.out_i, nflag, s);
         if (rc != SE_OK) return rc;
         phase_mark("fallback", s);
         phase_note_counters(nflag, rows, s);      // final by now (refinement + exact fallback have been enqueued): copied on this stream
@@ -1492,10 +1387,10 @@ extern "C" int se_retrieve_topk(const float *queries, int64_t ldq, const float *
     const size_t lds_lists = (size_t)PER * TK_THREADS * 8;
     SE_HIP_CHECK(hipFuncSetAttribute((const void *)topk_lists_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_lists));
     for (int64_t q0 = 0; q0 < q; q0 += L.qt) {
-        const int64_t rows = (q - q0 < L.qt) ? (q - q0) : L.qt;
-        const float *qs = queries + q0 * ldq;
-        const float *sq = sqq ? sqq + q0 : nullptr;
-        unsigned *nflag = rowcnt + rows;                               // [1] queries handed to the exact kernel; [0], [2..3] unused
+        const QueryTile t = query_tile(q0, L.qt, q, queries, ldq, sqq, k, out_d, out_i);
+        const int64_t rows = t.rows;
+        const float *qs = t.qs, *sq = t.sq;
+        unsigned *nflag = rowcnt + rows;                              // [1] queries handed to the exact kernel; [0], [2..3] unused
         SE_HIP_CHECK(hipMemsetAsync(rowcnt, 0, (size_t)rows * 4 + 16, s));
         FusedArgs fa = {gm, p.G, tau, rowcnt, lists, p.cap, p.step};
         int rc = launch_fused_pass(EPI_GROUPMIN, gallery, p.step * ldg, qs, ldq, sqg, sq, p.S, rows, d, metric, kbs, multi, fa, s);
@@ -1507,7 +1402,7 @@ extern "C" int se_retrieve_topk(const float *queries, int64_t ldq, const float *
         if (rc != SE_OK) return rc;
         const int64_t grid = rows < 2048 ? rows : 2048;
         hipLaunchKernelGGL(topk_lists_kernel, dim3((unsigned)grid), dim3(TK_THREADS), lds_lists, s, lists, rowcnt, (int64_t)p.cap, rows,
-                           col_offset, k, out_d + q0 * k, out_i + q0 * k, nflag);
+                           col_offset, k, t.out_d, t.out_i, nflag);
         SE_LAUNCH_CHECK();
         if (kTuning && tuning_env("SE_TOPK_VERBOSE")) {   // -DSE_TUNING build only: synchronises and reports how the lists came out
             SE_HIP_CHECK(hipStreamSynchronize(s));
@@ -1520,7 +1415,7 @@ extern "C" int se_retrieve_topk(const float *queries, int64_t ldq, const float *
             fprintf(stderr, "[se_retrieve_topk] fused: n=%lld k=%d S=%d step=%lld G=%d j=%d cap=%d rows=%lld flagged=%lld mean_candidates=%.1f\n",
                     (long long)n, k, p.S, (long long)p.step, p.G, p.j, p.cap, (long long)rows, (long long)flagged, sum / (double)rows);
         }
-        rc = launch_topk_fallback(metric, qs, ldq, gallery, ldg, sq, sqg, rows, n, d, kbs, col_offset, k, scratch, out_d + q0 * k, out_i + q0 * k, nflag, s);
+        rc = launch_topk_fallback(metric, qs, ldq, gallery, ldg, sq, sqg, rows, n, d, kbs, col_offset, k, scratch, t.out_d, t.out_i, nflag, s);
         if (rc != SE_OK) return rc;
     }
     return SE_OK;

@@ -100,7 +100,7 @@ def sample_positions(n):
 
 
 def sort_width(total, unit):
-    """TK_SORT_CAND / TK_SORT_LIST (unit 512) and RF_SORT_OUT (unit 64): values per thread / lane."""
+    """with_width behind sort_candidates<TK_THREADS> (unit 512) and sort_candidates<WAVE> (unit 64): values per thread / lane."""
     return next(w for w in SORT_WIDTHS if total <= w * unit or w == 16)
 
 
@@ -404,7 +404,7 @@ def _fp32_list_cases():
     ]
 
 
-M_EDGES = (63, 64, 65, 128, 129, 256, 257, 384, 385, 512, 513, 1024, 1025)       # k - 1 / k at k = 64, every RF_SORT_OUT width, RF_STAGE_M, RF_MAX
+M_EDGES = (63, 64, 65, 128, 129, 256, 257, 384, 385, 512, 513, 1024, 1025)       # k - 1 / k at k = 64, every sort_candidates<WAVE> width, RF_STAGE_M, RF_MAX
 TWO_LEVEL = ((100, 924), (100, 925), (384, 700), (385, 700))
 SPILL_N, SPILL_D = 600, 64                                                        # 5 gallery tiles = 5 sub-lists, one cluster per tile
 
