@@ -1087,6 +1087,60 @@ int se_tiny_batch(const float *images, int64_t N, const int64_t *index, const do
                   const float *stdp, int fill_mode, float cval, void *out, int out_dtype, int64_t B, int H, int W, int C,
                   se_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Bootstrap over queries: confidence intervals and paired tests of the retrieval metrics
+ * ------------------------------------------------------------------------------------------ */
+
+/*
+ * Means of per-query metric rows resampled with replacement, one launch for all replicates.
+ * Replaces: the host composition idx = randint(q, size = (R, q)); vals[idx].mean(axis = 1) (the reference prints bare means; the
+ *           evaluation tools resample se_hierarchical_precision's per-query rows, bootstrap.py).
+ *   vals   [q, m] float64, row pitch ldv >= m;  1 <= q <= 2^31 - 1,  1 <= m <= SE_BOOTSTRAP_COLS_MAX
+ *   seed   64 bits, read as UNSIGNED (int64_t only carries them)
+ *   out    [reps, m] float64, row pitch ldo >= m:  for rep0 <= r < rep0 + reps and c < m
+ *              out[r - rep0, c] = S / (double)q,   S = the float64 sum over t = 0 .. q - 1 of vals[idx(seed, r, t, q), c]
+ *          (columns m .. ldo - 1 of out stay as they are; columns m .. ldv - 1 of vals are never read)
+ *
+ * THE INDEX STREAM idx(seed, r, t, q) IS PART OF THIS ABI: the same seed gives the same replicates on every machine and in every
+ * later version, and two tables of the same q resampled with one seed are resampled with the same queries (paired).
+ *   Draw t of replicate r uses block b = t >> 1 and half h = t & 1.
+ *   (x0, x1, x2, x3) = Philox4x32-10(counter, key):
+ *       counter = (b & 0xffffffff, b >> 32, r & 0xffffffff, r >> 32)
+ *       key     = (seed & 0xffffffff, seed >> 32)
+ *   Multipliers are M0 = 0xD2511F53 on counter word 0 and M1 = 0xCD9E8D57 on counter word 2.
+ *   Key increments per round are 0x9E3779B9 (k0) and 0xBB67AE85 (k1), added after each of the first nine rounds.
+ *   Each of the ten rounds computes: c <- (hi(M1 * c2) ^ c1 ^ k0, lo(M1 * c2), hi(M0 * c0) ^ c3 ^ k1, lo(M0 * c0)).
+ *   u = x[2h] | x[2h + 1] << 32, and idx = (u * q) >> 64, the high half of the 128-bit product.  The bias is q / 2^64.
+ * 0 <= idx < q for every u, so every gather is inside the table whatever the seed.
+ * Known answers: Philox(counter 0,0,0,0; key 0,0) = 6627e8d5 e169c58d bc57ac4c 9b00dbd8;  seed 0, r 0, q 10, t 0..7: 8 6 3 0 3 2 4 4.
+ *
+ * SUMMATION ORDER (float64, no floating-point atomics; fixed by q and m alone, never by reps, rep0 or the launch geometry):
+ *   there are 256 chains; chain j starts at +0 and adds, in ascending t, the draws of the blocks b = j, j + 256, j + 512, ...
+ *   (draw 2 b, then draw 2 b + 1 where that is < q);
+ *   the chains of each group of 64 (j >> 6) combine in a butterfly: for off = 32, 16, 8, 4, 2, 1: s[l] <- s[l] + s[l ^ off];
+ *   the four group sums w0 .. w3 are added as ((w0 + w1) + w2) + w3, and that sum is divided by (double)q.
+ * The same inputs give the same bits, and a call for replicates 0 .. 9 equals the calls for 0 .. 3 and 4 .. 9 put together.  A NaN in
+ * a drawn row makes that replicate's column NaN (and no other).
+ * reps == 0 returns SE_OK without a launch.  q or m out of range, ldv < m, ldo < m, rep0 < 0, reps < 0, or a NULL pointer with
+ * reps > 0 is SE_ERR_INVALID.  Asynchronous on `stream`; no workspace, no allocation, no host synchronisation; capturable in a HIP
+ * graph.  A row is read by one lane: rows that do not cross a 128-byte line (an aligned base and a power-of-two pitch of >= m
+ * doubles, which sehip.bootstrap_means makes) cost one line per draw.
+ */
+#define SE_BOOTSTRAP_COLS_MAX 16
+int se_bootstrap_means(const double *vals, int64_t ldv, int64_t q, int m, int64_t seed, int64_t rep0, int64_t reps, double *out, int64_t ldo,
+                       se_stream_t stream);
+
+/*
+ * The index stream of se_bootstrap_means on its own (the same device function):
+ *     out[r - rep0, t - t0] = idx(seed, r, t, q)     for rep0 <= r < rep0 + reps and t0 <= t < t0 + count <= q
+ *   out  [reps, count] int32, row pitch ldo >= count.  1 <= q <= 2^31 - 1: with a small window the stream can be read at sizes at
+ *        which no value table would fit.
+ * reps == 0 or count == 0 returns SE_OK without a launch.  q out of range, a window outside [0, q], ldo < count, rep0 < 0, reps < 0, or
+ * a NULL out with work to do is SE_ERR_INVALID.  Asynchronous; no workspace; capturable in a HIP graph.
+ */
+int se_bootstrap_indices(int64_t q, int64_t seed, int64_t rep0, int64_t reps, int64_t t0, int64_t count, int32_t *out, int64_t ldo,
+                         se_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

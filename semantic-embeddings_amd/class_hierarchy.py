@@ -326,7 +326,9 @@ class ClassHierarchy(object):
         ``labels``: class label of image ``ids[i]`` (``ids`` defaults to ``range(N)``), as a sequence or a mapping.
         Returns ``(means, per_query)`` exactly like ``hierarchical_precision``; ``per_query=False`` returns ``(means, None)`` with
         the means taken on the device (the CLI only prints means: at N = 50k and 250 cut-offs the per-query dictionaries are
-        25 million Python floats, seconds of host time after milliseconds of kernels).
+        25 million Python floats, seconds of host time after milliseconds of kernels).  ``per_query='table'`` returns the means of
+        ``per_query=False`` and, in the place of the dictionaries, a ``bootstrap.MetricTable``: the float64 device tensor
+        ``[queries, columns]`` itself, the ``{metric name: column}`` map and the query ids in row order (what ``--bootstrap`` resamples).
 
         ``distributed`` (one process per GPU, ``torch.distributed`` initialised): every rank holds all features.
         * metrics that need full rankings (AP, un-clipped AHP): the QUERIES are sharded -- rank r ranks rows
@@ -394,7 +396,7 @@ class ClassHierarchy(object):
             raise ValueError('the gallery is empty')
         if rank_gallery and nq == 0:     # nothing to average
             names = list(_metric_columns(ks, compute_ahp, compute_ap))
-            return {m: float('nan') for m in names}, ({m: {} for m in names} if per_query else None)
+            return {m: float('nan') for m in names}, _empty_per_query(names, per_query, dev)
         world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
         rank = dist.get_rank(group) if world > 1 else 0
         if f64 and world > 1:
@@ -503,7 +505,8 @@ class ClassHierarchy(object):
         tensor of ids (``recall_precision.ranked_problem``).  ``labels`` maps id -> class label.  The gallery is ``all_ids`` when that
         is given: ids missing from a list are appended in its order (class_hierarchy.py:262-264), on the device
         (``se_complete_rankings``).  Without ``all_ids`` the gallery is the id set of the first list and every list must be a
-        permutation of it.  Returns ``(means, per_query)`` as the reference does; ``per_query=False`` returns ``(means, None)``.
+        permutation of it.  Returns ``(means, per_query)`` as the reference does; ``per_query=False`` returns ``(means, None)``,
+        ``per_query='table'`` ``(means, bootstrap.MetricTable)`` as ``hierarchical_precision_device`` does.
 
         Best-possible curves: the reference takes a class's curve from the first query of that class -- the sorted similarities of
         that query's (completed) list.  Every completed list holds the whole gallery, so that curve is the one
@@ -539,7 +542,7 @@ class ClassHierarchy(object):
         p = ranked_problem(retrieved, labels, ignore_qids, all_ids)
         nq, ng, C, dev = len(p.q_ids), len(p.g_ids), len(p.class_list), kernels['device']
         if nq == 0:         # nothing to average
-            return {m: float('nan') for m in columns}, ({m: {} for m in columns} if per_query else None)
+            return {m: float('nan') for m in columns}, _empty_per_query(columns, per_query, dev)
         if ng == 0:
             raise ValueError('the gallery is empty')
         kmax = max(ks + [ahp_clip or 0])
@@ -648,9 +651,28 @@ def _ranked_gallery_tile_rows(dev, nq, ng, C, feature_bytes, ncol, tile_rows, na
     return rows
 
 
+def _wants_table(per_query):
+    """``per_query='table'``: the per-query values as ``bootstrap.MetricTable`` -- the float64 device tensor [queries, columns], the
+    ``{metric name: column}`` map and the query ids in row order -- instead of dictionaries (minutes of host time at 50,000 queries x
+    500 columns)."""
+    return isinstance(per_query, str) and per_query == 'table'
+
+
+def _empty_per_query(names, per_query, dev):
+    """The second return value when there is no query at all."""
+    if not per_query:
+        return None
+    if _wants_table(per_query):
+        import torch
+        from bootstrap import MetricTable
+        names = list(names)
+        return MetricTable(torch.zeros((0, len(names)), dtype=torch.float64, device=dev), {m: c for c, m in enumerate(names)}, [])
+    return {m: {} for m in names}
+
+
 def _metric_rows_to_results(res_d, columns, n, ids, q0, q1, world, group, gather_per_query, per_query):
     """``(means, per_query)`` from this rank's rows ``q0 .. q1`` of se_hierarchical_precision's output (all-gathered, or only their
-    sums all-reduced, under several ranks); ``columns``: ``_metric_columns``."""
+    sums all-reduced, under several ranks); ``columns``: ``_metric_columns``.  ``per_query='table'``: ``_wants_table``."""
     import torch
     import torch.distributed as dist
     from sharded_retrieval import shard_bounds
@@ -668,11 +690,15 @@ def _metric_rows_to_results(res_d, columns, n, ids, q0, q1, world, group, gather
         else:                   # the means only: one all-reduce of ncol sums
             sums = res_d.sum(dim=0)
             dist.all_reduce(sums, group=group)
-    if not per_query:
+    if not per_query or _wants_table(per_query):
         if sums is None:        # every row is here (one process, or gathered): the column means
             sums = res_d.sum(dim=0)
         sums = sums.cpu().numpy()
-        return {name: float(sums[c]) / n for name, c in columns.items()}, None
+        means = {name: float(sums[c]) / n for name, c in columns.items()}
+        if per_query:           # 'table': the rows stay on the device (the means are those of per_query=False, bit for bit)
+            from bootstrap import MetricTable
+            return means, MetricTable(res_d, dict(columns), list(ids[q0:q1]))
+        return means, None
     res = res_d.cpu().numpy()
     prec = {name: dict(zip(ids[q0:q1], res[:, c].tolist())) for name, c in columns.items()}
     if sums is not None:

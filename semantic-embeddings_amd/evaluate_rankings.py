@@ -12,7 +12,8 @@ gallery id j of that split is ``('train', j)``, the convention of ``evaluate_ret
 are tagged on loading.  Ids missing from a list are appended in the split's index order (``all_ids``; class_hierarchy.py:262-264)
 unless ``--no_all_ids``, under which every list must rank the whole gallery.  The lists are scored on the device by
 ``ClassHierarchy.hierarchical_precision_ranked`` and, with ``--recprec_csv``, ``recall_precision.recall_precision_ranked``; tables,
-CSV and plots are those of ``evaluate_retrieval.py``."""
+CSV and plots are those of ``evaluate_retrieval.py``, and so are ``--bootstrap R`` / ``--compare_to LABEL`` (intervals over queries and paired differences between rankings of the same queries;
+``bootstrap.py``)."""
 import argparse
 import os.path
 import pickle
@@ -20,6 +21,7 @@ from collections import OrderedDict
 
 import numpy as np
 
+import bootstrap
 from evaluate_retrieval import METRICS, load_labels, plot_performance, print_performance, write_performance
 
 
@@ -51,11 +53,15 @@ def build_parser():
     g.add_argument('--recprec_csv', type=str, default=None,
                    help='Also compute the recall-precision curve and the mAP; write "ranking,level,mean_precision" rows to this file.')
     g.add_argument('--bins', type=int, default=None, help='Number of recall bins of the recall-precision curve.')
+    bootstrap.add_bootstrap_flags(p.add_argument_group('Bootstrap over queries'))
     return p
 
 
 def parse_args(argv=None):
-    return build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    bootstrap.check_bootstrap_flags(parser, args, [ranking_entry(args, i) for i in range(len(args.ranking))])
+    return args
 
 
 def ranking_entry(args, i):
@@ -124,15 +130,18 @@ def main(argv=None):
     for k in [1, 10, 50, 100]:
         if (len(ks) == 0) or (ks[-1] < k):
             ks.append(k)
-    perf, curves = OrderedDict(), OrderedDict()
+    perf, curves, tables = OrderedDict(), OrderedDict(), OrderedDict()     # tables: the per-query rows on the device, under --bootstrap only
     for i, path in enumerate(args.ranking):
         name = ranking_entry(args, i)
         retrieved = load_ranking(path)
         if args.gallery_split == 'train':
             retrieved = tag_train_ids(retrieved)
         common = dict(ignore_qids=not args.keep_queries, all_ids=None if args.no_all_ids else all_ids)
-        perf[name] = hierarchy.hierarchical_precision_ranked(retrieved, labels, ks, compute_ahp=args.clip_ahp if args.clip_ahp else True,
-                                                             compute_ap=not args.skip_ap, per_query=False, **common)[0]
+        perf[name], rows = hierarchy.hierarchical_precision_ranked(retrieved, labels, ks, compute_ahp=args.clip_ahp if args.clip_ahp else True,
+                                                                   compute_ap=not args.skip_ap,
+                                                                   per_query='table' if bootstrap.wanted(args) else False, **common)
+        if rows is not None:
+            tables[name] = rows
         if args.recprec_csv:
             levels, means, mAP, _ = recall_precision_ranked(retrieved, labels, bins=args.bins, **common)
             curves[name] = (levels, means, mAP)
@@ -146,6 +155,8 @@ def main(argv=None):
         metrics[4] = 'AHP@{} (WUP)'.format(args.clip_ahp)
         metrics[9] = 'AHP@{} (LCS_HEIGHT)'.format(args.clip_ahp)
     print_performance(perf, metrics)
+    if tables:
+        bootstrap.report(args, tables, metrics)
     if args.csv:
         write_performance(perf, args.csv, args.prec_type)
     if args.recprec_csv:

@@ -26,7 +26,10 @@ reference: evaluate_retrieval.py:22-73 (pairwise_retrieval), :76-151 (reporting 
 * ``--float64`` (extension; ``pairwise_retrieval(..., precision='float64')``): float64 feature files are evaluated in float64 like the
   reference does -- float64 distances from one sequential FMA chain (``se_pairwise_dist_f64``), ranked exactly (``se_rank_rows`` on
   their float32 image, then ``se_rank_refine_f64``) -- instead of being cast to float32 behind a warning.  All-pairs, one process
-  only: ``--gallery_feat`` / ``--rank_gallery`` and the sharded multi-GPU evaluation stay float32 and refuse the flag.
+  only: ``--gallery_feat`` / ``--rank_gallery`` and the sharded multi-GPU evaluation stay float32 and refuse the flag;
+* ``--bootstrap R`` (extension; ``bootstrap.py``): below the table of means, ``mean [lo, hi]`` percentile intervals of the printed
+  columns from R resamples of the queries (``se_bootstrap_means``; ``--bootstrap_seed``, ``--confidence``), with ``--compare_to LABEL``
+  the paired difference ``delta [lo, hi] p=...`` of every other entry to that one, and ``--bootstrap_csv FILE``.  One process only.
 """
 import argparse
 import os.path
@@ -35,6 +38,8 @@ import warnings
 from collections import OrderedDict
 
 import numpy as np
+
+import bootstrap
 
 try:
     from tqdm import tqdm
@@ -506,6 +511,7 @@ def build_parser():
     g.add_argument('--rank_gallery', action='store_true', default=argparse.SUPPRESS,
                    help='With --gallery_feat: rank every query against the WHOLE gallery and read every metric off that ranking; '
                         'gives the un-clipped AHP columns, so --clip_ahp is not required (with it, AHP@K comes from the same ranking).')
+    bootstrap.add_bootstrap_flags(g)
     return p
 
 
@@ -551,6 +557,7 @@ def parse_args(argv=None):
     if getattr(args, 'rank_gallery', False) and not args.gallery_feat:
         parser.error('--rank_gallery needs --gallery_feat (without a gallery every ranking is a full one already)')
     check_float64_flag(parser, args)
+    bootstrap.check_bootstrap_flags(parser, args, [feat_entry(args, i)[0] for i in range(len(args.feat))])
     return args
 
 
@@ -623,7 +630,7 @@ def main(argv=None):
     for k in [1, 10, 50, 100]:
         if (len(ks) == 0) or (ks[-1] < k):
             ks.append(k)
-    perf = OrderedDict()
+    perf, tables = OrderedDict(), OrderedDict()     # tables: the per-query rows on the device, under --bootstrap only
     for i, feat_dump in tqdm(enumerate(args.feat), total=len(args.feat), disable=rank != 0):
         feat_name, normalize = feat_entry(args, i)
         # reference: hierarchy.hierarchical_precision(pairwise_retrieval(feat_dump, normalize), labels_test, ks, ...)
@@ -636,11 +643,13 @@ def main(argv=None):
             gallery_kw['rank_gallery'] = True
         if float64_precision(args, features):       # (the keyword is only passed when the flag asks for it)
             gallery_kw['precision'] = 'float64'
-        perf[feat_name] = hierarchy.hierarchical_precision_device(
+        perf[feat_name], rows = hierarchy.hierarchical_precision_device(
             features, labels_test, ks, compute_ahp=args.clip_ahp if args.clip_ahp else True, compute_ap=not args.skip_ap,
             normalize=normalize, ids=None if ind2id is None else ind2id.tolist(), distributed=world > 1,
-            kblocks=args.kblocks, per_query=False,         # the tables / plots below use the means only
-            **gallery_kw)[0]
+            kblocks=args.kblocks, per_query='table' if bootstrap.wanted(args) else False,     # the tables / plots below use the means only
+            **gallery_kw)
+        if rows is not None:
+            tables[feat_name] = rows
     if rank != 0:
         return perf
 
@@ -651,6 +660,8 @@ def main(argv=None):
         metrics[4] = 'AHP@{} (WUP)'.format(args.clip_ahp)
         metrics[9] = 'AHP@{} (LCS_HEIGHT)'.format(args.clip_ahp)
     print_performance(perf, metrics)
+    if tables:
+        bootstrap.report(args, tables, metrics)
     if args.csv:
         write_performance(perf, args.csv, args.prec_type)
     if args.plot_max > 0:

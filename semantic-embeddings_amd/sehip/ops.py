@@ -21,7 +21,7 @@ __all__ = [
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "pairwise_dist_f64",
     "rank_refine_f64_", "rank_rows_f64", "topk_rows",
-    "topk_merge", "retrieve_topk", "knn_vote", "KNN_TOP_MAX", "complete_rankings", "COMPLETE_LDS_ITEMS", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
+    "topk_merge", "retrieve_topk", "knn_vote", "KNN_TOP_MAX", "bootstrap_means", "bootstrap_indices", "BOOTSTRAP_COLS_MAX", "complete_rankings", "COMPLETE_LDS_ITEMS", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
     "recall_precision_reduce", "count_preceding", "count_to_positions", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
     "svm_axpby", "class_pair_tables", "cholesky_lower_", "eigh", "eigh_schedule", "EIGH_NOT_CONVERGED", "EIGH_NONFINITE", "image_batch", "resample_tables", "tiny_batch", "TINY_BATCH_MAX_BLOCKS", "FILL_MODES",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
@@ -1223,6 +1223,59 @@ def knn_vote(idx, cls, num_classes, ks, top=5, qidx=None):
     call("se_knn_vote", idx, ldi, Q, L, cls, cls.numel(), int(num_classes), qidx, (ctypes.c_int32 * len(ks))(*ks), len(ks), int(top),
          out_cls, out_votes)
     return out_cls, out_votes
+
+
+BOOTSTRAP_COLS_MAX = DEFINES["SE_BOOTSTRAP_COLS_MAX"]     # columns se_bootstrap_means resamples per call
+
+
+def _seed_arg(seed):
+    """A seed of up to 64 bits as the int64 that carries them across the C ABI (read there as unsigned)."""
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 64):
+        raise SehipError("seed must fit 64 bits")
+    seed &= (1 << 64) - 1
+    return seed - (1 << 64) if seed >= (1 << 63) else seed
+
+
+def bootstrap_means(vals, reps, seed=0, rep0=0):
+    """Means of the rows of ``vals`` resampled with replacement (``se_bootstrap_means``): replicate ``rep0 + i`` draws ``q`` rows by
+    the index stream pinned in include/sehip.h and row ``i`` of the result is the mean of each column over them.
+
+    vals [q, m] float64 device tensor, any row pitch, 1 <= m <= ``BOOTSTRAP_COLS_MAX``; ``seed``: up to 64 bits.  The same
+    ``(seed, q)`` draws the same queries whatever the values, and a replicate has the same bits whichever call computes it.
+    A table whose rows could straddle 128-byte lines is first copied to a power-of-two pitch (m up to 16 doubles: one line per
+    drawn row).  Returns float64 ``[reps, m]``."""
+    require_gpu(vals)
+    if vals.dtype != torch.float64 or vals.dim() != 2 or (vals.shape[1] > 1 and vals.stride(1) != 1):
+        raise SehipError("vals must be a 2-d float64 tensor with contiguous rows")
+    q, m = vals.shape
+    reps, rep0 = int(reps), int(rep0)
+    if q < 1 or not 1 <= m <= BOOTSTRAP_COLS_MAX:
+        raise SehipError("vals must hold at least one row of 1 .. %d columns, not %s" % (BOOTSTRAP_COLS_MAX, tuple(vals.shape)))
+    if reps < 0 or rep0 < 0:
+        raise SehipError("reps and rep0 must be non-negative")
+    ldv = vals.stride(0) if q > 1 else max(vals.stride(0), m)
+    pitch = 1 << (m - 1).bit_length()
+    if reps > 0 and q > 1 and (ldv < m or ldv % pitch or vals.data_ptr() % (8 * pitch)):
+        padded = torch.empty((q, pitch), dtype=torch.float64, device=vals.device)
+        padded[:, :m] = vals
+        vals, ldv = padded, pitch
+    out = torch.empty((reps, m), dtype=torch.float64, device=vals.device)
+    call("se_bootstrap_means", vals, ldv, q, m, _seed_arg(seed), rep0, reps, out, m)
+    return out
+
+
+def bootstrap_indices(q, reps, seed=0, rep0=0, t0=0, count=None, device=None):
+    """The index stream of ``bootstrap_means`` (``se_bootstrap_indices``): int32 ``[reps, count]``, entry ``[i, j]`` the row that
+    draw ``t0 + j`` of replicate ``rep0 + i`` takes from a table of ``q`` rows.  ``count`` defaults to ``q - t0``."""
+    require_gpu()
+    q, reps, rep0, t0 = int(q), int(reps), int(rep0), int(t0)
+    count = q - t0 if count is None else int(count)
+    if reps < 0 or count < 0:
+        raise SehipError("reps and count must be non-negative")
+    out = torch.empty((reps, count), dtype=torch.int32, device=torch.device("cuda", _device_index(device)))
+    call("se_bootstrap_indices", q, _seed_arg(seed), rep0, reps, t0, count, out, count)
+    return out
 
 
 COMPLETE_LDS_ITEMS = DEFINES["SE_COMPLETE_LDS_ITEMS"]     # galleries up to this size need no workspace in complete_rankings

@@ -9,6 +9,9 @@
     python tools/bench_kernels.py ranked         (se_complete_rankings at 10,000 x 10,000 and 50,000 x 50,000, list lengths 0 / 250 / N, both
                                                   order forms, next to a copy of the same bytes and a torch composition; the whole
                                                   hierarchical_precision_ranked next to the host function; --n / --d are not used)
+    python tools/bench_kernels.py bootstrap      (se_bootstrap_means at q = 10,000 and 50,000 queries x 11 columns x 10,000 replicates next to
+                                                  the torch composition randint -> index_select -> mean in chunks that fit memory; --n / --d
+                                                  are not used)
     python tools/bench_kernels.py recprec        (10k x 10k and 50k x 50k, 100 classes; --n is not used)
     python tools/bench_kernels.py svm            (margin + reduction kernels and whole LinearSVC fits: 50,000 x 100 x 100 and
                                                   1,281,167 x 1000 x 1000; --n / --d are not used; --svm-sizes small skips the large one)
@@ -105,7 +108,7 @@ def windows(fns, reps, batch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn", "ranked"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn", "ranked", "bootstrap"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -151,6 +154,8 @@ def main():
         return bench_knn()
     if args.what == "ranked":
         return bench_ranked()
+    if args.what == "bootstrap":
+        return bench_bootstrap()
     if args.what == "pdist64":
         return bench_pdist64(args.n, args.d, max(args.reps, 10))
     n, d = args.n, args.d
@@ -1213,6 +1218,45 @@ def bench_knn(reps=30, batch=10):
         print("knn_classification %d x %d x %d, k=%d, C=%d, features on the device: median %.2f ms (min %.2f, max %.2f) per call, rankings on the host"
               % (q, n, d, k, C, float(np.median(ts)), min(ts), max(ts)), flush=True)
         del train, test, lists, lists64, ones
+
+
+def bench_bootstrap(rounds=10, reps=10000, m=11, chunk_bytes=512 << 20):
+    """Bootstrap over queries: se_bootstrap_means (sehip.bootstrap_means on a [q, 11] float64 table, row pitch padded to 16 doubles
+    once, outside the timing) next to the torch composition of the same work -- torch.randint -> index_select -> mean(dim=1), in
+    chunks of replicates whose gathered rows fit `chunk_bytes` -- the two timed alternately in one process: `rounds` rounds of one
+    call each (HIP events around a call) after 3 warm-up calls, median / 10th / 90th percentile.  The composition draws another
+    stream, so the legs are compared on their spread, not on their values.  GB/s: reps x q gathered rows of m doubles over the
+    kernel's time.  Shapes: q = 10,000 and 50,000 queries, m = 11 metric columns, 10,000 replicates; seeded uniform values."""
+    rng = np.random.default_rng(0)
+    for q in (10000, 50000):
+        vals = torch.from_numpy(rng.random((q, m))).cuda()
+        padded = torch.zeros((q, 16), dtype=torch.float64, device="cuda")
+        padded[:, :m] = vals
+        table = padded[:, :m]          # pitch 16: a row inside one 128-byte line; the binding takes it as it is
+        chunk = max(1, min(reps, chunk_bytes // (q * m * 8)))
+
+        def kernel():
+            return sehip.bootstrap_means(table, reps, seed=1)
+
+        def composition():
+            out = torch.empty((reps, m), dtype=torch.float64, device="cuda")
+            for r0 in range(0, reps, chunk):
+                c = min(chunk, reps - r0)
+                idx = torch.randint(q, (c * q,), device="cuda")
+                out[r0:r0 + c] = vals.index_select(0, idx).view(c, q, m).mean(dim=1)
+            return out
+        k, t = kernel(), composition()
+        sd = float(vals.std(dim=0, unbiased=False).mean()) / np.sqrt(q)
+        for name, x in (("kernel", k), ("composition", t)):      # both legs resample: the spread of their replicate means is the theory's
+            ratio = float(x.std(dim=0, unbiased=False).mean()) / sd
+            assert abs(ratio - 1.0) < 0.05, (name, ratio)
+        kt, tt = windows((kernel, composition), rounds, 1)
+        moved = 8.0 * m * q * reps
+        print("bootstrap q=%d m=%d reps=%d: se_bootstrap_means %.2f ms (%.2f-%.2f), torch composition in chunks of %d replicates %.2f ms "
+              "(%.2f-%.2f): x%.2f; the kernel gathers %.1f GB of rows = %.0f GB/s"
+              % (q, m, reps, kt[0] / 1e3, kt[1] / 1e3, kt[2] / 1e3, chunk, tt[0] / 1e3, tt[1] / 1e3, tt[2] / 1e3, tt[0] / kt[0], moved / 1e9,
+                 moved / (kt[0] * 1e-6) / 1e9), flush=True)
+        del vals, padded, table
 
 
 def bench_ranked(reps=10, batch=3, host_rows=500):
