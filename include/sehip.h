@@ -790,6 +790,35 @@ int se_hprec_reciprocal_curves(const double *best_wup, const double *best_lcs, i
                                int num_classes, int64_t list_len, double *rcp, se_stream_t stream);
 
 /*
+ * Normalised discounted cumulative gain of every query from its ranking, with the class similarity tables as gains: the graded,
+ * position-discounted companion of se_hierarchical_precision's columns, read from the same rank tile.
+ * Replaces: a host loop over pairwise_retrieval(..., return_generator=False) (the reference has no NDCG; the host statement of
+ *           these semantics is ClassHierarchy.ndcg).
+ *   rank, ldr, cls, qcls, qidx   exactly as in se_hierarchical_precision (qidx NULL = keep every entry)
+ *   gain_a, gain_b  [C, C] f64: the gain of a retrieved item is gain[qcls[i] * C + cls[item]] (row = the query's class; no
+ *             symmetry is assumed)
+ *   disc      [disc_len >= list_len] f64: disc[p - 1] weighs position p (1-based, counted after the query's own entry is dropped).
+ *             The kernel computes no logarithm: the caller passes 1 / log2(p + 1)
+ *   ideal     [C, 2, 2, nk + 1] f64, [class][member][table][cut-off slot], slot nk = the whole list; member = 1 when
+ *             qidx != NULL && qidx[i] >= 0 (the query is a gallery item: the ideal list holds one item of its class fewer)
+ *   ks        [nk <= 512] int32 cut-offs >= 1, any order, duplicates allowed; a k beyond the list scores the list's end
+ *   out       [q, 2 nk + 2] f64: NDCG@k of table a x nk, of table b x nk, whole-list a, whole-list b (ldo elements between rows);
+ *             DCG / ideal where ideal > 0, else 0.  The last two columns are written only when want_full; without it only the
+ *             first min(list_len, max(ks) + 1) ranks of a row are read (top-L lists)
+ * The query's own entry is dropped where it occurs among the entries read; a member whose entry is not among them drops
+ * nothing (and still takes the member = 1 ideal).  A row's result depends on that row's inputs only.  q == 0 or list_len == 0:
+ * SE_OK, nothing launched.  No allocation, no host synchronisation, capturable.
+ */
+#define SE_NDCG_CHUNK 2048   /* ranks a workgroup takes per step (tests: list lengths around it) */
+int se_ndcg(const int32_t *rank, int64_t ldr, int64_t q, int64_t list_len,
+            const int32_t *cls, int64_t gallery, const int32_t *qcls, const int32_t *qidx,
+            const double *gain_a, const double *gain_b, int num_classes,
+            const double *disc, int64_t disc_len,
+            const double *ideal,
+            const int32_t *ks, int nk, int want_full,
+            double *out, int64_t ldo, se_stream_t stream);
+
+/*
  * Positions of the relevant items in every query's ranking: the exact primary data of the recall-precision curve and the mAP.
  * Replaces: the relevance list of plot_recall_precision.py:52-79 (`labels[r] == labels[qid] for r in retrieved if r != qid`).
  *   rank      [q, list_len] int32 gallery indices, best first (ldr elements between rows)

@@ -36,6 +36,10 @@ def replicate_means(table, reps, seed=0, chunk=REP_CHUNK):
     if reps < 1:
         raise ValueError('reps must be a positive number of replicates')
     chunk = max(1, int(chunk))
+    wide = sehip.BOOTSTRAP_COLS_MAX
+    if table.shape[1] > wide:       # more columns than one launch resamples (--ndcg next to the 11 of the table): groups of columns -- the
+        groups = [table[:, c0:c0 + wide].contiguous() for c0 in range(0, table.shape[1], wide)]     # index stream depends on (seed, q) only, so
+        return np.concatenate([replicate_means(g, reps, seed, chunk) for g in groups], axis=1)        # replicate r draws the same queries in each
     parts = [sehip.bootstrap_means(table, min(chunk, reps - r0), seed=seed, rep0=r0) for r0 in range(0, reps, chunk)]
     return (parts[0] if len(parts) == 1 else torch.cat(parts)).cpu().numpy()
 

@@ -310,12 +310,63 @@ class ClassHierarchy(object):
 
         return {metric: sum(values.values()) / len(values) for metric, values in prec.items()}, prec
 
+    def ndcg(self, retrieved, labels, ks=[1, 10, 0], ignore_qids=True, all_ids=None, gallery_ids=None, disc=None):
+        """Normalised discounted cumulative gain per query + means, with the class similarities as gains: the plain host statement
+        of what ``se_ndcg`` computes (``hierarchical_precision_device(..., ndcg=ks)``), for small inputs and as the tests' reference.
+
+        ``retrieved``, ``labels``, ``ignore_qids``, ``all_ids`` as in ``hierarchical_precision``; ``ks``: cut-offs, 0 = the whole list.
+        Returns ``(means, per_query)`` with the metrics ``"NDCG@K (WUP)"``, ``"NDCG@K (LCS_HEIGHT)"`` and, for 0, ``"NDCG (WUP)"`` /
+        ``"NDCG (LCS_HEIGHT)"``.
+
+        Per query: the ranked list (completed in ``all_ids`` order when it is shorter), the query's own id dropped where it occurs
+        (``ignore_qids``); ``DCG@k = sum_{p = 1 .. min(k, len)} sim(query class, class of item p) * disc[p - 1]`` with
+        ``disc[p - 1] = 1 / log2(p + 1)`` unless ``disc`` is given.  The ideal DCG takes the same sum over the GALLERY's
+        similarities to the query's class in descending order -- the gallery is ``gallery_ids``, else ``all_ids``, else the ids of the
+        first list -- without the query's own item when the query is a gallery item (and ``ignore_qids``), whether or not that item
+        occurs in the list.  NDCG = DCG / ideal, 0 where the ideal is 0."""
+        nd = _ndcg_request(ks)
+        if nd is None:
+            raise ValueError('no NDCG cut-off given')
+        cuts, whole = nd
+        columns = _metric_columns([], False, False, nd)
+        items = list(retrieved) if isinstance(retrieved, types.GeneratorType) else list(retrieved.items())
+        prec = {n: {} for n in columns}
+        if not items:
+            return {n: float('nan') for n in columns}, prec
+        g_ids = list(gallery_ids if gallery_ids is not None else (all_ids if all_ids else items[0][1]))
+        g_set = set(g_ids)
+        class_list = sorted(set(labels[i] for i in g_ids) | set(labels[q] for q, _ in items), key=repr)
+        class_pos = {c: i for i, c in enumerate(class_list)}
+        tables = self.similarity_tables(class_list)
+        g_cls = np.asarray([class_pos[labels[i]] for i in g_ids], dtype=np.int64)
+        n_max = max(len(g_ids), max(len(r) for _, r in items))
+        w = 1 / np.log2(np.arange(2, n_max + 2)) if disc is None else np.asarray(disc, dtype=np.float64)
+        for qid, ret in items:
+            ret = list(ret)
+            if all_ids and len(ret) < len(all_ids):
+                seen = set(ret)
+                ret = ret + [i for i in all_ids if i not in seen]
+            if ignore_qids and qid in ret:
+                del ret[ret.index(qid)]
+            qc = class_pos[labels[qid]]
+            cols = np.asarray([class_pos[labels[r]] for r in ret], dtype=np.int64)
+            pool = g_cls
+            if ignore_qids and qid in g_set:
+                pool = np.delete(g_cls, g_ids.index(qid))
+            for tname, table in zip(('WUP', 'LCS_HEIGHT'), tables):
+                gains = table[qc, cols]
+                best = np.sort(table[qc, pool])[::-1]
+                for k in cuts + ([0] if whole else []):
+                    kk, kb = (min(k, len(gains)), min(k, len(best))) if k else (len(gains), len(best))
+                    dcg, idcg = float(np.dot(gains[:kk], w[:kk])), float(np.dot(best[:kb], w[:kb]))
+                    prec[('NDCG@{} ({})'.format(k, tname)) if k else 'NDCG ({})'.format(tname)][qid] = dcg / idcg if idcg > 0 else 0.0
+        return {metric: sum(values.values()) / len(values) for metric, values in prec.items()}, prec
 
     def hierarchical_precision_device(self, features, labels, ks=[1, 10, 50, 100], compute_ahp=False, compute_ap=False,
                                       normalize=False, ids=None, tile_rows=None, distributed=False, group=None, kblocks=None,
                                       gather_per_query=True, kernels=None, per_query=True, head_via_topk=True,
                                       gallery=None, gallery_labels=None, gallery_ids=None, tile_cols=None, rank_gallery=False,
-                                      precision=None):
+                                      precision=None, ndcg=None):
         """``hierarchical_precision(pairwise_retrieval(features, normalize), labels, ...)`` (ignore_qids = True, every
         image is query and gallery item) without leaving the GPU: the rankings stay device tensors
         (``evaluate_retrieval.ranking_tiles``) and the per-query gather + prefix sums run in
@@ -366,7 +417,15 @@ class ClassHierarchy(object):
         ``precision='float64'`` (opt-in; CLI: ``--float64``): float64 ``features`` are ranked in float64, as the reference ranks them --
         ``ranking_tiles(..., precision='float64')`` -- and every metric is read from those full rankings (the fused top-L path is a
         float32 path and is not taken).  The metric kernels read ranks only and are the same.  All-pairs in one process only: a
-        ``gallery``, ``kblocks`` or several ranks raise ``ValueError``, as float32 features do."""
+        ``gallery``, ``kblocks`` or several ranks raise ``ValueError``, as float32 features do.
+
+        ``ndcg`` (opt-in; CLI: ``--ndcg K [K ...]``): a list of cut-offs, 0 = the whole list.  Appends the columns ``NDCG@K (WUP)``,
+        ``NDCG@K (LCS_HEIGHT)`` and, for 0, ``NDCG (WUP)`` / ``NDCG (LCS_HEIGHT)`` behind the others -- normalised discounted cumulative
+        gain with the class similarities as gains and ``1 / log2(position + 1)`` as weights (``se_ndcg``; the host statement is
+        ``ClassHierarchy.ndcg``) -- read from the same rank tile as the other metrics, directly after them.  Whole-list NDCG needs
+        whole rankings: it takes the full-ranking path as AP does, and with a ``gallery`` and no ``rank_gallery`` it raises
+        ``ValueError`` like un-clipped AHP; cut-offs K > 0 are served from the top-L lists, L = max(ks, clip, ndcg) + 1.  Without
+        ``ndcg`` every output is what it was.  ``kernels`` (tests): ``'ndcg'``."""
         import torch
         import torch.distributed as dist
         from evaluate_retrieval import RANKING_KERNELS, _resolve_kblocks, is_float64, resolve_kernels, to_device_f64
@@ -378,6 +437,10 @@ class ClassHierarchy(object):
             raise ValueError('un-clipped AHP needs the whole ranking of the gallery, which a separate gallery does not get by default: '
                              'pass compute_ahp=K (--clip_ahp K on the command line), or opt into that ranking with rank_gallery=True '
                              '(--rank_gallery)')
+        nd = _ndcg_request(ndcg)
+        if nd is not None and nd[1] and gallery is not None and not rank_gallery:
+            raise ValueError('whole-list NDCG (cut-off 0) needs the whole ranking of the gallery, which a separate gallery does not get by '
+                             'default: ask for cut-offs K > 0 only, or opt into that ranking with rank_gallery=True (--rank_gallery)')
         f64 = is_float64(precision)
         if f64 and (gallery is not None or kblocks is not None):
             raise ValueError("precision='float64' ranks all pairs of one float64 feature matrix with ONE FMA chain per distance: a "
@@ -385,17 +448,17 @@ class ClassHierarchy(object):
         # ---- the problem, the device and this rank's queries ----
         given = dict(kernels or {})
         native_metrics = 'hierarchical_precision' not in given
-        kernels = resolve_kernels(given, ('hierarchical_precision', 'ranking_tiles', 'device'))
+        kernels = resolve_kernels(given, ('hierarchical_precision', 'ranking_tiles', 'device') + (('ndcg',) if nd else ()))
         ks = [ks] if isinstance(ks, int) else list(ks)
         ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
         ahp_len = -1 if not compute_ahp else (0 if ahp_clip is None else ahp_clip)
-        ncol = 2 * len(ks) + 3
+        ncol = 2 * len(ks) + 3 + (2 * len(nd[0]) + 2 if nd else 0)
         p = gallery_problem(features, labels, ids, gallery, gallery_labels, gallery_ids)
         nq, ng, C, dev = int(p.qf.shape[0]), int(p.gf.shape[0]), len(p.class_list), kernels['device']
         if rank_gallery and ng == 0:
             raise ValueError('the gallery is empty')
         if rank_gallery and nq == 0:     # nothing to average
-            names = list(_metric_columns(ks, compute_ahp, compute_ap))
+            names = list(_metric_columns(ks, compute_ahp, compute_ap, nd))
             return {m: float('nan') for m in names}, _empty_per_query(names, per_query, dev)
         world = dist.get_world_size(group) if (distributed and dist.is_initialized()) else 1
         rank = dist.get_rank(group) if world > 1 else 0
@@ -403,7 +466,7 @@ class ClassHierarchy(object):
             raise ValueError("precision='float64' runs in one process: the sharded multi-GPU evaluation stays float32")
         q0, q1 = shard_bounds(nq, world)[rank] if world > 1 else (0, nq)
         # top-L lists are enough when no metric reads past the head of a ranking; a separate gallery is ranked in full on request only
-        head_only = (not compute_ap) and (not compute_ahp or ahp_clip is not None)
+        head_only = (not compute_ap) and (not compute_ahp or ahp_clip is not None) and not (nd and nd[1])
         use_top_lists = (not rank_gallery) if gallery is not None else (head_only and (world > 1 or head_via_topk) and not f64)
         if rank_gallery:    # before anything is launched
             tile_rows = _ranked_gallery_tile_rows(dev, q1 - q0, ng, C, 4 * int(p.qf.shape[1]) * (nq + ng), ncol, tile_rows,
@@ -422,7 +485,7 @@ class ClassHierarchy(object):
         # then one float64 prefix sum per row.
         counts = np.bincount(p.gcls, minlength=C)
         best = [_best_curves(t, counts, ng, dev) for t in (wup_t, lcs_t)]
-        L = min(ng, max(ks + [ahp_clip or 0]) + 1)
+        L = min(ng, max(ks + [ahp_clip or 0] + (nd[0] if nd else [])) + 1)
         if use_top_lists:
             best = [b[:, :L + 1].contiguous() for b in best]
             topk_kblocks = _resolve_kblocks(kblocks, int(p.qf.shape[1]))     # (here: its D > 448 warning names the caller)
@@ -443,11 +506,13 @@ class ClassHierarchy(object):
         else:
             qcls_d, qidx_d = torch.from_numpy(p.qcls).to(dev), torch.from_numpy(p.qidx).to(dev)
         ks_d = torch.tensor(ks, dtype=torch.int32, device=dev)
+        score_ndcg = _ndcg_scorer(nd, kernels, tables[0], tables[1], counts, ng, dev)
 
         def score(ranks, r0, want_ap, extra):       # metric rows of queries r0 .. r0 + len(ranks)
             r1 = r0 + ranks.shape[0]
-            return kernels['hierarchical_precision'](ranks, gcls_d, qcls_d[r0:r1].contiguous(), qidx_d[r0:r1].contiguous(), *tables, ks_d,
-                                                     ahp_len=ahp_len, want_ap=want_ap, **extra)
+            qc, qi = qcls_d[r0:r1].contiguous(), qidx_d[r0:r1].contiguous()
+            rows = kernels['hierarchical_precision'](ranks, gcls_d, qc, qi, *tables, ks_d, ahp_len=ahp_len, want_ap=want_ap, **extra)
+            return rows if score_ndcg is None else torch.cat([rows, score_ndcg(ranks, gcls_d, qc, qi)], dim=1)   # the same tile, directly after
 
         def top_lists():
             """Fused distance + top-L (the Q x N matrix is never written) over this rank's shard of the gallery, lists merged across the
@@ -475,7 +540,7 @@ class ClassHierarchy(object):
             # (16-bit ranks between the two kernels -- ranking_tiles(idx16=True), se_hierarchical_precision_r16 -- give the same results
             # from half the bytes, but measured at 50k x 50k the ranking gains 0.24 ms and the metric kernel, which is not bound by its
             # rank stream, loses 0.41 ms to the unpacking: int32 stays the default; SE_EVAL_IDX16=1 switches)
-            elif native_metrics and 'ranking_tiles' not in given and ng <= 53248 and os.environ.get('SE_EVAL_IDX16'):
+            elif native_metrics and 'ranking_tiles' not in given and ng <= 53248 and os.environ.get('SE_EVAL_IDX16') and not nd:    # (se_ndcg: int32 ranks)
                 tiles_kw = {'idx16': True}
             else:
                 tiles_kw = {}
@@ -484,7 +549,7 @@ class ClassHierarchy(object):
 
         outs = top_lists() if use_top_lists else ranked_tiles()
         res_d = outs[0] if len(outs) == 1 else (torch.cat(outs) if outs else torch.zeros((0, ncol), dtype=torch.float64, device=dev))
-        columns = _metric_columns(ks, compute_ahp, compute_ap)      # (host work from here on runs under the kernels launched above)
+        columns = _metric_columns(ks, compute_ahp, compute_ap, nd)      # (host work from here on runs under the kernels launched above)
         if use_top_lists and compute_ap:    # a separate gallery: counted, not ranked; every rank gets every query's AP
             with warnings.catch_warnings():
                 warnings.simplefilter('ignore', RuntimeWarning)      # queries without a relevant item: AP 0, as in the reference
@@ -495,7 +560,7 @@ class ClassHierarchy(object):
         return _metric_rows_to_results(res_d, columns, nq, p.q_ids, q0, q1, world, group, gather_per_query, per_query)
 
     def hierarchical_precision_ranked(self, retrieved, labels, ks=[1, 10, 50, 100], compute_ahp=False, compute_ap=False,
-                                      ignore_qids=True, all_ids=None, per_query=True, tile_rows=None, kernels=None):
+                                      ignore_qids=True, all_ids=None, per_query=True, tile_rows=None, kernels=None, ndcg=None):
         """``hierarchical_precision(retrieved, labels, ks, compute_ahp, compute_ap, ignore_qids, all_ids)`` (class_hierarchy.py:211-316)
         for GIVEN rankings -- from another system, an approximate index, re-ranked or truncated lists -- scored on the device instead
         of in the reference's per-query Python loop.
@@ -527,32 +592,36 @@ class ClassHierarchy(object):
         partial lists without ``all_ids`` (use the host ``hierarchical_precision``); ``max(ks)`` or the AHP clip beyond what a
         ranking holds (the gallery, less the query's own item when queries are gallery items and ``ignore_qids``); an empty
         gallery.  No queries: NaN means and empty dictionaries, as ``hierarchical_precision_device`` returns.  One process, one GPU.
-        ``kernels`` (tests): CPU stand-ins ``{'complete_rankings', 'hierarchical_precision', 'device'}``."""
+        ``kernels`` (tests): CPU stand-ins ``{'complete_rankings', 'hierarchical_precision', 'ndcg', 'device'}``.
+
+        ``ndcg``: as in ``hierarchical_precision_device`` -- cut-offs, 0 = the whole list; columns appended behind the others.  Cut-offs
+        K > 0 count like ``ks`` towards the heads and their bounds; 0 needs completed lists and disables the head-only shortcut."""
         import torch
         from evaluate_retrieval import resolve_kernels
         from recall_precision import _raise_on_bad_rows, ranked_problem, ranked_tile_rows
         given = dict(kernels or {})
         native_metrics = 'hierarchical_precision' not in given
-        kernels = resolve_kernels(given, ('complete_rankings', 'hierarchical_precision', 'device'))
+        nd = _ndcg_request(ndcg)
+        kernels = resolve_kernels(given, ('complete_rankings', 'hierarchical_precision', 'device') + (('ndcg',) if nd else ()))
         ks = [ks] if isinstance(ks, int) else list(ks)
         ahp_clip = None if isinstance(compute_ahp, bool) else int(compute_ahp)
         ahp_len = -1 if not compute_ahp else (0 if ahp_clip is None else ahp_clip)
-        ncol = 2 * len(ks) + 3
-        columns = _metric_columns(ks, compute_ahp, compute_ap)
+        ncol = 2 * len(ks) + 3 + (2 * len(nd[0]) + 2 if nd else 0)
+        columns = _metric_columns(ks, compute_ahp, compute_ap, nd)
         p = ranked_problem(retrieved, labels, ignore_qids, all_ids)
         nq, ng, C, dev = len(p.q_ids), len(p.g_ids), len(p.class_list), kernels['device']
         if nq == 0:         # nothing to average
             return {m: float('nan') for m in columns}, _empty_per_query(columns, per_query, dev)
         if ng == 0:
             raise ValueError('the gallery is empty')
-        kmax = max(ks + [ahp_clip or 0])
+        kmax = max(ks + [ahp_clip or 0] + (nd[0] if nd else []))
         scored = ng - 1 if (p.qidx is not None and (p.qidx >= 0).any()) else ng      # entries of the shortest scored ranking
         if kmax > scored or min(ks) < 1 or (ahp_clip is not None and ahp_clip < 1):
             raise ValueError('cut-offs {} and AHP clip {} must lie in [1, {}]: a ranking of the {} gallery items{} holds no more'
                              .format(ks, ahp_clip, scored, ng, ', the query\'s own item dropped,' if scored < ng else ''))
         # top-L heads are enough when no metric reads past the head of a ranking and every list has one
         L = min(ng, kmax + 1)
-        head_only = (not compute_ap) and (not compute_ahp or ahp_clip is not None) and int(p.lengths.min()) >= L
+        head_only = (not compute_ap) and (not compute_ahp or ahp_clip is not None) and not (nd and nd[1]) and int(p.lengths.min()) >= L
 
         # ---- class tables and best-possible curves, as hierarchical_precision_device builds them ----
         if (not given) and dev.type == 'cuda':
@@ -580,11 +649,13 @@ class ClassHierarchy(object):
         gcls_d, qcls_d = torch.from_numpy(p.gcls).to(dev), torch.from_numpy(p.qcls).to(dev)
         qidx_d = None if p.qidx is None else torch.from_numpy(p.qidx).to(dev)
         ks_d = torch.tensor(ks, dtype=torch.int32, device=dev)
+        score_ndcg = _ndcg_scorer(nd, kernels, tables[0], tables[1], counts, ng, dev)
 
         def score(ranks, r0, want_ap):       # metric rows of queries r0 .. r0 + len(ranks)
             r1 = r0 + ranks.shape[0]
-            return kernels['hierarchical_precision'](ranks, gcls_d, qcls_d[r0:r1].contiguous(), None if qidx_d is None else qidx_d[r0:r1].contiguous(),
-                                                     *tables, ks_d, ahp_len=ahp_len, want_ap=want_ap, **extra)
+            qc, qi = qcls_d[r0:r1].contiguous(), None if qidx_d is None else qidx_d[r0:r1].contiguous()
+            rows = kernels['hierarchical_precision'](ranks, gcls_d, qc, qi, *tables, ks_d, ahp_len=ahp_len, want_ap=want_ap, **extra)
+            return rows if score_ndcg is None else torch.cat([rows, score_ndcg(ranks, gcls_d, qc, qi)], dim=1)   # the same tile, directly after
 
         outs = []
         for r0 in range(0, nq, tile_rows):      # each tile is consumed before the next one is made
@@ -600,9 +671,11 @@ class ClassHierarchy(object):
         return _metric_rows_to_results(res_d, columns, nq, p.q_ids, 0, nq, 1, None, True, per_query)
 
 
-def _metric_columns(ks, compute_ahp, compute_ap):
+def _metric_columns(ks, compute_ahp, compute_ap, ndcg=None):
     """Metric name -> column of se_hierarchical_precision's ``[Q, 2 len(ks) + 3]`` output, in the order of the result dictionaries:
-    ``P@k (WUP)`` and ``P@k (LCS_HEIGHT)`` per cut-off, ``AHP[@K] (WUP)`` / ``(LCS_HEIGHT)`` (``compute_ahp``: True or K), ``AP``."""
+    ``P@k (WUP)`` and ``P@k (LCS_HEIGHT)`` per cut-off, ``AHP[@K] (WUP)`` / ``(LCS_HEIGHT)`` (``compute_ahp``: True or K), ``AP``.
+    ``ndcg`` (``_ndcg_request``'s pair, or None): se_ndcg's ``[Q, 2 len(cuts) + 2]`` columns stand behind those -- ``NDCG@K (WUP)``
+    and ``NDCG@K (LCS_HEIGHT)`` per cut-off, then ``NDCG (WUP)`` / ``NDCG (LCS_HEIGHT)`` when the whole list was asked for."""
     nk = len(ks)
     col = {}
     for t, k in enumerate(ks):
@@ -614,7 +687,51 @@ def _metric_columns(ks, compute_ahp, compute_ap):
         col['AHP{} (LCS_HEIGHT)'.format(sfx)] = 2 * nk + 1
     if compute_ap:
         col['AP'] = 2 * nk + 2
+    if ndcg:
+        cuts, whole = ndcg
+        for t, k in enumerate(cuts):
+            col['NDCG@{} (WUP)'.format(k)] = 2 * nk + 3 + t
+            col['NDCG@{} (LCS_HEIGHT)'.format(k)] = 2 * nk + 3 + len(cuts) + t
+        if whole:
+            col['NDCG (WUP)'] = 2 * nk + 3 + 2 * len(cuts)
+            col['NDCG (LCS_HEIGHT)'] = 2 * nk + 3 + 2 * len(cuts) + 1
     return col
+
+
+def _ndcg_request(ndcg):
+    """The ``ndcg`` argument of the evaluations -- None, an int or a list of cut-offs, 0 = the whole list -- as ``(cut-offs > 0 in
+    the order given, each once; whether the whole list is asked for)``, or None when nothing is."""
+    if ndcg is None or ndcg is False:
+        return None
+    asked = [ndcg] if isinstance(ndcg, (int, np.integer)) else list(ndcg)
+    if not asked:
+        return None
+    if any(int(k) != k or k < 0 for k in asked):
+        raise ValueError('NDCG cut-offs must be integers >= 0 (0: the whole list), got {}'.format(asked))
+    cuts = []
+    for k in asked:
+        if k > 0 and int(k) not in cuts:
+            cuts.append(int(k))
+    return cuts, any(k == 0 for k in asked)
+
+
+def _ndcg_scorer(nd, kernels, wup_d, lcs_d, counts, ng, dev):
+    """``score(ranks, gcls, qcls, qidx) -> [rows, 2 len(cuts) + 2]`` float64 rows of ``kernels['ndcg']`` (``sehip.ndcg``) for one
+    gallery, or None when no NDCG is asked for (``nd``: ``_ndcg_request``).  Built once per evaluation: the discounts
+    ``1 / log2(p + 1)`` of every gallery position and the ideal DCG of every query class from the gallery's class counts
+    (``sehip.ndcg_ideal``: member and non-member queries, both tables, every cut-off and the whole list)."""
+    if not nd:
+        return None
+    import torch
+    import sehip
+    cuts, whole = nd
+    disc = sehip.ndcg_discounts(ng, dev)
+    ideal = torch.stack([sehip.ndcg_ideal(t, counts, disc, cuts, full=whole) for t in (wup_d, lcs_d)], dim=2).contiguous()
+    cuts_d = torch.tensor(cuts, dtype=torch.int32, device=dev)
+
+    def score(ranks, gcls_d, qcls_d, qidx_d):
+        return kernels['ndcg'](ranks, gcls_d, qcls_d, qidx_d, wup_d, lcs_d, disc, ideal, cuts_d, want_full=whole)
+    return score
 
 
 def _ranked_gallery_tile_rows(dev, nq, ng, C, feature_bytes, ncol, tile_rows, native_metrics, native_ranking):

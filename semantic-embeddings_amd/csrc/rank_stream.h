@@ -1,7 +1,8 @@
-// rank_stream.h -- what the kernels that stream rankings share (hprec.hip, recprec.hip): persistent workgroups that walk the rows
-// `se_rank_rows` wrote, N consecutive ranks per thread and load, and turn every rank into the class of that gallery item.
+// rank_stream.h -- what the kernels that stream rankings share (hprec.hip, ndcg.hip, recprec.hip): persistent workgroups that walk
+// the rows `se_rank_rows` wrote, N consecutive ranks per thread and load, and turn every rank into the class of that gallery item.
 // One copy of: the class table in LDS and its look-up, the vector load of a thread's ranks with its alignment rule, the host rule
-// that picks the table, and the launch of a persistent grid.
+// that picks the table, and the launch of a persistent grid; for the metric kernels also the sorted cut-off list and the search
+// for the query's own entry (ndcg.hip calls them; hprec_kernel keeps the forms it was measured with).
 #pragma once
 #include "se_common.h"
 
@@ -77,6 +78,64 @@ __device__ __forceinline__ void load_ranks(int (&dst)[N], const RT *__restrict__
 #pragma unroll
         for (int e = 0; e < N; e++) dst[e] = (at + e < bound) ? (int)row[at + e] : 0;
     }
+}
+
+// The cut-offs of a metric kernel, once per workgroup: s_ks[0 .. nk) = ks ascending (ties keep the caller's order), s_perm = the
+// slot of each in the caller's order.  Returns whether ks is 1, 2, ..., nk in that order (the CLI's case: effective rank j then IS
+// slot j and nothing is looked up).  nk <= MAX_KS; s_flag: one int of LDS.  Holds barriers: every thread of the workgroup calls it.
+template <int THREADS, int MAX_KS>
+__device__ __forceinline__ bool sort_cutoffs(const int32_t *__restrict__ ks, int nk, int *s_ks, int *s_perm, int *s_flag, const int tid)
+{
+    constexpr int PER = (MAX_KS + THREADS - 1) / THREADS;
+    for (int s = tid; s < nk; s += THREADS) s_perm[s] = ks[s];      // raw copy, ranked by counting below
+    if (tid == 0) *s_flag = 1;
+    wg_barrier();
+    int mine[PER], at[PER];
+#pragma unroll
+    for (int v = 0; v < PER; v++) {
+        const int s = tid + v * THREADS;
+        mine[v] = s < nk ? s_perm[s] : 0;
+        at[v] = 0;
+        if (s < nk)
+            for (int u = 0; u < nk; u++) { const int o = s_perm[u]; at[v] += (o < mine[v] || (o == mine[v] && u < s)) ? 1 : 0; }
+    }
+    wg_barrier();
+#pragma unroll
+    for (int v = 0; v < PER; v++) {
+        const int s = tid + v * THREADS;
+        if (s < nk) {
+            s_ks[at[v]] = mine[v]; s_perm[at[v]] = s;
+            if (mine[v] != s + 1) *s_flag = 0;
+        }
+    }
+    wg_barrier();
+    return *s_flag != 0;
+}
+
+// Position of the first entry of row[0 .. len) equal to `self`, or len: what a kernel that drops the query from its own ranking
+// needs before it walks the row.  The common answers cost no pass -- self < 0 (not a gallery item) and self first in its own row;
+// otherwise block by block with a uniform early exit.  s_pos: one int of LDS.  Holds barriers: every thread of the workgroup calls it.
+template <int THREADS, class RT>
+__device__ __forceinline__ int find_own_entry(const RT *__restrict__ row, int len, int32_t self, int *s_pos, const int tid)
+{
+    const int32_t first = (self >= 0 && len > 0) ? (int32_t)row[0] : -1;
+    if (tid == 0) *s_pos = (self >= 0 && first == self) ? 0 : 0x7FFFFFFF;
+    wg_barrier();
+    if (self >= 0 && first != self) {
+        for (int b0 = 0; b0 < len; b0 += 4 * THREADS) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int i = b0 + e * THREADS + tid;
+                if (i < len && (int32_t)row[i] == self) atomicMin(s_pos, i);
+            }
+            wg_barrier();
+            const int found = *s_pos;       // into a register before the second barrier: no wave may start the next block's atomicMin
+            wg_barrier();                   // while another has yet to read the flag (they would leave the loop at different blocks)
+            if (found != 0x7FFFFFFF) break;
+        }
+    }
+    const int pos = *s_pos;
+    return pos == 0x7FFFFFFF ? len : pos;
 }
 
 // ---- host ----

@@ -22,7 +22,7 @@ from collections import OrderedDict
 import numpy as np
 
 import bootstrap
-from evaluate_retrieval import METRICS, load_labels, plot_performance, print_performance, write_performance
+from evaluate_retrieval import METRICS, add_ndcg_flag, load_labels, ndcg_metric_names, plot_performance, print_performance, write_performance
 
 
 def build_parser():
@@ -53,6 +53,7 @@ def build_parser():
     g.add_argument('--recprec_csv', type=str, default=None,
                    help='Also compute the recall-precision curve and the mAP; write "ranking,level,mean_precision" rows to this file.')
     g.add_argument('--bins', type=int, default=None, help='Number of recall bins of the recall-precision curve.')
+    add_ndcg_flag(g)
     bootstrap.add_bootstrap_flags(p.add_argument_group('Bootstrap over queries'))
     return p
 
@@ -137,9 +138,10 @@ def main(argv=None):
         if args.gallery_split == 'train':
             retrieved = tag_train_ids(retrieved)
         common = dict(ignore_qids=not args.keep_queries, all_ids=None if args.no_all_ids else all_ids)
+        ndcg_kw = {'ndcg': args.ndcg} if getattr(args, 'ndcg', None) else {}
         perf[name], rows = hierarchy.hierarchical_precision_ranked(retrieved, labels, ks, compute_ahp=args.clip_ahp if args.clip_ahp else True,
                                                                    compute_ap=not args.skip_ap,
-                                                                   per_query='table' if bootstrap.wanted(args) else False, **common)
+                                                                   per_query='table' if bootstrap.wanted(args) else False, **common, **ndcg_kw)
         if rows is not None:
             tables[name] = rows
         if args.recprec_csv:
@@ -154,6 +156,7 @@ def main(argv=None):
     if args.clip_ahp:
         metrics[4] = 'AHP@{} (WUP)'.format(args.clip_ahp)
         metrics[9] = 'AHP@{} (LCS_HEIGHT)'.format(args.clip_ahp)
+    metrics += ndcg_metric_names(getattr(args, 'ndcg', None))
     print_performance(perf, metrics)
     if tables:
         bootstrap.report(args, tables, metrics)

@@ -30,6 +30,10 @@ reference: evaluate_retrieval.py:22-73 (pairwise_retrieval), :76-151 (reporting 
 * ``--bootstrap R`` (extension; ``bootstrap.py``): below the table of means, ``mean [lo, hi]`` percentile intervals of the printed
   columns from R resamples of the queries (``se_bootstrap_means``; ``--bootstrap_seed``, ``--confidence``), with ``--compare_to LABEL``
   the paired difference ``delta [lo, hi] p=...`` of every other entry to that one, and ``--bootstrap_csv FILE``.  One process only.
+* ``--ndcg K [K ...]`` (extension; ``se_ndcg``): ``NDCG@K (WUP)`` / ``NDCG@K (LCS_HEIGHT)`` columns behind the others -- discounted
+  cumulative gain with the class similarities as gains and ``1 / log2(position + 1)`` as weights over that of the ideal ranking of
+  the gallery -- and, for ``K = 0``, the whole-list ``NDCG (...)`` columns (whole rankings: with ``--gallery_feat`` pass
+  ``--rank_gallery``).  Read from the same rank tiles; part of the ``--bootstrap`` output; ``--csv`` and the plots are unchanged.
 """
 import argparse
 import os.path
@@ -511,8 +515,30 @@ def build_parser():
     g.add_argument('--rank_gallery', action='store_true', default=argparse.SUPPRESS,
                    help='With --gallery_feat: rank every query against the WHOLE gallery and read every metric off that ranking; '
                         'gives the un-clipped AHP columns, so --clip_ahp is not required (with it, AHP@K comes from the same ranking).')
+    add_ndcg_flag(g)
     bootstrap.add_bootstrap_flags(g)
     return p
+
+
+def _ndcg_cutoff(v):
+    k = int(v)
+    if k < 0:
+        raise argparse.ArgumentTypeError('NDCG cut-offs are integers >= 0 (0: the whole list), got %r' % v)
+    return k
+
+
+def add_ndcg_flag(group):
+    """--ndcg of evaluate_retrieval.py and evaluate_rankings.py (absent from the namespace unless given, like --rank_gallery)."""
+    group.add_argument('--ndcg', type=_ndcg_cutoff, nargs='+', default=argparse.SUPPRESS, metavar='K',
+                       help='Also report NDCG@K (WUP / LCS_HEIGHT): discounted cumulative gain with the class similarities as gains and '
+                            '1 / log2(position + 1) as weights, over the ideal ranking of the gallery; K = 0: the whole list '
+                            '(needs whole rankings: with --gallery_feat pass --rank_gallery).')
+
+
+def ndcg_metric_names(cuts):
+    """The columns --ndcg adds, in the order they are printed behind the others."""
+    from class_hierarchy import _metric_columns, _ndcg_request
+    return list(_metric_columns([], False, False, _ndcg_request(cuts))) if cuts else []
 
 
 def add_gallery_flags(group):
@@ -556,6 +582,8 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if getattr(args, 'rank_gallery', False) and not args.gallery_feat:
         parser.error('--rank_gallery needs --gallery_feat (without a gallery every ranking is a full one already)')
+    if 0 in getattr(args, 'ndcg', ()) and args.gallery_feat and not getattr(args, 'rank_gallery', False):
+        parser.error('--ndcg 0 (the whole list) needs whole rankings of the gallery: pass --rank_gallery with --gallery_feat, or cut-offs K > 0 only')
     check_float64_flag(parser, args)
     bootstrap.check_bootstrap_flags(parser, args, [feat_entry(args, i)[0] for i in range(len(args.feat))])
     return args
@@ -643,6 +671,8 @@ def main(argv=None):
             gallery_kw['rank_gallery'] = True
         if float64_precision(args, features):       # (the keyword is only passed when the flag asks for it)
             gallery_kw['precision'] = 'float64'
+        if getattr(args, 'ndcg', None):
+            gallery_kw['ndcg'] = args.ndcg
         perf[feat_name], rows = hierarchy.hierarchical_precision_device(
             features, labels_test, ks, compute_ahp=args.clip_ahp if args.clip_ahp else True, compute_ap=not args.skip_ap,
             normalize=normalize, ids=None if ind2id is None else ind2id.tolist(), distributed=world > 1,
@@ -659,6 +689,7 @@ def main(argv=None):
     if args.clip_ahp:
         metrics[4] = 'AHP@{} (WUP)'.format(args.clip_ahp)
         metrics[9] = 'AHP@{} (LCS_HEIGHT)'.format(args.clip_ahp)
+    metrics += ndcg_metric_names(getattr(args, 'ndcg', None))
     print_performance(perf, metrics)
     if tables:
         bootstrap.report(args, tables, metrics)

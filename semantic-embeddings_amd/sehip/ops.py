@@ -21,7 +21,7 @@ __all__ = [
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
     "phase_timing", "phase_timing_read", "rank_rows_workspace_bytes", "RANK_U16_MAX_N", "rank_rows", "rank_rows_check", "pairwise_dist_f64",
     "rank_refine_f64_", "rank_rows_f64", "topk_rows",
-    "topk_merge", "retrieve_topk", "knn_vote", "KNN_TOP_MAX", "bootstrap_means", "bootstrap_indices", "BOOTSTRAP_COLS_MAX", "complete_rankings", "COMPLETE_LDS_ITEMS", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "relevant_positions",
+    "topk_merge", "retrieve_topk", "knn_vote", "KNN_TOP_MAX", "bootstrap_means", "bootstrap_indices", "BOOTSTRAP_COLS_MAX", "complete_rankings", "COMPLETE_LDS_ITEMS", "HprecCurves", "hprec_reciprocal_curves", "hierarchical_precision", "ndcg_discounts", "ndcg_ideal", "ndcg", "NDCG_CHUNK", "relevant_positions",
     "recall_precision_reduce", "count_preceding", "count_to_positions", "svm_margin", "svm_loss_blocks", "svm_reduce_workspace_bytes", "svm_reduce", "svm_gram", "svm_rowsum",
     "svm_axpby", "class_pair_tables", "cholesky_lower_", "eigh", "eigh_schedule", "EIGH_NOT_CONVERGED", "EIGH_NONFINITE", "image_batch", "resample_tables", "tiny_batch", "TINY_BATCH_MAX_BLOCKS", "FILL_MODES",
     "METRIC_COSINE", "METRIC_EUCLID", "METRIC_DOT",
@@ -1373,6 +1373,90 @@ def hierarchical_precision(rank, cls, qcls, qidx, wup, lcs, best_wup, best_lcs, 
     call("se_hierarchical_precision_r16" if rank.dtype == torch.int16 else "se_hierarchical_precision",
          rank, rank.stride(0), Q, L, cls, cls.numel(), qcls, qidx, wup, lcs, C, curves.data, curves.list_len, ks, nk,
          int(ahp_len), int(bool(want_ap)), out, out.stride(0), order_ws)
+    return out
+
+
+NDCG_CHUNK = DEFINES["SE_NDCG_CHUNK"]     # ranks a workgroup of se_ndcg takes per step
+
+
+def ndcg_discounts(n, device=None):
+    """The position weights of NDCG, ``1 / log2(p + 1)`` for p = 1 .. n, as a float64 tensor on ``device``: built by NumPy on the
+    host and uploaded, so that every caller (and every test) divides by the same bits -- ``se_ndcg`` computes no logarithm."""
+    disc = torch.from_numpy(1 / np.log2(np.arange(2, int(n) + 2)))
+    return disc if device is None else disc.to(device)
+
+
+def ndcg_ideal(gain, counts, disc, ks, full=True):
+    """The ideal DCG of every query class for one gain table: float64 ``[C, 2, nk + 1]`` on ``disc``'s device, indexed
+    ``[class][member][slot]``; slot t < nk is the cut-off ``ks[t]``, slot nk the whole list (0 unless ``full``).
+
+    The ideal list of class c is row c of ``gain`` ([C, C], row = query class) sorted descending, each value repeated by the
+    gallery's count of its class (``counts`` [C]); member 1 -- the query is a gallery item and is dropped from its own ranking --
+    holds one item of class c fewer (where there is one).  No [C, G] list is made: with D = the float64 prefix sums of ``disc``,
+    a run of equal values ``v`` over positions (start, end] contributes ``v * (D[end] - D[start])``, clipped at the cut-off, so a
+    class costs its C runs plus one binary search per cut-off.  A cut-off beyond the list takes the list's end.  ``disc`` must
+    reach the longest ideal list that is asked for: ``max(ks)``, or the gallery when ``full``."""
+    g = gain.detach().cpu().numpy() if torch.is_tensor(gain) else np.asarray(gain)
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    cnt = (counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)).astype(np.int64)
+    C, ks = g.shape[0], [int(k) for k in ks]
+    if g.shape != (C, C) or cnt.shape != (C,) or (cnt < 0).any():
+        raise SehipError("gain must be [C, C] and counts [C] non-negative")
+    if any(k < 1 for k in ks):
+        raise SehipError("cut-offs must be >= 1")
+    total = int(cnt.sum())
+    reach = min(total, max([total if full else 0] + ks))
+    if disc.dtype != torch.float64 or disc.dim() != 1 or disc.numel() < reach:
+        raise SehipError("disc must be a float64 vector of >= %d positions" % reach)
+    D = np.concatenate(([0.0], np.cumsum(disc[:reach].detach().cpu().numpy())))
+    cut = np.asarray(ks + [total if full else 0], dtype=np.int64)
+    out = np.zeros((C, 2, len(ks) + 1))
+    order = np.argsort(-g, axis=1, kind='stable')
+    for c in range(C):
+        vals = g[c, order[c]]
+        for member in (0, 1):
+            reps = cnt[order[c]].copy()
+            if member and cnt[c] > 0:
+                reps[order[c] == c] -= 1
+            ends = np.cumsum(reps)
+            starts = ends - reps
+            runs = np.concatenate(([0.0], np.cumsum(vals * (D[np.minimum(ends, reach)] - D[np.minimum(starts, reach)]))))   # whole runs in front of run r
+            k = np.minimum(cut, ends[-1])                       # a cut-off beyond the list scores its end
+            at = np.minimum(np.searchsorted(ends, k, side='left'), C - 1)       # the run that position k lies in
+            out[c, member] = runs[at] + vals[at] * (D[k] - D[np.minimum(starts[at], k)])
+    if not full:
+        out[:, :, -1] = 0.0
+    return torch.from_numpy(out).to(disc.device)
+
+
+def ndcg(rank, cls, qcls, qidx, gain_a, gain_b, disc, ideal, ks, want_full=False, list_len=None):
+    """Per-query NDCG with two class-gain tables from device rankings (``se_ndcg``; host statement: ``ClassHierarchy.ndcg``).
+
+    rank [Q, >=L] int32, cls [N] int32, qcls [Q] int32, qidx [Q] int32 | None (gallery index of the query itself, dropped from its
+    ranking; -1: not a gallery item), gain_a / gain_b [C, C] f64 (row = query class), disc [>= L] f64 (``ndcg_discounts``), ideal
+    [C, 2, 2, nk + 1] f64 (``torch.stack`` of the two tables' ``ndcg_ideal`` along dim 2), ks [nk] int32 cut-offs.  Without
+    ``want_full`` only the first ``max(ks) + 1`` ranks of a row are read.
+    Returns f64 [Q, 2 nk + 2]: NDCG@k (a), NDCG@k (b), NDCG (a), NDCG (b); the last two are 0 unless ``want_full``."""
+    require_gpu(rank, cls, qcls, qidx, gain_a, gain_b, disc, ideal, ks)
+    if rank.dtype != torch.int32 or rank.dim() != 2 or rank.stride(1) != 1:
+        raise SehipError("rank must be a 2-d int32 tensor with contiguous rows")
+    for t, name in ((cls, "cls"), (qcls, "qcls"), (ks, "ks")) + (((qidx, "qidx"),) if qidx is not None else ()):
+        _i32(t, name)
+    _check_curves(gain_a, gain_b)
+    Q = rank.shape[0]
+    L = rank.shape[1] if list_len is None else int(list_len)
+    C, nk = gain_a.shape[0], ks.numel()
+    if gain_a.shape != (C, C) or gain_b.shape != (C, C) or not (gain_a.is_contiguous() and gain_b.is_contiguous()):
+        raise SehipError("gain_a and gain_b must be contiguous [C, C] float64 tables")
+    if disc.dtype != torch.float64 or disc.dim() != 1 or not disc.is_contiguous():
+        raise SehipError("disc must be a contiguous float64 vector")
+    if ideal.dtype != torch.float64 or tuple(ideal.shape) != (C, 2, 2, nk + 1) or not ideal.is_contiguous():
+        raise SehipError("ideal must be a contiguous float64 [C, 2, 2, nk + 1] tensor, C = %d, nk = %d" % (C, nk))
+    if L > rank.shape[1] or qcls.numel() != Q or (qidx is not None and qidx.numel() != Q):
+        raise SehipError("list_len exceeds the rankings, or qcls / qidx do not have one entry per row")
+    out = torch.zeros((Q, 2 * nk + 2), dtype=torch.float64, device=rank.device)
+    call("se_ndcg", rank, rank.stride(0) if Q > 1 else max(rank.stride(0), L), Q, L, cls, cls.numel(), qcls, qidx, gain_a, gain_b, C,
+         disc, disc.numel(), ideal, ks, nk, int(bool(want_full)), out, out.stride(0))
     return out
 
 

@@ -108,7 +108,7 @@ def windows(fns, reps, batch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn", "ranked", "bootstrap"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn", "ranked", "bootstrap", "ndcg"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -128,6 +128,8 @@ def main():
         return bench_classemb(args.reps)
     if args.what == "center":
         return bench_center()
+    if args.what == "ndcg":
+        return bench_ndcg()
     if args.what == "xent":
         return bench_xent()
     if args.what == "image":
@@ -1218,6 +1220,50 @@ def bench_knn(reps=30, batch=10):
         print("knn_classification %d x %d x %d, k=%d, C=%d, features on the device: median %.2f ms (min %.2f, max %.2f) per call, rankings on the host"
               % (q, n, d, k, C, float(np.median(ts)), min(ts), max(ts)), flush=True)
         del train, test, lists, lists64, ones
+
+
+def bench_ndcg(rounds=12, batch=3):
+    """se_ndcg next to se_hierarchical_precision on the SAME int32 rankings (all pairs of seeded Gaussian features, cosine, 100 classes):
+    ks = 1..250 with the whole list (want_full = 1) against ks = 1..250 with whole-list AHP and AP in class order (ahp_len = 0,
+    want_ap = 1), the two timed alternately in one process: `rounds` windows of `batch` back-to-back calls each (HIP events around a
+    window) after 3 warm-up calls, median / 10th / 90th percentile of the per-call time.  Shapes: 50,000 x 50,000, 10,000 x 10,000, and
+    the head-only form -- 50,000 lists of 251 entries, want_full = 0 against AHP@250 without AP.  (profiles/ndcg_bench.txt)"""
+    C, d = 100, 100
+    ks = torch.arange(1, 251, dtype=torch.int32, device="cuda")
+    for n, head in ((10000, False), (50000, False), (50000, True)):
+        rng = np.random.default_rng(1)
+        x = torch.from_numpy(rng.standard_normal((n, d)).astype(np.float32)).cuda()
+        sehip.normalize_rows_(x)
+        cls = torch.from_numpy(rng.integers(0, C, size=n).astype(np.int32)).cuda()
+        tab = rng.random((C, C)); tab = (tab + tab.T) / 2; np.fill_diagonal(tab, 1.0)
+        counts = np.bincount(cls.cpu().numpy(), minlength=C)
+        order = [np.argsort(-tab[c], kind="stable") for c in range(C)]
+        best = np.stack([np.cumsum(np.repeat(tab[c][order[c]], counts[order[c]])) for c in range(C)])
+        tab_d, best_d = torch.from_numpy(tab).cuda(), torch.from_numpy(best).cuda()
+        rk = sehip.rank_rows(sehip.pairwise_dist(x, x, metric=sehip.METRIC_COSINE))
+        qidx = torch.arange(n, dtype=torch.int32, device="cuda")
+        disc = sehip.ndcg_discounts(n, "cuda")
+        one = sehip.ndcg_ideal(tab_d, counts, disc, ks.tolist(), full=not head)
+        ideal = torch.stack([one, one], dim=2).contiguous()
+        if head:
+            rk = rk[:, :251].contiguous()
+            best_d = best_d[:, :252].contiguous()
+        L = rk.shape[1]
+        curves = sehip.hprec_reciprocal_curves(best_d, best_d)
+
+        def ndcg():
+            return sehip.ndcg(rk, cls, cls, qidx, tab_d, tab_d, disc, ideal, ks, want_full=not head, list_len=L)
+
+        def hprec():
+            return sehip.hierarchical_precision(rk, cls, cls, qidx, tab_d, tab_d, best_d, best_d, ks, ahp_len=250 if head else 0,
+                                                want_ap=not head, curves=curves, list_len=L)
+        got = ndcg()
+        assert bool(torch.isfinite(got).all()) and float(got.min()) >= 0.0 and float(got.max()) <= 1.0 + 1e-9, "NDCG outside [0, 1]"
+        nt, ht = windows((ndcg, hprec), rounds, batch)
+        print("ndcg %-9s q=%d list_len=%d C=%d nk=250: se_ndcg %.1f us (%.1f-%.1f), se_hierarchical_precision %.1f us (%.1f-%.1f): x%.2f; "
+              "%.1f GB/s of ranks" % ("head only" if head else "whole", n, L, C, nt[0], nt[1], nt[2], ht[0], ht[1], ht[2], ht[0] / nt[0],
+                                      4.0 * n * L / (nt[0] * 1e-6) / 1e9), flush=True)
+        del x, rk, best_d, curves
 
 
 def bench_bootstrap(rounds=10, reps=10000, m=11, chunk_bytes=512 << 20):

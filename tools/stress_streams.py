@@ -44,6 +44,9 @@ pd64[:, 100:1300] = 1.0 + pd64[:, 100:1300] * 2.0 ** -30; img64 = pd64.float()  
 ks = torch.arange(1, 251, dtype=torch.int32, device="cuda")
 qidx = torch.arange(1024, dtype=torch.int32, device="cuda")
 curves = sehip.hprec_reciprocal_curves(best_d, best_d)
+nd_disc = sehip.ndcg_discounts(20000, "cuda")
+nd_one = sehip.ndcg_ideal(tab_d, counts, nd_disc, ks.tolist(), full=True)
+nd_ideal = torch.stack([nd_one, nd_one], dim=2).contiguous()
 cr_len = dev(rng.integers(0, 251, size=1024).astype(np.int32))       # se_complete_rankings: ragged top-250 lists, a shuffled all_ids order
 cr_order = dev(rng.permutation(20000).astype(np.int32))
 emb = dev(f32(C, 100)); sehip.normalize_rows_(emb)
@@ -111,6 +114,7 @@ OPS = {
     "retrieve_topk slab (3,001 rows)": lambda: sehip.retrieve_topk(g3[:512], g3, 64),
     "hierarchical_precision": lambda: sehip.hierarchical_precision(rk_mid, cls, cls[:1024].contiguous(), qidx, tab_d, tab_d, best_d, best_d, ks,
                                                                      ahp_len=0, want_ap=True, curves=curves),
+    "ndcg": lambda: sehip.ndcg(rk_mid, cls, cls[:1024].contiguous(), qidx, tab_d, tab_d, nd_disc, nd_ideal, ks, want_full=True),
     "knn_vote (LDS vote tables)": lambda: sehip.knn_vote(rk_mid[:, :201], cls, C, [1, 5, 20, 200], top=5, qidx=qidx),
     "complete_rankings (LDS bitmap, ragged)": lambda: sehip.complete_rankings(rk_mid[:, :250], 20000, lengths=cr_len, order=cr_order),
     "complete_rankings (whole lists)": lambda: sehip.complete_rankings(rk_mid, 20000),
