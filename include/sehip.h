@@ -376,6 +376,58 @@ int se_softmax_xent_bwd(const void *logits, int z_dtype, int64_t ldz, const int6
                         int dz_dtype, int64_t lddz, se_stream_t stream);
 
 /*
+ * Hierarchy-aware classifier losses on LOGITS: hierarchical cross-entropy (HXE) and cross-entropy against soft labels; forward and
+ * backward, with the metrics of se_softmax_xent_fwd.  The reference has neither loss; they are the hierarchy-aware classification
+ * baselines of later work.  The weights follow OUR rule (ClassHierarchy.hxe_encoding); no bit parity with any published code is claimed.
+ *   logits [B, C] f32 / bf16 (ldz), labels [B] int64 (clamped to [0, C - 1]).  No probability clip in either loss.
+ *
+ * HXE.  The tree encoding (built on the host, ClassHierarchy.hxe_encoding): pos [C] int32, the position of every class in a
+ *   depth-first order of the class tree, so that the classes below any node are one range of positions; path_off [C + 1] int32;
+ *   lvl_lo, lvl_hi [nnz] int32 and lvl_w [nnz] float32.  Entries path_off[y] .. path_off[y + 1] are the h_y levels of label y, walking
+ *   up: entry l holds the position range [lo, hi) of the l + 1-th ancestor a_{l+1} (a_0 = y; the last range is [0, C)) and the weight
+ *   lambda_l of the edge a_l -> a_{l+1}.  Ranges grow strictly along a path (the host drops levels that add no class) and
+ *   h_y <= SE_HXE_MAX_LEVELS.  path_off_host is the SAME array in HOST memory: the entry points check it before any launch (starts at
+ *   0, every h_y in [0, SE_HXE_MAX_LEVELS]; anything else is SE_ERR_INVALID) and take nnz from it; the kernels read the device copy.
+ *   Per row z with label y:  M = max z,  e_c = exp(z_c - M),  L_0 = z_y - M (exact: no exp / log round trip),
+ *       S_{l+1} = sum of e_c over lo_l <= pos[c] < hi_l        L_{l+1} = max(log S_{l+1}, L_0)
+ *       loss_i  = sum_{l = 0}^{h - 1} lambda_l * (L_{l+1} - L_l)        (a term whose two logs are equal, -inf included, is 0)
+ *   Mathematically S_{l+1} >= e_y, so the floor at L_0 only acts when a whole range underflows in float32; the loss then stays finite,
+ *   and where the floor acts the term is a BOUND of the exact value, not the exact value.
+ *   With lev(c) the smallest k such that c lies in R_k (R_0 = {y}, R_k = range k - 1), r_k = 1 / S_k (0 where S_k == 0), lambda_h = 0:
+ *       H_k  = sum_{j = max(k, 1)}^{h} (lambda_{j-1} - lambda_j) * r_j     (= sum_{l >= k-1} lambda_l / S_{l+1} - sum_{l >= max(k,1)} lambda_l / S_l)
+ *       dz_c = w_i * e_c * H_lev(c)   (c != y)          dz_y = w_i * (e_y * H_0 - lambda_0)
+ *   The label's own l = 0 term is the constant -lambda_0, never e_y / S_0.  With every lambda = 1 this is p - onehot; the exact sum of
+ *   a row's gradients is 0.  aux: se_hxe_aux_floats(B) = (2 + SE_HXE_MAX_LEVELS) B floats, row i at aux + (2 + SE_HXE_MAX_LEVELS) i:
+ *   M_i, then H_0 .. H_h (the rest unused), so that bwd is ONE pass over [B, C].
+ *
+ * Soft labels.  table [C, C] float32 (ldt): row y is the target distribution Q[y, :] (ClassHierarchy.soft_label_table).
+ *       loss_i = sum_c Q[y,c] * ((M - z_c) + log S),  evaluated as  sum_c Q[y,c] (M - z_c)  +  (sum_c Q[y,c]) * log S,   S = sum_c e_c
+ *       dz_k   = w_i * ((sum_c Q[y,c]) * p_k - Q[y,k])        p_k = exp(-((M - z_k) + log S))
+ *   A class with Q[y,c] == 0 contributes nothing, whatever its logit.  aux: 3 B floats (M [B], log S [B], sum_c Q[y,c] [B]).
+ *
+ * All four: best, above, loss_mean and the rules for rows with a NaN or +inf or nothing but -inf are those of se_softmax_xent_fwd
+ *   (the same row code); best, above and loss_mean may be NULL.  w_i = grad_loss_i[i] (NULL: grad_scale for every row).  Every C that
+ *   se_softmax_xent_fwd accepts; B = 0 is accepted.  Any row pitch; 16-byte loads / stores when pointers and pitches are 16-byte
+ *   aligned.  A wave per row up to C = 1024, a workgroup per row above; each row is read twice (the second read hits the cache).
+ *   Asynchronous on `stream`, no allocation, no atomics, no host synchronisation: capturable in a HIP graph.  Every reduction runs in
+ *   a fixed order: the same inputs give the same bits, and a row's bits depend neither on B nor on the other rows.
+ */
+#define SE_HXE_MAX_LEVELS 32
+int64_t se_hxe_aux_floats(int64_t B);
+int se_hxe_fwd(const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, const int32_t *pos, const int32_t *path_off,
+               const int32_t *path_off_host, const int32_t *lvl_lo, const int32_t *lvl_hi, const float *lvl_w, int64_t B, int64_t C,
+               float *loss_i, float *aux, int32_t *best, int32_t *above, float *loss_mean, se_stream_t stream);
+int se_hxe_bwd(const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, const int32_t *pos, const int32_t *path_off,
+               const int32_t *path_off_host, const int32_t *lvl_lo, const int32_t *lvl_hi, const float *lvl_w, const float *aux,
+               const float *grad_loss_i, float grad_scale, int64_t B, int64_t C, void *dz, int dz_dtype, int64_t lddz,
+               se_stream_t stream);
+int se_soft_xent_fwd(const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, const float *table, int64_t ldt, int64_t B,
+                     int64_t C, float *loss_i, float *aux, int32_t *best, int32_t *above, float *loss_mean, se_stream_t stream);
+int se_soft_xent_bwd(const void *logits, int z_dtype, int64_t ldz, const int64_t *labels, const float *table, int64_t ldt,
+                     const float *aux, const float *grad_loss_i, float grad_scale, int64_t B, int64_t C, void *dz, int dz_dtype,
+                     int64_t lddz, se_stream_t stream);
+
+/*
  * Adagrad update of a flat float32 parameter buffer in one launch, gradient scale and L2 regulariser folded in.
  * Replaces: Keras 2.2 optimizers.Adagrad.get_updates [third party, not in the reference tree] as learn_devise.py:87,114 uses it
  *           (keras.optimizers.Adagrad(lr=...) in both compile() calls), and the whole-buffer passes that would otherwise scale the

@@ -20,6 +20,18 @@ import numpy as np
 
 _trapz = getattr(np, "trapezoid", None) or np.trapz
 
+HXE_MAX_LEVELS = 32     # levels of one class's path in ClassHierarchy.hxe_encoding (SE_HXE_MAX_LEVELS of include/sehip.h)
+
+
+class _VirtualTop(object):
+    """The node ``hxe_encoding`` puts above the roots of a forest."""
+
+    def __repr__(self):
+        return '<virtual top>'
+
+
+_VIRTUAL_TOP = _VirtualTop()
+
 
 class ClassHierarchy(object):
     """A DAG of classes given as parent->children / child->parents adjacency dictionaries."""
@@ -214,6 +226,142 @@ class ClassHierarchy(object):
         if miss >= 0:
             raise KeyError('classes {!r} and {!r} have no common ancestor'.format(key[miss // len(key)], key[miss % len(key)]))
         return wup, lcs
+
+    # ------------------------------------------------------------------ hierarchy-aware classifier losses
+
+    def _class_tree(self, classes):
+        """The sub-hierarchy spanned by ``classes`` (their ancestor closure) as a tree whose leaves are the classes:
+        ``(top, parent, kids, d, rng)`` -- the top node (``_VIRTUAL_TOP`` above several roots), node -> parent, node -> children in
+        sorted order, node -> number of edges from the top, node -> ``(lo, hi)`` range of leaf positions in depth-first order.
+        ``ValueError`` naming the node: an unknown or repeated class, a node with several parents, a class above another class."""
+        key = list(classes)
+        cls_set = set()
+        for c in key:
+            if c not in self.nodes:
+                raise ValueError('class {!r} is unknown to the hierarchy'.format(c))
+            if c in cls_set:
+                raise ValueError('class {!r} is listed twice'.format(c))
+            cls_set.add(c)
+        parent, kids = {}, {}
+        for c in key:
+            node = c
+            while node not in parent:
+                ps = self.parents.get(node) or []
+                if len(set(ps)) > 1:
+                    raise ValueError('the hierarchy spanned by the classes is not a tree: node {!r} has {} parents'.format(node, len(set(ps))))
+                parent[node] = ps[0] if ps else None
+                if not ps:
+                    break
+                kids.setdefault(ps[0], set()).add(node)
+                node = ps[0]
+                if node in cls_set:
+                    raise ValueError('class {!r} is an ancestor of class {!r}'.format(node, c))
+        for c in key:       # (a class reached from below after its own walk)
+            if c in kids:
+                raise ValueError('class {!r} is an ancestor of another class'.format(c))
+        roots = [n for n, p in parent.items() if p is None]
+        if len(roots) > 1:
+            top = _VIRTUAL_TOP
+            kids[top] = set(roots)
+            for r in roots:
+                parent[r] = top
+            parent[top] = None
+        else:
+            top = roots[0]
+
+        def ordered(nodes):
+            try:
+                return sorted(nodes)
+            except TypeError:
+                return sorted(nodes, key=repr)
+        kids = {n: ordered(k) for n, k in kids.items()}
+        d, rng, nleaf = {top: 0}, {}, 0
+        stack = [(top, 0)]
+        while stack:        # depth-first, children in sorted order; a node's range closes when its last child's has
+            node, i = stack.pop()
+            ch = kids.get(node, ())
+            if i == 0 and not ch:
+                rng[node] = (nleaf, nleaf + 1)
+                nleaf += 1
+            elif i < len(ch):
+                stack.append((node, i + 1))
+                d[ch[i]] = d[node] + 1
+                stack.append((ch[i], 0))
+            else:
+                rng[node] = (rng[ch[0]][0], rng[ch[-1]][1])
+        return top, parent, kids, d, rng
+
+    def hxe_encoding(self, classes, alpha=0.1, weights=None):
+        """What ``se_hxe_fwd`` / ``se_hxe_bwd`` read (``sehip.hierarchical_cross_entropy``): the class tree as position ranges.
+
+        The classes are the leaves of the sub-hierarchy they span.  In a depth-first order of that tree (children visited in sorted
+        order, so the encoding is reproducible) the classes below any node are one range of positions.  Returns a dict of
+        ``pos`` int32 [C] (position of class ``c``: a permutation of 0 .. C - 1), ``path_off`` int32 [C + 1], ``lvl_lo`` / ``lvl_hi``
+        int32 [nnz], ``lvl_w`` float32 [nnz] and ``max_levels`` (the longest path).  Entries ``path_off[y] .. path_off[y + 1]`` are
+        the levels ``l = 0 .. h_y - 1`` of class ``y`` walking up, ``a_0 = y, a_1, ..., a_h = top``: entry ``l`` stands for the edge
+        ``a_l -> a_{l+1}`` and holds the range ``[lo, hi)`` of the PARENT ``a_{l+1}`` and the weight ``lambda_l``; the last range is
+        ``[0, C)``.  An edge whose parent covers the same classes as its child is dropped (its conditional probability is 1, its
+        term 0), so the ranges of a path grow strictly; more than 32 remaining levels raise ``ValueError``.
+
+        OUR weight rule: ``lambda_l = exp(-alpha * d(a_l))`` with ``d(v)`` the number of edges from the top to ``v`` in the hierarchy
+        as given (before edges are dropped): the edge below the top weighs ``exp(-alpha)``, deeper edges less, and nothing is
+        normalised.  Several roots get a virtual top at ``d = 0`` (the roots then have ``d = 1``).  ``weights``, a callable
+        ``node -> float`` evaluated at ``a_l``, replaces the rule -- to restate another convention; published implementations differ
+        (on normalisation among other things) and no bit parity with any of them is claimed.
+
+        ``ValueError`` naming the node: the spanned sub-hierarchy is not a tree (DAG hierarchies are refused, not mis-scored), a
+        class is an ancestor of another class, a class is unknown to the hierarchy."""
+        key = list(classes)
+        top, parent, _, d, rng = self._class_tree(key)
+        pos = np.asarray([rng[c][0] for c in key], dtype=np.int32)
+        path_off = np.zeros(len(key) + 1, dtype=np.int32)
+        lo, hi, w = [], [], []
+        for i, c in enumerate(key):
+            node = c
+            while node != top:
+                up = parent[node]
+                if rng[up] != rng[node]:
+                    lo.append(rng[up][0])
+                    hi.append(rng[up][1])
+                    w.append(float(weights(node)) if weights is not None else float(np.exp(-float(alpha) * d[node])))
+                node = up
+            path_off[i + 1] = len(lo)
+            if path_off[i + 1] - path_off[i] > HXE_MAX_LEVELS:
+                raise ValueError('class {!r} has {} levels above it, more than the {} a path may have'
+                                 .format(c, int(path_off[i + 1] - path_off[i]), HXE_MAX_LEVELS))
+        return {'pos': pos, 'path_off': path_off, 'lvl_lo': np.asarray(lo, dtype=np.int32), 'lvl_hi': np.asarray(hi, dtype=np.int32),
+                'lvl_w': np.asarray(w, dtype=np.float32), 'max_levels': int(np.diff(path_off).max()) if len(key) else 0}
+
+    def soft_label_table(self, classes, beta):
+        """float32 [C, C] targets of ``sehip.soft_label_cross_entropy``: row ``y`` is ``softmax_c(-beta * d(y, c))`` with
+        ``d(y, c) = lcs_height(y, c)`` = height of the lowest common subsumer / height of the hierarchy, 1 minus the LCS_HEIGHT
+        similarity of the retrieval metrics.  Computed in float64 and rounded once.  (Where the classes span a tree the heights
+        are read off the tree's position ranges, C path walks instead of C * C ``lcs`` calls; the values are the same.)"""
+        key = list(classes)
+        C = len(key)
+        h = np.empty((C, C), dtype=np.float64)
+        try:
+            top, parent, _, _, rng = self._class_tree(key)
+        except ValueError:
+            top = None
+        if top is not None and top is not _VIRTUAL_TOP:
+            pos = np.asarray([rng[c][0] for c in key])
+            for i, c in enumerate(key):
+                path, node = [], c
+                while node is not None:
+                    path.append(node)
+                    node = parent[node]
+                row = np.empty(C, dtype=np.float64)
+                for node in reversed(path):     # from the top down: the deepest node above both classes writes last
+                    row[rng[node][0]:rng[node][1]] = self.heights[node]
+                h[i] = row[pos]
+        else:
+            for i, a in enumerate(key):
+                for j in range(i, C):
+                    h[i, j] = h[j, i] = self.heights[self.lcs(a, key[j])]
+        logit = -float(beta) * (h / self.max_height)
+        e = np.exp(logit - logit.max(axis=1, keepdims=True))
+        return (e / e.sum(axis=1, keepdims=True)).astype(np.float32)
 
     # ------------------------------------------------------------------ retrieval metrics
 

@@ -1,7 +1,8 @@
 // softmax_xent.h -- the row code of the softmax cross-entropy (softmax_xent.hip explains the arithmetic): what one wave or one
 // workgroup does with its row of logits, forward on the register paths and backward.  se_softmax_xent_fwd / _bwd (softmax_xent.hip)
 // and the classifier role of se_joint_head_fwd / _bwd (joint_head.hip) both run this text, so the joint head carries the bits of
-// the stand-alone entry points by construction.
+// the stand-alone entry points by construction.  The hierarchy-aware losses of hxe.hip share the per-value scan (xe_scan), the
+// bad-row / arg-max rules, the row writers and the load / store helpers, so their metrics are this file's as well.
 #pragma once
 #include "se_common.h"
 #include <limits.h>
@@ -70,6 +71,22 @@ __device__ __forceinline__ bool xe_bad_row(int nan_at, float M) { return nan_at 
 // np.argmax of a row: its first NaN, else the first maximum (cand; INT_MAX: every value is -inf, class 0)
 __device__ __forceinline__ int xe_best_class(int nan_at, int cand) { return nan_at != INT_MAX ? nan_at : (cand == INT_MAX ? 0 : cand); }
 
+// one value of a row's scan (columns ascend within a thread): first NaN, first maximum, classes strictly above the label's logit
+__device__ __forceinline__ void xe_scan(float x, int c, float zy, float &m, int &am, int &nan_at, int &cnt)
+{
+    if (x != x) nan_at = min(nan_at, c);
+    if (x > m) { m = x; am = c; }
+    cnt += x > zy ? 1 : 0;
+}
+
+// the metrics of a row, shared by every loss on softmax logits (hxe.hip writes them with a loss of its own)
+__device__ __forceinline__ void xe_write_metrics(int64_t row, int C, bool bad, int nan_at, int cand, int cnt, int32_t *__restrict__ best,
+                                                 int32_t *__restrict__ above)
+{
+    if (best) best[row] = xe_best_class(nan_at, cand);
+    if (above) above[row] = bad ? C : cnt;
+}
+
 // what the last step of every forward path writes for its row
 __device__ __forceinline__ void xe_write_row(int64_t row, int64_t B, int C, bool bad, float loss, float m, float logsum, float A, int nan_at, int cand,
                                              int cnt, float *__restrict__ loss_i, float *__restrict__ aux, int32_t *__restrict__ best,
@@ -80,8 +97,7 @@ __device__ __forceinline__ void xe_write_row(int64_t row, int64_t B, int C, bool
     aux[row] = bad ? nan : m;
     aux[B + row] = bad ? nan : logsum;
     aux[2 * B + row] = bad ? nan : A;
-    if (best) best[row] = xe_best_class(nan_at, cand);
-    if (above) above[row] = bad ? C : cnt;
+    xe_write_metrics(row, C, bad, nan_at, cand, cnt, best, above);
 }
 
 // E values of a row from column c0, -inf past the row's end
@@ -126,11 +142,7 @@ __device__ __forceinline__ void xe_fwd_reg_rows(int64_t block, const void *__res
     int am = INT_MAX, nan_at = INT_MAX, cnt = 0;
 #pragma unroll
     for (int s = 0; s < NV; s++) {
-        const float x = v[s];
-        const int c = col(s);
-        if (x != x) nan_at = min(nan_at, c);
-        if (x > m) { m = x; am = c; }
-        cnt += x > zy ? 1 : 0;
+        xe_scan(v[s], col(s), zy, m, am, nan_at, cnt);
     }
     __shared__ XeShared sh;
     float M = wave_max(m);

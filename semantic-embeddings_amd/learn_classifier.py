@@ -11,6 +11,13 @@ The network emits logits; the categorical cross-entropy with label smoothing, it
 the fused HIP kernel pair (``sehip.softmax_cross_entropy``): one forward and one backward launch per step serve the loss and all
 metrics, with Keras 2.2's clip of the probabilities to [1e-7, 1 - 1e-7].
 
+An extension the reference does not have: ``--loss hxe`` (hierarchical cross-entropy, ``--hxe_alpha``) and ``--loss soft_labels``
+(cross-entropy against ``softmax(-beta * class distance)``, ``--soft_beta``) train the hierarchy-aware classification baselines on the
+class tree given by ``--hierarchy`` / ``--is_a`` / ``--str_ids`` (``sehip.hierarchical_cross_entropy`` / ``sehip.soft_label_cross_entropy``:
+again one forward and one backward launch for the loss and all metrics, no clip).  Without ``--loss`` nothing changes.
+
+    python learn_classifier.py --dataset CIFAR-100 --data_root . --architecture resnet-110-fc --loss hxe --hierarchy cifar.parent-child.txt
+
 Differences from the reference a user can observe: ``--gpus N`` expects to be launched with N processes (torchrun); ``--batch_size``
 stays the GLOBAL batch and is split across the ranks like ``multi_gpu_model`` split it across towers; models, weights and snapshots
 are torch ``state_dict`` / ``torch.save`` files, not Keras ``.h5`` (the saved model emits logits: its last layer is the dense layer
@@ -51,8 +58,11 @@ class SoftmaxCrossEntropy(object):
         self._last = None          # (logits, version, labels, best, above) of the last forward call
         self.acc = self._metric('acc', lambda y, best, above: best == y)
 
+    def _forward(self, y_pred, y_true):
+        return sehip.softmax_cross_entropy(y_pred, y_true, self.label_smoothing, reduction='none', return_metrics=True)
+
     def __call__(self, y_true, y_pred):
-        loss_i, best, above = sehip.softmax_cross_entropy(y_pred, y_true, self.label_smoothing, reduction='none', return_metrics=True)
+        loss_i, best, above = self._forward(y_pred, y_true)
         # the detached alias keeps the storage alive, so no other tensor can show up at this address with this version
         self._last = (y_pred.detach(), y_pred._version, y_true, best, above)
         return loss_i
@@ -64,7 +74,7 @@ class SoftmaxCrossEntropy(object):
                 and last[2] is y_true:
             return last[3], last[4]
         with torch.no_grad():
-            _, best, above = sehip.softmax_cross_entropy(y_pred.detach(), y_true, self.label_smoothing, return_metrics=True)
+            _, best, above = self._forward(y_pred.detach(), y_true)
         return best, above
 
     def _metric(self, name, rule):
@@ -79,10 +89,49 @@ class SoftmaxCrossEntropy(object):
         return self._metric('acc{}'.format(k), lambda y, best, above: above < int(k))
 
 
-def build_losses(label_smoothing, top_k_acc=()):
+class HierarchicalCrossEntropy(SoftmaxCrossEntropy):
+    """``SoftmaxCrossEntropy``'s interface (``__call__``, ``acc``, ``top_k(k)``) for the hierarchical cross-entropy of
+    ``ClassHierarchy.hxe_encoding`` (``--loss hxe``): one se_hxe_fwd forward, which also leaves the metrics, one se_hxe_bwd backward."""
+
+    name = 'hierarchical_crossentropy'
+
+    def __init__(self, encoding):
+        super(HierarchicalCrossEntropy, self).__init__(0.0)
+        self.encoding = sehip.HxeEncoding.of(encoding)
+
+    def _forward(self, y_pred, y_true):
+        return sehip.hierarchical_cross_entropy(y_pred, y_true, self.encoding, reduction='none', return_metrics=True)
+
+
+class SoftLabelCrossEntropy(SoftmaxCrossEntropy):
+    """``SoftmaxCrossEntropy``'s interface for the cross-entropy against the soft labels of ``ClassHierarchy.soft_label_table``
+    (``--loss soft_labels``): one se_soft_xent_fwd forward, which also leaves the metrics, one se_soft_xent_bwd backward."""
+
+    name = 'soft_label_crossentropy'
+
+    def __init__(self, table):
+        super(SoftLabelCrossEntropy, self).__init__(0.0)
+        self.table = table if isinstance(table, sehip.SoftLabelTable) else sehip.SoftLabelTable(table)
+
+    def _forward(self, y_pred, y_true):
+        return sehip.soft_label_cross_entropy(y_pred, y_true, self.table, reduction='none', return_metrics=True)
+
+
+def hierarchy_loss(args, classes):
+    """The loss object of ``--loss hxe`` / ``--loss soft_labels``: class ``c`` of the data generator is the hierarchy node
+    ``classes[c]``, as in evaluate_classification_accuracy.py --hierarchy."""
+    from class_hierarchy import ClassHierarchy
+    hierarchy = ClassHierarchy.from_file(args.hierarchy, is_a_relations=args.is_a, id_type=str if args.str_ids else int)
+    if args.loss == 'hxe':
+        return HierarchicalCrossEntropy(hierarchy.hxe_encoding(list(classes), alpha=args.hxe_alpha))
+    return SoftLabelCrossEntropy(hierarchy.soft_label_table(list(classes), args.soft_beta))
+
+
+def build_losses(label_smoothing, top_k_acc=(), loss=None):
     """Both compile() calls of the reference (learn_classifier.py:103-106, 116-117, 146-147): the categorical cross-entropy with
-    metrics 'accuracy' and utils.top_k_acc(k) for every ``--top_k_acc``."""
-    loss = SoftmaxCrossEntropy(label_smoothing)
+    metrics 'accuracy' and utils.top_k_acc(k) for every ``--top_k_acc``.  ``loss``: another loss object with that interface."""
+    if loss is None:
+        loss = SoftmaxCrossEntropy(label_smoothing)
     return {'prob': (loss, 1.0)}, {'prob': [loss.acc] + [loss.top_k(k) for k in top_k_acc]}
 
 
@@ -143,7 +192,22 @@ def predict_features(trainer, seq):
     return torch.cat(feats).numpy()
 
 
-def build_parser():
+def add_hierarchy_loss_arguments(group):
+    """The flags of the hierarchy-aware losses, which the reference's command line does not have."""
+    group.add_argument('--loss', type=str, default='xent', choices=['xent', 'hxe', 'soft_labels'],
+                       help='xent: categorical cross-entropy.  hxe: hierarchical cross-entropy, the softmax factorised along the path of the label in the '
+                            'class tree.  soft_labels: cross-entropy against softmax(-beta * class distance).  The last two need --hierarchy.')
+    group.add_argument('--hierarchy', type=str, default=None, help='Path to a file containing parent-child relationships (one per line): the class tree of --loss hxe / soft_labels.')
+    group.add_argument('--is_a', action='store_true', default=False, help='If given, --hierarchy is assumed to contain is-a instead of parent-child relationships.')
+    group.add_argument('--str_ids', action='store_true', default=False, help='If given, class IDs are treated as strings instead of integers.')
+    group.add_argument('--hxe_alpha', type=float, default=0.1,
+                       help='--loss hxe: the edge below a node d edges under the top weighs exp(-alpha * d).  The default lies inside the range the literature sweeps; this project has not measured it.')
+    group.add_argument('--soft_beta', type=float, default=10.0,
+                       help='--loss soft_labels: the target of class y is softmax_c(-beta * lcs_height(y, c)).  The default lies inside the range the literature sweeps; this project has not measured it.')
+
+
+def build_parser(hierarchy_losses=False):
+    """The reference's command line; with ``hierarchy_losses`` also --loss and the flags that go with it (``parse_args`` asks for them)."""
     parser = argparse.ArgumentParser(description='Learns an image classifier (MI355X build).', formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     g = parser.add_argument_group('Data parameters')
     g.add_argument('--dataset', type=str, required=True, help='Dataset name (see datasets.get_data_generator).')
@@ -153,6 +217,8 @@ def build_parser():
     g.add_argument('--architecture', type=str, default='simple', choices=utils.ARCHITECTURES, help='Network architecture.')
     g.add_argument('--label_smoothing', type=float, default=0.0,
                    help='Smooth the target distribution by subtracting this value from the target probability of the ground-truth class.')
+    if hierarchy_losses:
+        add_hierarchy_loss_arguments(g)
     train_cli.add_schedule_arguments(g)
     train_cli.add_snapshot_arguments(g)
     train_cli.add_finetune_and_device_arguments(g, 3, 'Epochs training only the last layer first.')
@@ -163,8 +229,19 @@ def build_parser():
     return parser
 
 
+def parse_args(argv=None):
+    parser = build_parser(hierarchy_losses=True)
+    args = parser.parse_args(argv)
+    if args.loss != 'xent':         # before any device work
+        if not args.hierarchy:
+            parser.error('--loss {} needs --hierarchy'.format(args.loss))
+        if args.label_smoothing > 0:
+            parser.error('--loss {} has a target of its own: it cannot be combined with --label_smoothing'.format(args.loss))
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.val_batch_size is None:
         args.val_batch_size = args.batch_size
 
@@ -179,7 +256,8 @@ def main(argv=None):
     model = build_classifier(data_generator.num_classes, args.architecture, input_channels=data_generator.num_channels).to(dev)
     train_cli.resume_from_snapshot(model, args.snapshot, dev)
 
-    losses, metrics = build_losses(args.label_smoothing, args.top_k_acc)
+    losses, metrics = build_losses(args.label_smoothing, args.top_k_acc,
+                                   hierarchy_loss(args, data_generator.classes) if args.loss != 'xent' else None)
     # Keras kernel regulariser of the network folded into the update
     l2_of = {id(p): model.regularizer for p in model.regularized_parameters()} if getattr(model, 'regularizer', 0) else {}
 

@@ -15,7 +15,7 @@ from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, MET
 
 __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
-    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "l2norm", "nn_accuracy", "embed_head_forward", "embedding_head", "joint_head", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
+    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "hierarchical_cross_entropy", "soft_label_cross_entropy", "HxeEncoding", "SoftLabelTable", "l2norm", "nn_accuracy", "embed_head_forward", "embedding_head", "joint_head", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
     "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
     "adagrad_step_", "ADAGRAD_MAX_BLOCKS", "grad_clip_factor", "sgd_step_", "SGD_MAX_BLOCKS", "shortcut_add", "LAYOUT_NCHW", "LAYOUT_NHWC",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
@@ -344,6 +344,168 @@ def softmax_cross_entropy(logits, labels, label_smoothing=0.0, reduction="none",
     out = _SoftmaxCrossEntropy.apply(logits, labels, float(label_smoothing), reduction == "mean")
     loss = out[3][0] if reduction == "mean" else (out[0].sum() if reduction == "sum" else out[0])
     return (loss, out[1], out[2]) if return_metrics else loss
+
+
+class HxeEncoding(object):
+    """``ClassHierarchy.hxe_encoding``'s arrays for the kernels: uploaded once per device and kept on this object; ``path_off``
+    also stays on the host, where the entry points check it before every launch."""
+
+    def __init__(self, encoding):
+        import numpy as np
+        self.host = {k: torch.from_numpy(np.ascontiguousarray(encoding[k], dtype=np.float32 if k == "lvl_w" else np.int32))
+                     for k in ("pos", "path_off", "lvl_lo", "lvl_hi", "lvl_w")}
+        self.num_classes = int(self.host["pos"].numel())
+        if self.host["path_off"].numel() != self.num_classes + 1:
+            raise SehipError("hxe encoding: path_off must hold C + 1 = %d entries" % (self.num_classes + 1))
+        nnz = int(self.host["path_off"][-1])
+        if any(int(self.host[k].numel()) != nnz for k in ("lvl_lo", "lvl_hi", "lvl_w")):
+            raise SehipError("hxe encoding: lvl_lo, lvl_hi and lvl_w must hold path_off[C] = %d entries" % nnz)
+        self._device = {}
+
+    def on(self, device):
+        key = (device.type, device.index)
+        if key not in self._device:
+            self._device[key] = {k: v.to(device) for k, v in self.host.items()}
+        return self._device[key]
+
+    @classmethod
+    def of(cls, encoding):
+        """``encoding`` itself, or the object kept with the dict ``hxe_encoding`` returned (so its uploads are shared by every call)."""
+        if isinstance(encoding, cls):
+            return encoding
+        if "_sehip" not in encoding:
+            encoding["_sehip"] = cls(encoding)
+        return encoding["_sehip"]
+
+
+class SoftLabelTable(object):
+    """A float32 [C, C] table of target distributions (``ClassHierarchy.soft_label_table``): uploaded once per device and kept here."""
+
+    def __init__(self, table):
+        t = table if torch.is_tensor(table) else torch.from_numpy(table)
+        if t.dim() != 2 or t.shape[0] != t.shape[1]:
+            raise SehipError("a soft-label table is a square [C, C] matrix, got %s" % (tuple(t.shape),))
+        self.host = t.to(torch.float32).contiguous()
+        self.num_classes = int(t.shape[0])
+        self._device = {}
+
+    def on(self, device):
+        key = (device.type, device.index)
+        if key not in self._device:
+            self._device[key] = self.host.to(device)
+        return self._device[key]
+
+
+def _logit_rows(logits, labels, C_want, what):
+    require_gpu(logits, labels)
+    if logits.dim() != 2:
+        raise SehipError("logits must be a 2-d [B, C] tensor")
+    B, C = logits.shape
+    if C != C_want:
+        raise SehipError("%s: the logits have %d classes, the %s %d" % (what, C, "encoding" if what.startswith("hier") else "table", C_want))
+    z = logits if logits.stride(1) == 1 and (B <= 1 or logits.stride(0) >= C) else logits.contiguous()
+    if labels.dtype != torch.int64 or labels.numel() != B or not labels.is_contiguous():
+        raise SehipError("labels must be a contiguous int64 [B] tensor")
+    if os.environ.get("SEHIP_CHECK_LABELS") == "1" and B and (int(labels.min()) < 0 or int(labels.max()) >= C):
+        raise SehipError("%s: labels outside [0, %d)" % (what, C))
+    return z, B, C, (z.stride(0) if B > 1 else max(z.stride(0), C))
+
+
+def _loss_outputs(B, dev, aux_floats, want_mean):
+    return (torch.empty((B,), dtype=torch.float32, device=dev), torch.empty((aux_floats,), dtype=torch.float32, device=dev),
+            torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+            torch.empty((1,), dtype=torch.float32, device=dev) if want_mean else None)
+
+
+def _row_grads(grad_loss_i, grad_mean, B):
+    g = grad_loss_i.to(torch.float32)
+    if grad_mean is not None:           # d mean / d loss_i = 1 / B
+        g = g + grad_mean.to(torch.float32) / max(B, 1)
+    return g.contiguous()
+
+
+class _HierarchicalCrossEntropy(torch.autograd.Function):
+    """One se_hxe_fwd forward (loss and the metrics of the same logits), one se_hxe_bwd backward."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, enc, want_mean):
+        z, B, C, ldz = _logit_rows(logits, labels, enc.num_classes, "hierarchical_cross_entropy")
+        t = enc.on(z.device)
+        loss_i, aux, best, above, loss_mean = _loss_outputs(B, z.device, call("se_hxe_aux_floats", B), want_mean)
+        call("se_hxe_fwd", z, _dtype_code(z), ldz, labels, t["pos"], t["path_off"], enc.host["path_off"], t["lvl_lo"], t["lvl_hi"],
+             t["lvl_w"], B, C, loss_i, aux, best, above, loss_mean)
+        ctx.save_for_backward(z, labels, aux)
+        ctx.enc, ctx.ldz = enc, ldz
+        ctx.mark_non_differentiable(best, above)
+        return (loss_i, best, above, loss_mean) if want_mean else (loss_i, best, above)
+
+    @staticmethod
+    def backward(ctx, grad_loss_i, _best, _above, grad_mean=None):
+        z, labels, aux = ctx.saved_tensors
+        B, C = z.shape
+        t = ctx.enc.on(z.device)
+        dz = torch.empty((B, C), dtype=z.dtype, device=z.device)
+        call("se_hxe_bwd", z, _dtype_code(z), ctx.ldz, labels, t["pos"], t["path_off"], ctx.enc.host["path_off"], t["lvl_lo"], t["lvl_hi"],
+             t["lvl_w"], aux, _row_grads(grad_loss_i, grad_mean, B), 0.0, B, C, dz, _dtype_code(dz), C)
+        return dz, None, None, None
+
+
+class _SoftLabelCrossEntropy(torch.autograd.Function):
+    """One se_soft_xent_fwd forward (loss and the metrics of the same logits), one se_soft_xent_bwd backward."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, table, want_mean):
+        z, B, C, ldz = _logit_rows(logits, labels, int(table.shape[0]), "soft_label_cross_entropy")
+        loss_i, aux, best, above, loss_mean = _loss_outputs(B, z.device, 3 * B, want_mean)
+        call("se_soft_xent_fwd", z, _dtype_code(z), ldz, labels, table, table.stride(0), B, C, loss_i, aux, best, above, loss_mean)
+        ctx.save_for_backward(z, labels, aux, table)
+        ctx.ldz = ldz
+        ctx.mark_non_differentiable(best, above)
+        return (loss_i, best, above, loss_mean) if want_mean else (loss_i, best, above)
+
+    @staticmethod
+    def backward(ctx, grad_loss_i, _best, _above, grad_mean=None):
+        z, labels, aux, table = ctx.saved_tensors
+        B, C = z.shape
+        dz = torch.empty((B, C), dtype=z.dtype, device=z.device)
+        call("se_soft_xent_bwd", z, _dtype_code(z), ctx.ldz, labels, table, table.stride(0), aux, _row_grads(grad_loss_i, grad_mean, B), 0.0,
+             B, C, dz, _dtype_code(dz), C)
+        return dz, None, None, None
+
+
+def _reduced(out, reduction, return_metrics):
+    if reduction not in ("none", "mean", "sum"):
+        raise SehipError("reduction must be none, mean or sum, got %r" % (reduction,))
+    loss = out[3][0] if reduction == "mean" else (out[0].sum() if reduction == "sum" else out[0])
+    return (loss, out[1], out[2]) if return_metrics else loss
+
+
+def hierarchical_cross_entropy(logits, labels, encoding, reduction="none", return_metrics=False):
+    """Differentiable hierarchical cross-entropy: the softmax of ``logits`` factorised along the label's path in the class tree,
+    ``sum_l lambda_l * -log p(a_l | a_{l+1})`` (include/sehip.h states the arithmetic; no probability clip): one HIP launch forward,
+    one backward.  ``encoding``: ``ClassHierarchy.hxe_encoding(classes, alpha)`` (the dict, or an ``HxeEncoding`` of it): uploaded
+    once per device and kept with that object.  logits [B, C] float32 or bfloat16 with any row pitch (``d logits`` in the same dtype),
+    labels contiguous int64 [B].  ``reduction`` and ``return_metrics`` as in ``softmax_cross_entropy``."""
+    if reduction not in ("none", "mean", "sum"):
+        raise SehipError("reduction must be none, mean or sum, got %r" % (reduction,))
+    out = _HierarchicalCrossEntropy.apply(logits, labels, HxeEncoding.of(encoding), reduction == "mean")
+    return _reduced(out, reduction, return_metrics)
+
+
+def soft_label_cross_entropy(logits, labels, table, reduction="none", return_metrics=False):
+    """Differentiable cross-entropy of ``softmax(logits)`` against row ``labels[i]`` of ``table`` -- float32 [C, C] target
+    distributions, ``ClassHierarchy.soft_label_table(classes, beta)`` -- without a probability clip: one HIP launch forward, one
+    backward.  ``table``: a ``SoftLabelTable`` (uploaded once per device and kept there), a device tensor (used as it is, any row
+    pitch) or an array (uploaded by this call).  Otherwise as ``hierarchical_cross_entropy``."""
+    if reduction not in ("none", "mean", "sum"):
+        raise SehipError("reduction must be none, mean or sum, got %r" % (reduction,))
+    require_gpu(logits)
+    if not (torch.is_tensor(table) and table.is_cuda):
+        table = (table if isinstance(table, SoftLabelTable) else SoftLabelTable(table)).on(logits.device)
+    if table.dim() != 2 or table.dtype != torch.float32 or table.stride(1) != 1 or table.shape[0] != table.shape[1]:
+        raise SehipError("table must be a float32 [C, C] tensor with unit column stride")
+    out = _SoftLabelCrossEntropy.apply(logits, labels, table, reduction == "mean")
+    return _reduced(out, reduction, return_metrics)
 
 
 class _L2Norm(torch.autograd.Function):

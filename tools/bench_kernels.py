@@ -3,6 +3,9 @@
     python tools/bench_kernels.py pdist|rank|loss|topk [--n 50000 --d 100 --reps 5]
     python tools/bench_kernels.py pdist64 [--n 50000 --d 100]   (the opt-in float64 retrieval step, leg by leg: float64 distances, their float32
                                                   image, se_rank_rows on it, se_rank_refine_f64; the float32 step next to them)
+    python tools/bench_kernels.py hxe            (se_hxe_fwd + _bwd and se_soft_xent_fwd + _bwd next to a torch composition of each loss and
+                                                  to se_softmax_xent_fwd + _bwd: 128 x 100 on the CIFAR tree, 128 x 1000 on the ILSVRC
+                                                  min-tree, 256 x 8142 on the iNaturalist 2018 tree; --n / --d are not used)
     python tools/bench_kernels.py knn            (se_knn_vote next to the torch composition gather -> scatter_add -> topk, and the whole
                                                   knn_classification: 10,000 x 50,000 x 100 with k = 20, 100 classes; 50,000 x 50,000 x 100 with
                                                   k = 200, 1000 classes; --n / --d are not used)
@@ -108,7 +111,7 @@ def windows(fns, reps, batch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn", "ranked", "bootstrap", "ndcg"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn", "ranked", "bootstrap", "ndcg", "hxe"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -132,6 +135,8 @@ def main():
         return bench_ndcg()
     if args.what == "xent":
         return bench_xent()
+    if args.what == "hxe":
+        return bench_hxe()
     if args.what == "image":
         return bench_image()
     if args.what == "adagrad":
@@ -715,6 +720,123 @@ def bench_xent(reps=60, batch=20, steps=200):
         step = float(np.median(ms[name]))
         print("ResNet-110 classifier step (%s head: loss + acc + acc5), batch 128, fp32, HIP-graph replay: %.3f ms/step (median of 3 x %d "
               "steps; %s), %.0f images/s" % (name, step, steps, ", ".join("%.3f" % v for v in ms[name]), 128 / step * 1e3))
+
+
+def _bench_tree(name, seed=0):
+    """(ClassHierarchy, classes, note) of a hierarchy fixture under tests/golden -- 'cifar', 'ilsvrc' (the WordNet min-tree) or
+    'inat2018' -- or, where the fixture is no tree, a seeded random tree with as many classes (the note says so)."""
+    from class_hierarchy import ClassHierarchy
+    golden = os.path.join(ROOT, "tests", "golden")
+    g = np.load(os.path.join(golden, "hierarchy_%s.npz" % name))
+    if name == "cifar":
+        id_type, classes = int, list(range(100))
+    elif name == "ilsvrc":
+        id_type, classes = str, np.load(os.path.join(golden, "imagenet_mintree_unitsphere.npz"))["ind2label"].tolist()
+    else:
+        id_type, classes = str, g["classes"].tolist()
+
+    def build(edges):
+        parents, children = {}, {}
+        for p, c in edges:
+            parents.setdefault(c, []).append(p)
+            children.setdefault(p, []).append(c)
+        return ClassHierarchy(parents, children)
+    h = build([(id_type(p), id_type(c)) for p, c in g["edges"].tolist()])
+    if h.is_tree():
+        return h, [id_type(c) for c in classes], "the %s tree" % name
+    rng = np.random.default_rng(seed)
+    C, inner = len(classes), max(2, len(classes) // 3)
+    edges = [(10 ** 6 + int(rng.integers(i // 2, i)), 10 ** 6 + i) for i in range(1, inner)]
+    edges += [(10 ** 6 + int(rng.integers(0, inner)), c) for c in range(C)]
+    return build(edges), list(range(C)), "a seeded random tree of %d classes (the %s fixture is not a tree)" % (C, name)
+
+
+def bench_hxe(reps=40, batch=20):
+    """Hierarchy-aware classifier losses: se_hxe_fwd + se_hxe_bwd and se_soft_xent_fwd + se_soft_xent_bwd (loss, arg-max, top-k count,
+    mean, gradient) through the C ABI on preallocated buffers, next to a torch composition of each loss (HXE: exp(z - max) times a
+    dense [C, nodes] membership matrix gives every node sum, then logs, a gather along the label's path and the weights; soft
+    labels: log_softmax times the gathered table rows; both with backward, argmax and topk(5)) and to se_softmax_xent_fwd + _bwd at
+    the same shape for scale.  All timed alternately in one process: per shape `reps` windows of `batch` back-to-back calls each (HIP
+    events around a window) after 3 warm-up calls, median / 10th / 90th percentile of the per-call time."""
+    import torch.nn.functional as F
+    from sehip._lib import call
+    print("hierarchy-aware losses, forward + backward, float32 logits; us per call, median (10th-90th percentile) of %d windows of %d "
+          "calls, candidates alternating" % (reps, batch))
+    for B, name in ((128, "cifar"), (128, "ilsvrc"), (256, "inat2018")):
+        h, classes, note = _bench_tree(name)
+        C = len(classes)
+        enc_h = h.hxe_encoding(classes, alpha=0.1)
+        enc = sehip.HxeEncoding(enc_h)
+        t = enc.on(torch.device("cuda", torch.cuda.current_device()))
+        table = torch.from_numpy(h.soft_label_table(classes, 10.0)).cuda()
+        rng = np.random.default_rng(B + C)
+        z = torch.from_numpy((rng.standard_normal((B, C)) * 3).astype(np.float32)).cuda()
+        y = torch.from_numpy(rng.integers(0, C, B)).cuda()
+        loss_i, mean = torch.empty(B, device="cuda"), torch.empty(1, device="cuda")
+        aux_h, aux = torch.empty(call("se_hxe_aux_floats", B), device="cuda"), torch.empty(3 * B, device="cuda")
+        best, above = torch.empty(B, dtype=torch.int32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+        dz = torch.empty(B, C, device="cuda")
+        zt = z.clone().requires_grad_(True)
+        # the composition's tables: one column of `member` per distinct range, the label's path as node indices (padded with the top)
+        off, lo, hi, w = enc_h["path_off"], enc_h["lvl_lo"], enc_h["lvl_hi"], enc_h["lvl_w"]
+        ranges = sorted(set(zip(lo.tolist(), hi.tolist())))
+        col = {r: i for i, r in enumerate(ranges)}
+        pos = enc_h["pos"].astype(np.int64)
+        member = torch.from_numpy(np.stack([(pos >= a) & (pos < b) for a, b in ranges], axis=1).astype(np.float32)).cuda()
+        hmax = int(enc_h["max_levels"])
+        par = np.full((C, hmax), col[(0, C)], dtype=np.int64)
+        wt = np.zeros((C, hmax), dtype=np.float32)
+        for c in range(C):
+            n = off[c + 1] - off[c]
+            par[c, :n] = [col[r] for r in zip(lo[off[c]:off[c + 1]].tolist(), hi[off[c]:off[c + 1]].tolist())]
+            wt[c, :n] = w[off[c]:off[c + 1]]
+        par, wt = torch.from_numpy(par).cuda(), torch.from_numpy(wt).cuda()
+
+        def hxe_kernels():
+            call("se_hxe_fwd", z, 0, C, y, t["pos"], t["path_off"], enc.host["path_off"], t["lvl_lo"], t["lvl_hi"], t["lvl_w"], B, C, loss_i,
+                 aux_h, best, above, mean)
+            call("se_hxe_bwd", z, 0, C, y, t["pos"], t["path_off"], enc.host["path_off"], t["lvl_lo"], t["lvl_hi"], t["lvl_w"], aux_h, None,
+                 1.0 / B, B, C, dz, 0, C)
+
+        def soft_kernels():
+            call("se_soft_xent_fwd", z, 0, C, y, table, C, B, C, loss_i, aux, best, above, mean)
+            call("se_soft_xent_bwd", z, 0, C, y, table, C, aux, None, 1.0 / B, B, C, dz, 0, C)
+
+        def xent_kernels():
+            call("se_softmax_xent_fwd", z, 0, C, y, B, C, 0.0, loss_i, aux, best, above, mean)
+            call("se_softmax_xent_bwd", z, 0, C, y, aux, None, 1.0 / B, B, C, 0.0, dz, 0, C)
+
+        def hxe_composition():
+            zt.grad = None
+            x = zt - zt.max(dim=1, keepdim=True).values
+            up = torch.log(x.exp() @ member).gather(1, par[y])
+            down = torch.cat([x.gather(1, y[:, None]), up[:, :-1]], dim=1)
+            (wt[y] * (up - down)).sum(dim=1).mean().backward()
+            zt.argmax(dim=-1)
+            zt.topk(5, dim=-1)
+
+        def soft_composition():
+            zt.grad = None
+            (-(table[y] * F.log_softmax(zt, dim=-1)).sum(dim=1)).mean().backward()
+            zt.argmax(dim=-1)
+            zt.topk(5, dim=-1)
+
+        # the composition computes the kernel's loss (checked once, so that the two sides time the same thing)
+        hxe_kernels()
+        x = z - z.max(dim=1, keepdim=True).values
+        up = torch.log(x.exp() @ member).gather(1, par[y])
+        want = float((wt[y] * (up - torch.cat([x.gather(1, y[:, None]), up[:, :-1]], dim=1))).sum(dim=1).mean())
+        assert abs(float(mean) - want) <= 1e-4 * max(1.0, abs(want)), (float(mean), want)
+        hk, sk, xk, hc_, sc = windows((hxe_kernels, soft_kernels, xent_kernels, hxe_composition, soft_composition), reps, batch)
+        print("B=%d C=%d on %s (%d levels at most, %d distinct ranges):" % (B, C, note, hmax, len(ranges)))
+        print("  hxe:         kernels %.1f us (%.1f-%.1f), torch composition %.1f us (%.1f-%.1f): %s by x%.2f"
+              % (hk[0], hk[1], hk[2], hc_[0], hc_[1], hc_[2], "kernels win" if hk[0] < hc_[0] else "composition wins",
+                 max(hk[0], hc_[0]) / min(hk[0], hc_[0])))
+        print("  soft labels: kernels %.1f us (%.1f-%.1f), torch composition %.1f us (%.1f-%.1f): %s by x%.2f"
+              % (sk[0], sk[1], sk[2], sc[0], sc[1], sc[2], "kernels win" if sk[0] < sc[0] else "composition wins",
+                 max(sk[0], sc[0]) / min(sk[0], sc[0])))
+        print("  for scale, se_softmax_xent_fwd + _bwd: %.1f us (%.1f-%.1f); hxe takes x%.2f of it, soft labels x%.2f"
+              % (xk[0], xk[1], xk[2], hk[0] / xk[0], sk[0] / xk[0]), flush=True)
 
 
 def bench_labelembed(reps=60, batch=20, steps=200):
