@@ -428,6 +428,40 @@ int se_soft_xent_bwd(const void *logits, int z_dtype, int64_t ldz, const int64_t
                      int64_t lddz, se_stream_t stream);
 
 /*
+ * Conditional risk minimisation (CRM) on a class TREE: the expected LCS height of every class under a row of class probabilities, and
+ * the `top` classes of smallest risk -- the inference-time baseline of the hierarchy-aware losses above (predict the class k that
+ * minimises sum_j p_j * height(lcs(k, j)) instead of the arg-max of p).  The reference has no such decoding.  The dense form is
+ * P @ H^T with the [C, C] height table, O(C^2) per row; on a tree it is O(C * levels):
+ *   probs [N, C] float32 (ldp).  pos, path_off, lvl_lo, lvl_hi: exactly what se_hxe_fwd reads (ClassHierarchy.tree_risk_encoding builds
+ *   them with the heights): entries path_off[k] .. path_off[k + 1] are the levels of class k walking up, entry e the position range
+ *   [lo, hi) of an ancestor; the ranges of a path are nested and grow strictly, the last one is [0, C), at most SE_HXE_MAX_LEVELS of
+ *   them.  lvl_h [nnz] int32: the height (an integer >= 0) of the node whose range entry e holds; own_h [C] int32: the height of
+ *   class k itself (NULL: all 0).  No host copy of path_off is needed: the kernel clamps what it reads (below).
+ *   Per row, with the float32 inputs widened to float64:  q[pos[c]] = p[c];  the mass of a range is the sum of q over it;
+ *       risk_k = own_h[k] * p_k + sum_{l = 0}^{h_k - 1} lvl_h[l] * (m_l - m_{l-1}),    m_{-1} = p_k,   m_l = mass of range l of k
+ *   (the classes whose lowest common subsumer with k is the level-l ancestor are that ancestor's range minus the range below it).
+ *   Every mass is a difference of two entries of ONE float64 prefix sum of q.  The order of its additions is a function of C alone:
+ *   a row's bits depend neither on N nor on the row's place in the batch nor on the launch geometry.
+ *   out_cls [N, top] int32: the `top` classes in ascending (risk, class index) order, the float64 risks compared as numbers
+ *   (-0 == +0, NaN last); out_risk [N, top] float64: their risks; risk [N, C] float64 (ldr) or NULL: all C values.  The lists are the
+ *   same bits whether or not risk is requested.
+ *   A row that holds a NaN or an infinity gets NaN for every risk and the classes 0 .. top - 1 (an explicit rule: otherwise the result
+ *   would depend on whether a mass is summed directly or taken as a difference of prefixes).
+ *   No gather leaves its table, whatever the device tables hold: pos is clamped into [0, C), lo / hi into [0, C] (hi <= lo: an empty
+ *   range), the level count of a path to min(SE_HXE_MAX_LEVELS, nnz) and its start into [0, nnz - levels].
+ *   SE_ERR_INVALID: a NULL required pointer, ldp < C, risk && ldr < C, top outside [1, min(C, SE_TREE_RISK_TOP_MAX)], C < 1, N < 0,
+ *   nnz < 0.  SE_ERR_UNSUPPORTED: C > SE_TREE_RISK_MAX_CLASSES (the prefix sums and the risks of a row in flight, two float64 rows,
+ *   live in the 160 KiB LDS).  N == 0 returns SE_OK without a launch.
+ *   A wave per row up to C = 1024, a workgroup per row above; any row pitch and alignment.  Asynchronous on `stream`, no allocation, no
+ *   workspace, no atomics, no host synchronisation: capturable in a HIP graph.
+ */
+#define SE_TREE_RISK_TOP_MAX 32
+#define SE_TREE_RISK_MAX_CLASSES 10000
+int se_tree_risk_topk(const float *probs, int64_t ldp, const int32_t *pos, const int32_t *path_off, const int32_t *lvl_lo,
+                      const int32_t *lvl_hi, const int32_t *lvl_h, int nnz, const int32_t *own_h, int64_t N, int C, int top,
+                      int32_t *out_cls, double *out_risk, double *risk, int64_t ldr, se_stream_t stream);
+
+/*
  * Adagrad update of a flat float32 parameter buffer in one launch, gradient scale and L2 regulariser folded in.
  * Replaces: Keras 2.2 optimizers.Adagrad.get_updates [third party, not in the reference tree] as learn_devise.py:87,114 uses it
  *           (keras.optimizers.Adagrad(lr=...) in both compile() calls), and the whole-buffer passes that would otherwise scale the

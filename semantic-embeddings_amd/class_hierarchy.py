@@ -312,25 +312,79 @@ class ClassHierarchy(object):
         ``ValueError`` naming the node: the spanned sub-hierarchy is not a tree (DAG hierarchies are refused, not mis-scored), a
         class is an ancestor of another class, a class is unknown to the hierarchy."""
         key = list(classes)
-        top, parent, _, d, rng = self._class_tree(key)
+        tree = self._class_tree(key)
+        d, rng = tree[3], tree[4]
         pos = np.asarray([rng[c][0] for c in key], dtype=np.int32)
         path_off = np.zeros(len(key) + 1, dtype=np.int32)
         lo, hi, w = [], [], []
-        for i, c in enumerate(key):
-            node = c
+        for i, edges in enumerate(self._kept_edges(key, tree)):
+            for node, up in edges:
+                lo.append(rng[up][0])
+                hi.append(rng[up][1])
+                w.append(float(weights(node)) if weights is not None else float(np.exp(-float(alpha) * d[node])))
+            path_off[i + 1] = len(lo)
+        return {'pos': pos, 'path_off': path_off, 'lvl_lo': np.asarray(lo, dtype=np.int32), 'lvl_hi': np.asarray(hi, dtype=np.int32),
+                'lvl_w': np.asarray(w, dtype=np.float32), 'max_levels': int(np.diff(path_off).max()) if len(key) else 0}
+
+    @staticmethod
+    def _kept_edges(key, tree):
+        """Per class of ``key``, walking up the ``tree`` of ``_class_tree``: the edges ``(node, parent)`` whose parent covers more
+        classes than the node -- the levels of the range encodings.  More than ``HXE_MAX_LEVELS`` of them raise ``ValueError``."""
+        top, parent, rng = tree[0], tree[1], tree[4]
+        for c in key:
+            edges, node = [], c
             while node != top:
                 up = parent[node]
                 if rng[up] != rng[node]:
-                    lo.append(rng[up][0])
-                    hi.append(rng[up][1])
-                    w.append(float(weights(node)) if weights is not None else float(np.exp(-float(alpha) * d[node])))
+                    edges.append((node, up))
                 node = up
+            if len(edges) > HXE_MAX_LEVELS:
+                raise ValueError('class {!r} has {} levels above it, more than the {} a path may have'.format(c, len(edges), HXE_MAX_LEVELS))
+            yield edges
+
+    def tree_risk_encoding(self, classes):
+        """What ``se_tree_risk_topk`` reads (``sehip.tree_risk_topk``, ``mistakes.crm_classification``): the position ranges of
+        ``hxe_encoding`` with the HEIGHT of every range's node in place of the weights.
+
+        Returns a dict of ``pos``, ``path_off``, ``lvl_lo``, ``lvl_hi`` (as ``hxe_encoding`` builds them), ``lvl_h`` int32 [nnz],
+        ``own_h`` int32 [C], ``max_levels`` and ``max_height``.  ``lvl_h[e]`` is ``heights`` of the DEEPEST node that covers the range
+        of entry ``e``: walking up from class ``k``, that node is ``lcs(k, j)`` for every class ``j`` the range adds, because ``lcs``
+        prefers depth (nodes above it with the same range are never a lowest common subsumer).  ``own_h[k]`` is the height of class
+        ``k`` itself, ``heights[lcs(k, k)]``.
+
+        ``ValueError``: whatever ``hxe_encoding`` refuses (a DAG, a class above a class, an unknown class), and a forest -- classes
+        under different roots have no common subsumer, so their risk has no value."""
+        key = list(classes)
+        tree = self._class_tree(key)
+        if tree[0] is _VIRTUAL_TOP:
+            raise ValueError('the classes span a forest ({} roots): classes under different roots have no common subsumer'
+                             .format(len(tree[2][_VIRTUAL_TOP])))
+        rng = tree[4]
+        path_off = np.zeros(len(key) + 1, dtype=np.int32)
+        lo, hi, h = [], [], []
+        for i, edges in enumerate(self._kept_edges(key, tree)):
+            for _, up in edges:
+                lo.append(rng[up][0])
+                hi.append(rng[up][1])
+                h.append(self.heights[up])
             path_off[i + 1] = len(lo)
-            if path_off[i + 1] - path_off[i] > HXE_MAX_LEVELS:
-                raise ValueError('class {!r} has {} levels above it, more than the {} a path may have'
-                                 .format(c, int(path_off[i + 1] - path_off[i]), HXE_MAX_LEVELS))
-        return {'pos': pos, 'path_off': path_off, 'lvl_lo': np.asarray(lo, dtype=np.int32), 'lvl_hi': np.asarray(hi, dtype=np.int32),
-                'lvl_w': np.asarray(w, dtype=np.float32), 'max_levels': int(np.diff(path_off).max()) if len(key) else 0}
+        return {'pos': np.asarray([rng[c][0] for c in key], dtype=np.int32), 'path_off': path_off,
+                'lvl_lo': np.asarray(lo, dtype=np.int32), 'lvl_hi': np.asarray(hi, dtype=np.int32), 'lvl_h': np.asarray(h, dtype=np.int32),
+                'own_h': np.asarray([self.heights[c] for c in key], dtype=np.int32),
+                'max_levels': int(np.diff(path_off).max()) if len(key) else 0, 'max_height': int(self.max_height)}
+
+    def height_table(self, classes, device=None, tables=None):
+        """int32 [C, C] device tensor of ``heights[lcs(a, b)]`` in levels -- the metric gathers of ``mistakes.mistake_metrics`` and
+        the dense path of ``mistakes.crm_classification``.  From ``similarity_tables_device(distance=True, want_wup=False)``, which
+        holds ``h / max_height`` in float64, as ``rint(table * max_height)``; nothing may move by more than 1e-9.  Works on a DAG.
+        ``tables`` (tests): a stand-in for ``similarity_tables_device``."""
+        import torch
+        make = tables if tables is not None else self.similarity_tables_device
+        _, lcs = make(classes, distance=True, want_wup=False, device=device)
+        scaled = lcs * float(self.max_height)
+        table = torch.round(scaled)
+        assert float((scaled - table).abs().max()) <= 1e-9, 'an LCS height is no whole number of levels'
+        return table.to(torch.int32)
 
     def soft_label_table(self, classes, beta):
         """float32 [C, C] targets of ``sehip.soft_label_cross_entropy``: row ``y`` is ``softmax_c(-beta * d(y, c))`` with

@@ -23,6 +23,11 @@ Mirrors the pieces of the reference's ``evaluate_classification_accuracy.py`` th
   classification of the test images against the training images -- ``se_retrieve_topk`` for the neighbour lists, ``se_knn_vote``
   (knn_vote.hip) for the vote; ties go to the smaller class index, as in scikit-learn's ``KNeighborsClassifier``.
 
+* ``--mistakes K [K ...]`` / ``--crm`` / ``--crm_logits`` (extensions of this build): the columns ``Mistake Severity`` and
+  ``Hier. Dist@K`` (``mistakes.mistake_metrics``, in levels of the hierarchy) for every row, and a second row ``"<name> [CRM]"`` for
+  every ``--prob_features`` model, decoded from the same outputs by conditional risk minimisation (``mistakes.crm_classification``:
+  ``se_tree_risk_topk`` on a class tree, the dense composition on the existing kernels otherwise).
+
 Class rankings of the new modes come from ``se_rank_rows`` on the negated scores: descending score, ties in ascending class
 index (the reference's ``argsort(-1)[:, ::-1]`` breaks ties in an unspecified order).
 """
@@ -65,13 +70,15 @@ def nn_classification(features, centroids, return_device=False):
     return rank if return_device else rank.cpu().numpy()
 
 
-def evaluate(y_pred, data_generator, hierarchy=None):
+def evaluate(y_pred, data_generator, hierarchy=None, mistakes=None, height_table=None):
     """Flat, top-5, class-balanced and hierarchical accuracy (evaluate_classification_accuracy.py:88-108).
-    ``y_pred``: ``[N]`` predicted class indices or an ``[N, >= 1]`` class ranking."""
+    ``y_pred``: ``[N]`` predicted class indices or an ``[N, >= 1]`` class ranking.
+    ``mistakes`` (an extension; needs ``hierarchy``): a list of K -- the keys of ``mistakes.mistake_metrics`` are added, computed
+    on ``height_table`` (default: ``hierarchy.height_table(data_generator.classes)``, built on the device)."""
     from train_cli import average_accuracy      # local like every torch import here: train_cli brings torch and the engine along
     perf = OrderedDict()
     y_true = np.asarray(data_generator.labels_test)
-    y_pred = np.asarray(y_pred)
+    y_pred = y_lists = np.asarray(y_pred)
     if y_pred.ndim == 2:
         perf['Top-5 Accuracy'] = float(np.mean(np.any(y_pred[:, :5] == y_true[:, None], axis=-1)))
         y_pred = y_pred[:, 0]
@@ -84,6 +91,13 @@ def evaluate(y_pred, data_generator, hierarchy=None):
         for yp, yt in zip(y_pred, y_true):
             total += 1.0 - hierarchy.lcs_height(classes[int(yp)], classes[int(yt)])
         perf['Hierarchical Accuracy'] = total / len(y_true)
+    if mistakes:
+        from mistakes import mistake_metrics
+        if hierarchy is None:
+            raise ValueError('the mistake metrics need a hierarchy')
+        if height_table is None:
+            height_table = hierarchy.height_table(data_generator.classes)
+        perf.update(mistake_metrics(y_lists, y_true, height_table, mistakes))
     return perf
 
 
@@ -222,6 +236,21 @@ def extract_predictions(data, model, layer=None, custom_objects={}, batch_size=1
     return _rank_descending(extract_features(data, model, layer, 'test', batch_size))
 
 
+def extract_outputs(data, model, layer=None, custom_objects={}, batch_size=1):
+    """The model outputs of the test set as a float32 device tensor [N, C]: what ``--prob_features`` ranks and ``--crm`` decodes."""
+    sys.stderr.write('Predicting and evaluating...\n')
+    return extract_features(data, model, layer, 'test', batch_size)
+
+
+def crm_predictions(outputs, hierarchy, classes, top=5, logits=False):
+    """``--crm``: class lists [N, top] of the model ``outputs`` (probabilities; ``logits``: softmax them first, float32) by
+    conditional risk minimisation (``mistakes.crm_classification``)."""
+    import torch
+    from mistakes import crm_classification
+    outputs = _as_device_f32(outputs)
+    return crm_classification(torch.softmax(outputs, dim=-1) if logits else outputs, hierarchy, classes, top)
+
+
 def nn_classification_model(data, centroids, model, layer=None, custom_objects={}, batch_size=1):
     """``--centroids`` mode: test features of ``model`` -> ``nn_classification`` (evaluate_classification_accuracy.py:51-71)."""
     sys.stderr.write('Extracting features...\n')
@@ -296,15 +325,15 @@ def knn_classification(X_train, y_train, X_test=None, ks=(1,), normalize=False, 
     return ranks
 
 
-def knn_classification_model(data, model, layer=None, normalize=False, ks=(1,), custom_objects={}, batch_size=1):
+def knn_classification_model(data, model, layer=None, normalize=False, ks=(1,), custom_objects={}, batch_size=1, top=5):
     """``--knn`` mode: train and test features of ``model`` like ``train_and_predict`` extracts them (one un-augmented pass over the
-    training set) -> ``knn_classification``: ``{k: class ranking of every test image}``."""
+    training set) -> ``knn_classification``: ``{k: class ranking of every test image}`` of ``top`` classes each."""
     sys.stderr.write('Extracting features...\n')
     X_train = extract_features(data, model, layer, 'train')
     X_test = extract_features(data, model, layer, 'test', batch_size)
     n = (data.num_train // 10) * 10
     sys.stderr.write('Searching for nearest training images...\n')
-    return knn_classification(X_train, np.asarray(data.labels_train)[:n], X_test, ks, normalize, num_classes=len(data.classes))
+    return knn_classification(X_train, np.asarray(data.labels_train)[:n], X_test, ks, normalize, num_classes=len(data.classes), top=top)
 
 
 def print_performance(perf, metrics=METRICS):
@@ -352,7 +381,13 @@ def build_parser():
     g.add_argument('--centroids', type=str, action='append', help='Optionally, a pickle dump containing a dictionary with an item "embedding" referring to a numpy array of class centroids for performing nearest-neighbor classification.')
     g = parser.add_argument_group('Extensions of this build (not in the reference)')
     g.add_argument('--knn', type=int, nargs='+', default=None, metavar='K', help='Classify the test images of every --model that is neither --prob_features nor --centroids by a vote among their K nearest training images instead of an SVM; one table row per K. --norm selects the cosine metric, otherwise squared Euclidean distances are used.')
+    g.add_argument('--mistakes', type=int, nargs='+', default=None, metavar='K', help='Adds the columns "Mistake Severity" (mean height of the lowest common subsumer of label and prediction over the misclassified images) and "Hier. Dist@K" (mean LCS height between the label and the K best classes) to every row, in levels of the hierarchy. Each K in [1, 32]. Needs --hierarchy.')
+    g.add_argument('--crm', action='store_true', default=False, help='Adds a row "<name> [CRM]" for every --prob_features model: the same outputs, taken as class probabilities, decoded by conditional risk minimisation (the class of smallest expected LCS height instead of the most probable one). Needs --hierarchy.')
+    g.add_argument('--crm_logits', action='store_true', default=False, help='Like --crm, for models whose output is logits: a softmax is applied first.')
     return parser
+
+
+MISTAKES_K_MAX = 32         # SE_TREE_RISK_TOP_MAX: the longest list the CRM decoding returns
 
 
 def _layer_arg(v):
@@ -364,16 +399,33 @@ def _layer_arg(v):
 
 def main(argv=None, modes=None):
     """The reference's command line (evaluate_classification_accuracy.py:138-188); returns the table's OrderedDict.
-    ``modes`` (tests): a dict overriding 'svm' / 'centroids' / 'prob' / 'knn' with callables of the same signatures.
+    ``modes`` (tests): a dict overriding 'svm' / 'centroids' / 'prob' / 'knn' with callables of the same signatures; with the
+    extension flags also 'probs' (``extract_outputs``), 'rank' (outputs -> descending class ranking), 'crm' (``crm_predictions``) and
+    'height_table' (no arguments -> the integer [C, C] table of the classes).
+    ``--mistakes`` / ``--crm`` / ``--crm_logits`` (extensions): the module docstring.
     ``--knn K [K ...]`` (an extension): models that would get an SVM are classified by k-NN, one row ``"<name> [k-NN, k=K]"`` per K."""
     from class_hierarchy import ClassHierarchy
     from evaluate_retrieval import load_labels
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    crm = args.crm or args.crm_logits
+    if (args.mistakes or crm) and not args.hierarchy:
+        parser.error('--mistakes and --crm need --hierarchy')
+    if args.mistakes and not all(1 <= k <= MISTAKES_K_MAX for k in args.mistakes):
+        parser.error('--mistakes: every K must lie in [1, {}]'.format(MISTAKES_K_MAX))
+    top = max([5] + (args.mistakes or []))
+    if args.mistakes and args.knn:
+        import sehip
+        if top > sehip.KNN_TOP_MAX:
+            parser.error('--mistakes with --knn: K = {} exceeds the longest class list of the vote, {}'.format(top, sehip.KNN_TOP_MAX))
     data_generator = load_labels(args)[0]
     id_type = str if args.str_ids else int
     hierarchy = ClassHierarchy.from_file(args.hierarchy, is_a_relations=args.is_a, id_type=id_type) if args.hierarchy else None
-    run = {'svm': train_and_predict, 'centroids': nn_classification_model, 'prob': extract_predictions, 'knn': knn_classification_model}
+    run = {'svm': train_and_predict, 'centroids': nn_classification_model, 'prob': extract_predictions, 'knn': knn_classification_model,
+           'probs': extract_outputs, 'rank': lambda outputs: _rank_descending(_as_device_f32(outputs)), 'crm': crm_predictions,
+           'height_table': lambda: hierarchy.height_table(data_generator.classes)}
     run.update(modes or {})
+    extra = {'mistakes': args.mistakes, 'height_table': run['height_table']()} if args.mistakes else {}
     perf = OrderedDict()
     for i, model in enumerate(args.model):
         model_name = args.label[i] if (args.label is not None) and (i < len(args.label)) else os.path.splitext(os.path.basename(model))[0]
@@ -382,18 +434,30 @@ def main(argv=None, modes=None):
         prob_features = args.prob_features[i] if (args.prob_features is not None) and (i < len(args.prob_features)) else False
         centroids = args.centroids[i] if (args.centroids is not None) and (i < len(args.centroids)) else ''
         sys.stderr.write('-- {} --\n'.format(model_name))
-        if prob_features:
+        if prob_features and crm:       # one extraction: the ranking and the CRM lists come from the same outputs
+            outputs = run['probs'](data_generator, model, layer, {}, args.batch_size)
+            perf[model_name] = evaluate(run['rank'](outputs), data_generator, hierarchy, **extra)
+            sys.stderr.write('Decoding by conditional risk minimisation...\n')
+            pred = run['crm'](outputs, hierarchy, data_generator.classes, min(top, len(data_generator.classes)), args.crm_logits)
+            perf['{} [CRM]'.format(model_name)] = evaluate(pred, data_generator, hierarchy, **extra)
+            continue
+        elif prob_features:
             pred = run['prob'](data_generator, model, layer, {}, args.batch_size)
         elif centroids:
             pred = run['centroids'](data_generator, centroids, model, layer, {}, args.batch_size)
         elif args.knn:
-            for k, pred in run['knn'](data_generator, model, layer, normalize, args.knn, {}, args.batch_size).items():
-                perf['{} [k-NN, k={}]'.format(model_name, k)] = evaluate(pred, data_generator, hierarchy)
+            knn_top = {'top': top} if args.mistakes else {}
+            for k, pred in run['knn'](data_generator, model, layer, normalize, args.knn, {}, args.batch_size, **knn_top).items():
+                perf['{} [k-NN, k={}]'.format(model_name, k)] = evaluate(pred, data_generator, hierarchy, **extra)
             continue
         else:
             pred = run['svm'](data_generator, model, layer, normalize, args.augmentation_epochs, args.C, {}, args.batch_size)
-        perf[model_name] = evaluate(pred, data_generator, hierarchy)
-    print_performance(perf)
+        perf[model_name] = evaluate(pred, data_generator, hierarchy, **extra)
+    if args.mistakes:
+        from mistakes import metric_names
+        print_performance(perf, METRICS + metric_names(args.mistakes))
+    else:
+        print_performance(perf)
     return perf
 
 

@@ -15,7 +15,7 @@ from ._lib import DEFINES, DTYPE_BF16, DTYPE_F32, METRIC_COSINE, METRIC_DOT, MET
 
 __all__ = [
     "cosine_embedding_loss", "cosine_loss_forward", "cosine_loss_backward", "squared_distance_loss", "sqdist_loss_forward",
-    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "hierarchical_cross_entropy", "soft_label_cross_entropy", "HxeEncoding", "SoftLabelTable", "l2norm", "nn_accuracy", "embed_head_forward", "embedding_head", "joint_head", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
+    "sqdist_loss_backward", "center_loss", "softmax_cross_entropy", "hierarchical_cross_entropy", "soft_label_cross_entropy", "HxeEncoding", "SoftLabelTable", "TreeRiskEncoding", "tree_risk_topk", "TREE_RISK_TOP_MAX", "TREE_RISK_MAX_CLASSES", "l2norm", "nn_accuracy", "embed_head_forward", "embedding_head", "joint_head", "labelembed_loss", "labelembed_table_loss", "labelembed_table_loss_packed", "LE_GRID_CAP",
     "devise_ranking_loss", "DEVISE_TORCH_ABOVE",
     "adagrad_step_", "ADAGRAD_MAX_BLOCKS", "grad_clip_factor", "sgd_step_", "SGD_MAX_BLOCKS", "shortcut_add", "LAYOUT_NCHW", "LAYOUT_NHWC",
     "row_sqnorm", "normalize_rows_", "empty_rows", "pairwise_dist", "rank_rows_init", "workspace_bytes", "release_workspace",
@@ -376,6 +376,64 @@ class HxeEncoding(object):
         if "_sehip" not in encoding:
             encoding["_sehip"] = cls(encoding)
         return encoding["_sehip"]
+
+
+TREE_RISK_TOP_MAX = DEFINES["SE_TREE_RISK_TOP_MAX"]
+TREE_RISK_MAX_CLASSES = DEFINES["SE_TREE_RISK_MAX_CLASSES"]
+
+
+class TreeRiskEncoding(object):
+    """``ClassHierarchy.tree_risk_encoding``'s arrays for ``se_tree_risk_topk``: uploaded once per device and kept on this object."""
+
+    KEYS = ("pos", "path_off", "lvl_lo", "lvl_hi", "lvl_h", "own_h")
+
+    def __init__(self, encoding):
+        self.host = {k: torch.from_numpy(np.ascontiguousarray(encoding[k], dtype=np.int32)) for k in self.KEYS}
+        self.num_classes = int(self.host["pos"].numel())
+        if self.host["path_off"].numel() != self.num_classes + 1 or self.host["own_h"].numel() != self.num_classes:
+            raise SehipError("tree risk encoding: path_off must hold C + 1 = %d entries, own_h C" % (self.num_classes + 1))
+        self.nnz = int(self.host["path_off"][-1])
+        if any(int(self.host[k].numel()) != self.nnz for k in ("lvl_lo", "lvl_hi", "lvl_h")):
+            raise SehipError("tree risk encoding: lvl_lo, lvl_hi and lvl_h must hold path_off[C] = %d entries" % self.nnz)
+        self._device = {}
+
+    on = HxeEncoding.on
+
+    @classmethod
+    def of(cls, encoding):
+        """``encoding`` itself, or the object kept with the dict ``tree_risk_encoding`` returned."""
+        if isinstance(encoding, cls):
+            return encoding
+        if "_sehip" not in encoding:
+            encoding["_sehip"] = cls(encoding)
+        return encoding["_sehip"]
+
+
+def tree_risk_topk(probs, encoding, top, return_risk=False):
+    """Conditional risk minimisation on a class tree (``se_tree_risk_topk``; include/sehip.h states the arithmetic): for every row
+    of ``probs`` (float32 [N, C] device tensor, any row pitch) the ``top`` classes of smallest expected LCS height
+    ``sum_j p_j * height(lcs(k, j))`` in ascending (risk, class index) order.  ``encoding``: ``ClassHierarchy.tree_risk_encoding``
+    (the dict, or a ``TreeRiskEncoding`` of it), uploaded once per device.  Returns ``(cls int32 [N, top], risk_top float64
+    [N, top])`` and, with ``return_risk``, the float64 [N, C] risks of every class.  A row with a NaN or an infinity: NaN risks,
+    classes ``0 .. top - 1``."""
+    require_gpu(probs)
+    enc = TreeRiskEncoding.of(encoding)
+    if probs.dim() != 2 or probs.dtype != torch.float32:
+        raise SehipError("probs must be a 2-d float32 [N, C] tensor")
+    N, C = probs.shape
+    if C != enc.num_classes:
+        raise SehipError("tree_risk_topk: the probabilities have %d classes, the encoding %d" % (C, enc.num_classes))
+    top = int(top)
+    if top < 1 or top > min(C, TREE_RISK_TOP_MAX):
+        raise SehipError("top must lie in [1, min(C = %d, %d)], got %d" % (C, TREE_RISK_TOP_MAX, top))
+    p = probs if probs.stride(1) == 1 and (N <= 1 or probs.stride(0) >= C) else probs.contiguous()
+    t = enc.on(p.device)
+    cls = torch.empty((N, top), dtype=torch.int32, device=p.device)
+    risk_top = torch.empty((N, top), dtype=torch.float64, device=p.device)
+    risk = torch.empty((N, C), dtype=torch.float64, device=p.device) if return_risk else None
+    call("se_tree_risk_topk", p, p.stride(0) if N > 1 else max(p.stride(0), C), t["pos"], t["path_off"], t["lvl_lo"], t["lvl_hi"],
+         t["lvl_h"], enc.nnz, t["own_h"], N, C, top, cls, risk_top, risk, C)
+    return (cls, risk_top, risk) if return_risk else (cls, risk_top)
 
 
 class SoftLabelTable(object):

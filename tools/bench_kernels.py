@@ -6,6 +6,9 @@
     python tools/bench_kernels.py hxe            (se_hxe_fwd + _bwd and se_soft_xent_fwd + _bwd next to a torch composition of each loss and
                                                   to se_softmax_xent_fwd + _bwd: 128 x 100 on the CIFAR tree, 128 x 1000 on the ILSVRC
                                                   min-tree, 256 x 8142 on the iNaturalist 2018 tree; --n / --d are not used)
+    python tools/bench_kernels.py crm            (CRM decoding with top = 20: se_tree_risk_topk next to the dense composition on se_pairwise_dist +
+                                                  se_topk_rows and to a torch float64 composition: 10,000 x 100 on the CIFAR tree, 50,000 x 1000
+                                                  on the ILSVRC min-tree, 24,426 x 8142 on the iNaturalist 2018 tree; --n / --d are not used)
     python tools/bench_kernels.py knn            (se_knn_vote next to the torch composition gather -> scatter_add -> topk, and the whole
                                                   knn_classification: 10,000 x 50,000 x 100 with k = 20, 100 classes; 50,000 x 50,000 x 100 with
                                                   k = 200, 1000 classes; --n / --d are not used)
@@ -111,7 +114,7 @@ def windows(fns, reps, batch):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("what", choices=["pdist", "rank", "loss", "topk", "fused", "hprec", "recprec", "shard", "rownorm", "svm", "classemb",
-                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn", "ranked", "bootstrap", "ndcg", "hxe"])
+                                     "center", "xent", "image", "adagrad", "labelembed", "tiny", "shortcut", "qg", "stream", "head", "joint", "sgd", "pdist64", "knn", "ranked", "bootstrap", "ndcg", "hxe", "crm"])
     ap.add_argument("--small", action="store_true", help="qg: 2,000 x 60,000 x 100 instead of 50,000 x 1,281,167 x 1000")
     ap.add_argument("--ranking-path", action="store_true", help="qg: time full rankings of --rank-rows queries of the same problem instead")
     ap.add_argument("--rank-rows", type=int, default=1024, help="qg --ranking-path: query rows ranked (the time is scaled to all queries)")
@@ -137,6 +140,8 @@ def main():
         return bench_xent()
     if args.what == "hxe":
         return bench_hxe()
+    if args.what == "crm":
+        return bench_crm()
     if args.what == "image":
         return bench_image()
     if args.what == "adagrad":
@@ -837,6 +842,57 @@ def bench_hxe(reps=40, batch=20):
                  max(sk[0], sc[0]) / min(sk[0], sc[0])))
         print("  for scale, se_softmax_xent_fwd + _bwd: %.1f us (%.1f-%.1f); hxe takes x%.2f of it, soft labels x%.2f"
               % (xk[0], xk[1], xk[2], hk[0] / xk[0], sk[0] / xk[0]), flush=True)
+
+
+def bench_crm(reps=12, top=20):
+    """CRM decoding (mistakes.crm_classification), top = 20 classes of smallest expected LCS height per row of probabilities, three
+    ways on the same device inputs and preallocated outputs where the interface allows: se_tree_risk_topk (float64 risks from one
+    prefix sum per row); the dense composition on the existing kernels, se_pairwise_dist(P, -H, cosine) in slabs of
+    mistakes.DENSE_TILE_ROWS rows + se_topk_rows (float32 chain); a torch composition, P.double() @ H.T then topk(largest=False)
+    (float64).  Timed alternately in one process: per shape `reps` windows of `batch` back-to-back calls (HIP events around a
+    window) after 3 warm-up calls, median / 10th / 90th percentile of the per-call time.  The agreement of the three class lists is
+    printed, not asserted: the float32 chain and another float64 summation order may order near-ties differently."""
+    import mistakes
+    from sehip._lib import call
+    print("CRM decoding, top = %d; ms per call, median (10th-90th percentile) of %d windows, candidates alternating" % (top, reps))
+    for N, name, batch in ((10000, "cifar", 10), (50000, "ilsvrc", 3), (24426, "inat2018", 2)):
+        h, classes, note = _bench_tree(name)
+        C = len(classes)
+        enc_h = h.tree_risk_encoding(classes)
+        enc = sehip.TreeRiskEncoding(enc_h)
+        t = enc.on(torch.device("cuda", torch.cuda.current_device()))
+        H = h.height_table(classes)
+        negH, H64 = -H.to(torch.float32), H.to(torch.float64)
+        rng = np.random.default_rng(N + C)
+        P = torch.softmax(torch.from_numpy((3.0 * rng.standard_normal((N, C))).astype(np.float32)).cuda(), dim=-1)
+        cls, rt = torch.empty((N, top), dtype=torch.int32, device="cuda"), torch.empty((N, top), dtype=torch.float64, device="cuda")
+        rows = mistakes.DENSE_TILE_ROWS
+        slab = torch.empty((min(rows, N), C), dtype=torch.float32, device="cuda")
+        dcls, dd = torch.empty((N, top), dtype=torch.int32, device="cuda"), torch.empty((N, top), dtype=torch.float32, device="cuda")
+        kept = {}
+
+        def tree_kernel():
+            call("se_tree_risk_topk", P, C, t["pos"], t["path_off"], t["lvl_lo"], t["lvl_hi"], t["lvl_h"], enc.nnz, t["own_h"], N, C, top,
+                 cls, rt, None, 0)
+
+        def dense_kernels():
+            for r0 in range(0, N, rows):
+                n = min(rows, N - r0)
+                call("se_pairwise_dist", P[r0:r0 + n], C, negH, C, None, None, n, C, C, sehip.METRIC_COSINE, None, 0, slab, C)
+                call("se_topk_rows", slab, C, n, C, 0, top, dd[r0:r0 + n], dcls[r0:r0 + n])
+
+        def torch_composition():
+            kept["torch"] = (P.double() @ H64.T).topk(top, dim=1, largest=False).indices
+
+        tk, dk, tc_ = windows((tree_kernel, dense_kernels, torch_composition), reps, batch)
+        same_d = float((cls == dcls).all(dim=1).float().mean())
+        same_t = float((cls.long() == kept["torch"]).all(dim=1).float().mean())
+        ms = lambda v: (v[0] / 1e3, v[1] / 1e3, v[2] / 1e3)
+        print("N=%d C=%d on %s (%d levels at most):" % (N, C, note, enc_h["max_levels"]))
+        print("  se_tree_risk_topk          %9.3f ms (%.3f-%.3f)   4 N C bytes of input over this time: %.2f TB/s" % (ms(tk) + (4.0 * N * C / tk[0] / 1e6,)))
+        print("  dense on existing kernels  %9.3f ms (%.3f-%.3f)   x%.2f of the tree kernel" % (ms(dk) + (dk[0] / tk[0],)))
+        print("  torch float64 composition  %9.3f ms (%.3f-%.3f)   x%.2f of the tree kernel" % (ms(tc_) + (tc_[0] / tk[0],)))
+        print("  rows whose %d classes agree with the tree kernel's: dense %.4f, torch %.4f" % (top, same_d, same_t), flush=True)
 
 
 def bench_labelembed(reps=60, batch=20, steps=200):
