@@ -13,12 +13,15 @@ _TREES = {}
 
 def tree(name):
     """(hierarchy, classes) of a named tree, built once: cifar / cub / ilsvrc / inat400 (a 400-class sample of iNaturalist 2018) /
-    wordnet_dag / rand<C> (``_hxe_canon.random_tree(C, 3)``) / c1 / c2."""
+    wordnet_dag / rand<C> (``_hxe_canon.random_tree(C, 3)``) / c1 / c2 / cat33 and cat33x1000 (``_hxe_canon.caterpillar_tree(33)`` and
+    ``(33, 1000)``: paths of every level count up to the 32 a path may hold)."""
     if name not in _TREES:
         if name == "c1":
             h, classes = _hierarchy([(10, 0)]), [0]
         elif name == "c2":
             h, classes = _hierarchy([(10, 0), (10, 1)]), [0, 1]
+        elif name.startswith("cat33"):
+            h, classes = hc.caterpillar_tree(33, 1000 if name == "cat33x1000" else 0)
         elif name.startswith("rand"):
             h, classes = hc.random_tree(int(name[4:]), 3)
         elif name == "inat400":

@@ -236,12 +236,7 @@ def test_alpha_zero_is_the_cross_entropy(name, B, dtype):
     assert (np.abs(dz - (np.exp(hc.log_softmax(z64)) - np.eye(C)[y])) <= gb).all()        # p - onehot
 
 
-def _soft_bounds(C, ref, w=1.0):
-    D = hc.sum_depth(C)
-    lb = (D + np.log(C) + 10.0) * U * ref["scale"]
-    with np.errstate(invalid="ignore"):
-        gb = np.where(ref["absgrad"] == 0, 0.0, U * abs(w) * (2.0 * np.abs(ref["x"]) + 7.0 * np.log(C) + 2.0 * D + 12.0) * ref["absgrad"])
-    return lb, gb
+_soft_bounds = hc.soft_bounds          # one copy, shared with tests/test_gpu_hxe_matrix.py
 
 
 @pytest.mark.parametrize("name,B,dtype,ldt", [("cifar", 32, torch.float32, None), ("cifar", 5, torch.bfloat16, 101),

@@ -50,13 +50,17 @@ CASES = [
     ("rand1024", 5, 32, 0, 0, True, False), ("rand1024", 33, 1, 3, 1, True, True),
     ("rand1025", 1, 5, 0, 0, True, False), ("rand1025", 5, 32, 3, 1, True, True), ("rand1025", 33, 20, 0, 0, False, False),
     ("inat2018", 3, 20, 0, 0, True, False), ("inat2018", 3, 32, 3, 1, False, True),
+    # caterpillar trees: paths of 1 .. 32 levels, the most a path may hold (TR_LEVELS), on either path
+    ("cat33", 5, 32, 0, 0, True, False), ("cat33", 33, 20, 3, 1, True, True),
+    ("cat33x1000", 5, 32, 3, 1, True, True), ("cat33x1000", 33, 5, 0, 0, True, False),
 ]
 IDS = ["%s-N%d-top%d-p%d-o%d-%s-%s" % (c[0], c[1], c[2], c[3], c[4], "risk" if c[5] else "norisk", "own" if c[6] else "leaf") for c in CASES]
 
 
 def test_case_table_reaches_every_instantiation_and_boundary():
     sizes = {len(tc.tree(c[0])[1]) for c in CASES}
-    assert sizes == {1, 2, 37, 64, 65, 100, 200, 1000, 1024, 1025, 8142}
+    assert sizes == {1, 2, 33, 37, 64, 65, 100, 200, 1000, 1024, 1025, 1033, 8142}
+    assert {host_encoding(n)["max_levels"] for n in ("cat33", "cat33x1000")} == {32}
     assert {path_of(C) for C in sizes} == {"wave", "workgroup"} and {WAVE_MAX_C, WAVE_MAX_C + 1} <= sizes
     for C in sizes:
         ns = {c[1] for c in CASES if len(tc.tree(c[0])[1]) == C}

@@ -116,6 +116,19 @@ def test_a_40_level_path_without_chains_is_refused_and_a_chain_is_not():
 
 def test_canon_self_checks(tree):
     h, classes, enc, canon = tree
+    canon_self_checks(h, classes, canon)
+
+
+@pytest.mark.parametrize("name", ["c1", "cat33", "cat33x1000", "rand20011"])
+def test_canon_self_checks_on_the_trees_of_the_instantiation_matrix(name):
+    """The one-class tree (no level), the caterpillar trees (every level count up to 32) and the long rows of
+    tests/test_hxe_matrix_host.py."""
+    import test_hxe_matrix_host as hm
+    h, classes, canon, enc = hm.tree(name)
+    canon_self_checks(h, classes, canon)
+
+
+def canon_self_checks(h, classes, canon):
     C, B = len(classes), 6
     rng = np.random.default_rng(5)
     z = rng.standard_normal((B, C)) * 3.0
@@ -127,19 +140,21 @@ def test_canon_self_checks(tree):
     got = canon.hxe(z, y, alpha=0.3)
     assert np.abs(got["dz"].sum(axis=1)).max() <= 1e-12                                     # every row's gradient sums to 0
     eps = 1e-5
-    for i, c in [(0, int(y[0])), (1, (int(y[1]) + 1) % C), (2, int(np.argmax(z[2]))), (3, 0)]:
+    for i, c in [(0, int(y[0])), (1, (int(y[1]) + 1) % C), (2, int(np.argmax(z[2]))), (3, 0), (4, C - 1), (5, min(C - 1, 31))]:
         zp, zm = z.copy(), z.copy()
         zp[i, c] += eps
         zm[i, c] -= eps
         num = (canon.hxe(zp, y, alpha=0.3)["loss"][i] - canon.hxe(zm, y, alpha=0.3)["loss"][i]) / (2 * eps)
         assert abs(num - got["dz"][i, c]) <= 1e-8, (i, c, num, got["dz"][i, c])
+    if C > 2000:
+        return                                                      # (a [C, C] table of the long rows: not worth its memory here)
     table = h.soft_label_table(classes, 4.0).astype(np.float64)
     s = hc.soft(z, y, table)
     assert np.abs(s["dz"].sum(axis=1)).max() <= 1e-6                # rows of the float32 table sum to 1 up to its rounding
     zp, zm = z.copy(), z.copy()
-    zp[0, 1] += eps
-    zm[0, 1] -= eps
-    assert abs((hc.soft(zp, y, table)["loss"][0] - hc.soft(zm, y, table)["loss"][0]) / (2 * eps) - s["dz"][0, 1]) <= 1e-8
+    zp[0, 1 % C] += eps
+    zm[0, 1 % C] -= eps
+    assert abs((hc.soft(zp, y, table)["loss"][0] - hc.soft(zm, y, table)["loss"][0]) / (2 * eps) - s["dz"][0, 1 % C]) <= 1e-8
     assert np.abs(hc.soft(z, y, np.eye(C))["loss"] - flat["loss"]).max() <= 1e-12
 
 
